@@ -4,10 +4,21 @@ metrics + backward + Adam [+ gradient all-reduce]) in fp32, batch 16 per GPU, on
 configs[1]).  Synthetic tiles, random-init weights, inputs resident in HBM before timing.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run does only what the headline figure needs: set-up, warm-up (on one GPU
+including the choice of the step form, config.train_step_choice), the `--steps` timed steps, the outputs of the last
+timed step if `--dump-outputs DIR` is given, and the line (metric, value, unit, higher_is_better, dtype, ms_per_step,
+config).  `--dump-outputs DIR` writes, right after the timed region, what a caller of the training step receives from
+its last step - loss.npy, confusion_counts.npy (tp, tn, fp, fn) and one <metric>.npy per compiled metric, float64 - and
+gradients_sample.npy: a fixed, seeded sample of that step's weight gradients (float32, at most 2^22 values).  Tiles and
+initial weights are seeded, and with --dump-outputs the last timed step starts from the initial state again (restored
+with the clock stopped), so the same arguments give that step the same inputs on every run.
+With `--full` the line also carries the objects below (the figures that need brackets, extra steps, child
+processes or the host CPU):
   roofline     the north_star target kernel set = the six dilated 3x3 convs (3 ASPP + 3 SK branches) fwd +
                dgrad + wgrad: algorithmic FLOPs (nominal 2*M*N*K, SURVEY §8d: 97.84 GFLOP/tile) divided by
                their summed device time, measured with HIP events on the launch stream inside the timed
@@ -135,12 +146,131 @@ def cpu_baseline(threads, batch, size, steps, model=None, warmup=2):
     return out
 
 
+def roofline_record(args, prof, fam, step_tflop):
+    """--full: the line's `roofline` object, from the HIP-event brackets of the timed steps (`prof`) and of the two
+    bracketed steps after them (`fam`), with the committed counter-pass constants of profiles/."""
+    dil_ms = prof.get("dilated_conv", 0.0) / max(args.steps, 1)
+    dil_tflop = DILATED_GFLOP_PER_TILE * args.batch / 1e3 * (args.size / 512.0) ** 2
+    achieved = dil_tflop / (dil_ms / 1e3) if dil_ms > 0 else None
+    # The fp32 products of these convolutions run as six bf16 MFMA passes over an exact 3-way bf16 split of the
+    # fp32 operands, fp32 accumulation (csrc/conv_x6.h; accuracy >= the fp32 MFMA, profiles/r01_exp_bf16x6.txt).
+    # The pipe that bounds them is therefore the bf16 one: 2500 TFLOP/s dense / 6 passes per fp32 FLOP.  With
+    # SG_CONV_X6=0 they run on the fp32 MFMA (157.3 TFLOP/s) instead.
+    b16 = args.dtype == "bf16"
+    x6 = os.environ.get("SG_CONV_X6", "1") != "0" or b16
+    peak = BF16_MFMA_PEAK_TFLOPS if b16 else (BF16_MFMA_PEAK_TFLOPS / 6.0 if x6 else FP32_MFMA_PEAK_TFLOPS)
+    peak_note = ("bf16 dense MFMA peak (one v_mfma_f32_32x32x16_bf16 pass per product, fp32 accumulation)" if b16 else
+                 ("bf16 dense MFMA peak 2500 TFLOP/s / 6 MFMA passes per fp32 product (x6 path: fp32 in, fp32 accumulate, "
+                  "exact 3-way bf16 split); the native fp32 MFMA peak is 157.3 TFLOP/s") if x6 else "fp32 MFMA 32x32x2 dense peak")
+    # fabric-side bytes of the same kernel set per step, from the committed PMC passes (separate rocprofv3
+    # --pmc runs of scripts/dilated_bench.py at this very configuration; scripts/pmc_traffic.py)
+    traffic, traffic_note = None, "PMC passes exist for the 512x512 bs16 fp32 configuration only"
+    pdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
+    tj = next((os.path.join(pdir, n) for n in ("r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json") if os.path.exists(os.path.join(pdir, n))), None)
+    if args.batch == 16 and args.size == 512 and tj and not b16:
+        with open(tj) as f:
+            tr = json.load(f)
+        traffic = int(tr["set_bytes_per_step"])
+        traffic_note = ("NOT measured in this run: a committed constant from the separate rocprofv3 --pmc passes of %s "
+                        "(FETCH_SIZE pass x2 for gfx950's 64-B tally + WRITE_SIZE pass, L2-miss side, Infinity-Cache hits "
+                        "included) over the same kernel set at this configuration, launched as the step launches it (round 5: "
+                        "scripts/dilated_step.py - activation planes made once per tensor, planes-in filter gradients); "
+                        "algorithmic bytes of the set = %d (x %.2f)"
+                        % (os.path.basename(tj), int(tr["algorithmic_bytes_per_step"]), traffic / tr["algorithmic_bytes_per_step"]))
+    # Executed share of the nominal FLOPs: the kernels skip whole padding taps (exact: the skipped products are x0), so
+    # the matrix pipe executes fewer bf16 MFMA operations than 6 x nominal.  Counted by SQ_INSTS_VALU_MFMA_MOPS_BF16
+    # (x512 FLOP) in a separate rocprofv3 --pmc pass over this kernel set (scripts/pmc_mfma.py); it depends on the
+    # shapes only, not on the run.
+    exec_ratio, exec_note = None, "no PMC pass for this configuration"
+    pdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
+    pj = next((q for q in (os.path.join(pdir, n) for n in ("r05_pmc_mfma.json", "r04_pmc_mfma.json", "r03_pmc_mfma.json", "r01_pmc_mfma.json")) if os.path.exists(q)),
+              os.path.join(pdir, "r01_pmc_mfma.json"))
+    if args.batch == 16 and args.size == 512 and x6 and os.path.exists(pj):
+        with open(pj) as f:
+            rec = json.load(f)
+        if "bf16_mfma_flops_per_step" in rec:   # round 5: scripts/pmc_set.py over scripts/dilated_step.py, already per step
+            executed = rec["bf16_mfma_flops_per_step"] / 6.0  # fp32-equivalent
+        else:
+            k = rec["kernels"]
+            # the profiled script launches every forward 3x, dgrad / wgrad 2x (warm-up + ITERS=1): 30 and 12 launches
+            executed = (k["x6_fwd_dgrad"]["bf16_mfma_flops"] * 12 / k["x6_fwd_dgrad"]["launches"]
+                        + k["x6_wgrad"]["bf16_mfma_flops"] * 6 / k["x6_wgrad"]["launches"]) / 6.0  # fp32-equivalent
+        exec_ratio = executed / (dil_tflop * 1e12)
+        exec_note = ("NOT measured in this run: a committed constant from a separate counter pass (SQ_INSTS_VALU_MFMA_MOPS_BF16 x "
+                     "512, profiles/%s; it depends on the layer shapes only - rounds 1, 3 and 4 count the same operations) "
+                     "/ 6 / nominal FLOPs: padding taps of the dilated convs are skipped, not multiplied" % os.path.basename(pj))
+    ro = {"bound": "mfma", "achieved": None if achieved is None else round(achieved, 2),
+          "peak": round(peak, 1), "unit": "TFLOP/s",
+          "frac": None if achieved is None else round(achieved / peak, 4),
+          "peak_note": peak_note,
+          "frac_vs_fp32_mfma_peak": None if achieved is None else round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
+          "executed_share_of_nominal": None if exec_ratio is None else round(exec_ratio, 4),
+          "frac_executed": None if (achieved is None or exec_ratio is None) else round(achieved * exec_ratio / peak, 4),
+          "frac_executed_note": exec_note,
+          "traffic": traffic, "traffic_note": traffic_note,
+          "kernel": (("conv_b16w_kernel / conv_b16_kernel / wgrad_x6_kernel<NPL=1,bf16>" if b16
+                      else "conv_x6w_kernel (ASPP forward + dgrad, activation planes once per tensor: x6w_split_kernel) / conv_x6_kernel (SK) / "
+                           "wgrad_x6_kernel<.., PIN> (ASPP filter gradients from the planes) / wgrad_x6_kernel (SK)") if x6
+                     else "igemm_conv_kernel / igemm_wgrad_kernel") + " on the 6 dilated 3x3 convs (fwd+dgrad+wgrad)",
+          "ms_per_step": round(dil_ms, 3), "launches_per_step": prof.get("dilated_conv_launches", 0) // max(args.steps, 1)}
+    fam_ms = fam.get("gemm_conv", 0.0) / 2
+    if fam_ms > 0:  # every convolution / pointwise / transposed-convolution GEMM launch of the step, same peak
+        ro["family"] = {
+            "kernel": "all GEMM convolution launches of the step (pw_wide / conv_x6 / conv_x6w / conv_x6p / wgrad_x6 / wgrad_pw_wide / "
+                      "thin kernels + their plane-split and split-K reduce helpers), measured in 2 extra steps after the timed region",
+            "achieved": round(step_tflop / (fam_ms / 1e3), 2), "frac": round(step_tflop / (fam_ms / 1e3) / peak, 4),
+            "ms_per_step": round(fam_ms, 3), "launches_per_step": fam.get("gemm_conv_launches", 0) // 2}
+    return ro
+
+
+GRADS_SAMPLE = 1 << 22   # float32 values in gradients_sample.npy (16 MiB)
+
+
+def snapshot_state(model):
+    """--dump-outputs: a device copy of everything a training step reads and updates - weights, BatchNorm moving statistics
+    (the frozen arena), Adam moments - and the optimiser's step count."""
+    rt = model._runtime()
+    return [(t, t.clone()) for t in (rt.w_train, rt.w_frozen, rt.adam_m, rt.adam_v)], model.optimizer.iterations
+
+
+def restore_state(model, snap):
+    """Writes a snapshot_state() back in place (the captured graphs read these very buffers)."""
+    bufs, iterations = snap
+    for dst, src in bufs:
+        dst.copy_(src)
+    model.optimizer.iterations = iterations
+    model._runtime().weights_changed()
+
+
+def dump_outputs(path, model, loss, counts):
+    """--dump-outputs: what the last timed step gave its caller, as <path>/<name>.npy - loss, confusion_counts (tp, tn, fp,
+    fn) and one file per compiled metric (float64; the values train_on_batch returns as its logs), and gradients_sample: the
+    step's trainable-weight gradients (get_gradients()) in their order, concatenated (float32; above GRADS_SAMPLE values, the
+    values at fixed positions drawn with a fixed seed).  Not the updated weights: Adam moves every weight by about the
+    learning rate whatever the size of its gradient, so a rounding-level difference in a near-zero gradient becomes a
+    learning-rate-sized one in the weight."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().double().cpu().numpy().reshape(1)}
+    if counts is not None:
+        arrays["confusion_counts"] = counts.detach().double().cpu().numpy().reshape(-1)
+        logs = model._logs(loss, counts)   # the dict train_on_batch returns without return_device_scalars
+        for name in model.metric_names:
+            arrays[name] = np.array([logs[name]], np.float64)
+    g = np.concatenate([a.reshape(-1) for a in model.get_gradients()]).astype(np.float32, copy=False)
+    if g.size > GRADS_SAMPLE:
+        g = g[np.sort(np.random.default_rng(1103).choice(g.size, GRADS_SAMPLE, replace=False))]
+    arrays["gradients_sample"] = g
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def bf16_leg(args):
     """BASELINE configs[2] on one GPU: `bench.py --dtype bf16` (same model, batch and tile size; 3 warm-up + 10 timed steps, its
     own family / dilated-set brackets) as a CHILD process; returns the figures the driver's record should carry."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--dtype", "bf16", "--steps", "10", "--warmup", "3",
-           "--batch", str(args.batch), "--size", str(args.size), "--model", args.model, "--no-cpu-baseline", "--no-bf16-leg"]
+           "--batch", str(args.batch), "--size", str(args.size), "--model", args.model, "--full", "--no-cpu-baseline", "--no-bf16-leg"]
     try:
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420)
         line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
@@ -250,10 +380,16 @@ def main():
                          "no slack); on one GPU the warm-up tries both forms and the timed region runs the faster one "
                          "(config.train_step_choice)")
     ap.add_argument("--no-jit", dest="jit", action="store_false")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (the dilated set bracketed inside the "
+                         "timed steps, the whole conv family in extra steps after them), cpu_baseline and config.bf16_leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="start the last timed step from the seeded initial state again and write its outputs (loss, "
+                         "confusion counts, metrics: float64; a seeded sample of its gradients: float32) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-bf16-leg", action="store_true",
                     help="skip config.bf16_leg (BASELINE configs[2]'s per-GPU workload: the same model and batch with bf16 storage, "
-                         "3 warm-up + 10 steps in a child process after the fp32 timed region; single-GPU fp32 DeepLabv3+ runs only)")
+                         "3 warm-up + 10 steps in a child process after the fp32 timed region; single-GPU fp32 DeepLabv3+ --full runs only)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--comm", default=os.environ.get("SG_BENCH_COMM", "sg"), choices=["sg", "torch"],
                     help="gradient all-reduce transport: sg = RCCL through libsegengine's sg_comm_* (C ABI), torch = "
@@ -261,6 +397,8 @@ def main():
     ap.add_argument("--force-dp", action="store_true",
                     help="run the RCCL data-parallel path even with one rank (rehearsal on a 1-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU).  The parent
@@ -324,6 +462,9 @@ def main():
             os._exit(13)
         args.comm = dp.tp.name   # what actually carries the gradients ("sg" may have fallen back to "torch")
 
+    # --dump-outputs: the seeded initial state, before any step; the last timed step starts from it again (below)
+    snap = snapshot_state(model) if args.dump_outputs else None
+
     # rank r takes tiles [16 r, 16 r + 16) of the global synthetic batch (weak scaling)
     x, y = synthetic_batch(args.batch, args.size, args.size, seed=1103 + rank)
     xd = torch.from_numpy(x).cuda()
@@ -363,35 +504,51 @@ def main():
         choice = {"untimed_trial_ms_per_step": {"eager_two_streams": round(t_eager, 3), "hipgraph_replay": round(t_replay, 3)},
                   "chosen": "hipgraph_replay" if jit else "eager_two_streams"}
         sync()
-    eng.profile_begin()
+    if args.full:
+        eng.profile_begin()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss, _ = model.train_on_batch(xd, yd, return_device_scalars=True)
+    for _ in range(args.steps - (snap is not None)):
+        loss, counts = model.train_on_batch(xd, yd, return_device_scalars=True)
     t_enq = time.perf_counter() - t0   # the host has queued every launch of the timed steps (the device may still be running)
     sync()
     dt = time.perf_counter() - t0
-    prof = eng.profile_end()
+    if snap is not None:
+        # --dump-outputs: the last timed step starts from the seeded initial state, restored with the clock stopped, so that its
+        # inputs are the same on every run and every build.  After a few Adam steps the state carries any rounding-level
+        # difference of an earlier step at the size of the learning rate, and the dumped outputs would differ by that much.
+        restore_state(model, snap)
+        sync()
+        t1 = time.perf_counter()
+        loss, counts = model.train_on_batch(xd, yd, return_device_scalars=True)
+        t_enq += time.perf_counter() - t1
+        sync()
+        dt += time.perf_counter() - t1
+        del snap
+    prof = eng.profile_end() if args.full else {}
     peak_mem = torch.cuda.max_memory_allocated(local_rank)
-    # outside the timed region: two more steps with EVERY GEMM-convolution launch bracketed (the whole kernel family)
-    # (every rank runs them - the data-parallel step all-reduces - but only rank 0 brackets its launches)
+    if args.dump_outputs and rank == 0:   # before any further step moves the weights
+        dump_outputs(args.dump_outputs, model, loss, counts)
+    # outside the timed region (--full only): two more steps with EVERY GEMM-convolution launch bracketed (the whole kernel
+    # family) (every rank runs them - the data-parallel step all-reduces - but only rank 0 brackets its launches)
     fam = {}
-    if jit:
-        model.jit_compile = False   # the two bracketed steps below run eagerly
-        # ... after one eager step that is neither timed nor bracketed: the replays ran on private buffers, and the first eager
-        # step behind them re-grows the shared workspaces - bracketed, it read 54 - 59 ms for the family instead of 52.5 and 6.3
-        # instead of 6.15 ms for the dilated set (gpurun_out/r5L; the default one-GPU line tries both forms first and never
-        # showed it, but every N > 1 line runs the replay)
-        model.train_on_batch(xd, yd, return_device_scalars=True)
-    if rank == 0:
-        eng.profile_begin(all_convs=True)
-    for _ in range(2):
-        model.train_on_batch(xd, yd, return_device_scalars=True)
-    if rank == 0:
-        fam = eng.profile_end()
-    sync()
-    if jit and rank == 0:   # the dilated set of the two eager steps stands in for the (unbracketable) replays
-        prof = {"dilated_conv": fam.get("dilated_conv", 0.0) * args.steps / 2.0,
-                "dilated_conv_launches": fam.get("dilated_conv_launches", 0) * args.steps // 2}
+    if args.full:
+        if jit:
+            model.jit_compile = False   # the two bracketed steps below run eagerly
+            # ... after one eager step that is neither timed nor bracketed: the replays ran on private buffers, and the first eager
+            # step behind them re-grows the shared workspaces - bracketed, it read 54 - 59 ms for the family instead of 52.5 and
+            # 6.3 instead of 6.15 ms for the dilated set (LAB_NOTEBOOK 12.11; the default one-GPU line tries both forms first and
+            # never showed it, but every N > 1 line runs the replay)
+            model.train_on_batch(xd, yd, return_device_scalars=True)
+        if rank == 0:
+            eng.profile_begin(all_convs=True)
+        for _ in range(2):
+            model.train_on_batch(xd, yd, return_device_scalars=True)
+        if rank == 0:
+            fam = eng.profile_end()
+        sync()
+        if jit and rank == 0:   # the dilated set of the two eager steps stands in for the (unbracketable) replays
+            prof = {"dilated_conv": fam.get("dilated_conv", 0.0) * args.steps / 2.0,
+                    "dilated_conv_launches": fam.get("dilated_conv_launches", 0) * args.steps // 2}
     if dist is not None:
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -401,56 +558,8 @@ def main():
     step_tflop = 3 * model.flops(args.batch) / 1e12  # fwd + dgrad + wgrad, nominal
 
     if rank == 0:
-        dil_ms = prof.get("dilated_conv", 0.0) / max(args.steps, 1)
-        dil_tflop = DILATED_GFLOP_PER_TILE * args.batch / 1e3 * (args.size / 512.0) ** 2
-        achieved = dil_tflop / (dil_ms / 1e3) if dil_ms > 0 else None
-        # The fp32 products of these convolutions run as six bf16 MFMA passes over an exact 3-way bf16 split of the
-        # fp32 operands, fp32 accumulation (csrc/conv_x6.h; accuracy >= the fp32 MFMA, profiles/r01_exp_bf16x6.txt).
-        # The pipe that bounds them is therefore the bf16 one: 2500 TFLOP/s dense / 6 passes per fp32 FLOP.  With
-        # SG_CONV_X6=0 they run on the fp32 MFMA (157.3 TFLOP/s) instead.
         b16 = args.dtype == "bf16"
         x6 = os.environ.get("SG_CONV_X6", "1") != "0" or b16
-        peak = BF16_MFMA_PEAK_TFLOPS if b16 else (BF16_MFMA_PEAK_TFLOPS / 6.0 if x6 else FP32_MFMA_PEAK_TFLOPS)
-        peak_note = ("bf16 dense MFMA peak (one v_mfma_f32_32x32x16_bf16 pass per product, fp32 accumulation)" if b16 else
-                     ("bf16 dense MFMA peak 2500 TFLOP/s / 6 MFMA passes per fp32 product (x6 path: fp32 in, fp32 accumulate, "
-                      "exact 3-way bf16 split); the native fp32 MFMA peak is 157.3 TFLOP/s") if x6 else "fp32 MFMA 32x32x2 dense peak")
-        # fabric-side bytes of the same kernel set per step, from the committed PMC passes (separate rocprofv3
-        # --pmc runs of scripts/dilated_bench.py at this very configuration; scripts/pmc_traffic.py)
-        traffic, traffic_note = None, "PMC passes exist for the 512x512 bs16 fp32 configuration only"
-        pdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
-        tj = next((os.path.join(pdir, n) for n in ("r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json") if os.path.exists(os.path.join(pdir, n))), None)
-        if args.batch == 16 and args.size == 512 and tj and not b16:
-            with open(tj) as f:
-                tr = json.load(f)
-            traffic = int(tr["set_bytes_per_step"])
-            traffic_note = ("NOT measured in this run: a committed constant from the separate rocprofv3 --pmc passes of %s "
-                            "(FETCH_SIZE pass x2 for gfx950's 64-B tally + WRITE_SIZE pass, L2-miss side, Infinity-Cache hits "
-                            "included) over the same kernel set at this configuration, launched as the step launches it (round 5: "
-                            "scripts/dilated_step.py - activation planes made once per tensor, planes-in filter gradients); "
-                            "algorithmic bytes of the set = %d (x %.2f)"
-                            % (os.path.basename(tj), int(tr["algorithmic_bytes_per_step"]), traffic / tr["algorithmic_bytes_per_step"]))
-        # Executed share of the nominal FLOPs: the kernels skip whole padding taps (exact: the skipped products are x0), so
-        # the matrix pipe executes fewer bf16 MFMA operations than 6 x nominal.  Counted by SQ_INSTS_VALU_MFMA_MOPS_BF16
-        # (x512 FLOP) in a separate rocprofv3 --pmc pass over this kernel set (scripts/pmc_mfma.py); it depends on the
-        # shapes only, not on the run.
-        exec_ratio, exec_note = None, "no PMC pass for this configuration"
-        pdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
-        pj = next((q for q in (os.path.join(pdir, n) for n in ("r05_pmc_mfma.json", "r04_pmc_mfma.json", "r03_pmc_mfma.json", "r01_pmc_mfma.json")) if os.path.exists(q)),
-                  os.path.join(pdir, "r01_pmc_mfma.json"))
-        if args.batch == 16 and args.size == 512 and x6 and os.path.exists(pj):
-            with open(pj) as f:
-                rec = json.load(f)
-            if "bf16_mfma_flops_per_step" in rec:   # round 5: scripts/pmc_set.py over scripts/dilated_step.py, already per step
-                executed = rec["bf16_mfma_flops_per_step"] / 6.0  # fp32-equivalent
-            else:
-                k = rec["kernels"]
-                # the profiled script launches every forward 3x, dgrad / wgrad 2x (warm-up + ITERS=1): 30 and 12 launches
-                executed = (k["x6_fwd_dgrad"]["bf16_mfma_flops"] * 12 / k["x6_fwd_dgrad"]["launches"]
-                            + k["x6_wgrad"]["bf16_mfma_flops"] * 6 / k["x6_wgrad"]["launches"]) / 6.0  # fp32-equivalent
-            exec_ratio = executed / (dil_tflop * 1e12)
-            exec_note = ("NOT measured in this run: a committed constant from a separate counter pass (SQ_INSTS_VALU_MFMA_MOPS_BF16 x "
-                         "512, profiles/%s; it depends on the layer shapes only - rounds 1, 3 and 4 count the same operations) "
-                         "/ 6 / nominal FLOPs: padding taps of the dilated convs are skipped, not multiplied" % os.path.basename(pj))
         out = {
             "metric": f"{args.size}x{args.size} tiles/sec fwd+bwd {LABEL.get(args.model, args.model)} (full train step: fwd+loss+bwd+Adam)",
             "value": round(tiles_per_s, 3), "unit": "tiles/s", "n_gpus": world, "steps": args.steps,
@@ -471,29 +580,10 @@ def main():
                        "train_step": (("one hipGraph replay per step (compile(jit_compile=True))" if dist is None else
                                        "hipGraph segments per gradient bucket, eager RCCL all-reduces between them "
                                        "(compile(jit_compile=True) under DataParallel)") if jit else "eager launches")},
-            "roofline": {"bound": "mfma", "achieved": None if achieved is None else round(achieved, 2),
-                         "peak": round(peak, 1), "unit": "TFLOP/s",
-                         "frac": None if achieved is None else round(achieved / peak, 4),
-                         "peak_note": peak_note,
-                         "frac_vs_fp32_mfma_peak": None if achieved is None else round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
-                         "executed_share_of_nominal": None if exec_ratio is None else round(exec_ratio, 4),
-                         "frac_executed": None if (achieved is None or exec_ratio is None) else round(achieved * exec_ratio / peak, 4),
-                         "frac_executed_note": exec_note,
-                         "traffic": traffic, "traffic_note": traffic_note,
-                         "kernel": (("conv_b16w_kernel / conv_b16_kernel / wgrad_x6_kernel<NPL=1,bf16>" if b16
-                                     else "conv_x6w_kernel (ASPP forward + dgrad, activation planes once per tensor: x6w_split_kernel) / conv_x6_kernel (SK) / "
-                                          "wgrad_x6_kernel<.., PIN> (ASPP filter gradients from the planes) / wgrad_x6_kernel (SK)") if x6
-                                    else "igemm_conv_kernel / igemm_wgrad_kernel") + " on the 6 dilated 3x3 convs (fwd+dgrad+wgrad)",
-                         "ms_per_step": round(dil_ms, 3), "launches_per_step": prof.get("dilated_conv_launches", 0) // max(args.steps, 1)},
         }
-        fam_ms = fam.get("gemm_conv", 0.0) / 2
-        if fam_ms > 0:  # every convolution / pointwise / transposed-convolution GEMM launch of the step, same peak
-            out["roofline"]["family"] = {
-                "kernel": "all GEMM convolution launches of the step (pw_wide / conv_x6 / conv_x6w / conv_x6p / wgrad_x6 / wgrad_pw_wide / "
-                          "thin kernels + their plane-split and split-K reduce helpers), measured in 2 extra steps after the timed region",
-                "achieved": round(step_tflop / (fam_ms / 1e3), 2), "frac": round(step_tflop / (fam_ms / 1e3) / peak, 4),
-                "ms_per_step": round(fam_ms, 3), "launches_per_step": fam.get("gemm_conv_launches", 0) // 2}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["roofline"] = roofline_record(args, prof, fam, step_tflop)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = args.cpu_threads or min(os.cpu_count() or 1, 16)
             try:
                 out["cpu_baseline"] = cpu_baseline(threads, 2, args.size, 5, model if args.model == "v3plus" else None)
@@ -503,7 +593,7 @@ def main():
                 out["cpu_baseline"] = {"value": None, "error": repr(e)}
         out["config"]["peak_device_memory_gib"] = round(peak_mem / 2.0 ** 30, 2)
         out["config"]["side_stream_filter_gradients"] = os.environ.get("SG_SIDE_WGRAD", "1") != "0"
-        if world == 1 and not b16 and args.model == "v3plus" and not args.no_bf16_leg:
+        if args.full and world == 1 and not b16 and args.model == "v3plus" and not args.no_bf16_leg:
             # BASELINE configs[2]'s per-GPU workload (bf16 storage), AFTER and OUTSIDE the fp32 timed region: a child process
             # (started, not exec'ed: this process has used the GPU) runs the same bench with --dtype bf16 and its line is
             # folded into config.bf16_leg.  The fp32 model's memory is released first.

@@ -10,7 +10,7 @@ for form in --no-jit --jit; do
   for r in $(seq 1 "$REP"); do
     for v in "$A" "$B"; do
       f="$OUT/bench_${VAR}_${v}_${form#--}_$r.json"
-      env "$VAR=$v" timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg $form > "$f" 2>> "$OUT/err.txt" || { echo "bench failed: $f" | tee -a "$OUT/ab.txt"; exit 1; }
+      env "$VAR=$v" timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg $form > "$f" 2>> "$OUT/err.txt" || { echo "bench failed: $f" | tee -a "$OUT/ab.txt"; exit 1; }
       python - "$f" "$VAR" "$v" "$form" <<'PY' | tee -a "$OUT/ab.txt"
 import sys, json
 f, var, v, form = sys.argv[1:5]

@@ -11,6 +11,6 @@ PY
 }
 for name in "no-jit:--no-jit" "jit:--jit" "jit_again:--jit" "dp1_jit:--force-dp --jit"; do
   n=${name%%:*}; a=${name#*:}
-  timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg $a > "$OUT/$n.json" 2>> "$OUT/err.txt" || { echo "$n failed"; tail -5 "$OUT/err.txt"; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg $a > "$OUT/$n.json" 2>> "$OUT/err.txt" || { echo "$n failed"; tail -5 "$OUT/err.txt"; exit 1; }
   show "$OUT/$n.json" "$n" | tee -a "$OUT/summary.txt"
 done

@@ -28,12 +28,12 @@ for s in $STAGES; do
   case $s in
     tests) run_stage tests 900 python -m pytest tests -m gpu -q -p no:cacheprovider ;;
     smoke) run_stage smoke 300 python __graft_entry__.py smoke ;;
-    bench) run_stage bench 600 python bench.py --steps 6 --warmup 2 ;;
-    prof)  run_stage prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rocprof" -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
+    bench) run_stage bench 600 python bench.py --full --steps 6 --warmup 2 ;;
+    prof)  run_stage prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rocprof" -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
            # keep only the small summaries
            find "$OUT/rocprof" -name '*kernel_stats*.csv' -exec cp {} "$OUT/kernel_stats.csv" \; 2>/dev/null
            find "$OUT/rocprof" -name '*kernel_trace*.csv' -size +20M -delete 2>/dev/null ;;
-    dp1)   run_stage dp1 600 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --force-dp ;;
+    dp1)   run_stage dp1 600 python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --force-dp ;;
     pmc)   # HBM traffic of the dilated-conv kernels: separate passes (FETCH_SIZE costs 3 TCC slots, WRITE_SIZE 2)
            export ONLY_DILATED=1 ITERS=1   # every launch of the set runs exactly twice (warm-up + 1)
            run_stage pmc_fetch 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -- python3 scripts/dilated_bench.py

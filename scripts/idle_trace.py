@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where is the GPU idle inside a training step?  From a rocprofv3 --kernel-trace CSV of bench.py: one steady-state step (between
+"""Where is the GPU idle inside a training step?  From a rocprofv3 --kernel-trace CSV of bench.py --full: one steady-state step (between
 two adam_kernel launches, the third from the end by default), the union of all kernels' intervals over all queues, the total idle
 time, the idle time by gap size, the largest gaps with the kernels on either side, and the time during which only the second queue
 ran.  Use: python scripts/idle_trace.py <kernel_trace.csv> [steps back from the end]"""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""How much of a training step runs on two streams at once: from a rocprofv3 --kernel-trace CSV of bench.py, takes the
+"""How much of a training step runs on two streams at once: from a rocprofv3 --kernel-trace CSV of bench.py --full, takes the
 dispatches between two consecutive adam_kernel launches (one steady-state step of the timed region: the third from the end
-by default, bench.py's last two steps are the bracketed single-stream ones) and prints the wall time, the summed kernel
+by default, the last two steps of bench.py --full are the bracketed single-stream ones) and prints the wall time, the summed kernel
 time per queue, the time during which kernels of BOTH queues were running, and per kernel family the mean duration
 (to compare with a SG_SIDE_WGRAD=0 trace).  Use: python scripts/overlap_trace.py <kernel_trace.csv>"""
 import csv

@@ -19,25 +19,25 @@ stage() {  # name timeout cmd...
 }
 stage tests 900 python -m pytest tests -m gpu -q -p no:cacheprovider
 tail -n 3 "$OUT/tests.log"
-stage bench 600 python bench.py
+stage bench 600 python bench.py --full
 tail -n 1 "$OUT/bench.log" | cut -c1-400
-stage stats2 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rp2" -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg --no-jit
+stage stats2 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rp2" -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg --no-jit
 find "$OUT/rp2" -name '*kernel_stats*.csv' -exec cp {} "$OUT/kernel_stats_two_streams.csv" \; ; rm -rf "$OUT/rp2"
-SG_SIDE_WGRAD=0 stage stats1 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rp1" -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg --no-jit
+SG_SIDE_WGRAD=0 stage stats1 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rp1" -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg --no-jit
 find "$OUT/rp1" -name '*kernel_stats*.csv' -exec cp {} "$OUT/kernel_stats_single_stream.csv" \; ; rm -rf "$OUT/rp1"
-stage statsbf 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rpb" -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --dtype bf16 --no-jit
+stage statsbf 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rpb" -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --dtype bf16 --no-jit
 find "$OUT/rpb" -name '*kernel_stats*.csv' -exec cp {} "$OUT/kernel_stats_bf16.csv" \; ; rm -rf "$OUT/rpb"
-SG_TRACE_MARK=1 stage trace 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/tr" -- python3 bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-bf16-leg --no-jit
+SG_TRACE_MARK=1 stage trace 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/tr" -- python3 bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --no-bf16-leg --no-jit
 python scripts/trace_dilated.py "$OUT/tr" 5 "$OUT/trace_dilated.json" > "$OUT/trace_dilated.txt" 2>&1; rm -rf "$OUT/tr"
 tail -n 3 "$OUT/trace_dilated.txt"
 for m in bam scse hrnet res34; do
-  stage bench_$m 500 python bench.py --model $m --steps 6 --warmup 3 --no-cpu-baseline
+  stage bench_$m 500 python bench.py --full --model $m --steps 6 --warmup 3 --no-cpu-baseline
   tail -n 1 "$OUT/bench_$m.log" | cut -c1-260
 done
-stage dp1 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg --force-dp
+stage dp1 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg --force-dp
 tail -n 1 "$OUT/dp1.log" | cut -c1-260
-stage single 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg
+stage single 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-bf16-leg
 tail -n 1 "$OUT/single.log" | cut -c1-260
-stage dp1bf 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --dtype bf16 --force-dp
-stage singlebf 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --dtype bf16
+stage dp1bf 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --dtype bf16 --force-dp
+stage singlebf 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --dtype bf16
 echo "== done" | tee -a "$OUT/summary.txt"

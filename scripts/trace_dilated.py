@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Re-derive bench.py's `roofline.ms_per_step` from a rocprofv3 per-launch kernel trace of the same run.
 
-    SG_TRACE_MARK=1 rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps K --warmup W ...
+    SG_TRACE_MARK=1 rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --full --steps K --warmup W ...
     python scripts/trace_dilated.py DIR K profiles/rNN_trace_dilated.json [profiles/rNN_trace_dilated_launches.csv]
 
 With SG_TRACE_MARK=1 every launch group that bench.py brackets with HIP events is also bracketed by two empty marker

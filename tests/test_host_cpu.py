@@ -796,7 +796,7 @@ def test_bench_bf16_leg_folds_the_child_line(monkeypatch):
     leg = bench.bf16_leg(args)
     cmd = seen["cmd"]
     assert cmd[0] == sys.executable and cmd[1].endswith("bench.py")
-    for flag in ("--dtype", "bf16", "--no-cpu-baseline", "--no-bf16-leg", "--steps", "10", "--warmup", "3"):
+    for flag in ("--dtype", "bf16", "--full", "--no-cpu-baseline", "--no-bf16-leg", "--steps", "10", "--warmup", "3"):
         assert flag in cmd, (flag, cmd)
     assert leg["ms_per_step"] == 31.7 and leg["tiles_per_s"] == 505.0 and leg["dtype"] == "bf16"
     assert leg["roofline"]["frac"] == 0.33 and leg["family"]["frac"] == 0.2 and leg["steps"] == 10

@@ -20,6 +20,8 @@ SG_PRO_UP2, SG_EPI_DOWN2 = 16, 32   # UpSampling2D(2) -> Conv2D 3x3 fused: forwa
 SG_X_UP2 = 0x200                   # ... and the dtype flag of its filter gradient
 SG_ACT_RELU, SG_ACT_SIGMOID = 0, 1
 SG_LOSS_CE2, SG_LOSS_FOCAL, SG_LOSS_EDGE_FOCAL = 0, 1, 2
+SG_AUGMENT_MAX_ITEMS = 64
+SG_AUG_FLIP_UD, SG_AUG_FLIP_LR, SG_AUG_SWAP_RB, SG_AUG_THRESHOLD = 1, 2, 4, 8
 
 
 class SgError(RuntimeError):
@@ -34,6 +36,11 @@ class PlanesJob(C.Structure):
 
 
 SG_WS_PREPARED = C.c_size_t(-1).value
+
+
+class AugmentItem(C.Structure):
+    """Mirror of `sg_augment_item` (include/segengine.h): one output tile of sg_augment_u8."""
+    _fields_ = [(n, C.c_int32) for n in ("src", "n", "shift", "flags")]
 
 
 class ConvDesc(C.Structure):
@@ -151,6 +158,7 @@ _SIGNATURES = {
     "sg_adam_step_lr": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f]),
     "sg_edge_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sg_resize_linear_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "sg_augment_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     "sg_argmax_accumulate_i8": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i]),
     "sg_vote_ge": (_i, [_vp, _vp, _i, _pp, _i64, _i, _vp]),
     "sg_mask_objects_ws_bytes": (_sz, [_i, _i]),

@@ -279,6 +279,17 @@ __device__ __forceinline__ void cv_linear_coeff(int d, double scale, int n_in, i
   c1 = __float2int_rn(f * 2048.f);
 }
 
+// The two-pass arithmetic above, from the four taps (s00, s01 of the upper row, s10, s11 of the lower one) and their
+// weights; and the fast INTER_AREA of an exact 2x downscale.  Shared by resize_linear_u8_kernel and augment_u8_kernel.
+__device__ __forceinline__ int cv_linear_mix(int s00, int s01, int s10, int s11, int a0, int a1, int b0, int b1) {
+  const int d0 = s00 * a0 + s01 * a1;
+  const int d1 = s10 * a0 + s11 * a1;
+  const int v = (((b0 * (d0 >> 4)) >> 16) + ((b1 * (d1 >> 4)) >> 16) + 2) >> 2;
+  return min(max(v, 0), 255);
+}
+
+__device__ __forceinline__ int cv_area2_mix(int s00, int s01, int s10, int s11) { return (s00 + s01 + s10 + s11 + 2) >> 2; }
+
 __global__ void resize_linear_u8_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int N, int H, int W,
                                         int C, int OH, int OW, double sx_scale, double sy_scale, int area2) {
   const int64_t total = (int64_t)N * OH * OW * C;
@@ -291,7 +302,7 @@ __global__ void resize_linear_u8_kernel(const unsigned char* __restrict__ src, u
     const unsigned char* img = src + (int64_t)n * H * W * C;
     if (area2) {
       const unsigned char* q = img + ((int64_t)(2 * dy) * W + 2 * dx) * C + c;
-      dst[i] = (unsigned char)((q[0] + q[C] + q[(int64_t)W * C] + q[(int64_t)W * C + C] + 2) >> 2);
+      dst[i] = (unsigned char)cv_area2_mix(q[0], q[C], q[(int64_t)W * C], q[(int64_t)W * C + C]);
       continue;
     }
     int sx, a0, a1, sy, b0, b1;
@@ -299,11 +310,102 @@ __global__ void resize_linear_u8_kernel(const unsigned char* __restrict__ src, u
     cv_linear_coeff(dy, sy_scale, H, sy, b0, b1, false);
     const int sx1 = min(sx + 1, W - 1);
     const int y0 = min(max(sy, 0), H - 1), y1 = min(max(sy + 1, 0), H - 1);
-    const int d0 = img[((int64_t)y0 * W + sx) * C + c] * a0 + img[((int64_t)y0 * W + sx1) * C + c] * a1;
-    const int d1 = img[((int64_t)y1 * W + sx) * C + c] * a0 + img[((int64_t)y1 * W + sx1) * C + c] * a1;
-    int v = (((b0 * (d0 >> 4)) >> 16) + ((b1 * (d1 >> 4)) >> 16) + 2) >> 2;
-    v = min(max(v, 0), 255);
-    dst[i] = (unsigned char)v;
+    dst[i] = (unsigned char)cv_linear_mix(img[((int64_t)y0 * W + sx) * C + c], img[((int64_t)y0 * W + sx1) * C + c],
+                                          img[((int64_t)y1 * W + sx) * C + c], img[((int64_t)y1 * W + sx1) * C + c], a0, a1, b0, b1);
+  }
+}
+
+// sg_augment_u8 (include/segengine.h).  One output tile per blockIdx.y, its item read from the by-value table (a uniform
+// index: scalar loads of the kernel-argument segment); each thread computes AUG_PX consecutive pixels of one output row, the
+// row taps once and the column taps once per pixel, all indices in 32 bits (the host bounds every tensor below 2 GiB), and
+// writes the AUG_PX * C bytes as C 32-bit words when the row is word-aligned (OW % 4 == 0), else byte by byte.
+constexpr int AUG_PX = 4;
+
+struct AugItemK {
+  int src, n, shift, flags;
+  double sx_scale, sy_scale;  // W / n, H / n rounded on the host, as sg_resize_linear_u8 passes them
+};
+struct AugTable {
+  AugItemK it[SG_AUGMENT_MAX_ITEMS];
+};
+
+template <int C>
+__global__ __launch_bounds__(256) void augment_u8_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
+                                                         const AugTable tab, int H, int W, int OH, int OW, int qw, int fill,
+                                                         int packed) {
+  const AugItemK it = tab.it[blockIdx.y];
+  const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (t >= OH * qw) return;
+  const int oy = t / qw;
+  const int ox0 = (t - oy * qw) * AUG_PX;
+  const unsigned char* __restrict__ img = src + it.src * (H * W * C);
+  const bool thr = it.flags & SG_AUG_THRESHOLD;
+  const bool lr = it.flags & SG_AUG_FLIP_LR;
+  const bool rb = C == 3 && (it.flags & SG_AUG_SWAP_RB);
+  const int n = it.n;
+  const int mode = (n == H && n == W) ? 0 : (H == 2 * n && W == 2 * n) ? 1 : 2;  // identity / INTER_AREA / INTER_LINEAR
+  const int ry = ((it.flags & SG_AUG_FLIP_UD) ? OH - 1 - oy : oy) + it.shift;
+  const bool row_in = (unsigned)ry < (unsigned)n;
+  int r0 = 0, r1 = 0, b0 = 0, b1 = 0;  // row offsets (in pixels) of the two source rows, their weights
+  if (row_in) {
+    if (mode == 2) {
+      int sy;
+      cv_linear_coeff(ry, it.sy_scale, H, sy, b0, b1, false);
+      r0 = min(max(sy, 0), H - 1) * W;
+      r1 = min(max(sy + 1, 0), H - 1) * W;
+    } else {
+      r0 = (mode == 1 ? 2 * ry : ry) * W;
+      r1 = r0 + W;
+    }
+  }
+  unsigned int word[C];
+#pragma unroll
+  for (int j = 0; j < C; ++j) word[j] = 0u;
+#pragma unroll
+  for (int k = 0; k < AUG_PX; ++k) {
+    const int ox = ox0 + k;
+    const int rx = (lr ? OW - 1 - ox : ox) + it.shift;
+    const bool in = row_in && ox < OW && (unsigned)rx < (unsigned)n;
+    int p00 = 0, p01 = 0, a0 = 0, a1 = 0;  // pixel offsets of the two source columns in the upper row, their weights
+    if (in) {
+      if (mode == 2) {
+        int sx;
+        cv_linear_coeff(rx, it.sx_scale, W, sx, a0, a1, true);
+        p00 = r0 + sx;
+        p01 = r0 + min(sx + 1, W - 1);
+      } else {
+        p00 = r0 + (mode == 1 ? 2 * rx : rx);
+        p01 = p00 + 1;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      int v = fill;
+      if (in) {
+        const int sc = rb ? 2 - c : c;
+        if (mode == 0) {
+          v = img[p00 * C + sc];
+        } else {
+          const int q00 = p00 * C + sc, q01 = p01 * C + sc, q10 = q00 + (r1 - r0) * C, q11 = q01 + (r1 - r0) * C;
+          v = mode == 1 ? cv_area2_mix(img[q00], img[q01], img[q10], img[q11])
+                        : cv_linear_mix(img[q00], img[q01], img[q10], img[q11], a0, a1, b0, b1);
+        }
+        if (thr) v = v > 125 ? 255 : 0;
+      }
+      const int b = k * C + c;
+      word[b >> 2] |= (unsigned int)v << (8 * (b & 3));
+    }
+  }
+  const int off = (int)blockIdx.y * (OH * OW * C) + (oy * OW + ox0) * C;
+  if (packed) {
+    unsigned int* __restrict__ d = reinterpret_cast<unsigned int*>(dst + off);
+#pragma unroll
+    for (int j = 0; j < C; ++j) d[j] = word[j];
+  } else {
+    const int nb = min(AUG_PX, OW - ox0) * C;
+#pragma unroll
+    for (int b = 0; b < AUG_PX * C; ++b)
+      if (b < nb) dst[off + b] = (unsigned char)(word[b >> 2] >> (8 * (b & 3)));
   }
 }
 
@@ -422,6 +524,39 @@ int sg_resize_linear_u8(sg_ctx* ctx, void* stream, int N, int H, int W, int C, c
   hipLaunchKernelGGL(resize_linear_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src_u8,
                      (unsigned char*)dst_u8, N, H, W, C, OH, OW, (double)W / (double)OW, (double)H / (double)OH, area2);
   SG_LAUNCH_CHECK("resize_linear_u8_kernel");
+  return 0;
+}
+
+int sg_augment_u8(sg_ctx* ctx, void* stream, int S, int H, int W, int C, const void* src_u8, int N, const sg_augment_item* items,
+                  int OH, int OW, int fill, void* dst_u8) {
+  SG_CHECK_ARG(ctx && src_u8 && items && dst_u8 && S > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "sg_augment_u8: bad argument");
+  SG_CHECK_ARG(C == 1 || C == 3, "sg_augment_u8: C = %d (1 or 3)", C);
+  SG_CHECK_ARG(N >= 1 && N <= SG_AUGMENT_MAX_ITEMS, "sg_augment_u8: N = %d outside [1, %d]", N, SG_AUGMENT_MAX_ITEMS);
+  SG_CHECK_ARG(fill >= 0 && fill <= 255, "sg_augment_u8: fill = %d outside [0, 255]", fill);
+  SG_CHECK_ARG((int64_t)S * H * W * C < (1ll << 31) && (int64_t)N * OH * OW * C < (1ll << 31) && OH < (1 << 30) && OW < (1 << 30),
+               "sg_augment_u8: tensors of %d x %d x %d x %d / %d x %d x %d x %d bytes exceed 2 GiB", S, H, W, C, N, OH, OW, C);
+  AugTable tab;
+  for (int i = 0; i < N; ++i) {
+    const sg_augment_item& a = items[i];
+    SG_CHECK_ARG(a.src >= 0 && a.src < S, "sg_augment_u8: item %d: source %d outside [0, %d)", i, a.src, S);
+    SG_CHECK_ARG(a.n >= 1 && a.n < (1 << 30), "sg_augment_u8: item %d: resized size %d", i, a.n);
+    SG_CHECK_ARG(a.shift > -(1 << 30) && a.shift < (1 << 30), "sg_augment_u8: item %d: shift %d", i, a.shift);
+    SG_CHECK_ARG((a.flags & ~(SG_AUG_FLIP_UD | SG_AUG_FLIP_LR | SG_AUG_SWAP_RB | SG_AUG_THRESHOLD)) == 0,
+                 "sg_augment_u8: item %d: unknown flags %#x", i, a.flags);
+    SG_CHECK_ARG(C == 3 || !(a.flags & SG_AUG_SWAP_RB), "sg_augment_u8: item %d: the R-B swap needs C = 3", i);
+    tab.it[i] = AugItemK{a.src, a.n, a.shift, a.flags, (double)W / (double)a.n, (double)H / (double)a.n};
+  }
+  for (int i = N; i < SG_AUGMENT_MAX_ITEMS; ++i) tab.it[i] = AugItemK{0, 1, 0, 0, 1.0, 1.0};
+  const int qw = (int)sg_cdiv(OW, AUG_PX);
+  const int packed = (OW % 4 == 0 && ((uintptr_t)dst_u8 & 3) == 0) ? 1 : 0;
+  const dim3 grid((unsigned)sg_cdiv((int64_t)OH * qw, 256), (unsigned)N);
+  if (C == 3)
+    hipLaunchKernelGGL(augment_u8_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src_u8,
+                       (unsigned char*)dst_u8, tab, H, W, OH, OW, qw, fill, packed);
+  else
+    hipLaunchKernelGGL(augment_u8_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src_u8,
+                       (unsigned char*)dst_u8, tab, H, W, OH, OW, qw, fill, packed);
+  SG_LAUNCH_CHECK("augment_u8_kernel");
   return 0;
 }
 

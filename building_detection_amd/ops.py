@@ -930,6 +930,24 @@ class Engine:
               "sg_resize_linear_u8")
         return dst
 
+    def augment_u8(self, src, items, fill, out_hw=None):
+        """data_enhancement.py's per-tile variants (sg_augment_u8): uint8 sources [S,H,W,3] or [S,H,W] -> [N,OH,OW(,3)], output i
+        described by items[i] = (source, n, shift, flags) (flags: _lib.SG_AUG_*), `fill` where the shifted index leaves the
+        n x n resized source.  out_hw defaults to (H, W); more than SG_AUGMENT_MAX_ITEMS items take several launches."""
+        assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() in (3, 4)
+        s, h, w = src.shape[:3]
+        c = src.shape[3] if src.dim() == 4 else 1
+        oh, ow = (h, w) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        items = [tuple(int(v) for v in it) for it in items]
+        dst = torch.empty((len(items), oh, ow) + tuple(src.shape[3:]), dtype=torch.uint8, device=self.device)
+        cap = _lib.SG_AUGMENT_MAX_ITEMS
+        for i0 in range(0, len(items), cap):
+            chunk = items[i0:i0 + cap]
+            table = (_lib.AugmentItem * len(chunk))(*[_lib.AugmentItem(*it) for it in chunk])
+            check(self.lib.sg_augment_u8(self.h, self.stream, s, h, w, c, _ptr(src), len(chunk), table, oh, ow, int(fill),
+                                         _ptr(dst[i0:i0 + len(chunk)])), "sg_augment_u8")
+        return dst
+
     def scale(self, t, a):
         check(self.lib.sg_scale_f32(self.h, self.stream, _ptr(t), t.numel(), float(a)), "sg_scale_f32")
         return t

@@ -493,6 +493,28 @@ int sg_edge_labels(sg_ctx* ctx, void* stream, int N, int H, int W, int iteration
  * INTER_AREA, as resize() substitutes it).  Bit-exact against oracle/input_pipeline.py:resize_linear_u8. */
 int sg_resize_linear_u8(sg_ctx* ctx, void* stream, int N, int H, int W, int C, const void* src_u8, int OH, int OW,
                         void* dst_u8);
+/* The per-tile variants of data_enhancement.py:62-135 (Data_Enhance.run / random_scale_resize / label_) in one launch:
+ * src_u8[S,H,W,C] -> dst_u8[N,OH,OW,C], output tile i described by items[i].  Output pixel (oy, ox) is taken from canvas
+ * pixel (cy, cx) = (flip_ud ? OH-1-oy : oy, flip_lr ? OW-1-ox : ox) (the flips follow the pad / crop, as there); the canvas
+ * pixel is the pixel (cy + shift, cx + shift) of source `src` resized to n x n with cv.resize's INTER_LINEAR (the
+ * arithmetic of sg_resize_linear_u8, an exact 2x downscale included; n = H = W is the identity), or `fill` where that
+ * index is outside [0, n).  shift = -pad for a centred pad (s < 1), +crop for a crop (s >= 1).  SG_AUG_THRESHOLD maps a
+ * resized value v to v > 125 ? 255 : 0 (label_, :133-135; the fill is not thresholded); SG_AUG_SWAP_RB reads source
+ * channel 2 - c for channel c (C = 3 only: cvtColor(BGR2RGB), :98).  C is 1 or 3, N at most SG_AUGMENT_MAX_ITEMS, fill
+ * in [0, 255]; every item is checked on the host before the launch (SG_EINVAL otherwise). */
+#define SG_AUGMENT_MAX_ITEMS 64
+#define SG_AUG_FLIP_UD   1
+#define SG_AUG_FLIP_LR   2
+#define SG_AUG_SWAP_RB   4
+#define SG_AUG_THRESHOLD 8
+typedef struct sg_augment_item {
+  int32_t src;    /* source tile, 0 <= src < S */
+  int32_t n;      /* resized size n x n, n >= 1 */
+  int32_t shift;  /* resized index = canvas index + shift */
+  int32_t flags;  /* SG_AUG_* */
+} sg_augment_item;
+int sg_augment_u8(sg_ctx* ctx, void* stream, int S, int H, int W, int C, const void* src_u8, int N,
+                  const sg_augment_item* items, int OH, int OW, int fill, void* dst_u8);
 
 /* ------------------------------------------------------------------------------------ inference tail
  * predict.py:110-114: mask = argmax(p) (ties -> 0) added as int8 into the canvas window at (y0,x0) of a

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import _fit_check as FC
 from oracle import models as M
 
 pytestmark = pytest.mark.gpu
@@ -103,42 +104,15 @@ def test_train_step_parity(engine, name, size, kw):
 
     P32, p32, loss32, g32 = oracle_train(name, ws0, x, y, kw, torch.float32)
     _, _, loss64, g64 = oracle_train(name, ws0, x, y, kw, torch.float64)
-    assert len(g64) == len(grads_g)
     assert abs(logs["loss"] - loss64) <= 5 * abs(loss32 - loss64) + 1e-5 * abs(loss64), (logs["loss"], loss32, loss64)
     cm = M.metrics_from_counts(*M.confusion(torch.from_numpy(y), p32))
     for k in ("PA", "IoU", "MIoU", "F1_score"):
         assert abs(logs[k] - cm[k]) <= 2e-3, (k, logs[k], cm[k])  # a near-tie pixel may flip a count
 
-    # Whole-model gradients.  A ReLU whose pre-activation lies within fp32 rounding of zero takes a different
-    # branch in two correct implementations (and in fp32 vs fp64); one such flip near the output moves every
-    # upstream gradient by O(1e-3..1e-2) of its scale (signature: BN dbeta off, dgamma exact, since x_hat ~ 0
-    # there).  So whole-model fp32 gradients are held to L2 bounds that catch real bugs (a missing or mis-scaled
-    # term is O(1)), while exactness is carried by the per-op tests (2e-5) and test_backward_chain_exact below.
+    # Whole-model gradients: L2 bounds against the fp64 oracle, judged by the fp32 oracle's own distance from it (the block is
+    # shared with the per-step check of the fit loop: tests/_fit_check.py:compare_gradients explains the bounds).
     names = [p.name for p in model.params if p.trainable]
-    num = den = num_c = 0.0
-    per = []
-    for nm, gg, gc, gt in zip(names, grads_g, g32, g64):
-        n2 = float(np.square(gt).sum())
-        e2, c2 = float(np.square(gg - gt).sum()), float(np.square(gc - gt).sum())
-        num, den, num_c = num + e2, den + n2, num_c + c2
-        per.append((nm, n2, e2, c2))
-    worst = (0.0, None, 0.0, 0.0, 0.0)
-    for nm, n2, e2, c2 in per:
-        # skip structurally-zero gradients (conv bias feeding BatchNorm) and tensors that carry under a millionth
-        # of the gradient energy (a gate bias on a 2-sample batch: its relative error is flip noise by itself)
-        if n2 > 1e-6 * den:
-            r, rc = (e2 / n2) ** 0.5, (c2 / n2) ** 0.5
-            # a tensor is judged against the fp32 CPU oracle's own distance from fp64 on that tensor: where the
-            # oracle itself is several per cent off (a flip right at that layer) the GPU may be, too
-            excess = r / max(0.1, 4.0 * rc)
-            if excess > worst[0]:
-                worst = (excess, nm, r, rc, n2 / den)
-    g_rel, c_rel = (num / den) ** 0.5, (num_c / den) ** 0.5
-    print(f"{name}: global rel-L2 grad error gpu {g_rel:.2e} (cpu-fp32 oracle {c_rel:.2e}); worst tensor {worst[1]}: "
-          f"gpu {worst[2]:.2e}, cpu-fp32 oracle {worst[3]:.2e}, share of gradient energy {worst[4]:.1e}")
-    # ... and the whole gradient against the fp32 CPU oracle's own distance from fp64 (Res34: 1.6e-2 by itself)
-    assert g_rel <= max(2e-2, 2.5 * c_rel), f"{name}: global gradient error {g_rel:.3e} (fp32 oracle {c_rel:.3e})"
-    assert worst[0] <= 1.0, f"{name}: gradient of {worst[1]} off by {worst[2]:.3e} (relative L2; fp32 oracle {worst[3]:.3e})"
+    FC.compare_gradients(name, names, grads_g, g32, g64)
 
     # BN moving statistics after the training forward
     for i, p in enumerate(model.params):
@@ -268,9 +242,11 @@ def test_golden_fixture(engine, name, fn, size, kw):
 def test_fit_generator_tracks_the_oracle_over_several_steps(engine):
     """The training LOOP as the reference drives it (fit_generator + WarmUpCosineDecayScheduler, DeepLabv3plus.py:
     705-849): four steps on HRNet 32x32 through the engine, the same four steps on the CPU oracle (fp64 forward/backward,
-    Keras-Adam, the same per-step learning rates, BN moving statistics carried along).  State that leaks or goes stale
-    between steps (Adam moments, step counter, BN statistics handed from a conv epilogue to the wrong layer, the LR
-    variable) shows up as a diverging loss; Adam's first steps are sign-like, so weights are compared in aggregate."""
+    Keras-Adam, the same per-step learning rates, BN moving statistics carried along), free-running: the drift of the loss is
+    held to a multiple of the fp32 oracle's own, the weights are compared in aggregate (Adam's first steps are sign-like).
+    State that leaks or goes stale between steps (Adam moments, step counter, BN statistics handed from a conv epilogue to the
+    wrong layer, the LR variable) is caught step by step, far more tightly, by
+    test_fit_loop_every_step_from_the_engines_own_state."""
     from building_detection_amd import zoo
     from building_detection_amd.callbacks import Callback, WarmUpCosineDecayScheduler
     from building_detection_amd.data import synthetic_batch
@@ -297,44 +273,41 @@ def test_fit_generator_tracks_the_oracle_over_several_steps(engine):
     assert abs(hist.history["loss"][0] - float(np.mean(losses_gpu))) < 1e-6   # epoch log = mean of the batch values
 
     # the oracle's four steps, in fp64 (the yardstick) AND in fp32 (what a correct fp32 implementation does)
-    def oracle_run(dtype):
-        P = M.Params(weights=ws0, dtype=dtype)
-        tr = m = v = None
-        losses = []
-        for s, (x, y) in enumerate(batches):
-            p = M.hrnet(P, torch.from_numpy(x).to(dtype), training=True)
-            loss = M.loss_fn("edge_focal_loss", torch.from_numpy(y).to(dtype), p)
-            tr = P.trainable_tensors()
-            for t in tr:
-                t.grad = None
-            loss.backward()
-            losses.append(loss.item())
-            if m is None:
-                m, v = [torch.zeros_like(t) for t in tr], [torch.zeros_like(t) for t in tr]
-            lr = M.cosine_decay_with_warmup(s, 1e-3, 40, warmup_learning_rate=1e-5, warmup_steps=2)
-            M.adam_step(tr, [t.grad for t in tr], m, v, s + 1, lr)
-        return losses, [t.detach().double().numpy() for t in tr]
-
-    l64, w64 = oracle_run(torch.float64)
-    l32, w32 = oracle_run(torch.float32)
+    l64, w64 = FC.oracle_run(ws0, batches, torch.float64)
+    l32, w32 = FC.oracle_run(ws0, batches, torch.float32)
+    # ... and in fp32 under K_ENV other orders of summation (every convolution's input channels permuted): the envelope of what
+    # correct fp32 implementations do, printed beside the engine's numbers; it decides nothing here (see below)
+    K_ENV = 8
+    env, runs = FC.loss_envelope(ws0, batches, l64, k=K_ENV)
     print("loss per step gpu", [f"{a:.6f}" for a in losses_gpu], "cpu fp32", [f"{a:.6f}" for a in l32], "cpu fp64",
           [f"{a:.6f}" for a in l64])
-    # Step 0 sees identical weights.  Afterwards Adam's first updates are sign-like (m / sqrt(v) = +-1 whatever the
-    # gradient's size), which turns fp32 rounding of small gradients into O(lr) weight differences: the fp32 CPU oracle
-    # itself leaves the fp64 trajectory by 3e-5 / 3.5e-3 / 1.5e-2 at steps 1 / 2 / 3 (measured here, printed above).
-    # The engine is held to that yardstick: its distance from fp64 may not exceed K times the fp32 oracle's own.
-    # The yardstick has a floor from step 1 on: whether ONE ReLU of this tiny net (BatchNorm over 8 ... 512 samples) flips is
-    # luck - the one-step gradient of two correct fp32 evaluations is 2e-4 ... 3e-2 from fp64 depending on the tiles
-    # (scripts/diag_mf16.py, round 3: five seeds, two MFMA shapes, neither systematically better) - and a flip moves the next
-    # loss by up to ~1e-3 of its value; the fp32 oracle's own 3e-5 at step 1 is the lucky end of that range.
-    # The floor grows with the step, a factor 4 per step as the trajectories themselves do (the fp32 oracle leaves fp64 by
-    # 3e-5 / 3.5e-3 / 1.5e-2): round 5, two builds that differ ONLY in the summation order of two layers (256 -> 32 and 128 -> 64
-    # at 3x3: im2col slab vs 64-channel chunks of the patch kernel, both within 1e-6 of the oracle per op and both green in the
-    # one-step gradient test on this model) end step 3 at 0.26947 and 0.28297 - fp64 0.26567, fp32 oracle 0.27052
-    # (gpurun_out/r5D/fit.txt).  What this test is for - a stale learning rate, a step counter, moving statistics on the wrong layer -
-    # moves the loss by tens of per cent from step 1 on; the exact loop is held to 1e-5 on a flip-free block in
+    for r in runs:
+        print("  fp32 oracle, input channels of every convolution permuted:", [f"{a:.6f}" for a in r])
+    # Step 0 sees identical weights.  Afterwards the FREE-RUNNING loss of this tiny net (BatchNorm over 8 ... 512 samples) says
+    # little: Adam's first updates are sign-like (m / sqrt(v) = +-1 whatever the gradient's size), so fp32 rounding of small
+    # gradients and single ReLU flips become O(lr) weight differences that the next steps amplify.  Measured on the oracle alone
+    # (scripts/fit_envelope_cpu.py, LAB_NOTEBOOK 14, table a): eight fp32 runs that differ only in the order in which every
+    # convolution sums its input channels leave the fp64 loss by at most 1e-5 at step 0, by 4e-6 ... 6e-4 at step 1, 2e-4 ... 2e-2
+    # at step 2 and 7e-4 ... 1.1e-1 at step 3: a factor 40 to 100 between the luckiest and the unluckiest order.  No bound on
+    # these numbers can see a state bug of a few per cent.  Table b of the same section shows that ONE step from a common state
+    # stays within 6e-6 of the loss at every step, and THAT is where the loop's state is checked:
+    # test_fit_loop_every_step_from_the_engines_own_state below (a stale Adam moment, a step counter, a late learning rate,
+    # moving statistics on the wrong layer), and at 1e-5 on a flip-free block in
     # test_block_chains_gpu.py::test_fit_loop_on_a_flip_free_block_tracks_fp64_at_1e_5.
+    # This test only bounds the DRIFT: K times the plain fp32 oracle's own distance from fp64, plus a floor that grows by a factor
+    # 4 per step as the trajectories themselves do (hand-fitted in round 5: two builds that differ ONLY in the summation order
+    # of two layers, im2col slab vs 64-channel chunks of the patch kernel, end step 3 at 0.26947 and 0.28297; fp64 0.26567).
+    # A measured bound - 1.5 times the farthest of the plain and the K_ENV perturbed fp32 runs, capped by this expression - was
+    # tried in its place and is NOT asserted: the engine's step 3 (6.5e-2 of the loss) lies above it (4.4e-2 with 8 runs,
+    # 6.2e-2 with 16) although steps 1 and 2 lie inside the envelope and every single step is green from the engine's own
+    # state.  Of 64 such runs from these weights one lies farther out than the engine (6.9e-2), and 1.5 times the first eight's
+    # maximum is passed by other runs of the same population, too: the rule under-samples a heavy tail (LAB_NOTEBOOK 14.3,
+    # open finding).
     K = 3.0
+    for i, (a, c, b) in enumerate(zip(losses_gpu, l32, l64)):
+        floor = 1e-5 if i == 0 else 2e-3 * 4 ** (i - 1)
+        print(f"step {i}: |gpu - fp64| / fp64 = {abs(a - b) / abs(b):.2e}; fp32 oracle {abs(c - b) / abs(b):.2e}, envelope of "
+              f"{K_ENV} perturbed runs {env[i] / abs(b):.2e}; bound {(K * abs(c - b) + floor * abs(b)) / abs(b):.2e}")
     for i, (a, c, b) in enumerate(zip(losses_gpu, l32, l64)):
         floor = 1e-5 if i == 0 else 2e-3 * 4 ** (i - 1)
         assert abs(a - b) <= K * abs(c - b) + floor * abs(b), f"step {i}: gpu {a} cpu-fp32 {c} fp64 {b}"
@@ -345,6 +318,47 @@ def test_fit_generator_tracks_the_oracle_over_several_steps(engine):
     r_cpu = (sum(float(np.square(a - t).sum()) for a, t in zip(w32, w64)) / den) ** 0.5
     print(f"weights after {steps} steps, |w - w_fp64| / |w_fp64 - w_0|: gpu {r_gpu:.3f}, cpu fp32 oracle {r_cpu:.3f}")
     assert r_gpu <= 1.5 * r_cpu + 0.02   # the update itself is reproduced as well as an fp32 CPU run reproduces it
+
+
+@pytest.mark.parametrize("jit_compile", [False, True], ids=["eager", "captured"])
+@pytest.mark.parametrize("seed", [100, 200, 300])
+def test_fit_loop_every_step_from_the_engines_own_state(engine, seed, jit_compile):
+    """Six steps of fit_generator + WarmUpCosineDecayScheduler + Adam on HRNet 32 x 32, every step judged from the complete state
+    the ENGINE started it in (tests/_fit_check.py): the loss, the gradients and the moving statistics against the oracle's
+    one step from that state at the bounds of test_train_step_parity; Adam's moments and weights against Keras-2 Adam in fp64
+    applied to the step's own gradients, with the step number and the learning rate computed here (bounds of test_adam and of
+    test_train_step_parity); the step counter and the rate the model reports; and bit-for-bit equality of the state between two
+    steps.  With jit_compile the first two steps are eager and steps 2 - 5 replay the captured graphs, whose Adam reads its
+    rate from device memory (sg_adam_step_lr).  tests/test_fit_check_cpu.py shows that a planted error fails each check."""
+    from building_detection_amd import zoo
+    from building_detection_amd.callbacks import WarmUpCosineDecayScheduler
+    from building_detection_amd.data import synthetic_batch
+    from building_detection_amd.losses import edge_focal_loss, PA, IoU, MIoU, F1_score
+    size, steps = 32, 6
+    model = zoo.BUILDERS["hrnet"]((size, size, 3))
+    batches = [synthetic_batch(2, size, size, seed=seed + i) for i in range(steps)]
+    model.compile(optimizer="adam", loss=edge_focal_loss, metrics=[PA, IoU, MIoU, F1_score], jit_compile=jit_compile)
+    sched = WarmUpCosineDecayScheduler(**FC.SCHEDULE)
+    rec = FC.recorder(model)   # after the scheduler: it sees the rate set for the step
+    feed = iter(batches)
+    model.fit_generator(feed, steps_per_epoch=steps, epochs=1, verbose=0, callbacks=[sched, rec])
+    assert len(rec.steps) == steps
+    if jit_compile:
+        assert len(model._train_graphs) == 1, "steps 2 - 5 were meant to replay a captured graph"
+    # the recorder cuts the parameters out of the flat arenas (one device read each): the same arrays get_weights() returns
+    for a, b in zip(FC.engine_state(model).weights, model.get_weights()):
+        assert np.array_equal(a, b)
+    assert rec.steps[0].pre.iterations == 0 and not any(m.any() for m in rec.steps[0].pre.m + rec.steps[0].pre.v)
+    assert not any(a.any() for a in rec.steps[0].pre.pad.values())
+    names = [p.name for p in model.params]
+    trainable = [p.trainable for p in model.params]
+    figures = FC.check_trajectory(rec.steps, batches, names, trainable)
+    print(f"seed {seed} {'captured' if jit_compile else 'eager'}: worst over {steps} steps: |loss - fp64| / fp64 "
+          f"{max(f['loss_rel'] for f in figures):.2e} (fp32 oracle {max(f['loss32_rel'] for f in figures):.2e}), gradient rel-L2 "
+          f"{max(f['g_rel'] for f in figures):.2e} (fp32 oracle {max(f['c_rel'] for f in figures):.2e}), gradient excess "
+          f"{max(f['excess'] for f in figures):.2f}, moving statistics {max(f['stat_dev'] for f in figures):.2e}, Adam m "
+          f"{max(f['m_rel'] for f in figures):.2e} v {max(f['v_rel'] for f in figures):.2e}, |w' - w_gpu| "
+          f"{max(f['w_abs'] for f in figures):.2e}")
 
 
 def _chain2_reference(seed):

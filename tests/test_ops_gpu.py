@@ -722,6 +722,43 @@ def test_adam(engine):
     close(wd, w2, what="adam w")
 
 
+DENSE_CASES = [
+    # rows, in, out: BAM's channel gate (rows = batch, C -> C / 16 and back; 728 / 16 = 45), res34's attention pair, ragged sizes,
+    # a single row, an output thin enough (<= 4 columns) for the streaming kernels of the 1x1 convolution
+    (2, 256, 16), (2, 16, 256), (2, 728, 45), (2, 45, 728), (4, 512, 32), (4, 32, 512), (3, 45, 7), (1, 45, 7), (1, 512, 32),
+    (1, 64, 4), (5, 33, 2),
+]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("case", DENSE_CASES, ids=["x".join(map(str, c)) for c in DENSE_CASES])
+def test_dense_fwd(engine, case, dtype):
+    """sg_dense_fwd through the library itself (no model calls it: the zoo lowers Dense to a 1x1 convolution with a workspace,
+    this entry point takes the launch without one): y = x @ w (+ bias) (ReLU) against oracle.tfops.dense in fp64.  bf16
+    storage: x and y are bf16, weights and bias fp32; the reference starts from the same rounded x."""
+    import ctypes as C
+    from building_detection_amd import _lib
+    rows, cin, cout = case
+    g = torch.Generator().manual_seed(zlib.crc32(f"dense{rows}x{cin}x{cout}".encode()) % (2 ** 31))
+    x = rnd(g, rows, cin).to(dtype)
+    w = rnd(g, cin, cout) * (1.0 / np.sqrt(cin))
+    b = rnd(g, cout)
+    xd, wd, bd = x.cuda(), w.cuda(), b.cuda()
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    dt = _lib.SG_BF16 if dtype == torch.bfloat16 else _lib.SG_F32
+    tol = RTOL if dtype == torch.float32 else 2 ** -7
+    for bias in (False, True):
+        for relu in (False, True):
+            y = torch.full((rows + 1, cout), float("nan"), device="cuda").to(dtype)   # a guard row behind the output
+            flags = (_lib.SG_EPI_BIAS if bias else 0) | (_lib.SG_EPI_RELU if relu else 0)
+            _lib.check(engine.lib.sg_dense_fwd(engine.h, engine.stream, dt, rows, cin, cout, ptr(xd), ptr(wd),
+                                               ptr(bd) if bias else None, ptr(y), flags), "sg_dense_fwd")
+            want = T.dense(x.double(), w.double(), b.double() if bias else None)
+            want = torch.relu(want) if relu else want
+            close(y[:rows].float(), want, rtol=tol, what=f"dense {case} bias={bias} relu={relu}")
+            assert torch.isnan(y[rows].float()).all(), f"dense {case}: wrote behind its output"
+
+
 def test_edge_labels_match_generator(engine):
     """sg_edge_labels (separable row / column min-max through LDS) vs the ORACLE's restatement of train_data_gen's label
     channels (oracle/input_pipeline.py:label_channels, DeepLabv3plus.py:70-100): bit-exact, on rectangles touching every

@@ -16,7 +16,7 @@
 //   * M x N = 16384 x 256 is only 64 such tiles: the K walk is then CUT into S shares (split-K; grid = tiles x S), every share
 //     writes its fp32 partial tile, and b16w_reduce_kernel adds the S partials in order, applies bias / ReLU, rounds to bf16
 //     and - where the consumer is a training-mode BatchNormalization - produces the per-128-row-tile statistics the other
-//     kernels' epilogues produce.  S depends on ONE image's geometry only (b16w_plan), never on the batch: the rounding order
+//     kernels' epilogues produce.  S depends on ONE image's geometry only (b16w_shares), never on the batch: the rounding order
 //     of a pixel does not depend on its batch neighbours (bit-exact batch-slice invariance, tests/test_fullsize_gpu.py).
 // Padding-tap elimination, channel-block K order and the plane layout [K / 64][Npad][64] are conv_b16_kernel's (KS = 4).
 // Requires: stride-1 gather (div == 1, no parity-class rows), every 64-deep stage inside one tap (C % 64 == 0).
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(512, 2) void conv_b16w_kernel(const IgemmParams p, 
   };
 
   // ---- the K walk of this tile: active taps (padding-tap elimination), channel-block order, this share's range -----------------
-  // As in conv_x6w_kernel: the active taps are a 64-bit mask in SGPRs (b16w_plan: at most 64 taps), the position of the walk is
+  // As in conv_x6w_kernel: the active taps are a 64-bit mask in SGPRs (b16w_shares: at most 64 taps), the position of the walk is
   // (channel block, tap, slab in the block) and advances with scalar selects - no LDS table, no division, no branch per stage.
   const int ntaps = p.K / p.C;
   const int spt = p.C / BW_KD;          // stages per tap
@@ -420,11 +420,12 @@ __global__ __launch_bounds__(256) void b16w_reduce_kernel(const float* __restric
 // Which launches take the 256-wide kernel, and in how many K shares - from ONE image's geometry, the layer's channels and
 // the filter only (see the header).  A launch must bring >= 16 workgroups per image (256 at the benchmark's batch of 16);
 // fewer tiles are made up by split-K (<= 4 shares of >= 2048 reduction steps each).  SG_B16_WIDE=0 switches the kernel off.
-inline int b16w_plan(const IgemmParams& p) {
+// Geometry fields only (plan_conv, the one caller); a launch that adds a collected gradient takes conv_b16_kernel on the same planes.
+inline int b16w_shares(const IgemmParams& p) {
   static const int on = getenv("SG_B16_WIDE") ? atoi(getenv("SG_B16_WIDE")) : 1;
   if (!on) return 0;
-  if (p.div != 1 || p.perm2 || p.res || p.C % BW_KD != 0 || p.K < 1024 || p.K / p.C > 64) return 0;
-  if ((p.x_ld % 8) != 0 || (reinterpret_cast<uintptr_t>(p.x) & 15) != 0 || p.x_bytes == 0) return 0;
+  if (p.div != 1 || p.C % BW_KD != 0 || p.K < 1024 || p.K / p.C > 64) return 0;   // (div 1: never parity-class rows)
+  if ((p.x_ld % 8) != 0 || p.x_bytes == 0) return 0;
   if (p.Nout % 4 != 0) return 0;
   const int64_t ntn = sg_cdiv(p.Nout, BW_N);
   if ((double)p.Nout / (double)(ntn * BW_N) < 0.75) return 0;
@@ -437,8 +438,6 @@ inline int b16w_plan(const IgemmParams& p) {
   while (S > 1 && p.K / S < 2048) --S;
   return (S > 1 && img_wgs * S >= 16) ? S : 0;
 }
-
-inline size_t b16w_scratch_bytes(int S, int64_t M, int N) { return S > 1 ? (size_t)S * (size_t)M * (size_t)N * sizeof(float) : 0; }
 
 inline int launch_b16w(const IgemmParams& p, int S, float* scratch, hipStream_t st) {
   static const int var = getenv("SG_B16W_VAR") ? atoi(getenv("SG_B16W_VAR")) : 0;

@@ -116,9 +116,6 @@ struct IgemmParams {
   const unsigned short* a_planes;
   BnIn bn;   // conv_x6p_kernel only: the BatchNormalization applied in the patch loader (mean == nullptr: none)
   BnBwdIn bnb;   // pw_wide_kernel<.., BNB> only (x == nullptr: none)
-  // host side only: bytes of workspace that start at the weight planes (the planes, then scratch of a split-K launch:
-  // conv_b16w.h); SIZE_MAX = prepared planes, whose arena slot sg_conv2d_planes_job sized for both
-  size_t ws_room;
 };
 
 __device__ __forceinline__ int spt_of(const IgemmParams& p) { return p.C / BK; }  // slabs per tap (UT)
@@ -1175,9 +1172,6 @@ void plan_common(IgemmParams& p, bool vec, int bn, bool x6 = false, int eb = 4) 
   p.cb = ((conv_l2(x6) & 2) && ut && ntaps > 1 && spt > cbv && spt % cbv == 0 && img_bytes > (2ll << 20)) ? cbv : 0;
 }
 
-// set while a launch beyond 2 GiB runs as sub-batches of whole images (sg_conv2d_fwd_ws / sg_conv2d_dgrad recursion)
-thread_local bool g_sub_batch = false;
-
 #include "conv_x6.h"
 #include "conv_x6p.h"
 #include "conv_b16.h"
@@ -1189,12 +1183,7 @@ thread_local bool g_sub_batch = false;
 template <int NPL, typename TA>
 int dispatch_x6(const IgemmParams& p_in, int num_cus, hipStream_t st) {
   IgemmParams p = p_in;
-  int bn = pick_bn(p.M, p.Nout, num_cus);
-  {
-    // experiment switch: 128-wide tiles that give at most one tile per CU are halved (two workgroups per CU)
-    static const bool bn64 = getenv("SG_X6_BN64") != nullptr;
-    if (bn64 && bn == 128 && sg_cdiv(p.M, BM) * sg_cdiv(p.Nout, 128) <= (int64_t)num_cus) bn = 64;
-  }
+  const int bn = pick_bn(p.M, p.Nout, num_cus);
   plan_common(p, true, bn, true, EL<TA>::BYTES);
   {
     static int il = -1;  // SG_X6_INTERLEAVE=0: staggered halves instead of the hand-interleaved step (A/B switch)
@@ -1252,135 +1241,143 @@ int dispatch_x6(const IgemmParams& p_in, int num_cus, hipStream_t st) {
   }
 }
 
-// split the weights into the x6 planes (in `ws`) and run the x6 kernel
+// ---- who chooses the kernel --------------------------------------------------------------------------------------------
+// plan_conv() decides which kernel family a forward convolution or an input gradient takes and how its weight planes and the
+// scratch behind them are laid out - from the descriptor, the storage type, the arithmetic mode and the experiment switches, and
+// from nothing else: no pointers, no `res`.  The workspace queries, the `_supported` queries, sg_conv2d_planes_job and the launch
+// all read this one plan (the filter gradient's counterpart is plan_wgrad), so they cannot disagree.  What the descriptor does
+// not say - the alignment of the operands, the workspace a launch was handed - is checked once, at the launch, against the plan.
+enum ConvFamily {   // (from CONV_SLAB on: the kernels that read prepared weight planes, sg_planes_job.kind 1 / 2 / 3)
+  CONV_NATIVE,   // the fp32-MFMA kernels: any shape, any alignment
+  CONV_THIN,     // 1x1 with at most 4 output channels: the streaming kernels
+  CONV_HEAD,     // the softmax head of a bf16 model that is not thin: the native kernel on mixed storage types
+  CONV_SLAB,     // conv_x6 / conv_b16 and, on the same planes, their wide forms conv_x6w (planes-in) / conv_b16w
+  CONV_PATCH,    // conv_x6p
+  CONV_WIDE      // conv_pw
+};
+constexpr int PLAN_NOT_THIN = 1 << 30;   // plan_conv `flags` (no SG_EPI_* / SG_PRO_* bit): the operands of a thin launch missed its alignment
+
+struct ConvPlan {
+  ConvFamily family = CONV_NATIVE;
+  int nb = 0;         // images per launch: >= N the whole batch; fewer: sub-batches of whole images (2 GiB buffer descriptors),
+                      // none of which takes the wide pointwise kernel; 0: one image alone passes the limit (native, whole batch)
+  bool vec = false;   // 16-byte channel runs as far as the descriptor says (the launch adds the pointers' alignment)
+  int perm2 = 0;      // stride-2 dgrad: rows in parity-class order (IgemmParams::perm2; the slab kernels)
+  // the weight planes (family >= CONV_SLAB): sg_planes_job's fields; Ckp = the tap depth after virtual channel padding
+  int npl = 0, Ck = 0, Ckp = 0, K = 0, kd = 0, Kpad = 0, Npad = 0, nblocks = 0;
+  int wbn = 0;        // CONV_WIDE: tile width, 384 or 256
+  size_t w_bytes = 0;
+  // CONV_SLAB: K shares of the planes-in kernel / of the 256-wide bf16 kernel (0: conv_x6_kernel / conv_b16_kernel); deep bf16 slabs
+  int x6w_S = 0, b16w_S = 0;
+  bool deep = false;
+  size_t a_img_bytes = 0, part_img_bytes = 0;   // scratch behind the planes per image: activation planes, split-K partial slabs
+  // what the family can do
+  bool res = false;        // add a collected gradient (sg_conv2d_dgrad_acc).  Of the plane kernels only the slab family: a launch
+                           // with `res` whose plan names a wide slab form takes conv_x6_kernel / conv_b16_kernel on the same planes
+  bool bn_in = false;      // apply a BatchNormalization in its loader (thin; patch with 32 / 64 reduction channels per tap)
+  bool up2 = false;        // the fused up-sampling forms exist for this layer (SG_PRO_UP2; with CONV_PATCH: SG_EPI_DOWN2)
+  bool bnb = false;        // evaluate the BatchNormalization backward in its A path (wide pointwise dgrad)
+  bool planes_in = false;  // read the activation as bf16 planes the caller made (sg_split_planes)
+
+  // scratch behind the weight planes of a launch of `images` images
+  size_t scratch_bytes(int images) const {
+    return (((size_t)images * a_img_bytes + 255) & ~(size_t)255) + (size_t)images * part_img_bytes;
+  }
+  // the weight planes and that scratch
+  size_t ws_bytes(int images) const {
+    const size_t sc = scratch_bytes(images);
+    return sc ? ((w_bytes + 255) & ~(size_t)255) + sc : w_bytes;
+  }
+};
+
+// Run a launch of the plan's family (>= CONV_SLAB) on its weight planes in `ws`; the scratch of a wide slab form lies behind them.
+// prepared: `ws` already holds the planes (sg_prepare_planes, once per optimiser step), no split here.
 // NPL = 3: the exact fp32 emulation; NPL = 1: bf16 products (TA = float: fp32 storage rounded on the way into LDS,
-// TA = bf16_t: SG_BF16 storage).  p.C is the depth of one tap of the reduction (Cin forward, Cout dgrad).
+// TA = bf16_t: SG_BF16 storage).
 template <int NPL, typename TA>
-int run_x6(IgemmParams& p, const float* w, bool dgrad, int Cin, int Cout, int KH, int KW, void* ws, int num_cus,
-           hipStream_t st, bool prepared = false) {
-  // prepared: `ws` already holds this launch's weight planes (sg_prepare_planes, once per optimiser step), no split here
-  if (p.res) {  // only the slab kernels below add a collected gradient (callers ask sg_conv2d_planes_job: kind 1)
-    bool patch = false, wide = false;
-    if constexpr (NPL == 3) patch = x6p_ok(p, KH, KW);
-    if constexpr ((NPL == 3 && std::is_same<TA, float>::value) || (NPL == 1 && !std::is_same<TA, float>::value))
-      wide = pw_wide_ok(p, EL<TA>::BYTES);
-    if (patch || wide) {
-      IgemmParams q = p;
-      q.res = nullptr;
-      sg_set_error("sg_conv2d_dgrad_acc: this launch takes the %s kernel, which does not add a collected gradient "
-                   "(reduction channels per tap %d, K %d, output columns %d, %d x %d outputs per image; planes-in plan without res: %d)",
-                   patch ? "patch" : "wide pointwise", p.C, p.K, p.Nout, p.OH, p.OW, x6w_plan(q));
-      return SG_EUNSUPPORTED;
-    }
-  }
-  if constexpr (NPL == 3) {
-    if (x6p_ok(p, KH, KW)) return run_x6p(p, w, dgrad, Cin, Cout, ws, num_cus, st, prepared);
-  }
-  // 1x1 / stride 1 with enough columns for 384-wide tiles (the 728-wide middle flow and the exit flow): conv_pw.h, with its
-  // own k-block-major plane layout
-  if constexpr ((NPL == 3 && std::is_same<TA, float>::value) || (NPL == 1 && !std::is_same<TA, float>::value)) {
-    if (const int wbn = pw_wide_bn(p, EL<TA>::BYTES)) {
-      const int K = p.K, N = p.Nout;
-      p.Kpad = pw_kpad(K, NPL);
-      p.Npad = pw_npad(N, wbn);
+int run_x6(const ConvPlan& pl, IgemmParams& p, const float* w, bool dgrad, int Cin, int Cout, void* ws, int num_cus, hipStream_t st,
+           bool prepared) {
+  constexpr bool B16 = !std::is_same<TA, float>::value;
+  const int N = p.Nout;
+  switch (pl.family) {
+    case CONV_PATCH:
+      if constexpr (NPL == 3) return run_x6p(p, w, dgrad, Cin, Cout, ws, num_cus, st, prepared);
+      break;
+    case CONV_WIDE:
+      // 1x1 / stride 1 with enough columns for 384- or 256-wide tiles (the 728-wide middle flow and the exit flow)
+      if constexpr ((NPL == 3 && !B16) || (NPL == 1 && B16)) {
+        p.Kpad = pl.Kpad;
+        p.Npad = pl.Npad;
+        p.wq = (const unsigned short*)ws;
+        p.w_bytes = (uint32_t)pl.w_bytes;
+        if (!prepared) {
+          dim3 grid((unsigned)sg_cdiv(p.Kpad, 32), (unsigned)sg_cdiv(p.Npad, 32));
+          hipLaunchKernelGGL(split3_weights_kernel, grid, dim3(256), 0, st, w, (unsigned short*)ws, pl.K, N, p.Kpad, p.Npad, pl.K,
+                             Cin * Cout, dgrad ? 1 : Cout, dgrad ? Cout : 1, NPL, pl.K, pl.kd);
+          SG_LAUNCH_CHECK("split3_weights_kernel");
+        }
+        if constexpr (NPL == 3) {
+          if (p.bnb.x)   // the BatchNormalization backward in the A path (sg_conv2d_dgrad_bnb)
+            return pl.wbn == 256 ? launch_pw_wide<NPL, TA, 256, true>(p, st) : launch_pw_wide<NPL, TA, 384, true>(p, st);
+        }
+        return pl.wbn == 256 ? launch_pw_wide<NPL, TA, 256>(p, st) : launch_pw_wide<NPL, TA, 384>(p, st);
+      }
+      break;
+    case CONV_SLAB: {
+      const int Ck = p.C;
+      if (pl.Ckp != Ck) {   // virtual channel padding
+        p.K = pl.K;
+        p.C = pl.Ckp;
+        p.fd_c = make_fastdiv((uint32_t)pl.Ckp);
+      }
+      p.kd = pl.kd;
+      p.Kpad = pl.Kpad;
+      p.Npad = pl.Npad;
       p.wq = (const unsigned short*)ws;
-      p.w_bytes = (uint32_t)pw_planes_bytes(K, N, NPL, wbn);
+      p.w_bytes = (uint32_t)pl.w_bytes;
       if (!prepared) {
-        dim3 grid((unsigned)sg_cdiv(p.Kpad, 32), (unsigned)sg_cdiv(p.Npad, 32));
-        hipLaunchKernelGGL(split3_weights_kernel, grid, dim3(256), 0, st, w, (unsigned short*)ws, K, N, p.Kpad, p.Npad, K,
-                           Cin * Cout, dgrad ? 1 : Cout, dgrad ? Cout : 1, NPL, K, pw_kd(NPL));
+        dim3 grid((unsigned)(p.Kpad / 32), (unsigned)(p.Npad / 32));
+        hipLaunchKernelGGL(split3_weights_kernel, grid, dim3(256), 0, st, w, (unsigned short*)ws, pl.K, N, p.Kpad, p.Npad, Ck,
+                           Cin * Cout, dgrad ? 1 : Cout, dgrad ? Cout : 1, NPL, pl.Ckp, p.kd);
         SG_LAUNCH_CHECK("split3_weights_kernel");
       }
-      if constexpr (NPL == 3) {
-        if (p.bnb.x) {   // the BatchNormalization backward in the A path (sg_conv2d_dgrad_bnb)
-          if (wbn == 512) {
-            sg_set_error("pw_wide: no BatchNormalization-backward form of the 512-wide tile");
-            return SG_EUNSUPPORTED;
+      char* scratch = (char*)ws + ((pl.w_bytes + 255) & ~(size_t)255);
+      if constexpr (NPL == 3 && !B16) {
+        if (pl.x6w_S > 0 && !p.res) {   // scratch: the planes of A, then split-K partial slabs
+          IgemmParams q = p;
+          plan_common(q, true, 128, true, 4);
+          static const int abl = getenv("SG_X6W_ABLATE") ? atoi(getenv("SG_X6W_ABLATE")) : 0;
+          q.ablate = abl;
+          return launch_x6w(q, pl.x6w_S, scratch, st);
+        }
+      }
+      if constexpr (NPL == 1 && B16) {
+        if (pl.deep) {
+          if (pl.b16w_S > 0 && !p.res) {
+            IgemmParams q = p;
+            plan_common(q, true, 128, true, 2);
+            return launch_b16w(q, pl.b16w_S, pl.b16w_S > 1 ? reinterpret_cast<float*>(scratch) : nullptr, st);
           }
-          return wbn == 256 ? launch_pw_wide<NPL, TA, 256, true>(p, st) : launch_pw_wide<NPL, TA, 384, true>(p, st);
+          return dispatch_b16(p, num_cus, st);
         }
-        if (wbn == 512) return launch_pw_wide<NPL, TA, 512>(p, st);
       }
-      return wbn == 256 ? launch_pw_wide<NPL, TA, 256>(p, st) : launch_pw_wide<NPL, TA, 384>(p, st);
+      return dispatch_x6<NPL, TA>(p, num_cus, st);
     }
+    default:
+      break;
   }
-  if (p.bnb.x) {   // only the wide pointwise kernel above evaluates the BatchNormalization backward in its A path
-    sg_set_error("sg_conv2d_dgrad_bnb: this launch does not take the wide pointwise kernel");
-    return SG_EUNSUPPORTED;
-  }
-  const int Ck = p.C;
-  int Ckp = Ck;
-  if (Ck % BK != 0 && p.K != Ck) {  // virtual channel padding (x6_ok admitted the shape): whole slabs inside one tap
-    Ckp = x6_vpad_c(Ck);
-    p.K = (p.K / Ck) * Ckp;
-    p.C = Ckp;
-    p.fd_c = make_fastdiv((uint32_t)Ckp);
-  }
-  const int K = p.K, N = p.Nout;
-  p.kd = x6_plane_kd(NPL == 1 && !std::is_same<TA, float>::value, p.C, p.K == p.C);
-  p.Kpad = x6_kpad(K, p.kd);
-  p.Npad = x6_npad(N);
-  p.wq = (const unsigned short*)ws;
-  p.w_bytes = (uint32_t)x6_planes_bytes(K, N, NPL, p.kd);
-  if (!prepared) {
-    dim3 grid((unsigned)(p.Kpad / 32), (unsigned)(p.Npad / 32));
-    if (!dgrad)
-      hipLaunchKernelGGL(split3_weights_kernel, grid, dim3(256), 0, st, w, (unsigned short*)ws, K, N, p.Kpad, p.Npad, Ck,
-                         Cin * Cout, Cout, 1, NPL, Ckp, p.kd);
-    else
-      hipLaunchKernelGGL(split3_weights_kernel, grid, dim3(256), 0, st, w, (unsigned short*)ws, K, N, p.Kpad, p.Npad, Ck,
-                         Cin * Cout, 1, Cout, NPL, Ckp, p.kd);
-    SG_LAUNCH_CHECK("split3_weights_kernel");
-  }
-  if constexpr (NPL == 3 && std::is_same<TA, float>::value) {
-    // the dilated long-K convolutions: the activation split once into bf16 planes, then 128 x 256 tiles with both operands by
-    // LDS-DMA (conv_x6w.h); planes of A and split-K partial slabs lie behind the weight planes
-    const int S = p.kd == XW_KD ? x6w_plan(p) : 0;
-    if (S > 0) {
-      const size_t planes_end = ((size_t)p.w_bytes + 255) & ~(size_t)255;
-      const size_t need = planes_end + x6w_scratch_bytes(p, S);
-      if (p.ws_room != SIZE_MAX && p.ws_room < need) {
-        sg_set_error("conv_x6w: workspace %zu < %zu (weight planes + activation planes + %d partial slabs)", p.ws_room, need, S);
-        return SG_EWORKSPACE;
-      }
-      IgemmParams q = p;
-      plan_common(q, true, 128, true, 4);
-      {
-        static const int abl = getenv("SG_X6W_ABLATE") ? atoi(getenv("SG_X6W_ABLATE")) : 0;
-        q.ablate = abl;
-      }
-      return launch_x6w(q, S, (char*)ws + planes_end, st);
-    }
-  }
-  if constexpr (NPL == 1 && !std::is_same<TA, float>::value) {
-    static const bool deep = !(getenv("SG_B16_DEEP") && atoi(getenv("SG_B16_DEEP")) == 0);  // A/B switch
-    if (deep) {
-      // long reductions with 192+ output columns: 256 x 256 tiles, both operands by LDS-DMA, split-K where the tiles are few
-      // (conv_b16w.h); its scratch lies behind the planes
-      const int S = p.kd == BW_KD ? b16w_plan(p) : 0;
-      if (S > 0) {
-        const size_t planes_end = ((size_t)p.w_bytes + 255) & ~(size_t)255;
-        const size_t need = planes_end + b16w_scratch_bytes(S, p.M, p.Nout);
-        if (S > 1 && p.ws_room != SIZE_MAX && p.ws_room < need) {
-          sg_set_error("conv_b16w: workspace %zu < %zu (weight planes + %d split-K partial slabs)", p.ws_room, need, S);
-          return SG_EWORKSPACE;
-        }
-        IgemmParams q = p;
-        plan_common(q, true, 128, true, 2);
-        return launch_b16w(q, S, S > 1 ? reinterpret_cast<float*>((char*)ws + planes_end) : nullptr, st);
-      }
-      return dispatch_b16(p, num_cus, st);
-    }
-  }
-  return dispatch_x6<NPL, TA>(p, num_cus, st);
+  sg_set_error("run_x6: kernel family %d does not read weight planes in this arithmetic (%d planes)", (int)pl.family, NPL);
+  return SG_EINVAL;
 }
 
 // workspace of the weight planes for a launch with `taps` taps of depth C (virtual padding included), N columns
 inline size_t x6_ws_bytes(int taps, int C, int N) {
   const int k = taps > 1 ? taps * x6_vpad_c(C) : C;
   const size_t rows = x6_planes_bytes(k, N, 3, 64);   // (the deepest k-block any kernel asks for)
-  const size_t w384 = taps == 1 ? pw_planes_bytes(C, N, 3, 384) : 0, w256 = taps == 1 ? pw_planes_bytes(C, N, 3, 512) : 0;   // (512 >= 256)
-  const size_t wide = w384 > w256 ? w384 : w256;   // the wide pointwise kernel pads N to its tile width
+  // the wide pointwise kernel pads N to its tile width, 384 or 256.  The second term still pads to 512, the width of a tile form
+  // that is gone: it decides the value for e.g. 728 columns, and callers' workspaces keep the size they had
+  const size_t w384 = taps == 1 ? pw_planes_bytes(C, N, 3, 384) : 0, w512 = taps == 1 ? pw_planes_bytes(C, N, 3, 512) : 0;
+  const size_t wide = w384 > w512 ? w384 : w512;
   return rows > wide ? rows : wide;
 }
 
@@ -1888,7 +1885,6 @@ void fill_fwd_params(IgemmParams& p, const sg_conv_desc* d, const void* x, const
   p.a_planes = nullptr;
   p.bn.mean = nullptr;
   p.bnb.x = nullptr;
-  p.ws_room = 0;
 }
 
 void fill_dgrad_params(IgemmParams& p, const sg_conv_desc* d, const void* dy, const void* wt, const void* bias, void* dx,
@@ -1917,7 +1913,6 @@ void fill_dgrad_params(IgemmParams& p, const sg_conv_desc* d, const void* dy, co
   p.a_planes = nullptr;
   p.bn.mean = nullptr;
   p.bnb.x = nullptr;
-  p.ws_room = 0;
 }
 
 // any-shape fallback for bf16 storage: the native fp32-MFMA kernel with widening loads (TA) and a rounding store (TY).
@@ -1989,6 +1984,107 @@ int dispatch_wgrad_b16(const WgradParams& p_in, int S, bool vec8, bool vec4, hip
   return launch_wgrad_f<32, 4, 1, 1, false, 0, bf16_t>(p, S, st);
 }
 
+// ---- plan_conv(): fills the ConvPlan that every query and launch reads (the struct and run_x6: above, behind dispatch_x6) ----
+// `mode`: the arithmetic on fp32 storage (x6_mode(); the workspace queries, which know neither it nor the storage type, ask for 1)
+ConvPlan plan_conv_mode(int mode, int dtype, const sg_conv_desc* d, bool dgrad, int flags) {
+  ConvPlan pl;
+  const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0;
+  const bool f32 = dt_storage(dtype) == SG_F32 && !head32;
+  const int eb = dt_bytes(dtype);
+  const bool x_dense = !d->x_ld || d->x_ld == d->Cin, y_dense = !d->y_ld || d->y_ld == d->Cout;
+  pl.up2 = f32 && mode == 1 && x6p_up2_geom(d) && x6wp_geom(d);   // (forward and filter gradient both take the patch kernels)
+  const bool thin = thin_ok(d) && !(flags & PLAN_NOT_THIN) && !(dgrad && (flags & (SG_EPI_BIAS | SG_EPI_RELU)));
+  if (head32) {   // the thin head goes in one launch, the other one in sub-batches of bf16 x / fp32 y
+    pl.family = thin ? CONV_THIN : CONV_HEAD;
+    pl.nb = thin ? d->N : images_per_2gib_mixed(d, 2, 4);
+    return pl;
+  }
+  pl.nb = images_per_2gib(d, eb);
+  if (thin) {
+    pl.family = CONV_THIN;
+    pl.res = dgrad;
+    pl.bn_in = !dgrad && f32 && !(dtype & SG_X_UP2) && x_dense;
+    return pl;
+  }
+  if (pl.nb < 1 || (dgrad && d->stride != 1 && d->stride != 2)) return pl;
+  // the GEMM view of one launch (C = the depth of one tap of the reduction: Cin forward, Cout dgrad); geometry fields only
+  sg_conv_desc one = *d;
+  if (pl.nb < d->N) one.N = pl.nb;
+  IgemmParams g;
+  if (!dgrad) fill_fwd_params(g, &one, nullptr, nullptr, nullptr, nullptr, 0, eb);
+  else fill_dgrad_params(g, &one, nullptr, nullptr, nullptr, nullptr, 0, eb);
+  const int ch = b16 ? 8 : 4;
+  pl.vec = (g.C % ch == 0) && (g.x_ld % ch == 0) && (g.Nout % 4 == 0);
+  const bool vpad_safe = (g.C % BK == 0) || (g.K == g.C) || (g.x_ld == g.C);   // padded reads must stay inside the tensor
+  if (!(vpad_safe && x6_ok(g, pl.vec, b16 || mode != 0))) return pl;
+  static const int perm_on = getenv("SG_DGRAD_PERM2") ? atoi(getenv("SG_DGRAD_PERM2")) : 1;
+  pl.perm2 = (dgrad && perm_on && d->stride == 2 && d->dilation == 1 && d->H % 2 == 0 && d->W % 2 == 0 && d->KH * d->KW <= 64) ? 1 : 0;
+  pl.npl = (b16 || mode == 2) ? 1 : 3;   // 3: the exact fp32 emulation, 1: bf16 products
+  pl.Ck = pl.Ckp = g.C;
+  pl.K = g.K;
+  if (g.C % BK != 0 && g.K != g.C) {   // virtual channel padding: whole slabs inside one tap (slab family; the others never need it)
+    pl.Ckp = x6_vpad_c(g.C);
+    pl.K = (g.K / g.C) * pl.Ckp;
+    g.C = pl.Ckp;
+    g.K = pl.K;
+  }
+  const int N = g.Nout;
+  const int xw = (pl.npl == 3) ? x6w_shares(g) : 0;
+  if (pl.npl == 3 && pl.Ckp == pl.Ck && x6p_geom(g, d->KH, d->KW) && !(g.C > 64 && xw > 0)) {
+    pl.family = CONV_PATCH;
+    pl.Kpad = pl.K;
+    pl.Npad = N;
+    pl.nblocks = (int)sg_cdiv((int64_t)(pl.K / 16) * (N / 32) * 64, 256);
+    pl.w_bytes = (size_t)3 * pl.K * N * 2;
+    pl.bn_in = !dgrad && !(dtype & SG_X_UP2) && x_dense && (g.C == 32 || g.C == 64);   // (not the 64-channel-chunk form)
+    return pl;
+  }
+  const int wbn = (pl.nb >= d->N && (pl.npl == 3 || b16)) ? pw_wide_width(g) : 0;
+  if (wbn) {   // k-block-major planes (conv_pw.h)
+    pl.family = CONV_WIDE;
+    pl.wbn = wbn;
+    pl.Ckp = pl.K;
+    pl.kd = pw_kd(pl.npl);
+    pl.Kpad = pw_kpad(pl.K, pl.npl);
+    pl.Npad = pw_npad(N, wbn);
+    pl.nblocks = (int)(sg_cdiv(pl.Kpad, 32) * sg_cdiv(pl.Npad, 32));
+    pl.w_bytes = pw_planes_bytes(pl.K, N, pl.npl, wbn);
+    static const int var = getenv("SG_PW_VAR") ? atoi(getenv("SG_PW_VAR")) : 1;
+    pl.bnb = dgrad && pl.npl == 3 && !(dtype & SG_X_UP2) && x_dense && y_dense && d->Cout + 16 <= PW_BNB_MAXK && var == 1 &&
+             !getenv("SG_PW_ABLATE");
+    return pl;
+  }
+  pl.family = CONV_SLAB;
+  pl.res = dgrad;
+  static const bool deep = !(getenv("SG_B16_DEEP") && atoi(getenv("SG_B16_DEEP")) == 0);   // A/B switch
+  pl.deep = b16 && deep;
+  pl.kd = x6_plane_kd(b16, pl.Ckp, pl.K == pl.Ckp);
+  pl.Kpad = x6_kpad(pl.K, pl.kd);
+  pl.Npad = x6_npad(N);
+  pl.nblocks = (pl.Kpad / 32) * (pl.Npad / 32);
+  pl.w_bytes = x6_planes_bytes(pl.K, N, pl.npl, pl.kd);
+  const size_t img_part = (size_t)g.OH * g.OW * N * sizeof(float);   // one K share's partial slab of one image
+  if (pl.npl == 3 && pl.kd == XW_KD && xw > 0) {
+    // the long-K multi-tap convolutions: the activation split once into bf16 planes, 128 x 256 tiles with both operands by LDS-DMA
+    pl.x6w_S = xw;
+    pl.a_img_bytes = (size_t)3 * g.H * g.W * g.C * 2;
+    pl.part_img_bytes = xw > 1 ? xw * img_part : 0;
+    pl.planes_in = pl.Ckp == pl.Ck && x_dense && y_dense;   // (planes are dense and have the unpadded depth)
+  }
+  if (pl.deep && pl.kd == BW_KD) {
+    // long reductions with 192+ output columns: 256 x 256 tiles, both operands by LDS-DMA, split-K where the tiles are few
+    pl.b16w_S = b16w_shares(g);
+    pl.part_img_bytes = pl.b16w_S > 1 ? pl.b16w_S * img_part : 0;
+  }
+  return pl;
+}
+
+// num_cus: no choice depends on it today (the tile shapes that do - pick_bn, the 1024-tile crossover - are picked per launch)
+ConvPlan plan_conv(int num_cus, int dtype, const sg_conv_desc* d, bool dgrad, int flags) {
+  (void)num_cus;
+  return plan_conv_mode(x6_mode(), dtype, d, dgrad, flags);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1999,51 +2095,22 @@ int sg_set_conv_x6(int on) {
   return prev;
 }
 
-// scratch of a split-K launch of the 256-wide bf16 kernel for this geometry (0: none), behind the weight planes
-static size_t b16w_ws_extra(const sg_conv_desc* d, bool dgrad) {
-  if (check_desc(d, "b16w_ws_extra")) return 0;
-  if (dgrad && d->stride != 1) return 0;
-  static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-  IgemmParams p;
-  if (!dgrad) fill_fwd_params(p, d, dummy, dummy, nullptr, nullptr, 0, 2);
-  else fill_dgrad_params(p, d, dummy, dummy, nullptr, nullptr, 0, 2);
-  p.x = (const float*)(uintptr_t)16;
-  p.res = nullptr;
-  if (p.C % BK != 0 && p.K != p.C) {
-    const int Ckp = x6_vpad_c(p.C);
-    p.K = (p.K / p.C) * Ckp;
-    p.C = Ckp;
-  }
-  const int S = b16w_plan(p);
-  size_t extra = S > 1 ? b16w_scratch_bytes(S, p.M, p.Nout) + 256 : 0;
-  // the fp32 planes-in kernel (conv_x6w.h): same geometry seen as fp32 storage
-  IgemmParams q;
-  if (!dgrad) fill_fwd_params(q, d, dummy, dummy, nullptr, nullptr, 0, 4);
-  else fill_dgrad_params(q, d, dummy, dummy, nullptr, nullptr, 0, 4);
-  q.x = (const float*)(uintptr_t)16;
-  q.res = nullptr;
-  if (q.C % BK != 0 && q.K != q.C) {
-    const int Ckp = x6_vpad_c(q.C);
-    q.K = (q.K / q.C) * Ckp;
-    q.C = Ckp;
-  }
-  const int S3 = x6w_plan(q);
-  if (S3 > 0) {
-    const size_t e3 = x6w_scratch_bytes(q, S3) + 256;
-    if (e3 > extra) extra = e3;
-  }
-  return extra;
+// scratch behind the weight planes (0: none).  The workspace queries know neither the storage type nor the arithmetic: the larger
+// of the bf16 plan and the fp32 six-pass plan, for the whole batch
+static size_t conv_ws_scratch(const sg_conv_desc* d, bool dgrad) {
+  if (check_desc(d, "sg_conv2d_ws_bytes")) return 0;
+  const size_t b = plan_conv_mode(1, SG_BF16, d, dgrad, 0).scratch_bytes(d->N), f = plan_conv_mode(1, SG_F32, d, dgrad, 0).scratch_bytes(d->N);
+  const size_t n = b > f ? b : f;
+  return n ? n + 256 : 0;
 }
 
 int sg_conv2d_up2_supported(int dtype, const sg_conv_desc* d) {
-  if (!d || (dtype & 0xff) != SG_F32 || (dtype & SG_HEAD_F32)) return 0;
-  if (x6_mode() != 1) return 0;   // the six-pass arithmetic of the patch kernels
-  return (x6p_up2_geom(d) && x6wp_geom(d)) ? 1 : 0;
+  return (d && check_desc(d, "sg_conv2d_up2_supported") == 0 && plan_conv(0, dtype, d, false, 0).up2) ? 1 : 0;
 }
 
 size_t sg_conv2d_fwd_ws_bytes(const sg_conv_desc* d) {
   if (!d) return 0;
-  size_t n = x6_ws_bytes(d->KH * d->KW, d->Cin, d->Cout) + 256 + b16w_ws_extra(d, false);
+  size_t n = x6_ws_bytes(d->KH * d->KW, d->Cin, d->Cout) + 256 + conv_ws_scratch(d, false);
   if (n < x6p_up2_ws_bytes()) n = x6p_up2_ws_bytes();
   return n;
 }
@@ -2075,23 +2142,16 @@ static BnIn bn_in_of(const sg_bn_in* b) {
   }
   return o;
 }
-// geometry of the launches that can apply a BatchNormalization to their input: the thin 1x1 kernels (Cout <= 4) and the patch
-// kernels (3x3, stride 1, SAME, 32 / 64 input channels: conv_x6p.h forward, conv_x6wp.h filter gradient), fp32 storage
-static bool bn_in_geom(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, bool* thin_out) {
-  if ((dtype & 0xff) != SG_F32 || (dtype & (SG_HEAD_F32 | SG_X_UP2))) return false;
-  if ((d->x_ld && d->x_ld != d->Cin)) return false;
-  const bool thin = thin_ok(d);
-  if (thin_out) *thin_out = thin;
-  if (thin) return true;
-  if (x6_mode() != 1 || !x6p_enabled()) return false;
-  if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->dilation != 1 || d->pad_t != 1 || d->pad_l != 1 || d->Ho != d->H || d->Wo != d->W) return false;
-  if (!(d->Cin == 32 || d->Cin == 64) || (d->H % 8) || (d->W % 16)) return false;
-  if (!(d->Cout == 32 || d->Cout == 64 || d->Cout % 128 == 0)) return false;
-  return plan_wgrad(ctx->num_cus, d, false).patch != 0;   // forward AND filter gradient must both take the patch kernels
+// the launches that can apply a BatchNormalization to their input: the thin 1x1 kernels (Cout <= 4) and the patch kernels (3x3,
+// stride 1, SAME, 32 / 64 input channels: conv_x6p.h forward, conv_x6wp.h filter gradient), fp32 storage
+static bool bn_in_geom(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
+  const ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, false, 0);
+  // (patch: forward AND filter gradient must both take the patch kernels)
+  return pl.bn_in && (pl.family == CONV_THIN || plan_wgrad(ctx->num_cus, d, false).patch != 0);
 }
 
 int sg_conv2d_bn_in_supported(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
-  return (ctx && d && check_desc(d, "sg_conv2d_bn_in_supported") == 0 && bn_in_geom(ctx, dtype, d, nullptr)) ? 1 : 0;
+  return (ctx && d && check_desc(d, "sg_conv2d_bn_in_supported") == 0 && bn_in_geom(ctx, dtype, d)) ? 1 : 0;
 }
 
 int sg_conv2d_fwd_stats_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
@@ -2099,7 +2159,7 @@ int sg_conv2d_fwd_stats_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_d
                            const sg_bn_in* bn) {
   SG_CHECK_ARG(bn && bn->mean && bn->invstd && bn->gamma && bn->beta, "sg_conv2d_fwd_stats_bn: null BatchNormalization parameters");
   SG_CHECK_ARG(ctx && d, "sg_conv2d_fwd_stats_bn: null argument");
-  if (check_desc(d, "sg_conv2d_fwd_stats_bn") || !bn_in_geom(ctx, dtype, d, nullptr) || (flags & SG_PRO_UP2)) {
+  if (check_desc(d, "sg_conv2d_fwd_stats_bn") || !bn_in_geom(ctx, dtype, d) || (flags & SG_PRO_UP2)) {
     sg_set_error("sg_conv2d_fwd_stats_bn: this launch takes neither a thin 1x1 nor a patch kernel (3x3 s1 SAME, 32 / 64 input channels, "
                  "fp32 storage): no kernel to apply the BatchNormalization in");
     return SG_EUNSUPPORTED;
@@ -2122,17 +2182,52 @@ int sg_conv2d_fwd_stats_ap(sg_ctx* ctx, void* stream, int dtype, const sg_conv_d
 // does the fp32 launch of this geometry read its A operand as bf16 planes (conv_x6w.h)?  Then handing it planes that exist
 // already (sg_split_planes: shared by several consumers of one tensor, or kept for the filter gradient) saves its own split.
 int sg_conv2d_planes_in(const sg_conv_desc* d, int dgrad) {
-  if (!d || check_desc(d, "sg_conv2d_planes_in") || x6_mode() != 1) return 0;
-  if (dgrad && d->stride != 1) return 0;
-  if ((d->x_ld && d->x_ld != d->Cin) || (d->y_ld && d->y_ld != d->Cout)) return 0;   // planes are dense
-  static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-  IgemmParams q;
-  if (!dgrad) fill_fwd_params(q, d, dummy, dummy, nullptr, nullptr, 0, 4);
-  else fill_dgrad_params(q, d, dummy, dummy, nullptr, nullptr, 0, 4);
-  q.x = (const float*)(uintptr_t)16;
-  if (q.C % BK != 0 && q.K != q.C) return 0;   // (virtually padded channels: the planes would need the padded depth)
-  if (x6p_ok(q, d->KH, d->KW)) return 0;
-  return x6w_plan(q) > 0 ? 1 : 0;
+  return (d && check_desc(d, "sg_conv2d_planes_in") == 0 && plan_conv(0, SG_F32, d, dgrad != 0, 0).planes_in) ? 1 : 0;
+}
+
+// one launch of the plan: the whole batch or one sub-batch of it (`d`: its images).  The caller has checked the operands against
+// the plan: `fast` = they allow the plan's plane kernel (else: the native kernel)
+static int conv2d_fwd_launch(sg_ctx* ctx, hipStream_t st, int dtype, const sg_conv_desc* d, const ConvPlan& pl, bool fast,
+                             const void* x, const void* w, const void* bias, void* y, int flags, void* ws, bool prepared, void* stats,
+                             int* tiles_out, const void* x_planes, const sg_bn_in* bn) {
+  const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0;
+  if (pl.family == CONV_THIN) {
+    if (!b16) {
+#define CALL(CO) thin_fwd_t<CO, float, float>(d, (const float*)x, (const float*)w, (const float*)bias, (float*)y, flags, st, bn_in_of(bn))
+      THIN_SWITCH(d->Cout, CALL)
+#undef CALL
+    } else if (head32) {
+#define CALL(CO) thin_fwd_t<CO, bf16_t, float>(d, (const bf16_t*)x, (const float*)w, (const float*)bias, (float*)y, flags, st)
+      THIN_SWITCH(d->Cout, CALL)
+#undef CALL
+    } else {
+#define CALL(CO) thin_fwd_t<CO, bf16_t, bf16_t>(d, (const bf16_t*)x, (const float*)w, (const float*)bias, (bf16_t*)y, flags, st)
+      THIN_SWITCH(d->Cout, CALL)
+#undef CALL
+    }
+  }
+  IgemmParams p;
+  fill_fwd_params(p, d, x, w, bias, y, flags, dt_bytes(dtype));
+  if (pl.family == CONV_HEAD) {   // a head that is not a 1x1 convolution: the any-shape kernel, fp32 out
+    const bool vec4 = (d->Cin % 4 == 0) && (p.x_ld % 4 == 0) && (((uintptr_t)x & 7) == 0);
+    return dispatch_igemm_mixed<bf16_t, float>(p, vec4, ctx->num_cus, st);
+  }
+  if (fast) {
+    if (!b16 && p.x_ld == d->Cin) p.a_planes = (const unsigned short*)x_planes;
+    p.bn = bn_in_of(bn);
+    if (stats && tiles_out && !(flags & SG_EPI_RELU)) {  // the statistics ride in the x6 kernel's epilogue only
+      p.stats = (float*)stats;
+      *tiles_out = (int)sg_cdiv(p.M, BM);
+    }
+    if (b16) return run_x6<1, bf16_t>(pl, p, (const float*)w, false, d->Cin, d->Cout, ws, ctx->num_cus, st, prepared);
+    if (pl.npl == 1) return run_x6<1, float>(pl, p, (const float*)w, false, d->Cin, d->Cout, ws, ctx->num_cus, st, prepared);
+    return run_x6<3, float>(pl, p, (const float*)w, false, d->Cin, d->Cout, ws, ctx->num_cus, st, prepared);
+  }
+  if (b16) {
+    const bool vec4 = (d->Cin % 4 == 0) && (p.x_ld % 4 == 0) && (((uintptr_t)x & 7) == 0);
+    return dispatch_igemm_b16(p, vec4, ctx->num_cus, st);
+  }
+  return dispatch_igemm(p, (d->Cin % 4 == 0) && (p.x_ld % 4 == 0) && (d->Cout % 4 == 0) && aligned16(x) && aligned16(w), ctx->num_cus, st);
 }
 
 static int conv2d_fwd_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
@@ -2150,12 +2245,13 @@ static int conv2d_fwd_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_d
   SG_CHECK_ARG(!head32 || (b16 && d->Cout <= 4), "sg_conv2d_fwd: SG_HEAD_F32 needs Cout <= 4 (a softmax head) on bf16 storage");
   SG_CHECK_ARG(!(dtype & SG_X_UP2), "sg_conv2d_fwd: SG_X_UP2 is the filter gradient's flag (forward: SG_PRO_UP2)");
   hipStream_t st = (hipStream_t)stream;
+  ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, false, flags);
+  const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
   if (flags & SG_PRO_UP2) {
     // UpSampling2D(2) -> Conv2D 3x3, sub-pixel form (conv_x6p.h): x is the SOURCE [N, H/2, W/2, Cin]; the kernel sees a
     // convolution on the source grid with 4 phases x Cout columns.  (The patch kernel addresses with 64-bit pointers: no
     // 2 GiB sub-batches.)
-    const int xl = d->x_ld ? d->x_ld : d->Cin;
-    if (!sg_conv2d_up2_supported(dtype, d) || !aligned16(x) || (xl % 4)) {
+    if (!pl.up2 || !aligned16(x) || (xl % 4)) {
       sg_set_error("sg_conv2d_fwd: SG_PRO_UP2 on a launch the fused up-sampling kernel does not cover (3x3 s1 SAME, 64 -> 32, "
                    "H %% 16 = 0, W %% 32 = 0, fp32 storage, x6 arithmetic)");
       return SG_EUNSUPPORTED;
@@ -2166,102 +2262,57 @@ static int conv2d_fwd_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_d
     }
     sg_conv_desc sd = *d;
     sd.H = d->H / 2; sd.W = d->W / 2; sd.Ho = sd.H; sd.Wo = sd.W; sd.Cout = 4 * d->Cout;
-    sd.x_ld = xl; sd.y_ld = d->y_ld ? d->y_ld : d->Cout;
+    sd.x_ld = xl; sd.y_ld = yl;
     IgemmParams p;
     fill_fwd_params(p, &sd, x, w, bias, y, flags & (SG_EPI_BIAS | SG_EPI_RELU), eb);
     p.K = 4 * d->Cin;
-    p.y_ld = d->y_ld ? d->y_ld : d->Cout;
+    p.y_ld = yl;
     if (stats && tiles_out && !(flags & SG_EPI_RELU)) {
       p.stats = (float*)stats;
       *tiles_out = (int)sg_cdiv((int64_t)d->N * d->Ho * d->Wo, BM);   // one statistics tile per phase and source tile
     }
     return run_x6p_up2(p, (const float*)w, ws, ctx->num_cus, st);
   }
-  if (head32 && !(thin_ok(d) && aligned16(x))) {  // a head that is not a 1x1 convolution: the any-shape kernel, fp32 out
-    // sub-batches of whole images when the bf16 input or the fp32 output passes 2 GiB (1024 x 1024 ensemble tiles)
-    const int nb = images_per_2gib_mixed(d, 2, 4);
-    SG_CHECK_ARG(nb >= 1, "sg_conv2d_fwd: one image of the softmax head beyond 2 GiB");
-    const int64_t xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-    for (int n0 = 0; n0 < d->N; n0 += nb) {
-      sg_conv_desc sub = *d;
-      sub.N = (d->N - n0 < nb) ? d->N - n0 : nb;
-      const char* xs = (const char*)x + (int64_t)n0 * d->H * d->W * xl * 2;
-      char* ys = (char*)y + (int64_t)n0 * d->Ho * d->Wo * yl * 4;
-      IgemmParams ph;
-      fill_fwd_params(ph, &sub, xs, w, bias, ys, flags, eb);
-      const bool vec4 = (d->Cin % 4 == 0) && (ph.x_ld % 4 == 0) && (((uintptr_t)xs & 7) == 0);
-      int rch = dispatch_igemm_mixed<bf16_t, float>(ph, vec4, ctx->num_cus, st);
-      if (rch) return rch;
-    }
-    return 0;
-  }
-  if (!head32) {
-    // The fast kernels address their operands through 2 GiB buffer descriptors.  A larger batch is run as
-    // sub-batches of whole images (independent in a forward conv), so every image takes the same kernel - and
-    // therefore the same rounding - whatever batch it travels in.
-    const int nb = images_per_2gib(d, eb);
-    if (nb < d->N && nb >= 1) {
-      const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-      for (int n0 = 0; n0 < d->N; n0 += nb) {
-        sg_conv_desc sub = *d;
-        sub.N = (d->N - n0 < nb) ? d->N - n0 : nb;
-        const char* xs = (const char*)x + (int64_t)n0 * d->H * d->W * xl * eb;
-        char* ys = (char*)y + (int64_t)n0 * d->Ho * d->Wo * yl * eb;
-        g_sub_batch = true;   // the weight planes were laid out for the whole batch: no batch-size dependent kernel choice
-        int rcs = conv2d_fwd_impl(ctx, stream, dtype, &sub, xs, w, bias, ys, flags, ws, ws_bytes, nullptr, nullptr, nullptr, bn);  // (no statistics)
-        g_sub_batch = false;
-        if (rcs) return rcs;
-      }
-      return 0;
-    }
-  }
-  if (thin_ok(d) && aligned16(x)) {
-    if (!b16) {
-#define CALL(CO) thin_fwd_t<CO, float, float>(d, (const float*)x, (const float*)w, (const float*)bias, (float*)y, flags, st, bn_in_of(bn))
-      THIN_SWITCH(d->Cout, CALL)
-#undef CALL
-    } else if (head32) {
-#define CALL(CO) thin_fwd_t<CO, bf16_t, float>(d, (const bf16_t*)x, (const float*)w, (const float*)bias, (float*)y, flags, st)
-      THIN_SWITCH(d->Cout, CALL)
-#undef CALL
-    } else {
-#define CALL(CO) thin_fwd_t<CO, bf16_t, bf16_t>(d, (const bf16_t*)x, (const float*)w, (const float*)bias, (bf16_t*)y, flags, st)
-      THIN_SWITCH(d->Cout, CALL)
-#undef CALL
-    }
-  }
-  IgemmParams p;
-  fill_fwd_params(p, d, x, w, bias, y, flags, eb);
-  if (!b16 && p.x_ld == d->Cin) p.a_planes = (const unsigned short*)x_planes;
-  p.bn = bn_in_of(bn);
-  const int ch = b16 ? 8 : 4;
-  const bool vec = (d->Cin % ch == 0) && (p.x_ld % ch == 0) && (d->Cout % 4 == 0) && aligned16(x) && aligned16(w);
-  if (p.bn.mean && !(x6_ok(p, vec, b16) && x6p_ok(p, d->KH, d->KW) && ws && aligned16(ws))) {   // only the patch kernel applies it
-    sg_set_error("sg_conv2d_fwd_stats_bn: the launch does not take the patch kernel after all (alignment / workspace)");
-    return SG_EUNSUPPORTED;
-  }
-  const bool vpad_safe = (p.C % BK == 0) || (p.K == p.C) || (p.x_ld == p.C);  // padded reads must stay inside this tensor
+  // ---- the operands against the plan, once and before anything is written
   const bool prepared = ws_bytes == SG_WS_PREPARED;
-  const bool have_ws = ws && aligned16(ws) && (prepared || ws_bytes >= x6_ws_bytes(d->KH * d->KW, d->Cin, d->Cout));
-  if (prepared && !(have_ws && vpad_safe && x6_ok(p, vec, b16))) {
-    sg_set_error("sg_conv2d_fwd: SG_WS_PREPARED planes given, but this launch does not take a prepared-planes kernel");
-    return SG_EINVAL;
+  const int ebx = head32 ? 2 : eb, eby = head32 ? 4 : eb;
+  if (pl.family == CONV_THIN && !(aligned16(x) && (pl.nb >= d->N || pl.nb < 1 || ((int64_t)d->H * d->W * xl * ebx) % 16 == 0)))
+    pl = plan_conv(ctx->num_cus, dtype, d, false, flags | PLAN_NOT_THIN);   // (every sub-batch's x must meet the thin kernels' alignment)
+  if (pl.family == CONV_HEAD) SG_CHECK_ARG(pl.nb >= 1, "sg_conv2d_fwd: one image of the softmax head beyond 2 GiB");
+  // The fast kernels address their operands through 2 GiB buffer descriptors.  A larger batch is run as sub-batches of whole
+  // images (independent in a forward conv), so every image takes the same kernel - and therefore the same rounding - whatever
+  // batch it travels in.  Sub-batches leave no statistics and read no activation planes.
+  const int nb = (pl.nb >= 1 && pl.nb < d->N) ? pl.nb : d->N;
+  bool fast = false;
+  if (pl.family >= CONV_SLAB) {
+    const bool have_ws = ws && aligned16(ws) && (prepared || ws_bytes >= x6_ws_bytes(d->KH * d->KW, d->Cin, d->Cout));
+    fast = have_ws && pl.vec && aligned16(x) && aligned16(w);
   }
-  if (have_ws && vpad_safe && x6_ok(p, vec, b16)) {
-    if (stats && tiles_out && !(flags & SG_EPI_RELU)) {  // the statistics ride in the x6 kernel's epilogue only
-      p.stats = (float*)stats;
-      *tiles_out = (int)sg_cdiv(p.M, BM);
+  if (pl.family != CONV_THIN && pl.family != CONV_HEAD) {
+    if (bn && bn->mean && !(fast && pl.bn_in)) {   // only the patch kernel applies it
+      sg_set_error("sg_conv2d_fwd_stats_bn: the launch does not take the patch kernel after all (alignment / workspace)");
+      return SG_EUNSUPPORTED;
     }
-    p.ws_room = prepared ? SIZE_MAX : ws_bytes;
-    if (b16) return run_x6<1, bf16_t>(p, (const float*)w, false, d->Cin, d->Cout, d->KH, d->KW, ws, ctx->num_cus, st, prepared);
-    if (x6_mode() == 2) return run_x6<1, float>(p, (const float*)w, false, d->Cin, d->Cout, d->KH, d->KW, ws, ctx->num_cus, st, prepared);
-    return run_x6<3, float>(p, (const float*)w, false, d->Cin, d->Cout, d->KH, d->KW, ws, ctx->num_cus, st, prepared);
+    if (prepared && !fast) {
+      sg_set_error("sg_conv2d_fwd: SG_WS_PREPARED planes given, but this launch does not take a prepared-planes kernel");
+      return SG_EINVAL;
+    }
+    if (fast && !prepared && ws_bytes < pl.ws_bytes(nb)) {
+      sg_set_error("sg_conv2d_fwd: workspace %zu < %zu (weight planes + activation planes + split-K partial slabs of %d + %d shares)",
+                   ws_bytes, pl.ws_bytes(nb), pl.x6w_S, pl.b16w_S);
+      return SG_EWORKSPACE;
+    }
   }
-  if (b16) {
-    const bool vec4 = (d->Cin % 4 == 0) && (p.x_ld % 4 == 0) && (((uintptr_t)x & 7) == 0);
-    return dispatch_igemm_b16(p, vec4, ctx->num_cus, st);
+  if (nb >= d->N) return conv2d_fwd_launch(ctx, st, dtype, d, pl, fast, x, w, bias, y, flags, ws, prepared, stats, tiles_out, x_planes, bn);
+  for (int n0 = 0; n0 < d->N; n0 += nb) {
+    sg_conv_desc sub = *d;
+    sub.N = (d->N - n0 < nb) ? d->N - n0 : nb;
+    const char* xs = (const char*)x + (int64_t)n0 * d->H * d->W * xl * ebx;
+    char* ys = (char*)y + (int64_t)n0 * d->Ho * d->Wo * yl * eby;
+    rc = conv2d_fwd_launch(ctx, st, dtype, &sub, pl, fast, xs, w, bias, ys, flags, ws, prepared, nullptr, nullptr, nullptr, bn);
+    if (rc) return rc;
   }
-  return dispatch_igemm(p, vec, ctx->num_cus, st);
+  return 0;
 }
 
 int sg_get_conv_x6(void) { return x6_mode(); }
@@ -2272,95 +2323,24 @@ int sg_conv2d_planes_job(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, in
   *bytes = 0;
   int rc = check_desc(d, "sg_conv2d_planes_job");
   if (rc) return rc;
-  if ((dtype & SG_HEAD_F32) || thin_ok(d)) return 0;  // kind 0: streaming kernels, no planes
-  if (dgrad && d->stride != 1 && d->stride != 2) return 0;
-  const bool b16 = dt_storage(dtype) == SG_BF16;
-  const int eb = dt_bytes(dtype);
-  IgemmParams p;
-  // geometry only: the pointers are assumed 16-byte aligned and the operands dense, as the host's arenas and torch's
-  // allocator make them; a launch for which that does not hold refuses the prepared planes (SG_EINVAL)
-  static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-  if (!dgrad) fill_fwd_params(p, d, dummy, dummy, nullptr, nullptr, 0, eb);
-  else fill_dgrad_params(p, d, dummy, dummy, nullptr, nullptr, 0, eb);
-  const int ch = b16 ? 8 : 4;
-  const bool vec = !dgrad ? ((d->Cin % ch == 0) && (p.x_ld % ch == 0) && (d->Cout % 4 == 0))
-                          : ((d->Cout % ch == 0) && (p.x_ld % ch == 0) && (d->Cin % 4 == 0));
-  const bool vpad_safe = (p.C % BK == 0) || (p.K == p.C) || (p.x_ld == p.C);
-  const int nb = images_per_2gib(d, eb);
-  if (nb < 1) return 0;
-  if (nb < d->N) {  // the launch will run as sub-batches: describe one of them
-    const int64_t pix = !dgrad ? (int64_t)nb * d->H * d->W : (int64_t)nb * d->Ho * d->Wo;
-    const int64_t xb = ((pix - 1) * p.x_ld + p.C) * eb;
-    p.x_bytes = xb < (1ll << 31) ? (uint32_t)xb : 0;
-  }
-  if (!(vpad_safe && x6_ok(p, vec, b16))) return 0;
-  const int npl = (b16 || x6_mode() == 2) ? 1 : 3;
-  const int Ck = p.C;
+  // geometry only: the pointers are assumed 16-byte aligned, as the host's arenas and torch's allocator make them; a launch for
+  // which that does not hold refuses the prepared planes (SG_EINVAL)
+  const ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, dgrad != 0, 0);
+  if (pl.family < CONV_SLAB) return 0;   // kind 0: streaming kernels, no planes
+  out->kind = pl.family == CONV_SLAB ? 1 : (pl.family == CONV_PATCH ? 2 : 3);
   out->s_tap = d->Cin * d->Cout;
   out->s_k = dgrad ? 1 : d->Cout;
   out->s_n = dgrad ? d->Cout : 1;
-  out->N = p.Nout;
-  out->Ck = Ck;
-  out->kd = 0;
-  if (npl == 3) {
-    p.x = (const float*)(uintptr_t)16;  // x6p_ok tests the alignment of x
-    if (x6p_ok(p, d->KH, d->KW)) {
-      out->kind = 2;
-      out->npl = 3;
-      out->K = p.K;
-      out->Ckp = Ck;
-      out->Kpad = p.K;
-      out->Npad = p.Nout;
-      const int64_t threads = (int64_t)(p.K / 16) * (p.Nout / 32) * 64;
-      out->nblocks = (int32_t)sg_cdiv(threads, 256);
-      *bytes = (size_t)3 * p.K * p.Nout * 2;
-      return 0;
-    }
-  }
-  p.x = (const float*)(uintptr_t)16;
-  const int wbn = nb >= d->N ? pw_wide_bn(p, eb) : 0;
-  if (wbn) {   // the wide pointwise kernel's k-block-major planes (conv_pw.h); never for sub-batches
-    out->kind = 3;
-    out->npl = npl;
-    out->K = p.K;
-    out->Ckp = p.K;
-    out->kd = pw_kd(npl);
-    out->Kpad = pw_kpad(p.K, npl);
-    out->Npad = pw_npad(p.Nout, wbn);
-    out->nblocks = (int32_t)(sg_cdiv(out->Kpad, 32) * sg_cdiv(out->Npad, 32));
-    *bytes = pw_planes_bytes(p.K, p.Nout, npl, wbn);
-    return 0;
-  }
-  int Ckp = Ck, K = p.K;
-  if (Ck % BK != 0 && K != Ck) {
-    Ckp = x6_vpad_c(Ck);
-    K = (K / Ck) * Ckp;
-  }
-  out->kind = 1;
-  out->npl = npl;
-  out->K = K;
-  out->Ckp = Ckp;
-  out->kd = x6_plane_kd(b16 && npl == 1, Ckp, K == Ckp);
-  out->Kpad = x6_kpad(K, out->kd);
-  out->Npad = x6_npad(p.Nout);
-  out->nblocks = (out->Kpad / 32) * (out->Npad / 32);
-  *bytes = x6_planes_bytes(K, p.Nout, npl, out->kd);
-  if (!b16 && npl == 3 && out->kd == XW_KD) {   // conv_x6w.h: the activation's planes and split-K partial slabs behind the weight planes
-    IgemmParams q = p;
-    q.C = Ckp;
-    q.K = K;
-    q.res = nullptr;
-    const int S = x6w_plan(q);
-    if (S > 0) *bytes = ((*bytes + 255) & ~(size_t)255) + x6w_scratch_bytes(q, S);
-  }
-  if (b16 && npl == 1 && out->kd == BW_KD) {   // a split-K launch of the 256-wide kernel keeps its partial slabs behind the planes
-    IgemmParams q = p;
-    q.C = Ckp;
-    q.K = K;
-    q.res = nullptr;
-    const int S = b16w_plan(q);
-    if (S > 1) *bytes = ((*bytes + 255) & ~(size_t)255) + b16w_scratch_bytes(S, q.M, q.Nout);
-  }
+  out->N = dgrad ? d->Cin : d->Cout;
+  out->npl = pl.npl;
+  out->K = pl.K;
+  out->Ck = pl.Ck;
+  out->Ckp = pl.Ckp;
+  out->kd = pl.kd;
+  out->Kpad = pl.Kpad;
+  out->Npad = pl.Npad;
+  out->nblocks = pl.nblocks;
+  *bytes = pl.ws_bytes(d->N);   // (a launch in sub-batches: the arena slot is sized for the whole batch all the same)
   return 0;
 }
 
@@ -2403,7 +2383,7 @@ int sg_bn_train_fwd_tiles(sg_ctx* ctx, void* stream, int dtype, int64_t rows, in
 size_t sg_conv2d_dgrad_ws_bytes(const sg_conv_desc* d) {
   if (!d) return 0;
   const size_t native = (size_t)d->KH * d->KW * d->Cin * d->Cout * sizeof(float);
-  const size_t x6 = x6_ws_bytes(d->KH * d->KW, d->Cout, d->Cin) + 256 + b16w_ws_extra(d, true);
+  const size_t x6 = x6_ws_bytes(d->KH * d->KW, d->Cout, d->Cin) + 256 + conv_ws_scratch(d, true);
   return native > x6 ? native : x6;
 }
 
@@ -2413,17 +2393,7 @@ static int conv2d_dgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv
 
 // the input gradient of a pointwise convolution with the BatchNormalization backward apply in its A path (conv_pw.h, BNB form)
 static bool dgrad_bnb_geom(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
-  if ((dtype & 0xff) != SG_F32 || (dtype & (SG_HEAD_F32 | SG_X_UP2)) || x6_mode() != 1) return false;
-  if (d->KH != 1 || d->KW != 1 || d->stride != 1 || (d->x_ld && d->x_ld != d->Cin) || (d->y_ld && d->y_ld != d->Cout)) return false;
-  if (images_per_2gib(d, 4) < d->N || d->Cout + 16 > PW_BNB_MAXK) return false;
-  static const int var = getenv("SG_PW_VAR") ? atoi(getenv("SG_PW_VAR")) : 1;
-  if (var != 1 || getenv("SG_PW_ABLATE")) return false;
-  static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-  IgemmParams q;
-  fill_dgrad_params(q, d, dummy, dummy, nullptr, nullptr, 0, 4);
-  q.x = (const float*)(uintptr_t)16;
-  const int wbn = pw_wide_bn(q, 4);
-  return wbn == 384 || wbn == 256;
+  return plan_conv(ctx->num_cus, dtype, d, true, 0).bnb;
 }
 
 int sg_conv2d_dgrad_bnb_supported(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
@@ -2461,6 +2431,68 @@ int sg_conv2d_dgrad_acc(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc
   return conv2d_dgrad_impl(ctx, stream, dtype, d, dy, w, bias, dx, flags, ws, ws_bytes, res);
 }
 
+// one launch of the plan: the whole batch or one sub-batch of it (see conv2d_fwd_launch)
+static int conv2d_dgrad_launch(sg_ctx* ctx, hipStream_t st, int dtype, const sg_conv_desc* d, const ConvPlan& pl, bool fast,
+                               const void* dy, const void* w, const void* bias, void* dx, int flags, void* ws, bool prepared,
+                               const void* res, const void* dy_planes, const sg_bn_bwd_in* bnb) {
+  const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0;
+  if (pl.family == CONV_THIN) {
+    if (!b16) {
+#define CALL(CO) thin_dgrad_t<CO, float, float>(d, (const float*)dy, (const float*)w, (float*)dx, st, res)
+      THIN_SWITCH(d->Cout, CALL)
+#undef CALL
+    } else if (head32) {
+#define CALL(CO) thin_dgrad_t<CO, bf16_t, float>(d, (const float*)dy, (const float*)w, (bf16_t*)dx, st)
+      THIN_SWITCH(d->Cout, CALL)
+#undef CALL
+    } else {
+#define CALL(CO) thin_dgrad_t<CO, bf16_t, bf16_t>(d, (const bf16_t*)dy, (const float*)w, (bf16_t*)dx, st, res)
+      THIN_SWITCH(d->Cout, CALL)
+#undef CALL
+    }
+  }
+  float* wt = (float*)ws;   // the native kernels read the per-tap transpose of w
+  IgemmParams p;
+  fill_dgrad_params(p, d, dy, wt, bias, dx, flags, head32 ? 4 : dt_bytes(dtype));
+  if (fast) {
+    p.res = (const float*)res;
+    if (!b16 && p.x_ld == d->Cout) p.a_planes = (const unsigned short*)dy_planes;
+    if (bnb) {
+      p.bnb.x = (const float*)bnb->x; p.bnb.mean = (const float*)bnb->mean; p.bnb.invstd = (const float*)bnb->invstd;
+      p.bnb.gamma = (const float*)bnb->gamma; p.bnb.beta = (const float*)bnb->beta; p.bnb.dgamma = (const float*)bnb->dgamma;
+      p.bnb.dbeta = (const float*)bnb->dbeta; p.bnb.dz = (float*)bnb->dz; p.bnb.relu = bnb->relu ? 1 : 0;
+      {
+        static const int abl = getenv("SG_BNB_ABLATE") ? atoi(getenv("SG_BNB_ABLATE")) : 0;   // timing only: 2 = no dz store, 4 = no x load
+        p.bnb.relu |= abl & 6;
+      }
+      p.bnb.inv_n = 1.0f / (float)bnb->rows;
+    }
+    if (pl.perm2) {   // rows in parity-class order: see IgemmParams::perm2
+      p.perm2 = 1;
+      p.fd_mc = make_fastdiv((uint32_t)(p.M / 4));
+      p.fd_hcwc = make_fastdiv((uint32_t)((d->H / 2) * (d->W / 2)));
+      p.fd_wc = make_fastdiv((uint32_t)(d->W / 2));
+    }
+    if (b16) return run_x6<1, bf16_t>(pl, p, (const float*)w, true, d->Cin, d->Cout, ws, ctx->num_cus, st, prepared);
+    if (pl.npl == 1) return run_x6<1, float>(pl, p, (const float*)w, true, d->Cin, d->Cout, ws, ctx->num_cus, st, prepared);
+    return run_x6<3, float>(pl, p, (const float*)w, true, d->Cin, d->Cout, ws, ctx->num_cus, st, prepared);
+  }
+  {
+    dim3 grid((unsigned)sg_cdiv(d->Cout, 32), (unsigned)sg_cdiv(d->Cin, 32), (unsigned)(d->KH * d->KW));
+    hipLaunchKernelGGL(transpose_taps_kernel, grid, dim3(256), 0, st, (const float*)w, wt, d->Cin, d->Cout);
+    SG_LAUNCH_CHECK("transpose_taps_kernel");
+  }
+  if (pl.family == CONV_HEAD) {   // fp32 dy in, bf16 dx out, any shape
+    const bool vec4 = (d->Cout % 4 == 0) && (p.x_ld % 4 == 0) && aligned16(dy);
+    return dispatch_igemm_mixed<float, bf16_t>(p, vec4, ctx->num_cus, st);
+  }
+  if (b16) {
+    const bool vec4 = (d->Cout % 4 == 0) && (p.x_ld % 4 == 0) && (((uintptr_t)dy & 7) == 0);
+    return dispatch_igemm_b16(p, vec4, ctx->num_cus, st);
+  }
+  return dispatch_igemm(p, (d->Cout % 4 == 0) && (p.x_ld % 4 == 0) && (d->Cin % 4 == 0) && aligned16(dy), ctx->num_cus, st);
+}
+
 static int conv2d_dgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
                             const void* bias, void* dx, int flags, void* ws, size_t ws_bytes, const void* res, const void* dy_planes,
                             const sg_bn_bwd_in* bnb) {
@@ -2483,7 +2515,6 @@ static int conv2d_dgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv
   SG_CHECK_ARG(aligned16(ws), "sg_conv2d_dgrad: workspace must be 16-byte aligned");
   const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0;
   const int eb = dt_bytes(dtype);
-  const bool thin = thin_ok(d) && aligned16(dx) && !(flags & (SG_EPI_BIAS | SG_EPI_RELU));
   SG_CHECK_ARG(!head32 || (b16 && d->Cout <= 4), "sg_conv2d_dgrad: SG_HEAD_F32 needs Cout <= 4 (a softmax head) on bf16 storage");
   hipStream_t st = (hipStream_t)stream;
   if (res && head32) {
@@ -2491,122 +2522,60 @@ static int conv2d_dgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv
     return SG_EUNSUPPORTED;
   }
   SG_CHECK_ARG(!(dtype & SG_X_UP2) && !(flags & SG_PRO_UP2), "sg_conv2d_dgrad: the up-sampling flag of the input gradient is SG_EPI_DOWN2");
+  // ---- the operands against the plan, once and before anything is written
+  const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
+  const int ebx = head32 ? 2 : eb, eby = head32 ? 4 : eb;   // dx (the forward's x) / dy
+  ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, true, flags);
+  if (pl.family == CONV_THIN && !(aligned16(dx) && (pl.nb >= d->N || pl.nb < 1 || ((int64_t)d->H * d->W * xl * ebx) % 16 == 0)))
+    pl = plan_conv(ctx->num_cus, dtype, d, true, flags | PLAN_NOT_THIN);   // (every sub-batch's dx must meet the thin kernels' alignment)
+  if (pl.family == CONV_HEAD) SG_CHECK_ARG(pl.nb >= 1, "sg_conv2d_dgrad: one image of the softmax head beyond 2 GiB");
+  const int nb = (pl.nb >= 1 && pl.nb < d->N) ? pl.nb : d->N;   // sub-batches of whole images: see conv2d_fwd_impl
+  const bool fast = pl.family >= CONV_SLAB && pl.vec && aligned16(dy);
   const bool down2 = (flags & SG_EPI_DOWN2) != 0;
   if (down2) {  // dx = the SOURCE's gradient [N, H/2, W/2, Cin]: the patch kernel's epilogue adds the 2 x 2 cells (conv_x6p.h)
-    const int yl_ = d->y_ld ? d->y_ld : d->Cout;
-    if (!sg_conv2d_up2_supported(dtype, d) || res || (flags & (SG_EPI_BIAS | SG_EPI_RELU)) || !aligned16(dy) || (yl_ % 4)) {
+    if (!pl.up2 || res || (flags & (SG_EPI_BIAS | SG_EPI_RELU)) || !aligned16(dy) || (yl % 4)) {
       sg_set_error("sg_conv2d_dgrad: SG_EPI_DOWN2 on a launch the fused up-sampling kernel does not cover (3x3 s1 SAME, 64 -> 32, "
                    "H %% 16 = 0, W %% 32 = 0, fp32 storage, x6 arithmetic, no bias / ReLU / collected gradient)");
       return SG_EUNSUPPORTED;
     }
-  }
-  if (head32 && !thin) {  // fp32 dy in, bf16 dx out, any shape
-    const int nb = images_per_2gib_mixed(d, 2, 4);  // dx bf16 (the forward's x), dy fp32
-    SG_CHECK_ARG(nb >= 1, "sg_conv2d_dgrad: one image of the softmax head beyond 2 GiB");
-    float* wth = (float*)ws;
-    dim3 grid((unsigned)sg_cdiv(d->Cout, 32), (unsigned)sg_cdiv(d->Cin, 32), (unsigned)(d->KH * d->KW));
-    hipLaunchKernelGGL(transpose_taps_kernel, grid, dim3(256), 0, st, (const float*)w, wth, d->Cin, d->Cout);
-    SG_LAUNCH_CHECK("transpose_taps_kernel");
-    const int64_t xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-    for (int n0 = 0; n0 < d->N; n0 += nb) {
-      sg_conv_desc sub = *d;
-      sub.N = (d->N - n0 < nb) ? d->N - n0 : nb;
-      const char* dys = (const char*)dy + (int64_t)n0 * d->Ho * d->Wo * yl * 4;
-      char* dxs = (char*)dx + (int64_t)n0 * d->H * d->W * xl * 2;
-      IgemmParams ph;
-      fill_dgrad_params(ph, &sub, dys, wth, bias, dxs, flags, 4);
-      const bool vec4 = (d->Cout % 4 == 0) && (ph.x_ld % 4 == 0) && aligned16(dys);
-      int rch = dispatch_igemm_mixed<float, bf16_t>(ph, vec4, ctx->num_cus, st);
-      if (rch) return rch;
-    }
-    return 0;
-  }
-  if (!head32) {
-    const int nb = images_per_2gib(d, eb);  // see sg_conv2d_fwd_ws
-    if (nb < d->N && nb >= 1) {
-      const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-      for (int n0 = 0; n0 < d->N; n0 += nb) {
-        sg_conv_desc sub = *d;
-        sub.N = (d->N - n0 < nb) ? d->N - n0 : nb;
-        const char* dys = (const char*)dy + (int64_t)n0 * d->Ho * d->Wo * yl * eb;
-        char* dxs = (char*)dx + (int64_t)n0 * (down2 ? (d->H / 2) * (d->W / 2) : d->H * d->W) * xl * eb;
-        const char* ress = res ? (const char*)res + (int64_t)n0 * d->H * d->W * xl * eb : nullptr;
-        g_sub_batch = true;
-        int rcs = conv2d_dgrad_impl(ctx, stream, dtype, &sub, dys, w, bias, dxs, flags, ws, ws_bytes, ress);
-        g_sub_batch = false;
-        if (rcs) return rcs;
-      }
-      return 0;
+    if (!(fast && pl.family == CONV_PATCH)) {  // only the patch kernel knows the flag
+      sg_set_error("sg_conv2d_dgrad: SG_EPI_DOWN2, but this launch does not take the patch kernel");
+      return SG_EUNSUPPORTED;
     }
   }
-  if (thin) {
-    if (!b16) {
-#define CALL(CO) thin_dgrad_t<CO, float, float>(d, (const float*)dy, (const float*)w, (float*)dx, st, res)
-      THIN_SWITCH(d->Cout, CALL)
-#undef CALL
-    } else if (head32) {
-#define CALL(CO) thin_dgrad_t<CO, bf16_t, float>(d, (const float*)dy, (const float*)w, (bf16_t*)dx, st)
-      THIN_SWITCH(d->Cout, CALL)
-#undef CALL
-    } else {
-#define CALL(CO) thin_dgrad_t<CO, bf16_t, bf16_t>(d, (const bf16_t*)dy, (const float*)w, (bf16_t*)dx, st, res)
-      THIN_SWITCH(d->Cout, CALL)
-#undef CALL
+  if (pl.family != CONV_THIN && pl.family != CONV_HEAD) {
+    if (prepared && !fast) {
+      sg_set_error("sg_conv2d_dgrad: SG_WS_PREPARED planes given, but this launch does not take a prepared-planes kernel");
+      return SG_EINVAL;
+    }
+    if (res && !(fast && pl.res)) {   // of the plane kernels only the slab family adds a collected gradient (callers ask sg_conv2d_planes_job: kind 1)
+      sg_set_error("sg_conv2d_dgrad_acc: this launch takes the %s, which do not add a collected gradient (reduction channels per tap %d, "
+                   "K %d, output columns %d, %d x %d outputs per image)",
+                   !fast ? "fp32-MFMA kernels" : (pl.family == CONV_PATCH ? "patch kernels" : "wide pointwise kernels"), d->Cout,
+                   d->KH * d->KW * d->Cout, d->Cin, d->H, d->W);
+      return SG_EUNSUPPORTED;
+    }
+    if (bnb && !(fast && pl.family == CONV_WIDE && pl.bnb)) {   // only the wide pointwise kernel evaluates the BatchNormalization backward in its A path
+      sg_set_error("sg_conv2d_dgrad_bnb: this launch does not take the wide pointwise kernel");
+      return SG_EUNSUPPORTED;
+    }
+    if (fast && !prepared && !res && ws_bytes < pl.ws_bytes(nb)) {
+      sg_set_error("sg_conv2d_dgrad: workspace %zu < %zu (weight planes + activation planes + split-K partial slabs of %d + %d shares)",
+                   ws_bytes, pl.ws_bytes(nb), pl.x6w_S, pl.b16w_S);
+      return SG_EWORKSPACE;
     }
   }
-  float* wt = (float*)ws;
-  IgemmParams p;
-  fill_dgrad_params(p, d, dy, wt, bias, dx, flags, eb);
-  p.res = (const float*)res;
-  if (!b16 && p.x_ld == d->Cout) p.a_planes = (const unsigned short*)dy_planes;
-  if (bnb) {
-    p.bnb.x = (const float*)bnb->x; p.bnb.mean = (const float*)bnb->mean; p.bnb.invstd = (const float*)bnb->invstd;
-    p.bnb.gamma = (const float*)bnb->gamma; p.bnb.beta = (const float*)bnb->beta; p.bnb.dgamma = (const float*)bnb->dgamma;
-    p.bnb.dbeta = (const float*)bnb->dbeta; p.bnb.dz = (float*)bnb->dz; p.bnb.relu = bnb->relu ? 1 : 0;
-    {
-      static const int abl = getenv("SG_BNB_ABLATE") ? atoi(getenv("SG_BNB_ABLATE")) : 0;   // timing only: 2 = no dz store, 4 = no x load
-      p.bnb.relu |= abl & 6;
-    }
-    p.bnb.inv_n = 1.0f / (float)bnb->rows;
+  if (nb >= d->N) return conv2d_dgrad_launch(ctx, st, dtype, d, pl, fast, dy, w, bias, dx, flags, ws, prepared, res, dy_planes, bnb);
+  for (int n0 = 0; n0 < d->N; n0 += nb) {
+    sg_conv_desc sub = *d;
+    sub.N = (d->N - n0 < nb) ? d->N - n0 : nb;
+    const char* dys = (const char*)dy + (int64_t)n0 * d->Ho * d->Wo * yl * eby;
+    char* dxs = (char*)dx + (int64_t)n0 * (down2 ? (d->H / 2) * (d->W / 2) : d->H * d->W) * xl * ebx;
+    const char* ress = res ? (const char*)res + (int64_t)n0 * d->H * d->W * xl * ebx : nullptr;
+    rc = conv2d_dgrad_launch(ctx, st, dtype, &sub, pl, fast, dys, w, bias, dxs, flags, ws, prepared, ress, nullptr, nullptr);
+    if (rc) return rc;
   }
-  const int ch = b16 ? 8 : 4;
-  const bool vec = (d->Cout % ch == 0) && (p.x_ld % ch == 0) && (d->Cin % 4 == 0) && aligned16(dy);
-  const bool vpad_safe = (p.C % BK == 0) || (p.K == p.C) || (p.x_ld == p.C);
-  if (down2 && !(vpad_safe && x6_ok(p, vec, b16) && x6p_ok(p, d->KH, d->KW))) {  // only the patch kernel knows the flag
-    sg_set_error("sg_conv2d_dgrad: SG_EPI_DOWN2, but this launch does not take the patch kernel");
-    return SG_EUNSUPPORTED;
-  }
-  if (vpad_safe && x6_ok(p, vec, b16)) {
-    static const int perm_on = getenv("SG_DGRAD_PERM2") ? atoi(getenv("SG_DGRAD_PERM2")) : 1;
-    if (perm_on && d->stride == 2 && d->dilation == 1 && d->H % 2 == 0 && d->W % 2 == 0 && d->KH * d->KW <= 64) {
-      p.perm2 = 1;  // rows in parity-class order: see IgemmParams::perm2
-      p.fd_mc = make_fastdiv((uint32_t)(p.M / 4));
-      p.fd_hcwc = make_fastdiv((uint32_t)((d->H / 2) * (d->W / 2)));
-      p.fd_wc = make_fastdiv((uint32_t)(d->W / 2));
-    }
-    p.ws_room = prepared ? SIZE_MAX : ws_bytes;
-    if (b16) return run_x6<1, bf16_t>(p, (const float*)w, true, d->Cin, d->Cout, d->KH, d->KW, ws, ctx->num_cus, st, prepared);
-    if (x6_mode() == 2) return run_x6<1, float>(p, (const float*)w, true, d->Cin, d->Cout, d->KH, d->KW, ws, ctx->num_cus, st, prepared);
-    return run_x6<3, float>(p, (const float*)w, true, d->Cin, d->Cout, d->KH, d->KW, ws, ctx->num_cus, st, prepared);
-  }
-  if (prepared) {
-    sg_set_error("sg_conv2d_dgrad: SG_WS_PREPARED planes given, but this launch does not take a prepared-planes kernel");
-    return SG_EINVAL;
-  }
-  if (res) {
-    sg_set_error("sg_conv2d_dgrad_acc: this launch takes the fp32-MFMA kernels, which do not add a collected gradient");
-    return SG_EUNSUPPORTED;
-  }
-  {
-    dim3 grid((unsigned)sg_cdiv(d->Cout, 32), (unsigned)sg_cdiv(d->Cin, 32), (unsigned)(d->KH * d->KW));
-    hipLaunchKernelGGL(transpose_taps_kernel, grid, dim3(256), 0, st, (const float*)w, wt, d->Cin, d->Cout);
-    SG_LAUNCH_CHECK("transpose_taps_kernel");
-  }
-  if (b16) {
-    const bool vec4 = (d->Cout % 4 == 0) && (p.x_ld % 4 == 0) && (((uintptr_t)dy & 7) == 0);
-    return dispatch_igemm_b16(p, vec4, ctx->num_cus, st);
-  }
-  return dispatch_igemm(p, (d->Cout % 4 == 0) && (p.x_ld % 4 == 0) && (d->Cin % 4 == 0) && aligned16(dy), ctx->num_cus, st);
+  return 0;
 }
 
 size_t sg_conv2d_wgrad_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d) {
@@ -2629,7 +2598,7 @@ int sg_conv2d_wgrad_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc*
                        void* dw, void* dbias, void* ws, size_t ws_bytes, const sg_bn_in* bn) {
   SG_CHECK_ARG(bn && bn->mean && bn->invstd && bn->gamma && bn->beta, "sg_conv2d_wgrad_bn: null BatchNormalization parameters");
   SG_CHECK_ARG(ctx && d, "sg_conv2d_wgrad_bn: null argument");
-  if (check_desc(d, "sg_conv2d_wgrad_bn") || !bn_in_geom(ctx, dtype, d, nullptr)) {
+  if (check_desc(d, "sg_conv2d_wgrad_bn") || !bn_in_geom(ctx, dtype, d)) {
     sg_set_error("sg_conv2d_wgrad_bn: this launch takes neither the thin 1x1 nor the patch filter-gradient kernel");
     return SG_EUNSUPPORTED;
   }

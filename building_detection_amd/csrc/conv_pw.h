@@ -604,7 +604,7 @@ __global__ __launch_bounds__(512, 2) void pw_wide_kernel(const IgemmParams p) {
     // Branch-free stores through a buffer descriptor: a lane outside the tensor (column >= Nout, row >= M) carries an
     // out-of-range offset and the hardware drops its store.  (A per-store `if` is a basic block of its own, and across
     // block boundaries the compiler's wait insertion falls back to vmcnt(0): 96 stores, each waiting for the one before.)
-    const uint32_t y_bytes = (uint32_t)((((int64_t)p.M - 1) * p.y_ld + p.Nout) * 4);   // < 2^31: pw_wide_ok
+    const uint32_t y_bytes = (uint32_t)((((int64_t)p.M - 1) * p.y_ld + p.Nout) * 4);   // < 2^31: launch_pw_wide
     const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)y_bytes, 0x00020000);
     const bool full = m0 + PW_BM <= p.M;   // uniform: no row of this tile is past the end
     const unsigned row0 = (unsigned)(m0 + wm + 4 * lh);
@@ -775,41 +775,35 @@ inline size_t pw_planes_bytes(int K, int N, int npl, int bn = PW_BN) { return (s
 // 2048 -> 6; 256 stays on the 128-wide tiles); at least 6144 rows - 96 workgroups: below that the 128-wide tiles spread the
 // work over more CUs and win (profiles/r03_pw_wide_mscan.txt: 4096 rows 72 vs 47 us, 6144 rows 75 vs 78 us); operands 16-byte
 // aligned.  The weight planes are laid out for one kernel or the other when they are prepared (sg_conv2d_planes_job, which
-// knows the batch), so the same rule must give the same answer at the launch: it reads nothing but the descriptor, and a
-// launch cut into sub-batches (g_sub_batch) never takes the wide kernel.  Both kernels add the same products in the same
+// knows the batch), so the same rule must give the same answer at the launch: both read it from plan_conv, which sees nothing
+// but the descriptor, and a launch cut into sub-batches never takes the wide kernel.  Both kernels add the same products in the same
 // order (16-deep k-steps ascending, the six x6 terms smallest first, one fp32 accumulator), so a tile's result does not
 // depend on which of them its batch size selected (tests/test_fullsize_gpu.py: batch-slice invariance, bit exact).
 // SG_PW_WIDE=0 switches it off, 2 takes every aligned 1x1 (tests).
 // Tile width (round 4): 384 where the last 384-wide tile is at least three quarters full (728, 1536); else 256 where THAT fits
 // (1024, 2048, 256) and the launch brings at least one 128 x 256 tile per CU (16384 rows x 256 columns are 128 tiles: those stay
 // on conv_x6_kernel's 256 tiles of 128 x 128).  SG_PW_WIDE=3: 384 only.
-inline int pw_wide_bn(const IgemmParams& p, int eb) {
+// Geometry fields only; the 16-byte channel runs are x6_ok's `vec` (plan_conv, the one caller).
+inline int pw_wide_width(const IgemmParams& p) {
   static int on = -1;
   if (on < 0) on = getenv("SG_PW_WIDE") ? atoi(getenv("SG_PW_WIDE")) : 1;
   if (!on) return 0;
   if (p.K != p.C || p.a_mul != 1 || p.div != 1 || p.off_h != 0 || p.off_w != 0) return 0;
   // (both activation tensors of a launch are below 2 GiB by construction: larger batches run as sub-batches of whole images,
   // images_per_2gib; launch_pw_wide re-checks)
-  if (eb == 2 && (p.K % 8 != 0 || p.x_ld % 8 != 0 || (reinterpret_cast<uintptr_t>(p.x) & 15) != 0)) return 0;
-  if (eb == 4 && (p.x_ld % 4 != 0 || (reinterpret_cast<uintptr_t>(p.x) & 15) != 0)) return 0;
-  if (g_sub_batch) return 0;
   if (on == 2) return PW_BN;
   if (p.K < 256 || p.M < 6144) return 0;
   // Width by a two-line cost model: one workgroup per CU, so a launch takes ceil(tiles / CUs) rounds of a time proportional to
   // the tile's width - 728 columns at 16384 rows: 384-wide tiles, one round; 1024 columns: 256-wide, two rounds (384-wide tiles
   // were 384 workgroups = two rounds with the second half empty: 167 -> 128 us); 2048 and 512 columns: 256-wide.  A width must
-  // fill three quarters of its columns and, below 384, bring at least 192 tiles.  Ties go to 384, then 256.  SG_PW_WIDE=3: 384
-  // only.  SG_PW_512=1 adds 512-wide tiles (fp32 only: 128 accumulator registers, barrier at the end of the k-step): one round of
-  // them measured no better than two rounds of 256-wide ones (1024 -> 1024: 182 vs 178 us), so they are off.
-  static const int w512 = getenv("SG_PW_512") ? atoi(getenv("SG_PW_512")) : 0;
+  // fill three quarters of its columns and, below 384, bring at least 192 tiles.  Ties go to 384.  SG_PW_WIDE=3: 384 only.
+  // (512-wide tiles - one round instead of two of 256-wide ones - measured no better, 1024 -> 1024: 182 vs 178 us,
+  // profiles/r04_pw_bn256_ab.txt, and are gone.)
   const int64_t ntm = sg_cdiv(p.M, PW_BM);
   int best = 0;
   int64_t best_cost = 0;
-  const int widths[3] = {384, 256, 512};
-  for (int i = 0; i < 3; ++i) {
-    const int bn = widths[i];
+  for (int bn : {384, 256}) {
     if (bn != 384 && on == 3) continue;
-    if (bn == 512 && (!w512 || eb != 4)) continue;
     const int64_t ntn = sg_cdiv(p.Nout, bn), tiles = ntm * ntn;
     if ((double)p.Nout / (double)(ntn * bn) < 0.75) continue;
     if (bn != 384 && tiles < 192) continue;
@@ -818,7 +812,6 @@ inline int pw_wide_bn(const IgemmParams& p, int eb) {
   }
   return best;
 }
-inline bool pw_wide_ok(const IgemmParams& p, int eb) { return pw_wide_bn(p, eb) != 0; }
 
 // =====================================================================================================================
 // The filter gradient of the same layers: dw[ci][co] = sum over pixels x[p][ci] * dy[p][co]   (1x1, stride 1; fp32, x6)

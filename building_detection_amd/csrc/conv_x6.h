@@ -827,7 +827,7 @@ inline bool x6_vpad_on() {
 }
 
 // Can this launch take the bf16-pipe kernels?  UT gather: every 32-deep slab inside one tap - Cin % 32 == 0, a 1x1
-// kernel, or (virtual channel padding, run_x6) any channel count that keeps the pixel rows 16-byte aligned; `vec` =
+// kernel, or (virtual channel padding, plan_conv) any channel count that keeps the pixel rows 16-byte aligned; `vec` =
 // 16-byte channel runs (4 fp32 / 8 bf16).  force: SG_BF16 storage has no other fast kernel, so the mode switch is not asked.
 inline bool x6_ok(const IgemmParams& p, bool vec, bool force = false) {
   const bool ut = (p.C % BK == 0) || (p.K == p.C) || x6_vpad_on();

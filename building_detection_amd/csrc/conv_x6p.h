@@ -43,7 +43,6 @@
 #pragma once
 
 struct IgemmParams;
-inline int x6w_plan(const IgemmParams& p);   // conv_x6w.h: launches of the planes-in kernel keep it (x6p_ok below)
 
 template <int C>
 struct X6P {
@@ -592,11 +591,12 @@ inline bool x6p_enabled() {
   return on;
 }
 
-// geometry the patch form covers; KH, KW are the filter's (IgemmParams carries only K)
-inline bool x6p_ok(const IgemmParams& p, int KH, int KW) {
+// geometry the patch form covers; KH, KW are the filter's (IgemmParams carries only K).  Geometry fields only: plan_conv, the
+// one caller, has the 16-byte channel runs from x6_ok's `vec` and keeps the launches of the planes-in kernel (K >= 2048 and >= 192
+// output columns: conv_x6w.h) off this form
+inline bool x6p_geom(const IgemmParams& p, int KH, int KW) {
   if (!x6p_enabled() || KH != 3 || KW != 3) return false;
-  // 32 or 64 reduction channels per tap in one patch; 128 / 256 / ... in chunks of 64 (round 5) unless the planes-in kernel takes
-  // the launch (K >= 2048 and >= 192 output columns: conv_x6w.h)
+  // 32 or 64 reduction channels per tap in one patch; 128 / 256 / ... in chunks of 64 (round 5)
   if (p.K != 9 * p.C) return false;
   if (!(p.C == 32 || p.C == 64)) {
     static const int multi = getenv("SG_X6P_CHUNKS") ? atoi(getenv("SG_X6P_CHUNKS")) : 1;
@@ -606,14 +606,7 @@ inline bool x6p_ok(const IgemmParams& p, int KH, int KW) {
   const bool fwd = p.k_mul == 1 && p.off_h == -1 && p.off_w == -1, bwd = p.k_mul == -1 && p.off_h == 1 && p.off_w == 1;
   if (!fwd && !bwd) return false;
   if (p.OH != p.H || p.OW != p.W || (p.H % 8) || (p.W % 16)) return false;
-  if (!(p.Nout == 32 || p.Nout == 64 || p.Nout % 128 == 0)) return false;
-  if ((p.x_ld % 4) || (((uintptr_t)p.x) & 15)) return false;
-  if (p.C > 64) {   // (the planes-in kernel declines a launch that adds a collected gradient; the weight planes were laid out
-    IgemmParams q = p;   // for it all the same, so the answer here must not depend on `res`)
-    q.res = nullptr;
-    if (x6w_plan(q) > 0) return false;
-  }
-  return true;
+  return p.Nout == 32 || p.Nout == 64 || p.Nout % 128 == 0;
 }
 
 template <int C, int BN, bool UP2 = false, bool MULTI = false>

@@ -15,7 +15,7 @@
 //   * the weight planes are conv_x6_kernel's own ([3][K / 32][Npad][32], prepared once per step);
 //   * few tiles (the ASPP forward: 128) -> the K walk is cut in two shares, fp32 partial slabs behind the planes, summed (with
 //     bias / ReLU and the BatchNormalization statistics per 128-row tile) by b16w_reduce_kernel<float>.  Shares and kernel
-//     choice depend on one image's geometry only (x6w_plan).
+//     choice depend on one image's geometry only (x6w_shares).
 // Order of additions of an output element: stages in the walk's order (padding taps skipped, channel-block order as in
 // conv_x6_kernel), inside a stage two 16-deep k-steps, inside a k-step the six terms a3b1, a1b3, a2b2, a2b1, a1b2, a1b1 into one
 // fp32 accumulator; shares added in order.  Deterministic and independent of the batch.
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(512, 2) void conv_x6w_kernel(const IgemmParams p, c
   };
 
   // ---- the K walk (conv_b16w_kernel's): active taps, channel-block order, this share's range ------------------------------------
-  // The active taps are a 64-bit mask in SGPRs (x6w_plan: at most 64 taps), the position of the walk is (channel block, tap, slab
+  // The active taps are a 64-bit mask in SGPRs (x6w_shares: at most 64 taps), the position of the walk is (channel block, tap, slab
   // in the block), advanced with scalar selects only: nothing in the stage loop branches, reads LDS or divides for the walk.
   const int ntaps = p.K / p.C;
   const int spt = p.C / XW_KD;
@@ -393,12 +393,14 @@ __global__ __launch_bounds__(512, 2) void conv_x6w_kernel(const IgemmParams p, c
 // and >= 192 output columns - the ASPP forward (two shares) and dgrad (whole), the 3x3 convolutions of the decoder at 256 / 512
 // channels - from ONE image's geometry.  SG_X6_WIDE: 0 off, 1 the dilated ones only (round 4's first form), 2 (default) all of them
 // (step -0.26 ms on alternating runs, profiles/r04_ab_runs.txt block r4t).
-inline int x6w_plan(const IgemmParams& p) {
+// Geometry fields only (plan_conv, the one caller, has the 16-byte channel runs from x6_ok's `vec`).  A launch that adds a collected
+// gradient reads the same weight planes through conv_x6_kernel instead (run_x6): this kernel has no such epilogue.
+inline int x6w_shares(const IgemmParams& p) {
   static const int on = getenv("SG_X6_WIDE") ? atoi(getenv("SG_X6_WIDE")) : 2;
   if (!on) return 0;
-  if (p.div != 1 || p.perm2 || p.res || p.C % XW_KD != 0 || p.K == p.C || p.K < 2048 || p.K / p.C > 64) return 0;
+  if (p.div != 1 || p.C % XW_KD != 0 || p.K == p.C || p.K < 2048 || p.K / p.C > 64) return 0;   // (div 1: never parity-class rows)
   if (on < 2 && !(p.k_mul > 1 || p.k_mul < -1)) return 0;   // 1: dilated taps only
-  if (p.x_ld % 4 != 0 || (reinterpret_cast<uintptr_t>(p.x) & 15) != 0 || p.x_bytes == 0 || p.Nout % 4 != 0) return 0;
+  if (p.x_ld % 4 != 0 || p.x_bytes == 0 || p.Nout % 4 != 0) return 0;
   const int64_t ntn = sg_cdiv(p.Nout, XW_N);
   if ((double)p.Nout / (double)(ntn * XW_N) < 0.75) return 0;
   const int64_t img_px = (int64_t)p.OH * p.OW;
@@ -409,13 +411,11 @@ inline int x6w_plan(const IgemmParams& p) {
   return 0;
 }
 
-// planes of the A operand (3 x pixels x C bf16, 256-byte aligned) + partial slabs of a split-K launch
+// planes of the A operand (3 x pixels x C bf16, 256-byte aligned); the partial slabs of a split-K launch follow them
+// (ConvPlan::scratch_bytes sizes both)
 inline size_t x6w_a_planes_bytes(const IgemmParams& p) {
   const int64_t batch = p.M / ((int64_t)p.OH * p.OW);
   return (((size_t)3 * (size_t)batch * p.H * p.W * p.C * 2) + 255) & ~(size_t)255;
-}
-inline size_t x6w_scratch_bytes(const IgemmParams& p, int S) {
-  return x6w_a_planes_bytes(p) + (S > 1 ? (size_t)S * (size_t)p.M * p.Nout * sizeof(float) : 0);
 }
 
 // scratch: [A planes][partial slabs]

@@ -461,9 +461,11 @@ def test_conv_dgrad_adds_a_collected_gradient(engine, case, dtype):
 def test_dgrad_kernel_choice_does_not_depend_on_a_collected_gradient(engine, case, kind_wanted, same_kernel):
     """include/segengine.h, sg_conv2d_dgrad_acc: a launch adds `res` exactly when sg_conv2d_planes_job (which knows no `res`) says
     kind 1 for it - the weight planes of a step are laid out from that answer, so the launch must come to the same one with `res` as
-    without.  Round 5: x6p_ok asked x6w_plan, which declines a launch that carries `res`; the decoder's 64^2 x 512 -> 256 dgrad then took
-    the patch kernel on planes laid out for the slab kernel's family and refused (loudly) in the training step - no op test saw it
-    (scripts/regress_kernel_choice.sh rebuilds with that form: `long_k_256ch` then fails with the step's rc=-3, profiles/r05_regress_kernel_choice.txt).
+    without.  Round 5: the patch kernel's predicate asked the planes-in kernel's, which declined a launch that carried `res`; the
+    decoder's 64^2 x 512 -> 256 dgrad then took the patch kernel on planes laid out for the slab kernel's family and refused (loudly)
+    in the training step - no op test saw it (profiles/r05_regress_kernel_choice.txt is the record: with that form `long_k_256ch`
+    failed with the step's rc=-3).  The job and the launch now read one plan, plan_conv(), whose signature has neither pointers nor
+    `res`, so the choice cannot depend on it; this test stays as the check from outside.
     Kind 1: accepted, and dgrad + res - bit for bit where the launch takes the same kernel with and without `res`, within the
     rounding of two fp32 summation orders where it does not.  Kinds 2 / 3: SG_EUNSUPPORTED and nothing launched (dx untouched)."""
     import ctypes as C

@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""The plan table: what the library answers about every convolution site of the five models - the planes-job fields and slot size
+(sg_conv2d_planes_job), the workspace query and the planes_in / up2_supported / bn_in_supported / dgrad_bnb_supported answers for
+every unique (site, storage, arithmetic mode, direction).  A change of plan_conv() (csrc/conv_igemm.hip) is diffed against its
+parent with this: every line that moved is a launch that takes another kernel, other planes or another workspace.  The sites are the
+ones tests/test_plane_sites_gpu.py sweeps (tests/_plane_sites.py enumerates them).  Needs the GPU only for the library context.
+
+Folded so that the table can be read: one line per (direction, head, descriptor without N) with the batch sizes it occurs at and the
+workspace query (which knows neither storage nor mode); behind it one group per set of arithmetics with equal answers (x0 / x1 / x2:
+fp32 storage under sg_set_conv_x6 0 / 1 / 2, b16: bf16 storage); inside a group the batch sizes with equal answers share one
+entry, and a value that is the same at every batch is printed once.
+Use: python scripts/plan_table.py > profiles/plan_table.txt"""
+import collections
+import ctypes as C
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+Row = collections.namedtuple("Row", "arith dgrad head desc kind npl kd K Kpad N Npad Ck Ckp nblocks bytes ws pin up2 bn_in bnb")
+
+
+def rows():
+    """every answer of the library, unfolded (needs the GPU)"""
+    import _plane_sites as PS
+    from building_detection_amd import _lib
+    from building_detection_amd.ops import get_engine
+    e = get_engine(0)
+    uniq, _ = PS.unique_sites(PS.enumerate_groups())
+    info = PS.survey(e, uniq)
+    out = []
+    for mode in (0, 1, 2, None):
+        with PS.mode_set(e, mode):
+            for (k, m), i in info.items():
+                if m != mode:
+                    continue
+                s = uniq[k]
+                d = PS.make_desc(s)
+                st = _lib.SG_F32 if s.policy == "float32" else _lib.SG_BF16
+                out.append(Row("b16" if mode is None else f"x{mode}", s.dgrad, s.head, dict(zip(PS.desc_fields(), s.desc)), i.kind, i.npl, i.kd,
+                               i.K, i.Kpad, i.N, i.Npad, i.Ck, i.Ckp, i.nblocks, i.bytes, i.ws, i.pin,
+                               e.lib.sg_conv2d_up2_supported(st, C.byref(d)), e.lib.sg_conv2d_bn_in_supported(e.h, st, C.byref(d)),
+                               e.lib.sg_conv2d_dgrad_bnb_supported(e.h, st, C.byref(d))))
+    return len(uniq), out
+
+
+def once(vals):
+    vals = [str(v) for v in vals]
+    return vals[0] if len(set(vals)) == 1 else ",".join(vals)
+
+
+def fold(n_unique, rs):
+    table, ws = collections.OrderedDict(), collections.defaultdict(dict)   # line -> arithmetic -> batch -> (answer, slot bytes)
+    for r in rs:
+        f = r.desc
+        key = (f"{'dgrad' if r.dgrad else 'fwd'}{' head' if r.head else ''} {f['H']}x{f['W']}x{f['Cin']}>{f['Cout']} "
+               f"k{f['KH']}s{f['stride']}d{f['dilation']} o{f['Ho']}x{f['Wo']}")
+        sup = f"sup{r.up2}{r.bn_in}{r.bnb}"
+        ans = f"kind0 {sup}" if r.kind == 0 else (f"kind{r.kind} npl{r.npl} kd{r.kd} K{r.K}/{r.Kpad} N{r.N}/{r.Npad} Ck{r.Ck}/{r.Ckp} "
+                                                   f"nb{r.nblocks} pin{r.pin} {sup}")
+        table.setdefault(key, collections.OrderedDict()).setdefault(r.arith, {})[f["N"]] = (ans, r.bytes)
+        assert ws[key].setdefault(f["N"], r.ws) == r.ws   # (the query knows neither storage nor mode)
+    lines = [f"# {n_unique} unique sites, {len(rs)} (site, storage, mode, direction) answers on {len(table)} lines",
+             "# <direction> [head] HxWxCin>Cout k<K>s<stride>d<dilation> o<Ho>x<Wo> b<batch sizes> ws <sg_conv2d_{fwd,dgrad}_ws_bytes per batch>",
+             "#   | <arithmetics with equal answers>: [b<batches>:] kind npl kd K/Kpad N/Npad Ck/Ckp nb<nblocks> pin<planes_in> "
+             "sup<up2, bn_in, dgrad_bnb supported> B<slot bytes per batch> ; ...   (an arithmetic that is absent has no such site)"]
+    for key, ariths in table.items():
+        batches = sorted(ws[key])
+        line = f"{key} b{','.join(map(str, batches))} ws {once(ws[key][b] for b in batches)}"
+        texts = collections.OrderedDict()
+        for arith, per in ariths.items():
+            by_ans = collections.OrderedDict()
+            for b in sorted(per):
+                by_ans.setdefault(per[b][0], []).append(b)
+            parts = []
+            for ans, bs in by_ans.items():
+                size = "" if ans.startswith("kind0") else f" B{once(per[b][1] for b in bs)}"
+                parts.append((f"b{','.join(map(str, bs))}: " if (len(by_ans) > 1 or sorted(per) != batches) else "") + ans + size)
+            texts.setdefault("; ".join(parts), []).append(arith)
+        for txt, names in texts.items():
+            line += f" | {','.join(names)}: {txt}"
+        lines.append(line)
+    return lines
+
+
+if __name__ == "__main__":
+    print("\n".join(fold(*rows())))

@@ -1,0 +1,236 @@
+"""Guarded device operands and plain float64 references for tests/test_bandwidth_variants_gpu.py.
+
+Every operand of a launch lives in its own uint8 arena: BAND bytes of 0xFF, the operand, BAND bytes of 0xFF.  0xFF.. is a NaN
+in fp32 and in bf16, so a read outside an operand that reaches the arithmetic poisons the result, and a write outside it changes
+a band.  The arena's bytes as uploaded are kept on the host; after the launch the bands (and, for an input, the operand) must be
+byte-identical.  Nothing here needs a GPU: `device` may be "cpu" (the self-checks of the harness run there).
+"""
+import math
+
+import torch
+
+BAND = 1024   # bytes in front of and behind every operand (a multiple of 16: the operand starts 16-byte aligned)
+INF = float("inf")
+
+
+def _bits(t):
+    return t.contiguous().reshape(-1).view(torch.uint8)
+
+
+class Guarded:
+    """One device operand between two guard bands.  role: "in" (bits must survive the launch), "out" (anything may be written
+    inside the operand) or "ws" (a workspace: only the bands are looked at)."""
+
+    def __init__(self, host, device, off=False, role="in"):
+        host = host.detach().cpu()
+        self.shape, self.dtype, self.role = tuple(host.shape), host.dtype, role
+        self.es = host.element_size()
+        self.nb = host.numel() * self.es
+        # 16-byte aligned, or one element further: the dispatch code promises its scalar kernels for such tensors
+        self.start = BAND + (self.es if off else 0)
+        arena = torch.full((self.start + self.nb + BAND,), 0xFF, dtype=torch.uint8)
+        arena[self.start:self.start + self.nb] = _bits(host)
+        self.before = arena
+        self.dev = arena.clone().to(device)
+        assert self.dev.data_ptr() % 16 == 0, "allocator returned a block that is not 16-byte aligned"
+        self.after = None
+
+    @classmethod
+    def out(cls, shape, dtype, device, off=False, role="out", fill=0xFF):
+        """A non-accumulating output: every byte `fill` (0xFF = NaN for float types) before the launch."""
+        shape = tuple(shape)
+        n = math.prod(shape)
+        es = torch.empty((), dtype=dtype).element_size()
+        host = torch.full((n * es,), fill, dtype=torch.uint8).view(dtype).reshape(shape)
+        return cls(host, device, off=off, role=role)
+
+    @classmethod
+    def ws(cls, nbytes, device):
+        """A workspace of exactly `nbytes` bytes (16-byte aligned), NaN-filled, a band right behind its last byte."""
+        return cls.out((max(int(nbytes), 1),), torch.uint8, device, role="ws")
+
+    def ptr(self, elem_off=0):
+        return self.dev.data_ptr() + self.start + elem_off * self.es
+
+    def fetch(self):
+        self.after = self.dev.cpu()
+        return self
+
+    def read(self):
+        if self.after is None:
+            self.fetch()
+        return self.after[self.start:self.start + self.nb].clone().view(self.dtype).reshape(self.shape)
+
+    def check(self, what=""):
+        if self.after is None:
+            self.fetch()
+        a, b, s, e = self.after, self.before, self.start, self.start + self.nb
+        assert torch.equal(a[:s], b[:s]), f"{what}: the band in front of a {self.role} operand {self.shape} changed"
+        assert torch.equal(a[e:], b[e:]), f"{what}: the band behind a {self.role} operand {self.shape} changed"
+        if self.role == "in":
+            assert torch.equal(a[s:e], b[s:e]), f"{what}: an input operand {self.shape} changed"
+
+
+def check_all(ops, what=""):
+    for o in ops:
+        o.fetch().check(what)
+
+
+def assert_written(t, what="", fill=0xFF):
+    """No prefill value may remain inside a non-accumulating output (float: NaN; integer: the fill byte)."""
+    if t.dtype.is_floating_point:
+        bad = torch.isnan(t.float())
+    else:
+        bad = _bits(t) == fill
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {t.numel()} output elements still hold the prefill value"
+
+
+def close(got, ref, tol, what=""):
+    """max|got - ref| <= tol * max|ref| over the whole tensor; nothing masked."""
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
+    assert torch.isfinite(got).all(), f"{what}: non-finite values in the result"
+    scale = ref.abs().max().item() if ref.numel() else 0.0
+    err = (got - ref).abs().max().item() if ref.numel() else 0.0
+    assert err <= tol * scale, f"{what}: max err {err:.3e} > {tol:.3e} * {scale:.3e} (rel {err / max(scale, 1e-300):.2e})"
+    return err
+
+
+def same_outside(after, before, sl, what=""):
+    """Channels outside the written slice `sl` (last axis) keep their exact prior bits."""
+    keep = torch.ones(before.shape[-1], dtype=torch.bool)
+    keep[sl] = False
+    a = after[..., keep].contiguous()
+    b = before[..., keep].contiguous()
+    assert torch.equal(_bits(a), _bits(b)), f"{what}: channels outside the slice changed"
+
+
+# ------------------------------------------------------------------------------------------------ references (float64)
+def sigmoid(v):
+    return 1.0 / (1.0 + torch.exp(-v))
+
+
+def seg_plan_s(cus, rows, C, vec):
+    """The row split S of seg_plan<1> (csrc/sg_reduce.h) for one segment of `rows` rows and C channels."""
+    V = 4 if (vec and C % 4 == 0) else 1
+    chunks = C // V
+    tx = 1
+    while tx < chunks and tx < 16:
+        tx <<= 1
+    ty = 256 // tx
+    gx = -(-chunks // tx)
+    S = min(-(-4 * cus // gx), -(-rows // (ty * 4)))
+    if rows <= ty * 16:
+        S = 1
+    return max(1, min(S, 1024))
+
+
+def regime(S):
+    return "one" if S == 1 else ("few" if S < 32 else "many")
+
+
+def pool_geom(H, k, s, same):
+    """(Ho, pad_before) of MaxPooling2D: TF 'same' / 'valid'."""
+    if same:
+        Ho = -(-H // s)
+        return Ho, max((Ho - 1) * s + k - H, 0) // 2
+    return (H - k) // s + 1, 0
+
+
+def _pool_slices(a, b, s, Ho, Wo):
+    return slice(a, a + (Ho - 1) * s + 1, s), slice(b, b + (Wo - 1) * s + 1, s)
+
+
+def maxpool_ref(x, k, s, pt, pl, Ho, Wo):
+    """Window max with -inf padding and the cell (a * k + b, scan order) of the FIRST maximum (strict '>')."""
+    N, H, W, C = x.shape
+    Hp, Wp = max((Ho - 1) * s + k, pt + H), max((Wo - 1) * s + k, pl + W)
+    xp = torch.full((N, Hp, Wp, C), -INF, dtype=x.dtype)
+    xp[:, pt:pt + H, pl:pl + W] = x
+    inside = torch.zeros(Hp, Wp, dtype=torch.bool)
+    inside[pt:pt + H, pl:pl + W] = True
+    best = torch.full((N, Ho, Wo, C), -INF, dtype=x.dtype)
+    idx = torch.full((N, Ho, Wo, C), 255, dtype=torch.int64)
+    for a in range(k):
+        for b in range(k):
+            sa, sb = _pool_slices(a, b, s, Ho, Wo)
+            v = xp[:, sa, sb]
+            take = inside[sa, sb][None, :, :, None] & ((v > best) | (idx == 255))
+            best = torch.where(take, v, best)
+            idx = torch.where(take, torch.full_like(idx, a * k + b), idx)
+    return best, idx.to(torch.uint8)
+
+
+def maxpool_bwd_ref(dy, idx, k, s, pt, pl, H, W):
+    """dy routed to the recorded cell of every window, summed per input element."""
+    N, Ho, Wo, C = dy.shape
+    Hp, Wp = max((Ho - 1) * s + k, pt + H), max((Wo - 1) * s + k, pl + W)
+    dxp = torch.zeros((N, Hp, Wp, C), dtype=dy.dtype)
+    for a in range(k):
+        for b in range(k):
+            sa, sb = _pool_slices(a, b, s, Ho, Wo)
+            dxp[:, sa, sb] += dy * (idx == a * k + b)
+    return dxp[:, pt:pt + H, pl:pl + W].contiguous()
+
+
+def avgpool_ref(x, kh, kw):
+    N, H, W, C = x.shape
+    Ho, Wo = H // kh, W // kw
+    return x[:, :Ho * kh, :Wo * kw].reshape(N, Ho, kh, Wo, kw, C).mean(dim=(2, 4))
+
+
+def avgpool_bwd_ref(dy, H, W, kh, kw):
+    N, Ho, Wo, C = dy.shape
+    dx = torch.zeros((N, H, W, C), dtype=dy.dtype)
+    dx[:, :Ho * kh, :Wo * kw] = dy.repeat_interleave(kh, 1).repeat_interleave(kw, 2) / (kh * kw)
+    return dx
+
+
+def upsample_ref(x, sh, sw):
+    return x.repeat_interleave(sh, 1).repeat_interleave(sw, 2)
+
+
+def upsample_bwd_ref(dy, sh, sw):
+    N, OH, OW, C = dy.shape
+    return dy.reshape(N, OH // sh, sh, OW // sw, sw, C).sum(dim=(2, 4))
+
+
+K_EPS = 1e-7   # tf.keras.backend.epsilon()
+
+
+def loss_coeffs(kind, yt):
+    y = yt[:, :2]
+    if kind == 0:
+        return y
+    if kind == 1:
+        return 0.5 * y
+    return torch.tensor([0.35, 0.65], dtype=yt.dtype) * yt[:, 2:4] * y
+
+
+def loss_ref(kind, p, yt):
+    a = loss_coeffs(kind, yt)
+    f = torch.ones_like(p) if kind == 0 else (1 - p) ** 2
+    return -(a * f * torch.log(p + K_EPS)).sum() / p.shape[0]
+
+
+def loss_bwd_ref(kind, p, yt, scale):
+    a = loss_coeffs(kind, yt)
+    if kind == 0:
+        g = 1 / (p + K_EPS)
+    else:
+        g = -2 * (1 - p) * torch.log(p + K_EPS) + (1 - p) ** 2 / (p + K_EPS)
+    return -(scale / p.shape[0]) * a * g
+
+
+def confusion_ref(p, yt):
+    """{TP, TN, FP, FN}; argmax ties go to class 0 on both sides."""
+    pred, truth = p[:, 1] > p[:, 0], yt[:, 1] > yt[:, 0]
+    return torch.tensor([(pred & truth).sum(), (~pred & ~truth).sum(), (pred & ~truth).sum(), (~pred & truth).sum()],
+                        dtype=torch.int64)
+
+
+def adam_ref(w, m, v, g, lr_t, b1, b2, eps, gs):
+    g = g * gs
+    m = b1 * m + (1 - b1) * g
+    v = b2 * v + (1 - b2) * g * g
+    return w - lr_t * m / (torch.sqrt(v) + eps), m, v

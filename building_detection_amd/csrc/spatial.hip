@@ -1,6 +1,6 @@
 // HBM-bound spatial kernels of the hot path (NHWC, channels innermost so every access is a coalesced run of
 // 16-byte channel chunks): depthwise 3x3 (SeparableConv2D's first half) forward / dgrad / wgrad, max / average
-// pooling, nearest up-sampling.
+// pooling, nearest and bilinear up-sampling.
 #include "sg_reduce.h"
 
 namespace {
@@ -1286,6 +1286,191 @@ __global__ __launch_bounds__(256) void upsample_bwd_window_kernel(const T* __res
   }
 }
 
+// ---------------------------------------------------------------------------------------- bilinear up-sampling
+// tf.image.resize(method='bilinear'), half-pixel centres, integer factor s per axis.  Output o = i * s + p (phase p) sits at
+// in = i + t, t = (2p + 1 - s) / (2s) in [-1/2, 1/2):
+//   t < 0: lo = max(i - 1, 0), hi = i,                 f = t + 1
+//   t > 0: lo = i,             hi = min(i + 1, n - 1), f = t
+//   t = 0: lo = hi = i,                                f = 0      (odd s only; s = 1 is a copy)
+// so the weights depend on the phase alone and come from a per-axis table built in LDS by every workgroup (one correctly
+// rounded division of two small integers per entry; no division per element).
+__device__ __forceinline__ float bilinear_phase(int p, int s) {
+  const int t2 = 2 * p + 1 - s;
+  return (float)(t2 < 0 ? t2 + 2 * s : t2) / (float)(2 * s);
+}
+
+__device__ __forceinline__ void bilinear_taps(int i, int p, int s, int n, int& lo, int& hi) {
+  const int t2 = 2 * p + 1 - s;
+  lo = t2 < 0 ? max(i - 1, 0) : i;
+  hi = t2 > 0 ? min(i + 1, n - 1) : i;
+}
+
+// One work item = one output pixel x V channels: four loads (the 2 x 2 neighbours, three of them cache hits), columns
+// first, then rows (tf's order), one store.
+template <int V, typename T>
+__global__ void upsample_bilinear_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W, int C, int sh,
+                                             int sw, int y_ld, FastDiv fd_cv, FastDiv fd_w, FastDiv fd_h, FastDiv fd_sh,
+                                             FastDiv fd_sw) {
+  extern __shared__ float bilinear_tab[];   // [sh] row phases, then [sw] column phases
+  for (int p = threadIdx.x; p < sh + sw; p += blockDim.x) bilinear_tab[p] = p < sh ? bilinear_phase(p, sh) : bilinear_phase(p - sh, sw);
+  __syncthreads();
+  const float* fh = bilinear_tab;
+  const float* fw = bilinear_tab + sh;
+  const uint32_t cv = C / V;
+  const int OH = H * sh, OW = W * sw;
+  const uint32_t total = (uint32_t)((int64_t)N * OH * OW * cv), stride = gridDim.x * blockDim.x;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    uint32_t pix, cc, row, ow, n, oh, ih, ph, iw, pw;
+    fd_divmod(i, fd_cv, pix, cc);
+    fd_divmod(pix, fd_w, row, ow);
+    fd_divmod(row, fd_h, n, oh);
+    fd_divmod(oh, fd_sh, ih, ph);
+    fd_divmod(ow, fd_sw, iw, pw);
+    const int c = (int)cc * V;
+    int h0, h1, w0, w1;
+    bilinear_taps((int)ih, (int)ph, sh, H, h0, h1);
+    bilinear_taps((int)iw, (int)pw, sw, W, w0, w1);
+    const float fy = fh[ph], fx = fw[pw];
+    const T* r0 = x + ((int64_t)n * H + h0) * W * C + c;
+    const T* r1 = x + ((int64_t)n * H + h1) * W * C + c;
+    float tl[V], tr[V], bl[V], br[V], o[V];
+    ldv<V>(r0 + (int64_t)w0 * C, tl);
+    ldv<V>(r0 + (int64_t)w1 * C, tr);
+    ldv<V>(r1 + (int64_t)w0 * C, bl);
+    ldv<V>(r1 + (int64_t)w1 * C, br);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const float top = fmaf(tr[k] - tl[k], fx, tl[k]), bot = fmaf(br[k] - bl[k], fx, bl[k]);
+      o[k] = fmaf(bot - top, fy, top);
+    }
+    stv<V>(y + (int64_t)pix * y_ld + c, o);
+  }
+}
+
+// The transpose, as a gather so that no atomics are needed and the order of every sum is fixed (run-to-run bit-identity
+// and batch-slice invariance rest on that).  Per axis, dx[i] hears from the outputs o0 + d, o0 = (i - 1) * s + (s + 1) / 2,
+// d in [0, 2s - (s & 1)): the upper phases of block i - 1, block i, the lower phases of block i + 1.  Their weight is the
+// tent 1 - |in(o) - i| = wt[d], independent of i, except at the borders: outputs clamped onto row 0 / row n - 1 count in
+// full.  The table holds the numerators over 2s, each one correctly rounded division.
+__device__ __forceinline__ float bilinear_tent(int d, int s) {
+  const int orel = d + (s + 1) / 2, blk = orel / s, t2 = 2 * (orel - blk * s) + 1 - s;
+  const int num = blk == 0 ? t2 : blk == 1 ? (t2 < 0 ? t2 + 2 * s : 2 * s - t2) : (t2 < 0 ? -t2 : 0);
+  return (float)num / (float)(2 * s);
+}
+
+__device__ __forceinline__ void bilinear_tent_tables(float* tab, int sh, int sw) {   // [2 sh] rows, then [2 sw] columns
+  for (int p = threadIdx.x; p < 2 * (sh + sw); p += blockDim.x) tab[p] = p < 2 * sh ? bilinear_tent(p, sh) : bilinear_tent(p - 2 * sh, sw);
+  __syncthreads();
+}
+
+__device__ __forceinline__ float bilinear_weight(const float* wt, int d, int o, int i, int n, int s) {
+  return ((i == 0 && o < s / 2) || (i == n - 1 && o >= (n - 1) * s + (s + 1) / 2)) ? 1.f : wt[d];
+}
+
+// first and one-past-last d of axis position i whose output o0 + d exists
+__device__ __forceinline__ void bilinear_span(int i, int n, int s, int& o0, int& d0, int& d1) {
+  o0 = (i - 1) * s + (s + 1) / 2;
+  d0 = max(0, -o0);
+  d1 = min(2 * s - (s & 1), n * s - o0);
+}
+
+// One work item = one dx pixel x V channels; it walks its at most 2 sh x 2 sw outputs rows outer, columns inner.
+template <int V, typename T>
+__global__ void upsample_bilinear_bwd_kernel(const T* __restrict__ dy, int dy_ld, T* __restrict__ dx, int N, int H, int W,
+                                             int C, int sh, int sw, int accumulate, FastDiv fd_cv, FastDiv fd_w, FastDiv fd_h) {
+  extern __shared__ float bilinear_tab[];
+  bilinear_tent_tables(bilinear_tab, sh, sw);
+  const float* wth = bilinear_tab;
+  const float* wtw = bilinear_tab + 2 * sh;
+  const uint32_t cv = C / V;
+  const uint32_t total = (uint32_t)((int64_t)N * H * W * cv), stride = gridDim.x * blockDim.x;
+  const int OW = W * sw, OH = H * sh;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    uint32_t pix, cc, row, iw, n, ih;
+    fd_divmod(i, fd_cv, pix, cc);
+    fd_divmod(pix, fd_w, row, iw);
+    fd_divmod(row, fd_h, n, ih);
+    const int c = (int)cc * V;
+    int oh0, a0, a1, ow0, b0, b1;
+    bilinear_span((int)ih, H, sh, oh0, a0, a1);
+    bilinear_span((int)iw, W, sw, ow0, b0, b1);
+    float acc[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = 0.f;
+    for (int a = a0; a < a1; ++a) {
+      const float wy = bilinear_weight(wth, a, oh0 + a, (int)ih, H, sh);
+      const T* rowp = dy + (((int64_t)n * OH + oh0 + a) * OW + ow0) * dy_ld + c;
+      for (int b = b0; b < b1; ++b) {
+        const float wgt = wy * bilinear_weight(wtw, b, ow0 + b, (int)iw, W, sw);
+        float g[V];
+        ldv<V>(rowp + (int64_t)b * dy_ld, g);
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[k] = fmaf(g[k], wgt, acc[k]);
+      }
+    }
+    if (accumulate) {
+      float t[V];
+      ldv<V>(dx + (int64_t)pix * C + c, t);
+#pragma unroll
+      for (int k = 0; k < V; ++k) acc[k] += t[k];
+    }
+    stv<V>(dx + (int64_t)pix * C + c, acc);
+  }
+}
+
+// Large factors (the ASPP image-pooling branch again: 1x1 -> 32x32), the shape of upsample_bwd_window_kernel: a workgroup
+// owns one dx pixel and 8 channel chunks, 32 lanes share the pixel's cells (cell r = row-major index in its span, lane ty
+// takes r = ty, ty + 32, ...), the 32 partial sums are added in fixed order through LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void upsample_bilinear_bwd_window_kernel(const T* __restrict__ dy, int dy_ld, T* __restrict__ dx,
+                                                                           int H, int W, int C, int sh, int sw, int accumulate,
+                                                                           FastDiv fd_w, FastDiv fd_h) {
+  constexpr int TX = 8, TY = 32;
+  __shared__ float red[TY][TX][4];
+  extern __shared__ float bilinear_tab[];
+  bilinear_tent_tables(bilinear_tab, sh, sw);
+  const float* wth = bilinear_tab;
+  const float* wtw = bilinear_tab + 2 * sh;
+  const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> 3;
+  const int c = (blockIdx.x * TX + tx) * 4;
+  uint32_t row, iw, n, ih;
+  fd_divmod(blockIdx.y, fd_w, row, iw);
+  fd_divmod(row, fd_h, n, ih);
+  const int OW = W * sw, OH = H * sh;
+  int oh0, a0, a1, ow0, b0, b1;
+  bilinear_span((int)ih, H, sh, oh0, a0, a1);
+  bilinear_span((int)iw, W, sw, ow0, b0, b1);
+  const int nw = b1 - b0, cells = (a1 - a0) * nw;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (c < C) {
+    const T* base = dy + (((int64_t)n * OH + oh0) * OW + ow0) * dy_ld + c;
+    int a = a0 + ty / nw, b = b0 + ty % nw;
+    for (int r = ty; r < cells; r += TY) {
+      const float wgt = bilinear_weight(wth, a, oh0 + a, (int)ih, H, sh) * bilinear_weight(wtw, b, ow0 + b, (int)iw, W, sw);
+      const f32x4 g = ld4<T>(base + ((int64_t)a * OW + b) * dy_ld);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] = fmaf(g[e], wgt, acc[e]);
+      for (b += TY; b >= b1; b -= nw) ++a;
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) red[ty][tx][e] = acc[e];
+  __syncthreads();
+  if (ty == 0 && c < C) {
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    for (int y = 0; y < TY; ++y)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] += red[y][tx][e];
+    T* o = dx + (int64_t)blockIdx.y * C + c;
+    if (accumulate) {
+      const f32x4 t = ld4<T>(o);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] += t[e];
+    }
+    st4<T>(o, s);
+  }
+}
+
 int dw_check(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, const char* who) {
   SG_CHECK_ARG(ctx && (dtype == SG_F32 || dtype == SG_BF16) && d, "%s: bad ctx/dtype/desc", who);
   SG_CHECK_ARG(d->Cin == d->Cout, "%s: depthwise needs Cin == Cout (depth_multiplier 1)", who);
@@ -1784,6 +1969,66 @@ int sg_upsample_nearest_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, 
                          N, H, W, C, sh, sw, accumulate, a, b, c);
   });
   SG_LAUNCH_CHECK("upsample_bwd_kernel");
+  return 0;
+}
+
+// The phase tables live in LDS, so a factor is capped (far above any use: the ASPP branch's 32 is the largest known).
+#define SG_BILINEAR_MAX_FACTOR 1024
+
+int sg_upsample_bilinear_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int sh, int sw,
+                             const void* x, void* y, int y_ld) {
+  SG_CHECK_ARG(ctx && x && y, "sg_upsample_bilinear_fwd: bad argument");
+  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && sh > 0 && sw > 0 && sh <= SG_BILINEAR_MAX_FACTOR && sw <= SG_BILINEAR_MAX_FACTOR,
+               "sg_upsample_bilinear_fwd: bad geometry");
+  if (y_ld == 0) y_ld = C;
+  SG_CHECK_ARG(y_ld >= C, "sg_upsample_bilinear_fwd: y_ld < C");
+  SG_CHECK_ARG((int64_t)N * H * sh * W * sw * y_ld < (1ll << 31), "sg_upsample_bilinear_fwd: tensor exceeds 2^31 elements");
+  // the vector form under sg_upsample_nearest_fwd's conditions
+  const bool vec = (C % 4 == 0) && (y_ld % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
+  const int V = vec ? 4 : 1;
+  const unsigned blocks = ew_blocks((int64_t)N * H * sh * W * sw * (C / V));
+  const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)(W * sw)), c = make_fastdiv((uint32_t)(H * sh));
+  const FastDiv dh = make_fastdiv((uint32_t)sh), dw = make_fastdiv((uint32_t)sw);
+  const size_t lds = (size_t)(sh + sw) * sizeof(float);
+  SG_DTYPE_SWITCH(dtype, "sg_upsample_bilinear_fwd", {
+    if (vec)
+      hipLaunchKernelGGL((upsample_bilinear_fwd_kernel<4, T>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const T*)x, (T*)y,
+                         N, H, W, C, sh, sw, y_ld, a, b, c, dh, dw);
+    else
+      hipLaunchKernelGGL((upsample_bilinear_fwd_kernel<1, T>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const T*)x, (T*)y,
+                         N, H, W, C, sh, sw, y_ld, a, b, c, dh, dw);
+  });
+  SG_LAUNCH_CHECK("upsample_bilinear_fwd_kernel");
+  return 0;
+}
+
+int sg_upsample_bilinear_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int sh, int sw,
+                             const void* dy, int dy_ld, void* dx, int accumulate) {
+  SG_CHECK_ARG(ctx && dy && dx, "sg_upsample_bilinear_bwd: bad argument");
+  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && sh > 0 && sw > 0 && sh <= SG_BILINEAR_MAX_FACTOR && sw <= SG_BILINEAR_MAX_FACTOR,
+               "sg_upsample_bilinear_bwd: bad geometry");
+  if (dy_ld == 0) dy_ld = C;
+  SG_CHECK_ARG(dy_ld >= C, "sg_upsample_bilinear_bwd: dy_ld < C");
+  SG_CHECK_ARG((int64_t)N * H * sh * W * sw * dy_ld < (1ll << 31), "sg_upsample_bilinear_bwd: tensor exceeds 2^31 elements");
+  const bool vec = (C % 4 == 0) && (dy_ld % 4 == 0) && sg_aligned16(dy) && sg_aligned16(dx);
+  const int V = vec ? 4 : 1;
+  const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V));
+  const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)W), c = make_fastdiv((uint32_t)H);
+  const size_t lds = (size_t)2 * (sh + sw) * sizeof(float);
+  SG_DTYPE_SWITCH(dtype, "sg_upsample_bilinear_bwd", {
+    // The window kernel under sg_upsample_nearest_bwd's predicate: 16-byte channel chunks, at least 64 cells per block of
+    // the factor (a dx pixel then has up to 4 sh sw >= 256 taps), and few enough dx pixels for grid.y.
+    if (vec && sh * sw >= 64 && (int64_t)N * H * W < 65536) {
+      hipLaunchKernelGGL((upsample_bilinear_bwd_window_kernel<T>), dim3((unsigned)sg_cdiv(C / 4, 8), (unsigned)(N * H * W)), dim3(256),
+                         lds, (hipStream_t)stream, (const T*)dy, dy_ld, (T*)dx, H, W, C, sh, sw, accumulate, b, c);
+    } else if (vec)
+      hipLaunchKernelGGL((upsample_bilinear_bwd_kernel<4, T>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const T*)dy, dy_ld,
+                         (T*)dx, N, H, W, C, sh, sw, accumulate, a, b, c);
+    else
+      hipLaunchKernelGGL((upsample_bilinear_bwd_kernel<1, T>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const T*)dy, dy_ld,
+                         (T*)dx, N, H, W, C, sh, sw, accumulate, a, b, c);
+  });
+  SG_LAUNCH_CHECK("upsample_bilinear_bwd_kernel");
   return 0;
 }
 

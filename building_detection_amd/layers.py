@@ -719,22 +719,27 @@ GlobalAvgPool2D = GlobalAveragePooling2D
 class _UpNode(Node):
     op = "up_sampling2d"
 
-    def __init__(self, name, size):
+    def __init__(self, name, size, interpolation="nearest"):
         super().__init__(name)
         self.size = size
+        self.interpolation = interpolation   # "nearest" | "bilinear" (tf.image.resize, half-pixel centres)
 
     def build(self, x):
         _, h, w, c = x.shape
         return self.connect([x], (None, h * self.size, w * self.size, c))
 
-    fused_into = None   # the 3x3 convolution that reads this node's SOURCE directly (Model._fuse; _ConvNode.up_src)
+    fused_into = None   # the 3x3 convolution that reads this node's SOURCE directly (Model._fuse; _ConvNode.up_src); nearest only
 
     def forward(self, rt, xs, training):
+        if self.interpolation == "bilinear":
+            return rt.eng.upsample_bilinear_fwd(xs[0], self.size)
         if self.fused_into is not None and rt.up2_on(self):
             return xs[0]   # never materialised: the consumer's kernels address the source (h >> 1, w >> 1)
         return rt.eng.upsample_fwd(xs[0], self.size)
 
     def backward(self, rt, xs, y, dy):
+        if self.interpolation == "bilinear":
+            return [rt.eng.upsample_bilinear_bwd(dy, tuple(xs[0].shape), self.size)]
         if self.fused_into is not None and rt.up2_on(self):
             return [rt.shared(dy)]   # the consumer's dgrad already summed the 2 x 2 cells: dy has the source's shape
         return [rt.eng.upsample_bwd(dy, tuple(xs[0].shape), self.size)]
@@ -743,12 +748,14 @@ class _UpNode(Node):
 class UpSampling2D(Layer):
     def __init__(self, size=2, interpolation="nearest", name=None, **kw):
         super().__init__(name)
-        assert interpolation == "nearest", "the reference only uses nearest up-sampling"
+        if interpolation not in ("nearest", "bilinear"):
+            raise ValueError(f"UpSampling2D: interpolation {interpolation!r} is not supported (use 'nearest' or 'bilinear')")
         self.size = _pair(size)
+        self.interpolation = interpolation
 
     def __call__(self, x):
         self._once()
-        return _UpNode(self._name, self.size).build(x)
+        return _UpNode(self._name, self.size, self.interpolation).build(x)
 
 
 # ====================================================================================== structural nodes

@@ -853,6 +853,23 @@ class Engine:
                                                int(accumulate)), "sg_upsample_nearest_bwd")
         return dx
 
+    def upsample_bilinear_fwd(self, x, sh, sw=None, out=None, out_ld=0):
+        """tf.image.resize(method='bilinear') by an integer factor (half-pixel centres); arguments as upsample_fwd."""
+        sw = sh if sw is None else sw
+        n, h, w, c = x.shape
+        y = out if out is not None else self.empty(n, h * sh, w * sw, c, dtype=x.dtype)
+        check(self.lib.sg_upsample_bilinear_fwd(self.h, self.stream, _dt(x), n, h, w, c, sh, sw, _ptr(x), _ptr(y), out_ld),
+              "sg_upsample_bilinear_fwd")
+        return y
+
+    def upsample_bilinear_bwd(self, dy, xshape, sh, sw=None, out=None, accumulate=False, dy_ld=0):
+        sw = sh if sw is None else sw
+        n, h, w, c = xshape
+        dx = out if out is not None else self.empty(n, h, w, c, dtype=dy.dtype)
+        check(self.lib.sg_upsample_bilinear_bwd(self.h, self.stream, _dt(dy), n, h, w, c, sh, sw, _ptr(dy), dy_ld, _ptr(dx),
+                                                int(accumulate)), "sg_upsample_bilinear_bwd")
+        return dx
+
     # ------------------------------------------------------------------------------ loss / metrics / Adam
     def loss_fwd(self, kind, p, y_true):
         _chk32(p, "p"); _chk32(y_true, "y_true")

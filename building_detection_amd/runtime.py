@@ -129,7 +129,8 @@ class Model:
         # 4x tensor and its gradient are never built.  Marked here for every such pair; whether a runtime takes the fused
         # kernels (fp32 storage, geometry, SG_UP2_FUSE != 0) is _Runtime.up2_on.
         for n in self.nodes:
-            if isinstance(n, L._UpNode) and n.size == 2 and id(n.output) not in outs and len(n.output.consumers) == 1:
+            if (isinstance(n, L._UpNode) and n.size == 2 and n.interpolation == "nearest" and id(n.output) not in outs
+                    and len(n.output.consumers) == 1):
                 c = n.output.consumers[0]
                 if (isinstance(c, L._ConvNode) and c.k == 3 and c.stride == 1 and c.dilation == 1 and c.padding == "same"
                         and c.activation in (None, "linear", "relu")):

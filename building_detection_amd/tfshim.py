@@ -152,6 +152,21 @@ def reshape(t, shape, name=None):
     return L.Reshape(tuple(shape[1:]))(_r(t))
 
 
+def _image_resize(images, size, method="bilinear", name=None, **kw):
+    """tf.image.resize on a symbolic [N,H,W,C] tensor, for sizes that are the same integer multiple of the input's height
+    and width (the case UpSampling2D covers): it becomes that layer's node.  Other sizes have no kernel here."""
+    x = _r(images)
+    if method not in ("bilinear", "nearest"):
+        raise ValueError(f"tf.image.resize: method {method!r} is not supported (use 'bilinear' or 'nearest')")
+    if len(x.shape) != 4 or len(size) != 2:
+        raise ValueError(f"tf.image.resize: needs a [N,H,W,C] tensor and size=(height, width), got {x.shape} and {size}")
+    (h, w), (oh, ow) = x.shape[1:3], (int(size[0]), int(size[1]))
+    if oh <= 0 or ow <= 0 or oh % h or ow % w or oh // h != ow // w:
+        raise ValueError(f"tf.image.resize: size {(oh, ow)} is not one integer multiple of the input's {(h, w)}; "
+                         "only integer up-sampling is supported")
+    return L.UpSampling2D(size=oh // h, interpolation=method, name=name)(x)
+
+
 def argmax(a, axis=-1, output_type=None):
     return np.argmax(np.asarray(a), axis=axis)  # lowest index on ties, like tf.argmax
 
@@ -299,6 +314,7 @@ models = _module(__name__ + ".keras.models", Model=_ModelFactory())
 utils = _module(__name__ + ".keras.utils", to_categorical=to_categorical)
 keras = _module(__name__ + ".keras", layers=layers, backend=backend, callbacks=callbacks, models=models, utils=utils,
                 Model=_ModelFactory())
+image = _module(__name__ + ".image", resize=_image_resize)
 config = _module(__name__ + ".config", experimental=_module(
     __name__ + ".config.experimental", list_physical_devices=lambda kind=None: [], set_memory_growth=lambda *a: None))
 
@@ -310,7 +326,7 @@ def install(as_name: str = "tensorflow"):
     me = sys.modules[__name__]
     table = {as_name: me, as_name + ".keras": keras, as_name + ".keras.layers": layers,
              as_name + ".keras.backend": backend, as_name + ".keras.callbacks": callbacks,
-             as_name + ".keras.models": models, as_name + ".keras.utils": utils, as_name + ".config": config}
+             as_name + ".keras.models": models, as_name + ".keras.utils": utils, as_name + ".config": config, as_name + ".image": image}
     for k, v in table.items():
         sys.modules[k] = v
     return list(table)

@@ -91,18 +91,18 @@ def _sk_block(x, reduce=16):
     return L.Activation("relu")(L.BatchNormalization()(y))
 
 
-def _aspp(x, pool):
+def _aspp(x, pool, upsampling="nearest"):
     """ASPP (v3plus.py:295-307): 1x1 + three dilated 3x3 (rates 6/12/18) + pooled branch, concatenated."""
     outs = [_cbr(x, 256, 1)] + [_cbr(x, 256, 3, dilate=d) for d in (6, 12, 18)]
     p = L.AveragePooling2D(pool_size=pool)(x)
     p = _cbr(p, 256, 1)
-    outs.append(L.UpSampling2D(size=pool)(p))
+    outs.append(L.UpSampling2D(size=pool, interpolation=upsampling)(p))
     return L.concatenate(outs)
 
 
-def _neck(c5, aspp_pool):
-    sk = _sk_block(c5)
-    a = _aspp(c5, aspp_pool)
+def _neck(c5, aspp_pool, upsampling="nearest"):
+    sk = _sk_block(c5)   # its GAP broadcast (1x1 source) is the same tensor in both modes and stays a nearest node
+    a = _aspp(c5, aspp_pool, upsampling)
     y = _cbr(a, 256, 1)
     y = L.concatenate([y, sk])
     y = _cbr(y, 256, 3)
@@ -116,26 +116,28 @@ def _decode(y, filters):
     return L.scse_block(y)
 
 
-def Xception_DeepLabV3_Plus(shape=(512, 512, 3), num_classes=2, aspp_pool=32):
+def Xception_DeepLabV3_Plus(shape=(512, 512, 3), num_classes=2, aspp_pool=32, upsampling="nearest"):
+    """`upsampling` ("nearest", the reference's, or "bilinear") is the interpolation of the ASPP's and the decoder's
+    UpSampling2D layers; it changes no parameter."""
     inp = L.Input(shape=shape)
     c, c1, c2, c5 = _xception(inp, with_bam=False)
-    y = _neck(c5, aspp_pool)
-    y = _decode(L.concatenate([L.UpSampling2D(size=2)(y), c2]), 256)
+    y = _neck(c5, aspp_pool, upsampling)
+    y = _decode(L.concatenate([L.UpSampling2D(size=2, interpolation=upsampling)(y), c2]), 256)
     y = _decode(L.concatenate([L.Conv2DTranspose(128, 3, strides=2, padding="same")(y), c1]), 128)
     y = _decode(L.concatenate([c, L.Conv2DTranspose(64, 3, strides=2, padding="same")(y)]), 64)
-    y = L.UpSampling2D(size=2)(y)
+    y = L.UpSampling2D(size=2, interpolation=upsampling)(y)
     y = _cbr(y, 32, 3)
     y = _cbr(y, 32, 3)
     out = L.Conv2D(num_classes, 1, 1, activation="softmax")(y)
     return Model(inputs=inp, outputs=out, name="Xception_DeepLabV3_Plus")
 
 
-def Xception_DeepLabV3_Plus_bam(shape=(512, 512, 3), num_classes=2, aspp_pool=32):
+def Xception_DeepLabV3_Plus_bam(shape=(512, 512, 3), num_classes=2, aspp_pool=32, upsampling="nearest"):
     inp = L.Input(shape=shape)
     _, c1, c2, c5 = _xception(inp, with_bam=True)
-    y = _neck(c5, aspp_pool)
-    y = _decode(L.concatenate([c2, L.UpSampling2D(size=2)(y)]), 128)
-    y = _decode(L.concatenate([c1, L.UpSampling2D(size=2)(y)]), 64)
-    y = L.UpSampling2D(size=4)(y)
+    y = _neck(c5, aspp_pool, upsampling)
+    y = _decode(L.concatenate([c2, L.UpSampling2D(size=2, interpolation=upsampling)(y)]), 128)
+    y = _decode(L.concatenate([c1, L.UpSampling2D(size=2, interpolation=upsampling)(y)]), 64)
+    y = L.UpSampling2D(size=4, interpolation=upsampling)(y)
     out = L.Conv2D(num_classes, 1, 1, activation="softmax")(y)
     return Model(inputs=inp, outputs=out, name="Xception_DeepLabV3_Plus_bam")

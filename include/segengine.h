@@ -447,6 +447,19 @@ int sg_upsample_nearest_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, 
                             int sw, const void* x, void* y, int y_ld);
 int sg_upsample_nearest_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int sh,
                             int sw, const void* dy, int dy_ld, void* dx, int accumulate);
+/* UpSampling2D(size=s, interpolation='bilinear') = tf.image.resize(method='bilinear'): half-pixel centres, no
+ * antialiasing, each axis on its own.  For output index o, input extent n and integer factor s:
+ *   in = (o + 0.5) / s - 0.5
+ *   lo = max(floor(in), 0)    hi = min(ceil(in), n - 1)    f = in - floor(in)
+ *   y  = x[lo] + (x[hi] - x[lo]) * f                       (columns first, then rows; arithmetic in fp32)
+ * Same arguments as the nearest pair (y_ld / dy_ld: pixel stride, 0 = C; accumulate != 0 adds into dx); sh, sw <= 1024.
+ * The backward is the transpose as a gather: dx[i] sums (1 - f) dy[o] over lo(o) == i and f dy[o] over hi(o) == i, at most
+ * 2 sh x 2 sw outputs, walked rows outer / columns inner in a fixed order (no atomics: bit-identical from run to run and
+ * for every batch slice). */
+int sg_upsample_bilinear_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int sh,
+                             int sw, const void* x, void* y, int y_ld);
+int sg_upsample_bilinear_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int sh,
+                             int sw, const void* dy, int dy_ld, void* dx, int accumulate);
 
 /* -------------------------------------------------------------------------------- loss / metrics / Adam
  * The three losses of train_model/DeepLabv3plus.py:490-527 on softmax probabilities p[rows,2] and

@@ -442,7 +442,7 @@ int launch_b16_pd(const IgemmParams& p, hipStream_t st) {
 // everywhere else (the same convolutions' dgrad loses 10 - 18 % with two, the short-K layers 8 %: profiles/r02_b16_prefetch_ab.txt)
 template <int BN, int WGM, int WGN, int KS>
 int launch_b16(const IgemmParams& p, hipStream_t st) {
-  static const int pd = getenv("SG_B16_PD") ? atoi(getenv("SG_B16_PD")) : 0;
+  const int pd = sg_switch<SW_B16_PD>();
   const bool two = pd == 2 || (pd == 0 && p.k_mul > 0 && p.K != p.C && p.K >= 8192 && p.div == 1);
   return two ? launch_b16_pd<BN, WGM, WGN, KS, 2>(p, st) : launch_b16_pd<BN, WGM, WGN, KS, 1>(p, st);
 }
@@ -450,8 +450,7 @@ int launch_b16(const IgemmParams& p, hipStream_t st) {
 // slab depth (k-steps of 16) for a launch whose taps are `c` channels deep: the deepest of 8 / 4 / 2 that keeps every slab
 // inside one tap; 1x1 kernels (one tap, ragged tail masked) take the deepest.  SG_B16_KS forces a value (A/B runs).
 inline int b16_ks(int c, bool one_tap) {
-  static int force = -1;
-  if (force < 0) force = getenv("SG_B16_KS") ? atoi(getenv("SG_B16_KS")) : 0;
+  const int force = sg_switch<SW_B16_KS>();
   for (int ks : {4, 2}) {  // KS = 8 measured slower than 4 on most shapes (profiles/r02_b16_deep_ab.txt): not dispatched
     if (force && ks > force) continue;
     if (one_tap || c % (16 * ks) == 0) return ks;
@@ -466,7 +465,7 @@ inline int dispatch_b16(const IgemmParams& p_in, int num_cus, hipStream_t st) {
   p.stagger = 0;
   p.ablate = 0;
 #ifdef SG_B16_ABL
-  p.ablate = getenv("SG_B16_ABLATE") ? atoi(getenv("SG_B16_ABLATE")) : 0;
+  p.ablate = sg_switch<SW_B16_ABLATE>();
 #endif
   const int ks = b16_ks(p.C, p.K == p.C);
   if (bn == 128) {
@@ -487,6 +486,5 @@ inline int dispatch_b16(const IgemmParams& p_in, int num_cus, hipStream_t st) {
 // k-block depth of the weight planes a launch will read = the slab depth of its kernel: 32 for conv_x6_kernel (both plane
 // counts), 16 * KS for conv_b16_kernel (bf16 storage, SG_B16_DEEP).  `c` is the depth of one tap (after virtual padding).
 inline int x6_plane_kd(bool b16_storage, int c, bool one_tap) {
-  static const bool deep = !(getenv("SG_B16_DEEP") && atoi(getenv("SG_B16_DEEP")) == 0);
-  return (b16_storage && deep) ? 16 * b16_ks(c, one_tap) : 32;
+  return (b16_storage && sg_switch<SW_B16_DEEP>()) ? 16 * b16_ks(c, one_tap) : 32;
 }

@@ -29,7 +29,7 @@ constexpr int BW_LDS = (2 * BW_STAGE > BW_M * BW_TP ? 2 * BW_STAGE : BW_M * BW_T
 
 __device__ __forceinline__ int bw_swz(int row) { return (row >> 1) & 7; }   // B16L<4>::swz
 
-// VAR (SG_B16W_VAR; A/B switch): 0 = the eight DMA instructions of stage s + 1 issued at the top of stage s, in front of its
+// VAR: only 0 is instantiated (1 measured no difference: DESIGN.md, retired; the parameter is part of the kernel's name).  0 = the eight DMA instructions of stage s + 1 issued at the top of stage s, in front of its
 // MFMAs; 1 = woven - two of them behind the MFMAs of each of the four k-steps, so that the matrix pipe starts right behind the
 // barrier and the address unit works beside it.
 template <int VAR>
@@ -422,8 +422,7 @@ __global__ __launch_bounds__(256) void b16w_reduce_kernel(const float* __restric
 // fewer tiles are made up by split-K (<= 4 shares of >= 2048 reduction steps each).  SG_B16_WIDE=0 switches the kernel off.
 // Geometry fields only (plan_conv, the one caller); a launch that adds a collected gradient takes conv_b16_kernel on the same planes.
 inline int b16w_shares(const IgemmParams& p) {
-  static const int on = getenv("SG_B16_WIDE") ? atoi(getenv("SG_B16_WIDE")) : 1;
-  if (!on) return 0;
+  if (!sg_switch<SW_B16_WIDE>()) return 0;
   if (p.div != 1 || p.C % BW_KD != 0 || p.K < 1024 || p.K / p.C > 64) return 0;   // (div 1: never parity-class rows)
   if ((p.x_ld % 8) != 0 || p.x_bytes == 0) return 0;
   if (p.Nout % 4 != 0) return 0;
@@ -440,11 +439,9 @@ inline int b16w_shares(const IgemmParams& p) {
 }
 
 inline int launch_b16w(const IgemmParams& p, int S, float* scratch, hipStream_t st) {
-  static const int var = getenv("SG_B16W_VAR") ? atoi(getenv("SG_B16W_VAR")) : 0;
   static bool attr_done = false;
   if (!attr_done) {
     int rc = set_dyn_lds(conv_b16w_kernel<0>, (size_t)BW_LDS);
-    if (!rc) rc = set_dyn_lds(conv_b16w_kernel<1>, (size_t)BW_LDS);
     if (rc) return rc;
     attr_done = true;
   }
@@ -457,8 +454,7 @@ inline int launch_b16w(const IgemmParams& p, int S, float* scratch, hipStream_t 
     sg_set_error("conv_b16w: an operand of %lld rows does not fit one 2 GiB buffer descriptor", (long long)p.M);
     return SG_EINVAL;
   }
-  if (var == 1) hipLaunchKernelGGL(conv_b16w_kernel<1>, dim3((unsigned)(tiles * S)), dim3(512), (size_t)BW_LDS, st, p, S, scratch);
-  else hipLaunchKernelGGL(conv_b16w_kernel<0>, dim3((unsigned)(tiles * S)), dim3(512), (size_t)BW_LDS, st, p, S, scratch);
+  hipLaunchKernelGGL(conv_b16w_kernel<0>, dim3((unsigned)(tiles * S)), dim3(512), (size_t)BW_LDS, st, p, S, scratch);
   SG_LAUNCH_CHECK("conv_b16w_kernel");
   if (S > 1) {
     dim3 grid((unsigned)sg_cdiv(p.M, 128), (unsigned)sg_cdiv(p.Nout, 64));

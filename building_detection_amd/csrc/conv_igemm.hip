@@ -991,39 +991,6 @@ __global__ __launch_bounds__(256) void reduce_splits_kernel(const float* __restr
   }
 }
 
-// The same with FOUR lanes per output quad (round 4; for S >= 8): lane zl adds slabs zl, zl + 4, ... in order, the four lane sums
-// are added ((0 + 1) + 2) + 3 through LDS - deterministic.  A 21-slab reduction of a 728 x 728 gradient (44 MB) is 518
-// workgroups of the kernel above whose threads each walk 21 loads, eight in flight: 20 - 29 us, 2.2 TB/s
-// (profiles/r04_bench_kernel_stats_final.csv: 90 launches per step); four times the threads walk five loads each.
-__global__ __launch_bounds__(256) void reduce_splits_z4_kernel(const float* __restrict__ part, float* __restrict__ out, int64_t n, int S) {
-  __shared__ f32x4 red[4][64];
-  const int q = threadIdx.x & 63, zl = threadIdx.x >> 6;
-  const int64_t stride = (int64_t)gridDim.x * 64 * 4;
-  for (int64_t i0 = (int64_t)blockIdx.x * 64 * 4; i0 < n; i0 += stride) {   // (uniform trip count per workgroup: barriers inside)
-    const int64_t i = i0 + (int64_t)q * 4;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (i < n) {
-#pragma unroll 4
-      for (int z = zl; z < S; z += 4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(part + (int64_t)z * n + i);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[k] += v[k];
-      }
-    }
-    red[zl][q] = s;
-    __syncthreads();
-    if (zl == 0 && i < n) {
-      f32x4 t = red[0][q];
-#pragma unroll
-      for (int l = 1; l < 4; ++l)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t[k] += red[l][q][k];
-      *reinterpret_cast<f32x4*>(out + i) = t;
-    }
-    __syncthreads();
-  }
-}
-
 // bias gradient = column sums of dy[rows][C] (pixel stride ld), through the fixed-order segmented reducer
 template <typename T>
 struct ColSumOp {
@@ -1065,38 +1032,19 @@ int set_dyn_lds(KernelT k, size_t bytes) {
   return 0;
 }
 
-// Experiment switch (A/B runs of the micro-benchmark): SG_CONV_VARIANT bit 0 = 8-wave workgroups,
-// bit 1 = two-slab prefetch, bit 2 = staggered wave halves (needs bit 1).  Default = all (7).
-int conv_variant() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SG_CONV_VARIANT");
-    v = e ? atoi(e) & 7 : 7;
-  }
-  return v;
-}
-
 // x6 == true: the switches as the x6 kernels use them.  Re-measured with those kernels (profiles/r01_ab_l2_orders.txt,
 // second part): the grouped order takes the ASPP dgrad fetch from 1998 to 485 MiB and the tap-inner wgrad order from
 // 795 to 279 MiB at 0-3 % of kernel time (the fp32 kernels paid 6-13 %), so both are on there: default 7.
 int conv_l2(bool x6 = false) {
-  static int v = -1, vx = -1;
-  if (vx < 0) {
-    const char* e = getenv("SG_CONV_L2");
-    vx = e ? atoi(e) & 7 : 7;
-  }
-  if (x6) return vx;
-  if (v < 0) {
-    const char* e = getenv("SG_CONV_L2");
-    // default 2: measured on the ASPP convs (scripts/ab_l2.sh, 30 iterations, two interleaved rounds):
-    //   bit 1 (channel-block K order): forward fetch 1039 -> 451 MiB per launch, time unchanged      -> on
-    //   bit 0 (grouped tile order):    dgrad fetch 1808 -> 461 MiB, but 6-13 % SLOWER               -> off
-    //   bit 2 (wgrad tap-inner order): wgrad fetch 1018 -> 314 MiB, but 2-8 % SLOWER                 -> off
-    // The re-reads are served by the 256 MiB Infinity Cache (operands total < 150 MiB), not by HBM, and the
-    // orders that remove them make many CUs hit the same L2 lines at the same time.
-    v = e ? atoi(e) & 7 : 2;
-  }
-  return v;
+  if (sg_switch_set<SW_CONV_L2>()) return sg_switch<SW_CONV_L2>() & 7;
+  if (x6) return 7;
+  // the fp32 kernels, default 2: measured on the ASPP convs (scripts/ab_l2.sh, 30 iterations, two interleaved rounds):
+  //   bit 1 (channel-block K order): forward fetch 1039 -> 451 MiB per launch, time unchanged      -> on
+  //   bit 0 (grouped tile order):    dgrad fetch 1808 -> 461 MiB, but 6-13 % SLOWER               -> off
+  //   bit 2 (wgrad tap-inner order): wgrad fetch 1018 -> 314 MiB, but 2-8 % SLOWER                 -> off
+  // The re-reads are served by the 256 MiB Infinity Cache (operands total < 150 MiB), not by HBM, and the
+  // orders that remove them make many CUs hit the same L2 lines at the same time.
+  return 2;
 }
 
 template <int BN, int WGM, int WGN, int PF, bool VEC, bool UT, typename TA = float, typename TY = TA>
@@ -1151,8 +1099,7 @@ int pick_bn(int64_t M, int N, int num_cus) {
 
 // fields shared by the fp32 and the x6 kernel: padding-tap elimination, tile order, K order
 void plan_common(IgemmParams& p, bool vec, int bn, bool x6 = false, int eb = 4) {
-  static int noskip = -1;
-  if (noskip < 0) noskip = getenv("SG_CONV_NOSKIP") ? 1 : 0;  // A/B switch for the padding-tap elimination
+  const int noskip = sg_switch<SW_CONV_NOSKIP>();  // A/B switch for the padding-tap elimination
   const int ntaps = p.K / p.C, spt = p.C / BK;
   p.skip_taps = (!noskip && (p.k_mul > 1 || p.k_mul < -1) && ntaps > 1 && ntaps <= 64) ? 1 : 0;
   if (p.perm2) p.skip_taps = 1;  // parity-pure tiles: taps of the other parities have no valid row (also a lone 1x1 tap)
@@ -1161,14 +1108,13 @@ void plan_common(IgemmParams& p, bool vec, int bn, bool x6 = false, int eb = 4) 
   const int64_t ntn = sg_cdiv(p.Nout, bn);
   const int64_t a_per_xcd = p.x_bytes ? (int64_t)p.x_bytes / 8 : (1ll << 40);
   p.group_m = ((conv_l2(x6) & 1) && ntn >= 4) ? (a_per_xcd <= (2ll << 20) ? 16 : 8) : 1;
-  static const int gm_force = getenv("SG_CONV_GM") ? atoi(getenv("SG_CONV_GM")) : 0;   // experiment: row tiles per group
+  const int gm_force = sg_switch<SW_CONV_GM>();   // experiment: row tiles per group
   if (gm_force > 0 && ntn >= 2) p.group_m = gm_force;
   const bool ut = vec && (p.C % BK == 0) && p.x_bytes != 0 && p.w_bytes != 0;
   // decided from ONE image's footprint, never from the batch: the K order fixes the rounding order, and
   // inference must not depend on how many tiles travel together (tests/test_fullsize_gpu.py)
   const int64_t img_bytes = (int64_t)p.H * p.W * p.x_ld * eb;
-  static int cbv = -1;  // experiment switch SG_CONV_CB: slabs per channel block of the K order (default 4)
-  if (cbv < 0) cbv = getenv("SG_CONV_CB") ? atoi(getenv("SG_CONV_CB")) : 4;
+  const int cbv = sg_switch<SW_CONV_CB>();  // experiment switch: slabs per channel block of the K order (default 4)
   p.cb = ((conv_l2(x6) & 2) && ut && ntaps > 1 && spt > cbv && spt % cbv == 0 && img_bytes > (2ll << 20)) ? cbv : 0;
 }
 
@@ -1185,25 +1131,14 @@ int dispatch_x6(const IgemmParams& p_in, int num_cus, hipStream_t st) {
   IgemmParams p = p_in;
   const int bn = pick_bn(p.M, p.Nout, num_cus);
   plan_common(p, true, bn, true, EL<TA>::BYTES);
-  {
-    static int il = -1;  // SG_X6_INTERLEAVE=0: staggered halves instead of the hand-interleaved step (A/B switch)
-    if (il < 0) il = getenv("SG_X6_INTERLEAVE") ? atoi(getenv("SG_X6_INTERLEAVE")) : 1;
-    p.stagger = il ? 2 : 0;
-  }
-  {
-    static int abl = -1;
-    if (abl < 0) {
-      const char* e = getenv("SG_X6_ABLATE");
-      abl = e ? atoi(e) & 15 : 0;
-    }
-    p.ablate = abl;
-  }
+  p.stagger = sg_switch<SW_X6_INTERLEAVE>() ? 2 : 0;  // 0: staggered halves instead of the hand-interleaved step (A/B switch)
+  p.ablate = sg_switch<SW_X6_ABLATE>() & 15;
   // Structure by tile count (measured, profiles/r01_ab_x6.txt, r01_ab_x6_interleave.txt, r01_ab_tiles1024.txt): up to
   // 3 tiles per CU the double-buffered one-workgroup-per-CU form with the hand-interleaved step wins (ASPP forward
   // 1.02 -> 0.89 ms, pointwise 728 forward 0.150 -> 0.137 ms); from 4 tiles per CU - i.e. two full rounds of the
   // two-workgroups-per-CU single-buffer form - that one does (1024 tiles: 64x64 512->256 forward 887 vs 930 us,
   // 1024->1024 pointwise 233 vs 252 us; ASPP dgrad 0.83 vs 0.94 ms, decoder 128->64 dgrad 0.92 vs 1.03 ms).
-  // SG_X6_VARIANT overrides.
+  // SG_X6_VARIANT overrides.  (4-wave workgroups, 64x64 per wave, lost to both 8-wave structures and are gone: DESIGN.md, retired.)
   const int64_t tiles = sg_cdiv(p.M, BM) * sg_cdiv(p.Nout, bn);
   int var = x6_variant();
   if (var < 0) var = (tiles <= 3 * (int64_t)num_cus) ? 1 : 0;
@@ -1214,30 +1149,17 @@ int dispatch_x6(const IgemmParams& p_in, int num_cus, hipStream_t st) {
   } else {
   // 16x16x32 products for the multi-tap convolutions (conv_x6_kernel, MF): a property of the layer, never of the batch.
   // SG_X6_MF16=0 keeps every launch on 32x32x16 (A/B runs).
-  static const bool mf16_on = !(getenv("SG_X6_MF16") && atoi(getenv("SG_X6_MF16")) == 0);
-  const bool mf = mf16_on && p.K != p.C;
+  const bool mf = sg_switch<SW_X6_MF16>() && p.K != p.C;
   if (bn == 128) {
-    if (mf && var == 0) return launch_x6<128, 2, 4, 1, 3, float, 1>(p, st);
-    if (mf && var == 1) return launch_x6<128, 2, 4, 2, 3, float, 1>(p, st);
-    switch (var) {
-      case 0: return launch_x6<128, 2, 4, 1>(p, st);
-      case 1: return launch_x6<128, 2, 4, 2>(p, st);
-      case 2: return launch_x6<128, 2, 2, 1>(p, st);
-      default: return launch_x6<128, 2, 2, 2>(p, st);
-    }
+    if (mf) return var ? launch_x6<128, 2, 4, 2, 3, float, 1>(p, st) : launch_x6<128, 2, 4, 1, 3, float, 1>(p, st);
+    return var ? launch_x6<128, 2, 4, 2>(p, st) : launch_x6<128, 2, 4, 1>(p, st);
   }
   if (bn == 64) {
-    if (mf && var == 0) return launch_x6<64, 4, 2, 1, 3, float, 1>(p, st);
-    if (mf && var == 1) return launch_x6<64, 4, 2, 2, 3, float, 1>(p, st);
-    switch (var) {
-      case 0: return launch_x6<64, 4, 2, 1>(p, st);
-      case 1: return launch_x6<64, 4, 2, 2>(p, st);
-      case 2: return launch_x6<64, 2, 2, 1>(p, st);
-      default: return launch_x6<64, 2, 2, 2>(p, st);
-    }
+    if (mf) return var ? launch_x6<64, 4, 2, 2, 3, float, 1>(p, st) : launch_x6<64, 4, 2, 1, 3, float, 1>(p, st);
+    return var ? launch_x6<64, 4, 2, 2>(p, st) : launch_x6<64, 4, 2, 1>(p, st);
   }
-  if (mf) return (var & 1) ? launch_x6<32, 4, 1, 2, 3, float, 1>(p, st) : launch_x6<32, 4, 1, 1, 3, float, 1>(p, st);
-  return (var & 1) ? launch_x6<32, 4, 1, 2>(p, st) : launch_x6<32, 4, 1, 1>(p, st);
+  if (mf) return var ? launch_x6<32, 4, 1, 2, 3, float, 1>(p, st) : launch_x6<32, 4, 1, 1, 3, float, 1>(p, st);
+  return var ? launch_x6<32, 4, 1, 2>(p, st) : launch_x6<32, 4, 1, 1>(p, st);
   }
 }
 
@@ -1346,8 +1268,7 @@ int run_x6(const ConvPlan& pl, IgemmParams& p, const float* w, bool dgrad, int C
         if (pl.x6w_S > 0 && !p.res) {   // scratch: the planes of A, then split-K partial slabs
           IgemmParams q = p;
           plan_common(q, true, 128, true, 4);
-          static const int abl = getenv("SG_X6W_ABLATE") ? atoi(getenv("SG_X6W_ABLATE")) : 0;
-          q.ablate = abl;
+          q.ablate = sg_switch<SW_X6W_ABLATE>();
           return launch_x6w(q, pl.x6w_S, scratch, st);
         }
       }
@@ -1385,38 +1306,18 @@ int dispatch_igemm(const IgemmParams& p_in, bool vec, int num_cus, hipStream_t s
   IgemmParams p = p_in;
   const int bn = pick_bn(p.M, p.Nout, num_cus);
   plan_common(p, vec, bn);
-  const int var = conv_variant() & 3;
-  p.stagger = (conv_variant() >> 2) & 1;
-  {
-    static int abl = -1;
-    if (abl < 0) {
-      const char* e = getenv("SG_CONV_ABLATE");
-      abl = e ? atoi(e) & 3 : 0;
-    }
-    p.ablate = abl;
-  }
+  // the structure that won every A/B: 8-wave workgroups, two-slab prefetch, staggered wave halves (the 4-wave and one-slab
+  // forms are gone: DESIGN.md, retired)
+  p.stagger = 1;
+  p.ablate = sg_switch<SW_CONV_ABLATE>() & 3;
   if (!vec) {
     if (bn == 128) return launch_igemm<128, 2, 4, 1, false>(p, st);
     if (bn == 64) return launch_igemm<64, 4, 2, 1, false>(p, st);
     return launch_igemm<32, 4, 1, 1, false>(p, st);
   }
-  if (bn == 128) {
-    switch (var) {
-      case 0: return launch_igemm<128, 2, 2, 1, true>(p, st);
-      case 1: return launch_igemm<128, 2, 4, 1, true>(p, st);
-      case 2: return launch_igemm<128, 2, 2, 2, true>(p, st);
-      default: return launch_igemm<128, 2, 4, 2, true>(p, st);
-    }
-  }
-  if (bn == 64) {
-    switch (var) {
-      case 0: return launch_igemm<64, 2, 2, 1, true>(p, st);
-      case 1: return launch_igemm<64, 4, 2, 1, true>(p, st);
-      case 2: return launch_igemm<64, 2, 2, 2, true>(p, st);
-      default: return launch_igemm<64, 4, 2, 2, true>(p, st);
-    }
-  }
-  return (var & 2) ? launch_igemm<32, 4, 1, 2, true>(p, st) : launch_igemm<32, 4, 1, 1, true>(p, st);
+  if (bn == 128) return launch_igemm<128, 2, 4, 2, true>(p, st);
+  if (bn == 64) return launch_igemm<64, 4, 2, 2, true>(p, st);
+  return launch_igemm<32, 4, 1, 2, true>(p, st);
 }
 
 template <int BN, int WGM, int WGN, int PF, bool VEC, int FAST, typename TA = float, typename TD = TA>
@@ -1438,7 +1339,7 @@ template <int BN, int WGM, int WGN, int PF, bool VEC>
 int launch_wgrad(const WgradParams& p, int S, hipStream_t st) {
   if constexpr (VEC && PF == 2) {
     const bool fast = p.stride == 1 && p.OH == p.H && p.OW == p.W && p.x_bytes != 0 && p.dy_bytes != 0;
-    static const bool force1 = getenv("SG_WGRAD_FAST1") != nullptr;  // A/B switch
+    const bool force1 = sg_switch<SW_WGRAD_FAST1>();  // A/B switch
     const bool aligned = fast && !force1 && (p.OW % BK == 0) && (p.KH_KW == 1 || p.Cin % BM == 0) &&
                          ((int64_t)p.x_bytes + 2 * 32 * (int64_t)p.x_ld * 4 < (1ll << 31));
     if (aligned) return launch_wgrad_f<BN, WGM, WGN, PF, true, 2>(p, S, st);
@@ -1451,32 +1352,14 @@ inline int wgrad_bn(int cout) { return cout > 64 ? 128 : (cout > 32 ? 64 : 32); 
 
 int dispatch_wgrad(const WgradParams& p_in, int S, bool vec, hipStream_t st) {
   WgradParams p = p_in;
-  {
-    static int noskip = -1;
-    if (noskip < 0) noskip = getenv("SG_CONV_NOSKIP") ? 1 : 0;
-    p.KH_KW = p.K / p.Cin;
-    p.skip_slabs = (!noskip && p.dil > 1 && p.KH_KW > 1) ? 1 : 0;
-    p.tap_inner = ((conv_l2() & 4) && p.KH_KW > 1 && p.Cin % BM == 0) ? 1 : 0;
-  }
+  p.KH_KW = p.K / p.Cin;
+  p.skip_slabs = (!sg_switch<SW_CONV_NOSKIP>() && p.dil > 1 && p.KH_KW > 1) ? 1 : 0;
+  p.tap_inner = ((conv_l2() & 4) && p.KH_KW > 1 && p.Cin % BM == 0) ? 1 : 0;
   const int bn = wgrad_bn(p.Cout);
-  const int var = conv_variant() & 3;
-  p.stagger = (conv_variant() >> 2) & 1;
+  p.stagger = 1;
   if (wgrad_x6_ok(p, vec)) {
     p.tap_inner = ((conv_l2(true) & 4) && p.KH_KW > 1 && p.Cin % BM == 0) ? 1 : 0;
-    {
-      static int abl = -1;
-      if (abl < 0) {
-        const char* e = getenv("SG_X6_ABLATE");
-        abl = e ? atoi(e) & 7 : 0;
-      }
-      p.stagger = abl;  // the x6 wgrad kernel has no stagger; the field carries the ablation mask
-    }
-    static const int wpf2 = getenv("SG_X6_WGRAD_PF2") ? atoi(getenv("SG_X6_WGRAD_PF2")) : 0;  // A/B switch
-    if (wpf2 && p.stride == 1) {  // (the double-buffered experiment addresses its slabs for stride 1 only)
-      if (bn == 128) return launch_wgrad_x6<128, 2, 4, 2>(p, S, st);
-      if (bn == 64) return launch_wgrad_x6<64, 4, 2, 2>(p, S, st);
-      return launch_wgrad_x6<32, 4, 1, 2>(p, S, st);
-    }
+    p.stagger = sg_switch<SW_X6_ABLATE>() & 7;  // the x6 wgrad kernel has no stagger; the field carries the ablation mask
     if (x6_mode() == 2) {  // bf16 products in one pass on fp32 storage
       if (bn == 128) return launch_wgrad_x6<128, 2, 4, 1, 1, float>(p, S, st);
       if (bn == 64) return launch_wgrad_x6<64, 4, 2, 1, 1, float>(p, S, st);
@@ -1491,23 +1374,9 @@ int dispatch_wgrad(const WgradParams& p_in, int S, bool vec, hipStream_t st) {
     if (bn == 64) return launch_wgrad<64, 4, 2, 1, false>(p, S, st);
     return launch_wgrad<32, 4, 1, 1, false>(p, S, st);
   }
-  if (bn == 128) {
-    switch (var) {
-      case 0: return launch_wgrad<128, 2, 2, 1, true>(p, S, st);
-      case 1: return launch_wgrad<128, 2, 4, 1, true>(p, S, st);
-      case 2: return launch_wgrad<128, 2, 2, 2, true>(p, S, st);
-      default: return launch_wgrad<128, 2, 4, 2, true>(p, S, st);
-    }
-  }
-  if (bn == 64) {
-    switch (var) {
-      case 0: return launch_wgrad<64, 2, 2, 1, true>(p, S, st);
-      case 1: return launch_wgrad<64, 4, 2, 1, true>(p, S, st);
-      case 2: return launch_wgrad<64, 2, 2, 2, true>(p, S, st);
-      default: return launch_wgrad<64, 4, 2, 2, true>(p, S, st);
-    }
-  }
-  return (var & 2) ? launch_wgrad<32, 4, 1, 2, true>(p, S, st) : launch_wgrad<32, 4, 1, 1, true>(p, S, st);
+  if (bn == 128) return launch_wgrad<128, 2, 4, 2, true>(p, S, st);
+  if (bn == 64) return launch_wgrad<64, 4, 2, 2, true>(p, S, st);
+  return launch_wgrad<32, 4, 1, 2, true>(p, S, st);
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -1658,7 +1527,7 @@ struct ThinWgradOp {
 };
 
 inline bool thin_ok(const sg_conv_desc* d) {
-  static const bool off = getenv("SG_CONV_NOTHIN") != nullptr;  // A/B switch
+  const bool off = sg_switch<SW_CONV_NOTHIN>();  // A/B switch
   const int xl = d->x_ld ? d->x_ld : d->Cin;
   return !off && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->Cout <= 4 && d->Ho == d->H && d->Wo == d->W &&
          d->Cin % 4 == 0 && xl % 4 == 0 && d->Cin >= 16;
@@ -1733,13 +1602,8 @@ int thin_wgrad_t(int num_cus, const sg_conv_desc* d, const TA* x, const TY* dy, 
 // images per sub-batch such that both activation tensors stay under 2 GiB (>= N: no split needed); eb = bytes per element
 inline int64_t images_limit_bytes() {
   // test hook: SG_CONV_MAX_BYTES lowers the 2 GiB limit so that small tensors exercise the sub-batch paths
-  static int64_t lim = -1;
-  if (lim < 0) {
-    const char* e = getenv("SG_CONV_MAX_BYTES");
-    lim = e ? atoll(e) : ((1ll << 31) - (1ll << 20));
-    if (lim <= 0) lim = (1ll << 31) - (1ll << 20);
-  }
-  return lim;
+  const int64_t lim = sg_switch_ll<SW_CONV_MAX_BYTES>();
+  return lim > 0 ? lim : (1ll << 31) - (1ll << 20);
 }
 inline int images_per_2gib(const sg_conv_desc* d, int eb = 4) {
   const int64_t xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
@@ -1822,11 +1686,11 @@ WgradPlan plan_wgrad(int num_cus, const sg_conv_desc* d, bool b16 = false) {
   const int64_t slots = 2 * (int64_t)num_cus;
   const double flops = 2.0 * (double)tiles * BM * bn * (double)P;  // padded tile work
   // sustained rate of the kernel that will run: the x6 wgrad (geometry test as in wgrad_x6_ok) or the fp32 MFMA one
-  static const double rate_x6 = getenv("SG_WGRAD_PLAN_RATE") ? atof(getenv("SG_WGRAD_PLAN_RATE")) * 1e12 : 110e12;
+  const double rate_x6 = sg_switch_f<SW_WGRAD_PLAN_RATE>() * 1e12;
   const bool x6_geom = ((d->stride == 1 && d->Ho == d->H && d->Wo == d->W) || (d->stride == 2 && d->dilation == 1)) &&
                       d->Wo % 32 == 0 && d->Cout >= 16 && d->Cin % 4 == 0;
   // the one-pass bf16 kernel multiplies ~4x faster than the six-pass one: the split's partial-slab traffic weighs more
-  static const double rate_b16 = getenv("SG_WGRAD_PLAN_RATE_B16") ? atof(getenv("SG_WGRAD_PLAN_RATE_B16")) * 1e12 : 110e12;  // measured 110 / 250 / 450 / 900: no gain from a higher rate (profiles/r02_b16_deep_ab.txt)
+  const double rate_b16 = sg_switch_f<SW_WGRAD_PLAN_RATE_B16>() * 1e12;  // measured 110 / 250 / 450 / 900: no gain from a higher rate (profiles/r02_b16_deep_ab.txt)
   const double rate = x6_geom ? (b16 ? rate_b16 : rate_x6) : 110e12;
   int64_t maxS = nslab / 8;  // at least 8 slabs per split
   if (maxS < 1) maxS = 1;
@@ -1961,9 +1825,7 @@ int dispatch_wgrad_head32(const WgradParams& p_in, int S, bool vec4, hipStream_t
 int dispatch_wgrad_b16(const WgradParams& p_in, int S, bool vec8, bool vec4, hipStream_t st) {
   WgradParams p = p_in;
   p.KH_KW = p.K / p.Cin;
-  static int noskip = -1;
-  if (noskip < 0) noskip = getenv("SG_CONV_NOSKIP") ? 1 : 0;
-  p.skip_slabs = (!noskip && p.dil > 1 && p.KH_KW > 1) ? 1 : 0;
+  p.skip_slabs = (!sg_switch<SW_CONV_NOSKIP>() && p.dil > 1 && p.KH_KW > 1) ? 1 : 0;
   p.stagger = 0;
   const int bn = wgrad_bn(p.Cout);
   if (wgrad_x6_ok(p, vec8, true)) {
@@ -2017,7 +1879,7 @@ ConvPlan plan_conv_mode(int mode, int dtype, const sg_conv_desc* d, bool dgrad, 
   pl.vec = (g.C % ch == 0) && (g.x_ld % ch == 0) && (g.Nout % 4 == 0);
   const bool vpad_safe = (g.C % BK == 0) || (g.K == g.C) || (g.x_ld == g.C);   // padded reads must stay inside the tensor
   if (!(vpad_safe && x6_ok(g, pl.vec, b16 || mode != 0))) return pl;
-  static const int perm_on = getenv("SG_DGRAD_PERM2") ? atoi(getenv("SG_DGRAD_PERM2")) : 1;
+  const int perm_on = sg_switch<SW_DGRAD_PERM2>();
   pl.perm2 = (dgrad && perm_on && d->stride == 2 && d->dilation == 1 && d->H % 2 == 0 && d->W % 2 == 0 && d->KH * d->KW <= 64) ? 1 : 0;
   pl.npl = (b16 || mode == 2) ? 1 : 3;   // 3: the exact fp32 emulation, 1: bf16 products
   pl.Ck = pl.Ckp = g.C;
@@ -2049,15 +1911,14 @@ ConvPlan plan_conv_mode(int mode, int dtype, const sg_conv_desc* d, bool dgrad, 
     pl.Npad = pw_npad(N, wbn);
     pl.nblocks = (int)(sg_cdiv(pl.Kpad, 32) * sg_cdiv(pl.Npad, 32));
     pl.w_bytes = pw_planes_bytes(pl.K, N, pl.npl, wbn);
-    static const int var = getenv("SG_PW_VAR") ? atoi(getenv("SG_PW_VAR")) : 1;
-    pl.bnb = dgrad && pl.npl == 3 && !(dtype & SG_X_UP2) && x_dense && y_dense && d->Cout + 16 <= PW_BNB_MAXK && var == 1 &&
-             !getenv("SG_PW_ABLATE");
+    // (launch_pw_wide reads the same two switches: the BatchNormalization-backward form needs the default schedule, no ablation)
+    pl.bnb = dgrad && pl.npl == 3 && !(dtype & SG_X_UP2) && x_dense && y_dense && d->Cout + 16 <= PW_BNB_MAXK &&
+             sg_switch<SW_PW_VAR>() == 1 && sg_switch<SW_PW_ABLATE>() == 0;
     return pl;
   }
   pl.family = CONV_SLAB;
   pl.res = dgrad;
-  static const bool deep = !(getenv("SG_B16_DEEP") && atoi(getenv("SG_B16_DEEP")) == 0);   // A/B switch
-  pl.deep = b16 && deep;
+  pl.deep = b16 && sg_switch<SW_B16_DEEP>();   // A/B switch
   pl.kd = x6_plane_kd(b16, pl.Ckp, pl.K == pl.Ckp);
   pl.Kpad = x6_kpad(pl.K, pl.kd);
   pl.Npad = x6_npad(N);
@@ -2461,10 +2322,7 @@ static int conv2d_dgrad_launch(sg_ctx* ctx, hipStream_t st, int dtype, const sg_
       p.bnb.x = (const float*)bnb->x; p.bnb.mean = (const float*)bnb->mean; p.bnb.invstd = (const float*)bnb->invstd;
       p.bnb.gamma = (const float*)bnb->gamma; p.bnb.beta = (const float*)bnb->beta; p.bnb.dgamma = (const float*)bnb->dgamma;
       p.bnb.dbeta = (const float*)bnb->dbeta; p.bnb.dz = (float*)bnb->dz; p.bnb.relu = bnb->relu ? 1 : 0;
-      {
-        static const int abl = getenv("SG_BNB_ABLATE") ? atoi(getenv("SG_BNB_ABLATE")) : 0;   // timing only: 2 = no dz store, 4 = no x load
-        p.bnb.relu |= abl & 6;
-      }
+      p.bnb.relu |= sg_switch<SW_BNB_ABLATE>() & 6;   // timing only: 2 = no dz store, 4 = no x load
       p.bnb.inv_n = 1.0f / (float)bnb->rows;
     }
     if (pl.perm2) {   // rows in parity-class order: see IgemmParams::perm2
@@ -2777,15 +2635,9 @@ static int conv2d_wgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv
     const bool v4 = (n % 4 == 0) && aligned16(ws) && aligned16(dw);
     int64_t blocks = sg_cdiv(n, v4 ? 1024 : 256);
     if (blocks > 2048) blocks = 2048;
-    // SG_REDUCE_Z4=1: the four-lane kernel.  Measured (three alternating repetitions, gpurun_out/r4j): 73.98 against 74.08 ms per
-    // step - the reduce launches sit on the side stream behind their filter gradient and hide either way; the one-lane
-    // kernel of rounds 1 - 3 stays the default
-    static const int z4 = getenv("SG_REDUCE_Z4") ? atoi(getenv("SG_REDUCE_Z4")) : 0;
-    if (v4 && z4 && total_parts >= 8) {
-      int64_t b4 = sg_cdiv(n, 256);
-      if (b4 > 4096) b4 = 4096;
-      hipLaunchKernelGGL(reduce_splits_z4_kernel, dim3((unsigned)b4), dim3(256), 0, st, (const float*)ws, (float*)dw, n, total_parts);
-    } else if (v4)
+    // (a four-lanes-per-quad kernel measured no gain - the reduce launches sit on the side stream behind their filter gradient
+    // and hide either way - and is gone: DESIGN.md, retired)
+    if (v4)
       hipLaunchKernelGGL(reduce_splits_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, (float*)dw, n, total_parts);
     else
       hipLaunchKernelGGL(reduce_splits_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, (float*)dw, n, total_parts);
@@ -2817,7 +2669,7 @@ static bool wgrad_planes_geom(const sg_ctx* ctx, const sg_conv_desc* d, WgradPla
   if (pl.wide || pl.patch || pl.chunks > 1 || thin_ok(d)) return false;
   // SG_WGRAD_PIN_SMUL: more, shorter pixel shares than the fp32-operand plan (the planes are 1.5 x the bytes per pixel: the share
   // of x that the workgroups of an XCD walk together should still fit its L2)
-  static const int smul = getenv("SG_WGRAD_PIN_SMUL") ? atoi(getenv("SG_WGRAD_PIN_SMUL")) : 1;
+  const int smul = sg_switch<SW_WGRAD_PIN_SMUL>();
   if (smul > 1 && pl.S > 1) {
     const int64_t nslab = sg_cdiv((int64_t)d->N * d->Ho * d->Wo, BK);
     int64_t S = (int64_t)pl.S * smul;
@@ -2879,35 +2731,18 @@ int sg_conv2d_wgrad_planes(sg_ctx* ctx, void* stream, const sg_conv_desc* d, con
   p.dy_plane_bytes = (uint32_t)((int64_t)p.P * d->Cout * 2);
   p.x_bytes = 3 * p.x_plane_bytes;
   p.dy_bytes = 3 * p.dy_plane_bytes;
-  {
-    static int noskip = -1;
-    if (noskip < 0) noskip = getenv("SG_CONV_NOSKIP") ? 1 : 0;
-    p.KH_KW = p.K / p.Cin;
-    p.skip_slabs = (!noskip && p.dil > 1 && p.KH_KW > 1) ? 1 : 0;
-    p.tap_inner = ((conv_l2(true) & 4) && p.KH_KW > 1 && p.Cin % BM == 0) ? 1 : 0;   // as dispatch_wgrad: the same tile order
-  }
-  {
-    static const int abl = getenv("SG_X6_ABLATE") ? atoi(getenv("SG_X6_ABLATE")) & 15 : 0;   // timing-only diagnostics of the PF = 1 form
-    p.stagger = abl;
-  }
+  p.KH_KW = p.K / p.Cin;
+  p.skip_slabs = (!sg_switch<SW_CONV_NOSKIP>() && p.dil > 1 && p.KH_KW > 1) ? 1 : 0;
+  p.tap_inner = ((conv_l2(true) & 4) && p.KH_KW > 1 && p.Cin % BM == 0) ? 1 : 0;   // as dispatch_wgrad: the same tile order
+  p.stagger = sg_switch<SW_X6_ABLATE>() & 15;   // timing-only diagnostics
   const int bn = wgrad_bn(p.Cout);
-  // SG_WGRAD_PIN_PF: 1 = single LDS buffer, two workgroups per CU (the fp32-operand kernel's default structure); 2 = one workgroup
-  // per CU, two buffers, the stores of slab s + 1 and the loads of slab s + 3 woven between the MFMAs of slab s
-  // Measured (scripts/wgrad_planes_bench.py, fourteen long-K shapes, gpurun_out/r5h): 7301 us with PF 1, 7577 with PF 2, 8485 for
-  // the fp32-operand kernel - the read + MFMA loop itself takes 640 of the 810 us of the ASPP launch either way.
-  static const int pf = getenv("SG_WGRAD_PIN_PF") ? atoi(getenv("SG_WGRAD_PIN_PF")) : 1;
-  static const int w22 = getenv("SG_WGRAD_PIN_W22") ? atoi(getenv("SG_WGRAD_PIN_W22")) : 0;   // experiment: 4 waves of 64 x 64 per 128 x 128 tile
-  if (w22 && bn == 128) {
-    rc = (pf == 2) ? launch_wgrad_x6<128, 2, 2, 2, 3, bf16_t, true>(p, pl.S, st) : launch_wgrad_x6<128, 2, 2, 1, 3, bf16_t, true>(p, pl.S, st);
-  } else if (pf == 2) {
-    if (bn == 128) rc = launch_wgrad_x6<128, 2, 4, 2, 3, bf16_t, true>(p, pl.S, st);
-    else if (bn == 64) rc = launch_wgrad_x6<64, 4, 2, 2, 3, bf16_t, true>(p, pl.S, st);
-    else rc = launch_wgrad_x6<32, 4, 1, 2, 3, bf16_t, true>(p, pl.S, st);
-  } else {
-    if (bn == 128) rc = launch_wgrad_x6<128, 2, 4, 1, 3, bf16_t, true>(p, pl.S, st);
-    else if (bn == 64) rc = launch_wgrad_x6<64, 4, 2, 1, 3, bf16_t, true>(p, pl.S, st);
-    else rc = launch_wgrad_x6<32, 4, 1, 1, 3, bf16_t, true>(p, pl.S, st);
-  }
+  // Single LDS buffer, two workgroups per CU, the fp32-operand kernel's structure.  Measured (scripts/wgrad_planes_bench.py, fourteen
+  // long-K shapes): 7301 us against 8485 for the fp32-operand kernel; a double-buffered woven form took 7577 and four waves of 64 x 64
+  // per tile changed nothing - the read + MFMA loop itself takes 640 of the 810 us of the ASPP launch either way.  Both are gone
+  // (retired).
+  if (bn == 128) rc = launch_wgrad_x6<128, 2, 4, 1, 3, bf16_t, true>(p, pl.S, st);
+  else if (bn == 64) rc = launch_wgrad_x6<64, 4, 2, 1, 3, bf16_t, true>(p, pl.S, st);
+  else rc = launch_wgrad_x6<32, 4, 1, 1, 3, bf16_t, true>(p, pl.S, st);
   if (rc) return rc;
   if (pl.S > 1) {
     const int64_t n = (int64_t)K_all * d->Cout;

@@ -744,13 +744,8 @@ int launch_pw_wide(const IgemmParams& p, hipStream_t st) {
     return SG_EINVAL;
   }
   IgemmParams q = p;
-  {
-    static int abl = -1;
-    if (abl < 0) abl = getenv("SG_PW_ABLATE") ? atoi(getenv("SG_PW_ABLATE")) : 0;
-    q.ablate = abl;
-    static const int var = getenv("SG_PW_VAR") ? atoi(getenv("SG_PW_VAR")) : 1;
-    q.stagger = var;   // (the field is free in this kernel) 1: barrier in the middle of the k-step, 0: at its end
-  }
+  q.ablate = sg_switch<SW_PW_ABLATE>();
+  q.stagger = sg_switch<SW_PW_VAR>();   // (the field is free in this kernel) 1: barrier in the middle of the k-step, 0: at its end
   if constexpr (BNB) {
     if (q.ablate != 0 || q.stagger != 1 || p.K + 16 > PW_BNB_MAXK || p.x_ld != p.K) {
       sg_set_error("pw_wide: the BatchNormalization-backward form needs the default schedule (SG_PW_VAR=1, no ablation), a dense "
@@ -785,8 +780,7 @@ inline size_t pw_planes_bytes(int K, int N, int npl, int bn = PW_BN) { return (s
 // on conv_x6_kernel's 256 tiles of 128 x 128).  SG_PW_WIDE=3: 384 only.
 // Geometry fields only; the 16-byte channel runs are x6_ok's `vec` (plan_conv, the one caller).
 inline int pw_wide_width(const IgemmParams& p) {
-  static int on = -1;
-  if (on < 0) on = getenv("SG_PW_WIDE") ? atoi(getenv("SG_PW_WIDE")) : 1;
+  const int on = sg_switch<SW_PW_WIDE>();
   if (!on) return 0;
   if (p.K != p.C || p.a_mul != 1 || p.div != 1 || p.off_h != 0 || p.off_w != 0) return 0;
   // (both activation tensors of a launch are below 2 GiB by construction: larger batches run as sub-batches of whole images,
@@ -1285,8 +1279,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_pw_wide_b16_kernel(const WgradPa
 // plan of the wide filter gradient: tiles of 128 x 384, the pixel reduction cut into S shares of whole 16-pixel k-steps so
 // that tiles x S fills the CUs once
 inline bool wgrad_pw_wide_geom(const sg_conv_desc* d, int eb = 4) {
-  static int on = -1;
-  if (on < 0) on = getenv("SG_PW_WIDE") ? atoi(getenv("SG_PW_WIDE")) : 1;
+  const int on = sg_switch<SW_PW_WIDE>();
   if (!on) return false;
   if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad_t != 0 || d->pad_l != 0) return false;
   const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
@@ -1323,8 +1316,7 @@ inline int launch_wgrad_pw_wide(const WgradParams& p, int S, hipStream_t st) {
     sg_set_error("wgrad_pw_wide: bad grid (%lld tiles, %d splits)", (long long)tiles, S);
     return SG_EINVAL;
   }
-  static const int var = getenv("SG_WPW_VAR") ? atoi(getenv("SG_WPW_VAR")) : 1;
-  if (var == 1) hipLaunchKernelGGL(wgrad_pw_wide_kernel<1>, dim3((unsigned)tiles, 1, (unsigned)S), dim3(512), lds, st, p);
+  if (sg_switch<SW_WPW_VAR>() == 1) hipLaunchKernelGGL(wgrad_pw_wide_kernel<1>, dim3((unsigned)tiles, 1, (unsigned)S), dim3(512), lds, st, p);
   else hipLaunchKernelGGL(wgrad_pw_wide_kernel<0>, dim3((unsigned)tiles, 1, (unsigned)S), dim3(512), lds, st, p);
   SG_LAUNCH_CHECK("wgrad_pw_wide_kernel");
   return 0;

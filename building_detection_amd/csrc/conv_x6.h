@@ -796,15 +796,9 @@ int launch_x6(const IgemmParams& p, hipStream_t st) {
   return 0;
 }
 
-// Variant switch for A/B runs: SG_X6_VARIANT bit 0 = the one-workgroup-per-CU structure (PF == 2 above), bit 1 =
-// 4-wave workgroups (64x64 sub-tile per wave: half the LDS fragment traffic per MFMA).
+// Variant switch for A/B runs: SG_X6_VARIANT = 1: the one-workgroup-per-CU structure (PF == 2 above), 0: two workgroups per CU.
 inline int x6_variant() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SG_X6_VARIANT");
-    v = e ? atoi(e) & 3 : -1;  // -1: chosen per launch (dispatch_x6)
-  }
-  return v;
+  return sg_switch_set<SW_X6_VARIANT>() ? (sg_switch<SW_X6_VARIANT>() & 1) : -1;  // -1: chosen per launch (dispatch_x6)
 }
 
 // Convolution arithmetic on fp32 storage (sg_set_conv_x6 / SG_CONV_X6): 0 = native fp32 MFMA, 1 = the exact
@@ -813,18 +807,13 @@ inline int x6_variant() {
 int g_x6_enabled = -1;  // -1: not yet read from the environment; set by sg_set_conv_x6()
 inline int x6_mode() {
   if (g_x6_enabled < 0) {
-    const char* e = getenv("SG_CONV_X6");
-    g_x6_enabled = e ? atoi(e) : 1;
+    g_x6_enabled = sg_switch<SW_CONV_X6>();
     if (g_x6_enabled < 0 || g_x6_enabled > 2) g_x6_enabled = 1;
   }
   return g_x6_enabled;
 }
 inline bool x6_enabled() { return x6_mode() != 0; }
-inline bool x6_vpad_on() {
-  static int v = -1;
-  if (v < 0) v = getenv("SG_X6_VPAD") ? atoi(getenv("SG_X6_VPAD")) : 1;
-  return v != 0;
-}
+inline bool x6_vpad_on() { return sg_switch<SW_X6_VPAD>() != 0; }
 
 // Can this launch take the bf16-pipe kernels?  UT gather: every 32-deep slab inside one tap - Cin % 32 == 0, a 1x1
 // kernel, or (virtual channel padding, plan_conv) any channel count that keeps the pixel rows 16-byte aligned; `vec` =
@@ -863,9 +852,9 @@ struct X6WPitch {
   static constexpr int B = (BN == 128) ? 2 * BN + 64 : 192;   // 320 / 192 / 192
 };
 
-// PF == 1: single LDS buffer, two barriers per slab, two workgroups per CU.  PF == 2: one workgroup per CU, LDS
-// double-buffered, two register sets and the hand-interleaved step of conv_x6_kernel (the staging of slab s+1
-// and the loads of slab s+3 woven into the MFMA gaps of slab s).
+// PF == 1, the only form: single LDS buffer, two barriers per slab, two workgroups per CU.  (A PF == 2 form - one workgroup per
+// CU, LDS double-buffered, the hand-interleaved step of conv_x6_kernel - measured slower on fp32 operands and on planes and is
+// gone: DESIGN.md, retired.  The parameter stays: it is part of the kernels' names.)
 // NPL / TA as in conv_x6_kernel: NPL = 1 is the bf16 product (one plane, one MFMA per k-step and tile); with TA = bf16_t
 // both operands are bf16 in HBM and a thread's 16-byte chunk (8 channels) goes to LDS unchanged.
 constexpr int WG_NS = 1;  // register sets of the bf16 wgrad: 2 measured no faster (728 -> 728: 55 us either way,
@@ -877,7 +866,8 @@ constexpr int WG_NS = 1;  // register sets of the bf16 wgrad: 2 measured no fast
 // wave, between two barriers: as long as the MFMA phase itself.  Same LDS image, same fragments, same products in the same order
 // as the fp32 form: bit-identical results.
 template <int BN, int WGM, int WGN, int PF, int NPL = 3, typename TA = float, bool PIN = false>
-__global__ __launch_bounds__(64 * WGM * WGN, PF == 2 ? (WGM * WGN + 3) / 4 : WGM * WGN / 2) void wgrad_x6_kernel(const WgradParams p) {
+__global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN / 2) void wgrad_x6_kernel(const WgradParams p) {
+  static_assert(PF == 1, "one LDS buffer");
   static_assert(NPL == 3 || NPL == 1, "planes");
   static_assert(NPL == 1 || std::is_same<TA, float>::value || PIN, "the three-plane split is the fp32 path");
   static_assert(!PIN || (NPL == 3 && !std::is_same<TA, float>::value), "planes in: three bf16 planes per operand");
@@ -964,7 +954,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, PF == 2 ? (WGM * WGN + 3) / 4 : WGM
 
   // NS register sets of prefetched slabs.  The bf16-storage form has 4 MFMAs per wave and slab against a memory latency of
   // several slab times: it keeps WG_NS slabs of loads in flight (a set is two 16-byte registers there); the six-pass form
-  // (24 MFMAs per slab, 24 registers per set) keeps one, or two with the double-buffered structure.
+  // (24 MFMAs per slab, 24 registers per set) keeps one.
   constexpr int NS = (PF == 1 && NPL == 1 && A16) ? WG_NS : PF;
   u32x4_t ra[NS][NA * NLD], rb[NS][NB * NLD];
   auto load_AB = [&](int p0, auto SET) {
@@ -1200,119 +1190,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, PF == 2 ? (WGM * WGN + 3) / 4 : WGM
         const int pn = slab_of(s < lasti ? s + 1 : lasti) * BK;
         if (do_ld) load_AB(pn, IC<0>{});
         if (do_mm) compute(0);
-      }
-    } else if constexpr (NPL == 3) {
-      // fused step: MFMAs of the slab in buffer cbuf with, one piece per MFMA, the split + store of register set S
-      // into buffer sbuf and the loads of slab p0 into the same set
-      auto fused_step = [&](int p0, auto SET, int sbuf, int cbuf) {
-        constexpr int S = decltype(SET)::value;
-        constexpr int NM = 12 * TM * TN;
-        bf16x8_t af[2][TM][3], bf[2][TN][3];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-              constexpr int APL[3] = {2, 0, 1}, BPL[3] = {0, 2, 1};
-              const char* a = a_lane + cbuf * BUFSZ + (APL[u] * BK + 16 * ks) * PA + 64 * i;
-              af[ks][i][APL[u]] = tr_frag(a, a + 4 * PA);
-              if (i == 0) {
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                  const char* b = b_lane + cbuf * BUFSZ + (BPL[u] * BK + 16 * ks) * PB + 64 * j;
-                  bf[ks][j][BPL[u]] = tr_frag(b, b + 4 * PB);
-                }
-              }
-              if (ks == 0 && i == 0) __builtin_amdgcn_sched_barrier(0);
-            }
-        __builtin_amdgcn_sched_barrier(0);
-        uint32_t q_, ow0, n_, oh;
-        fd_divmod((uint32_t)p0, p.fd_ow, q_, ow0);
-        fd_divmod(q_, p.fd_oh, n_, oh);
-        const bool row_ok = (unsigned)((int)oh + s_dh) < (unsigned)p.H;
-        const int soff_a = p0 * p.x_ld * EB, soff_b = p0 * p.y_ld * EB;
-        const int col0 = (int)ow0 + s_dw + pr0;
-        unsigned ha[NA][2], ma[NA][2], la[NA][2], hb[NB][2], mb[NB][2], lb[NB][2];
-        constexpr int P_SA = PIN ? 0 : 2 * NA, P_WA = P_SA + NA * NLD, P_SB = P_WA + (PIN ? 0 : 2 * NB), P_WB = P_SB + NB * NLD,
-                      P_LA = P_WB + NA * NLD, P_LB = P_LA + NB * NLD;
-        auto piece = [&](int w) {
-          if constexpr (PIN) {
-            // planes in: nothing to compute - 12 LDS stores of register set S (slab s + 1) into buffer sbuf, then the 12 loads of
-            // slab p0 into the same set, one piece behind each of the slab's 24 MFMAs
-            if (w < P_WA) {
-              const int j = w / 3, pl = w % 3;
-              *reinterpret_cast<u32x4_t*>(Ap + sbuf * BUFSZ + pl * BK * PA + (pr0 + PS * j) * PA + rc * 16) = ra[S][j * 3 + pl];
-            } else if (w < P_WB) {
-              const int i = (w - P_WA) / 3, pl = (w - P_WA) % 3, idx = t + NT * i;
-              if ((NBC % NT == 0) || idx < NBC)
-                *reinterpret_cast<u32x4_t*>(Bp + sbuf * BUFSZ + pl * BK * PB + (idx / CPB) * PB + (idx % CPB) * 16) = rb[S][i * 3 + pl];
-            } else if (w < P_LA) {
-              const int j = (w - P_WB) / 3, pl = (w - P_WB) % 3;
-              const bool v = row_ok && ((unsigned)(col0 + PS * j) < (unsigned)p.W);
-              ra[S][j * 3 + pl] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, (int)(v ? a_voffc[j] : OOB), soff_a + pl * (int)p.x_plane_bytes, 0);
-            } else if (w < P_LB) {
-              const int i = (w - P_LA) / 3, pl = (w - P_LA) % 3;
-              rb[S][i * 3 + pl] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_dy, (int)b_voff[i], soff_b + pl * (int)p.dy_plane_bytes, 0);
-            }
-            return;
-          }
-          if (w < P_SA) {
-            const int j = w >> 1, hf = w & 1;
-            const f32x4 f = __builtin_bit_cast(f32x4, ra[S][j]);
-            split3_pair(f[2 * hf], f[2 * hf + 1], ha[j][hf], ma[j][hf], la[j][hf]);
-          } else if (w < P_WA) {
-            const int j = w - P_SA;
-            char* dst = Ap + sbuf * BUFSZ + (pr0 + PS * j) * PA + rc * 8;
-            *reinterpret_cast<u32x2_t*>(dst) = (u32x2_t){ha[j][0], ha[j][1]};
-            *reinterpret_cast<u32x2_t*>(dst + BK * PA) = (u32x2_t){ma[j][0], ma[j][1]};
-            *reinterpret_cast<u32x2_t*>(dst + 2 * BK * PA) = (u32x2_t){la[j][0], la[j][1]};
-          } else if (w < P_SB) {
-            const int i = (w - P_WA) >> 1, hf = (w - P_WA) & 1;
-            const f32x4 f = __builtin_bit_cast(f32x4, rb[S][i]);
-            split3_pair(f[2 * hf], f[2 * hf + 1], hb[i][hf], mb[i][hf], lb[i][hf]);
-          } else if (w < P_WB) {
-            const int i = w - P_SB, idx = t + NT * i;
-            if ((NBC % NT == 0) || idx < NBC) {
-              const int kr = idx / (BN / 4), c4 = idx % (BN / 4);
-              char* dst = Bp + sbuf * BUFSZ + kr * PB + c4 * 8;
-              *reinterpret_cast<u32x2_t*>(dst) = (u32x2_t){hb[i][0], hb[i][1]};
-              *reinterpret_cast<u32x2_t*>(dst + BK * PB) = (u32x2_t){mb[i][0], mb[i][1]};
-              *reinterpret_cast<u32x2_t*>(dst + 2 * BK * PB) = (u32x2_t){lb[i][0], lb[i][1]};
-            }
-          } else if (w < P_LA) {
-            const int j = w - P_WB;
-            const bool v = row_ok && ((unsigned)(col0 + PS * j) < (unsigned)p.W);
-            ra[S][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, (int)(v ? a_voffc[j] : OOB), soff_a, 0);
-          } else if (w < P_LB) {
-            const int i = w - P_LA;
-            rb[S][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_dy, (int)b_voff[i], soff_b, 0);
-          }
-        };
-#pragma unroll
-        for (int q = 0; q < NM; ++q) {
-          const int ks = q / (6 * TM * TN), r = q % (6 * TM * TN), tile = r / 6, term = r % 6;
-          const int i = tile / TN, j = tile % TN;
-          constexpr int PA_[6] = {2, 0, 1, 1, 0, 0}, PB_[6] = {0, 2, 1, 0, 1, 0};
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks][i][PA_[term]], bf[ks][j][PB_[term]], acc[i][j], 0, 0, 0);
-          piece(q);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int w = NM; w < P_LB; ++w) piece(w);
-      };
-      auto slab_at = [&](int i) -> int { return slab_of(i < lasti ? i : lasti) * BK; };
-      load_AB(slab_at(0), IC<0>{});
-      load_AB(slab_at(1), IC<1>{});
-      store_AB(IC<0>{}, 0);
-      load_AB(slab_at(2), IC<0>{});
-      __syncthreads();
-      for (int s = 0; s < nslab; s += 2) {
-        fused_step(slab_at(s + 3), IC<1>{}, 1, 0);
-        __syncthreads();
-        if (s + 1 >= nslab) break;
-        fused_step(slab_at(s + 4), IC<0>{}, 0, 1);
-        __syncthreads();
       }
     }
   }

@@ -587,8 +587,7 @@ __global__ __launch_bounds__(256, 2) void conv_x6p_kernel(const IgemmParams p, i
 }
 
 inline bool x6p_enabled() {
-  static const bool on = getenv("SG_X6_NOPATCH") == nullptr;
-  return on;
+  return !sg_switch<SW_X6_NOPATCH>();
 }
 
 // geometry the patch form covers; KH, KW are the filter's (IgemmParams carries only K).  Geometry fields only: plan_conv, the
@@ -599,8 +598,7 @@ inline bool x6p_geom(const IgemmParams& p, int KH, int KW) {
   // 32 or 64 reduction channels per tap in one patch; 128 / 256 / ... in chunks of 64 (round 5)
   if (p.K != 9 * p.C) return false;
   if (!(p.C == 32 || p.C == 64)) {
-    static const int multi = getenv("SG_X6P_CHUNKS") ? atoi(getenv("SG_X6P_CHUNKS")) : 1;
-    if (!multi || p.C % 64 != 0 || p.C > 512) return false;
+    if (!sg_switch<SW_X6P_CHUNKS>() || p.C % 64 != 0 || p.C > 512) return false;
   }
   if (p.a_mul != 1 || p.div != 1) return false;
   const bool fwd = p.k_mul == 1 && p.off_h == -1 && p.off_w == -1, bwd = p.k_mul == -1 && p.off_h == 1 && p.off_w == 1;
@@ -634,8 +632,7 @@ int launch_x6p(const IgemmParams& p, int num_cus, hipStream_t st) {
   // Experiment switch, default OFF (measured: no effect, the workgroups of a CU are not in lockstep): SG_X6P_DELAY = start
   // offset of the CU's 2nd (3rd) workgroup in 10 ns ticks (-1: one K loop of a tile at ~1.1 TFLOP/s per CU); only when
   // every workgroup walks at least two tiles
-  static int dly_env = -2;
-  if (dly_env == -2) dly_env = getenv("SG_X6P_DELAY") ? atoi(getenv("SG_X6P_DELAY")) : 0;
+  const int dly_env = sg_switch<SW_X6P_DELAY>();
   int delay = 0;
   if (dly_env != 0 && grid == slots && wg_per_cu > 1 && tiles >= 2 * slots)
     delay = dly_env > 0 ? dly_env : (int)(2.0 * 128 * BN * 9 * C / 1.1e6 * 100.0 + 0.5);
@@ -648,11 +645,7 @@ int launch_x6p(const IgemmParams& p, int num_cus, hipStream_t st) {
 int run_x6p(IgemmParams& p, const float* w, bool dgrad, int Cin, int Cout, void* ws, int num_cus, hipStream_t st,
             bool prepared = false) {
   const int K = p.K, N = p.Nout;
-  {
-    static int abl = -1;  // SG_X6P_ABLATE (timing only, results wrong): 1 = no K loop, 2 = no patch loads, 4 = phase clocks into y, 8 = no y stores
-    if (abl < 0) abl = getenv("SG_X6P_ABLATE") ? atoi(getenv("SG_X6P_ABLATE")) & 15 : 0;
-    p.ablate = abl;
-  }
+  p.ablate = sg_switch<SW_X6P_ABLATE>() & 15;  // timing only, results wrong: 1 = no K loop, 2 = no patch loads, 4 = phase clocks into y, 8 = no y stores
   p.wq = (const unsigned short*)ws;
   if (!prepared) {
     const int64_t threads = (int64_t)(K / 16) * (N / 32) * 64;

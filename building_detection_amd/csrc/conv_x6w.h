@@ -396,7 +396,7 @@ __global__ __launch_bounds__(512, 2) void conv_x6w_kernel(const IgemmParams p, c
 // Geometry fields only (plan_conv, the one caller, has the 16-byte channel runs from x6_ok's `vec`).  A launch that adds a collected
 // gradient reads the same weight planes through conv_x6_kernel instead (run_x6): this kernel has no such epilogue.
 inline int x6w_shares(const IgemmParams& p) {
-  static const int on = getenv("SG_X6_WIDE") ? atoi(getenv("SG_X6_WIDE")) : 2;
+  const int on = sg_switch<SW_X6_WIDE>();
   if (!on) return 0;
   if (p.div != 1 || p.C % XW_KD != 0 || p.K == p.C || p.K < 2048 || p.K / p.C > 64) return 0;   // (div 1: never parity-class rows)
   if (on < 2 && !(p.k_mul > 1 || p.k_mul < -1)) return 0;   // 1: dilated taps only
@@ -447,8 +447,7 @@ inline int launch_x6w(const IgemmParams& p, int S, char* scratch, hipStream_t st
     aq = (const unsigned short*)scratch;
   }
   float* part = S > 1 ? reinterpret_cast<float*>(scratch + a_bytes) : nullptr;
-  static const int var = getenv("SG_X6W_VAR") ? atoi(getenv("SG_X6W_VAR")) : 1;
-  if (var == 1)
+  if (sg_switch<SW_X6W_VAR>() == 1)
     hipLaunchKernelGGL(conv_x6w_kernel<1>, dim3((unsigned)(tiles * S)), dim3(512), (size_t)XW_LDS, st, p, aq,
                        (uint32_t)(3 * plane), (uint32_t)plane, S, part);
   else

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x6wp_kernel(const WgradParams p,
 }
 
 inline bool x6wp_enabled() {
-  static const bool on = getenv("SG_X6_NOWPATCH") == nullptr;
+  const bool on = !sg_switch<SW_X6_NOWPATCH>();
   return on;
 }
 

@@ -390,7 +390,7 @@ int launch_bn_apply(hipStream_t st, bool vec, const T* x, const float* mean, con
                     const float* beta, T* y, int64_t rows, int C, int relu, float eps, int infer, int num_cus) {
   const bool wide = vec && sizeof(T) == 2 && C % 8 == 0;  // bf16: 8 channels = one 16-byte access
   const int V = wide ? 8 : (vec ? 4 : 1);
-  static const int cols_on = getenv("SG_BN_COLS") ? atoi(getenv("SG_BN_COLS")) : 1;
+  const int cols_on = sg_switch<SW_BN_COLS>();
   int prow = 0;
   dim3 cgrid;
   if (vec && cols_on && bn_cols_grid(num_cus, rows, C / V, 4, prow, cgrid)) {
@@ -430,7 +430,7 @@ static void bn_bwd_apply_launch(sg_ctx* ctx, hipStream_t st, bool vec, int64_t r
     const int V = wide ? 8 : (vec ? 4 : 1);
     const unsigned blocks = ew_blocks(rows * (C / V));
     const int mode = !relu ? 0 : (beta ? 2 : 1);
-    static const int cols_on = getenv("SG_BN_COLS") ? atoi(getenv("SG_BN_COLS")) : 1;
+    const int cols_on = sg_switch<SW_BN_COLS>();
     auto apply = [&](auto vt, auto mt) {
       constexpr int V_ = decltype(vt)::value, M_ = decltype(mt)::value;
       if constexpr (V_ > 1) {

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/segengine.h"
+#include "sg_switch.h"
 
 struct sg_ctx {
   int device;

@@ -213,8 +213,7 @@ __global__ __launch_bounds__(256) void seg_finalize_kernel(const Op op, const in
 // the finalize launch: 16 lanes per channel where there are many partial rows
 template <class Op>
 static inline void seg_finalize_launch(const Op& op, int nseg, int C, int S, const float* part, hipStream_t st) {
-  static const int wide = getenv("SG_FINALIZE_LANES") ? atoi(getenv("SG_FINALIZE_LANES")) : 16;   // A/B switch: 4 = rounds 1 - 3
-  if (S >= 32 && wide == 16)
+  if (S >= 32 && sg_switch<SW_FINALIZE_LANES>() == 16)   // A/B switch: 4 = rounds 1 - 3
     hipLaunchKernelGGL((seg_finalize_kernel<Op, 16>), dim3((unsigned)sg_cdiv(C, 16), (unsigned)nseg), dim3(256), 0, st, op, nseg, C, S, part);
   else
     hipLaunchKernelGGL((seg_finalize_kernel<Op, 4>), dim3((unsigned)sg_cdiv(C, 64), (unsigned)nseg), dim3(256), 0, st, op, nseg, C, S, part);
@@ -298,7 +297,7 @@ static inline int seg_reduce_launch(const Op& op, const SegPlan& pl, int nseg, i
   // part: the agent-scope release / acquire pair makes every workgroup write back and invalidate its XCD's whole L2 -
   // which holds the previous kernel's output, i.e. this kernel's input - and the DeepLabv3+ step went 86 -> 117 ms (fp32),
   // 39 -> 63 ms (bf16).  Kept for re-measurement only.
-  static const int fused_mode = getenv("SG_SEG_FUSED") ? atoi(getenv("SG_SEG_FUSED")) : 1;
+  const int fused_mode = sg_switch<SW_SEG_FUSED>();
   unsigned* cnt = nullptr;
   int fuse = 0;
   if (fused_mode >= 1 && pl.S == 1) fuse = 1;

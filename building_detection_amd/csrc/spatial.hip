@@ -419,7 +419,8 @@ struct DwWgradRunOp {
 // DwWgradRunOp<.., BN = true>); the zero padding then has to be put back by masks, since BN(0) != 0.
 // (BN: held to two waves per SIMD - left to itself the variant takes a few registers more than 256, i.e. ONE wave per SIMD,
 // and ran 110 us where the plain kernel takes 50 (profiles/r04_bench_kernel_stats_final.csv))
-// OCC2 (SG_DW_STRIP_OCC2, A/B switch for the BN variants): two waves per SIMD with 12 - 62 spilled registers
+// OCC2: two waves per SIMD with 12 - 62 spilled registers; measured a loss and no longer instantiated (retired) -
+// the parameter stays, it is part of the kernel's name
 template <typename T, bool PRE, bool BN, bool OCC2 = false>
 __global__ __launch_bounds__(256, OCC2 ? 2 : 1) __attribute__((amdgpu_waves_per_eu(1, 2))) void dw_wgrad_strip_kernel(
     const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ part, const int H, const int W, const int C,
@@ -600,24 +601,24 @@ inline bool dw_run_ok(const sg_conv_desc* d) {
 }
 
 inline bool dw_strip_ok(const sg_conv_desc* d) {
-  static const int on = getenv("SG_DW_STRIP") ? atoi(getenv("SG_DW_STRIP")) : 1;
+  const int on = sg_switch<SW_DW_STRIP>();
   const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
   const int64_t pix = (int64_t)d->N * d->H * d->W;
   // byte offsets are 32-bit buffer offsets in which bit 30 / bit 31 mark a column / row outside the image: tensors below 1 GiB
   return on && dw_run_ok(d) && d->H % 4 == 0 && pix * (xl > yl ? xl : yl) * 4 < (1ll << 30);
 }
 
-// Rows per run, measured (profiles/r01_bw_census.txt, SG_DW_RR = 1 / 2 / 4): the stencil kernels want tall strips on
-// small maps (32x32x728 bs16: 35 -> 24 us at 4 rows) and 2 rows on large ones; the kernel-gradient reduction loses
-// more from the shrinking number of runs than it gains on small maps (51 -> 65 us at 4 rows) and takes 2 rows
-// only from 64x64 up (64x64x728: 248 -> 157 us).
+// Rows per run, measured (profiles/r01_bw_census.txt): the stencil kernels take 2 rows; the kernel-gradient reduction loses
+// more from the shrinking number of runs than it gains on small maps and takes 2 rows only from 64x64 up (64x64x728:
+// 248 -> 157 us).  SG_DW_RR = 1 / 2 forces a value.
+// (Four rows per run are gone: the four-row stencil window ran at the 168-register cap with 47 - 73 spilled registers - three
+// alternating repetitions on one box: 75.90 -> 75.04 ms per step without it, profiles/r04_ab_runs.txt - and the reduction
+// went 51 -> 65 us with it.  DESIGN.md, retired.)
 inline int dw_rows_per_run(int H, int64_t pixels, bool wgrad) {
-  static const int force = getenv("SG_DW_RR") ? atoi(getenv("SG_DW_RR")) : 0;  // A/B switch: 1, 2 or 4
+  const int force = sg_switch<SW_DW_RR>();  // A/B switch: 1 or 2
   const bool small = pixels <= 32768;
-  // (round 4: two rows per stencil run on the small maps too - the four-row window runs at the 168-register cap with 47 - 73
-  // spilled registers; three alternating repetitions on one box: 75.90 -> 75.04 ms per step, profiles/r04_ab_runs.txt)
   const int want = force ? force : (wgrad ? (small ? 1 : 2) : 2);
-  return (want >= 4 && H % 4 == 0) ? 4 : ((want >= 2 && H % 2 == 0) ? 2 : 1);
+  return (want >= 2 && H % 2 == 0) ? 2 : 1;
 }
 
 constexpr int DW_SUMS_MAX_ROWS = 1024;
@@ -828,7 +829,7 @@ inline bool dw_fstrip_ok(const DwRunParams<T>& p) {
   // 34.0 -> 30.7 us, 128x128x128 62.0 -> 54.9, 256x256x64 115.0 -> 106.1 (strips of 16 rows); the 32x32 maps of the middle flow run
   // no faster (27.2 -> 31.8 us alone, +-0.1 ms in the step at any strip height): with 1.4 waves per SIMD the strips are
   // latency-bound there, and the run kernel was not load-issue bound to begin with (76 % of copy speed).
-  static const int on = getenv("SG_DW_FSTRIP") ? atoi(getenv("SG_DW_FSTRIP")) : 1;
+  const int on = sg_switch<SW_DW_FSTRIP>();
   const int64_t pix = (int64_t)p.N * p.H * p.W;
   if (!on || (on == 1 && p.H < 64)) return false;
   // byte offsets are 32-bit buffer offsets in which bit 30 / bit 31 mark a column / row outside the image: inputs below 1 GiB
@@ -837,7 +838,7 @@ inline bool dw_fstrip_ok(const DwRunParams<T>& p) {
 
 template <typename T>
 int launch_dw_strip(const DwRunParams<T>& p, hipStream_t st, int* sums_rows) {
-  static const int hs_force = getenv("SG_DW_FSTRIP_HS") ? atoi(getenv("SG_DW_FSTRIP_HS")) : 0;
+  const int hs_force = sg_switch<SW_DW_FSTRIP_HS>();
   DwStripGeom<T> g;
   g.HS = hs_force > 0 ? hs_force : (p.H >= 64 ? 16 : (p.H >= 16 ? 8 : p.H));
   if (g.HS % 4 != 0 || g.HS > p.H) g.HS = 4;
@@ -888,8 +889,7 @@ int launch_dw_run(const DwRunParams<T>& p_in, hipStream_t st, int* sums_rows = n
     }
     return launch_dw_strip(p, st, sums_rows);
   }
-  int rr = dw_rows_per_run(p.H, (int64_t)p.N * p.H * p.W, false);
-  if (p.bs_part && rr == 4) rr = 2;   // the four-row window plus the BatchNormalization sums does not fit the register file
+  const int rr = dw_rows_per_run(p.H, (int64_t)p.N * p.H * p.W, false);
   p.nruns = (int64_t)p.N * (p.H / rr) * p.runs_per_row;
   p.fd_h = make_fastdiv((uint32_t)(p.H / rr));
   int lc = 1;
@@ -912,8 +912,7 @@ int launch_dw_run(const DwRunParams<T>& p_in, hipStream_t st, int* sums_rows = n
     if (p.mask) hipLaunchKernelGGL((dw_s1_run_kernel<RR_, T, false, true, false, true>), grid, dim3(256), 0, st, p);    \
     else hipLaunchKernelGGL((dw_s1_run_kernel<RR_, T, false, false, false, true>), grid, dim3(256), 0, st, p);          \
   } while (0)
-    if (rr == 4) SG_DW_RUN_SUMS(4);
-    else if (rr == 2) SG_DW_RUN_SUMS(2);
+    if (rr == 2) SG_DW_RUN_SUMS(2);
     else SG_DW_RUN_SUMS(1);
 #undef SG_DW_RUN_SUMS
     SG_LAUNCH_CHECK("dw_s1_run_kernel<SUMS>");
@@ -936,11 +935,9 @@ int launch_dw_run(const DwRunParams<T>& p_in, hipStream_t st, int* sums_rows = n
     else hipLaunchKernelGGL((dw_s1_run_kernel<RR_, T, false, false, true>), grid, dim3(256), 0, st, p);                 \
   } while (0)
   if (p.bn_gamma) {
-    if (rr == 4) SG_DW_RUN_BN(4);
-    else if (rr == 2) SG_DW_RUN_BN(2);
+    if (rr == 2) SG_DW_RUN_BN(2);
     else SG_DW_RUN_BN(1);
-  } else if (rr == 4) SG_DW_RUN(4);
-  else if (rr == 2) SG_DW_RUN(2);
+  } else if (rr == 2) SG_DW_RUN(2);
   else SG_DW_RUN(1);
 #undef SG_DW_RUN_BN
 #undef SG_DW_RUN
@@ -1709,12 +1706,6 @@ static int dwconv2d_wgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_co
       const unsigned yb_ = (unsigned)((int64_t)d->N * d->H * d->W * op.y_ld * (int64_t)sizeof(T));
       auto strip = [&](auto pre_, auto bn_) {
         constexpr bool PRE_ = decltype(pre_)::value, BN_ = decltype(bn_)::value;
-        static const int occ2 = getenv("SG_DW_STRIP_OCC2") ? atoi(getenv("SG_DW_STRIP_OCC2")) : 0;
-        if (BN_ && occ2)
-          hipLaunchKernelGGL((dw_wgrad_strip_kernel<T, PRE_, BN_, BN_>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)dy,
-                             (float*)ws, d->H, d->W, op.C, op.x_ld, op.y_ld, sp.HS, sp.nstrips, sp.S, xb_, yb_, fq, fh,
-                             (const float*)bn_gamma, (const float*)bn_beta, (const float*)bn_mean, (const float*)bn_invstd);
-        else
         hipLaunchKernelGGL((dw_wgrad_strip_kernel<T, PRE_, BN_>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)dy,
                            (float*)ws, d->H, d->W, op.C, op.x_ld, op.y_ld, sp.HS, sp.nstrips, sp.S, xb_, yb_, fq, fh,
                            (const float*)bn_gamma, (const float*)bn_beta, (const float*)bn_mean, (const float*)bn_invstd);
@@ -1749,20 +1740,16 @@ static int dwconv2d_wgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_co
       };
       if (bn_gamma) {
         if (pre_relu) {
-          if (rr == 4) return run(DwWgradRunOp<4, T, true, true>{});
           if (rr == 2) return run(DwWgradRunOp<2, T, true, true>{});
           return run(DwWgradRunOp<1, T, true, true>{});
         }
-        if (rr == 4) return run(DwWgradRunOp<4, T, false, true>{});
         if (rr == 2) return run(DwWgradRunOp<2, T, false, true>{});
         return run(DwWgradRunOp<1, T, false, true>{});
       }
       if (pre_relu) {
-        if (rr == 4) return run(DwWgradRunOp<4, T, true>{});
         if (rr == 2) return run(DwWgradRunOp<2, T, true>{});
         return run(DwWgradRunOp<1, T, true>{});
       }
-      if (rr == 4) return run(DwWgradRunOp<4, T, false>{});
       if (rr == 2) return run(DwWgradRunOp<2, T, false>{});
       return run(DwWgradRunOp<1, T, false>{});
     }

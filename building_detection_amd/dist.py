@@ -108,8 +108,8 @@ class CommInitError(RuntimeError):
 
 
 def _init_timeout_s() -> float:
-    import os
-    return float(os.environ.get("SG_COMM_INIT_TIMEOUT", "180"))
+    from . import switches
+    return switches.get("SG_COMM_INIT_TIMEOUT")
 
 
 def _comm_init(lib, _lib, uid, rank, world, device_index, timeout_s):

@@ -8,7 +8,6 @@ reference's un-fused spelling onto the generic nodes.
 """
 from __future__ import annotations
 
-import os
 
 from typing import List, Optional, Sequence
 
@@ -17,6 +16,7 @@ import numpy as np
 from .graph import KTensor, Node
 from .ops import conv_out_geometry, same_pad
 from . import _lib
+from . import switches
 
 
 def _pair(v):
@@ -181,7 +181,7 @@ class _ConvNode(Node):
                 # (not for the dilated ASPP / SK convolutions: they are the roofline kernel set, timed as pure convolutions)
                 # or the thin 1x1 kernel (scSE's spatial squeeze, Cout = 1)
                 thin = (self.k == 1 and self.stride == 1 and self.filters <= 4 and x.shape[-1] % 4 == 0 and x.shape[-1] >= 16
-                        and "SG_CONV_NOTHIN" not in os.environ)
+                        and not switches.get("SG_CONV_NOTHIN"))
                 if (self._tag is None and dz.dtype == x.dtype and not up2
                         and (thin or (rt.plane_kind(self, "d") == 1 and rt.planes(self, "d") is not None))):
                     root = self.inputs[0]

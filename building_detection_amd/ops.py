@@ -10,13 +10,13 @@ from __future__ import annotations
 import collections
 import contextlib
 import ctypes as C
-import os
 import threading
 from typing import Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
+from . import switches
 from ._lib import ConvDesc, SG_F32, SG_BF16, SG_HEAD_F32, check
 
 
@@ -65,7 +65,7 @@ def _dt(t: torch.Tensor) -> int:
     return SG_BF16 if t.dtype == torch.bfloat16 else SG_F32
 
 
-_TRACE_MARK = os.environ.get("SG_TRACE_MARK", "0") == "1"
+_TRACE_MARK = switches.get("SG_TRACE_MARK")
 _MARK_TAGS = {"dilated_conv": 0, "gemm_conv": 1}
 
 
@@ -141,7 +141,7 @@ class Engine:
         # Filter gradients beside the input-gradient chain: conv2d_wgrad / dwconv_wgrad launches go to a second
         # stream behind an event, so that these MFMA-bound kernels overlap the bandwidth-bound BatchNormalization / depthwise /
         # add kernels of the chain.  SG_SIDE_WGRAD=0 keeps everything on one stream.
-        self._side_mode = int(os.environ.get("SG_SIDE_WGRAD", "1"))   # 1: all filter gradients, 2: GEMM ones only, 3: depthwise only
+        self._side_mode = switches.get("SG_SIDE_WGRAD")   # 1: all filter gradients, 2: GEMM ones only, 3: depthwise only
         self._side_on = self._side_mode > 0
         self._side_stream = None
         self.side_launches = 0   # blocks that went to the side stream (tests)
@@ -156,7 +156,7 @@ class Engine:
         self._side_group_blocks = 0
         self._side_kept = 0          # bytes of operands held (an operand listed twice counts twice: an upper bound)
         self._side_blocks_since_join = 0
-        self._side_keep_bound = int(float(os.environ.get("SG_SIDE_KEEP_GIB", "4")) * 2 ** 30)
+        self._side_keep_bound = int(switches.get("SG_SIDE_KEEP_GIB") * 2 ** 30)
         self._in_side = False
         self.lane = None         # set while a training step is captured with a side lane (side_run defers into it)
         self._ws2 = torch.empty(1 << 20, dtype=torch.uint8, device=self.device)

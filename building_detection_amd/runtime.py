@@ -23,6 +23,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
+from . import switches
 from .graph import KTensor, Node, ParamSpec, collect_nodes, init_array
 from . import layers as L
 from . import losses as LS
@@ -163,7 +164,7 @@ class Model:
         # it sums (sg_add2_bn), the normalised tensor is never written or read: one of the layer's two forward passes
         # (SG_BN_ADD=0 keeps them apart).  The backward is untouched: dy of the Add IS dy of the BatchNormalization, whose
         # backward reads its raw input.
-        if os.environ.get("SG_BN_ADD", "1") == "1":
+        if switches.get("SG_BN_ADD"):
             for n in self.nodes:
                 if not isinstance(n, L._AddNode) or len(n.inputs) != 2 or len(n.output.shape) != 4:
                     continue
@@ -190,7 +191,7 @@ class Model:
         # input), so the reduction pass of the BatchNormalization's backward - two tensor reads of its five passes - is not run
         # (round 4; conv_bn_relu / the Xception blocks, train_model/DeepLabv3plus.py:323-416,424-429; SG_BN_SUMS=0 switches it
         # off).  Decided again at run time (geometry, training mode: _SepConvNode.backward).
-        if os.environ.get("SG_BN_SUMS", "1") == "1":
+        if switches.get("SG_BN_SUMS"):
             for n in self.nodes:
                 if not isinstance(n, L._BNNode) or len(n.output.shape) != 4 or id(n.output) in outs or n.defer_add is not None:
                     continue
@@ -225,7 +226,7 @@ class Model:
                 _, h, w, c = root.shape
                 if cands and w % 4 == 0 and c % 4 == 0:
                     cands[0].sums_from, sc.bnsum_src = sc, cands[0]
-        if os.environ.get("SG_BN_DEFER", "1") == "1":
+        if switches.get("SG_BN_DEFER"):
             for n in self.nodes:
                 if not isinstance(n, L._BNNode) or len(n.output.shape) != 4 or id(n.output) in outs:
                     continue
@@ -668,8 +669,8 @@ class GraphedTrainStep:
         dist = model.dist
         self.x, self.y = torch.empty_like(xd), torch.empty_like(yd)
         self.lr = eng.zeros(4)
-        lanes = os.environ.get("SG_JIT_LANES", "1") != "0" and eng._side_on
-        lane_blocks = max(1, int(os.environ.get("SG_JIT_LANE_BLOCKS", "24")))
+        lanes = switches.get("SG_JIT_LANES") and eng._side_on
+        lane_blocks = max(1, switches.get("SG_JIT_LANE_BLOCKS"))
         # (the eager sizing steps ran the filter gradients on the side stream with its own scratch; without lanes they run
         # inline here, on the main scratch)
         self.ws = torch.empty(max(eng._ws_peak, eng._ws2_peak, 256) + 256, dtype=torch.uint8, device=eng.device)
@@ -968,7 +969,7 @@ class _Runtime:
         self._planes_launch = (0, 0)
         self._planes_dirty = True
         self._w_version = 0   # bumped by weights_changed(): captured graphs compare it with the version their planes hold
-        self._use_planes = os.environ.get("SG_PREPARED_PLANES", "1") != "0"
+        self._use_planes = switches.get("SG_PREPARED_PLANES")
 
     # -- parameters ---------------------------------------------------------------------------------------
     def param(self, p: ParamSpec):
@@ -1020,7 +1021,7 @@ class _Runtime:
         if got is None:
             p = bn_node.bnb_to
             got = False
-            if p is not None and os.environ.get("SG_BN_PW", "0") == "1" and self.model.compute_dtype == "float32" and x.dtype == self.torch.float32:
+            if p is not None and switches.get("SG_BN_PW") and self.model.compute_dtype == "float32" and x.dtype == self.torch.float32:
                 n, h, w, c = x.shape
                 cin = p.inputs[0].shape[-1]
                 got = bool(self.eng.conv2d_dgrad_bnb_ok(self.eng.conv_desc((n, h, w, cin), c, 1, 1, 1, 1, "same")))
@@ -1035,7 +1036,7 @@ class _Runtime:
         if got is None:
             c = bn_node.defer_conv
             got = False
-            if c is not None and os.environ.get("SG_BN_CONV", "1") != "0" and self.model.compute_dtype == "float32":
+            if c is not None and switches.get("SG_BN_CONV") and self.model.compute_dtype == "float32":
                 _, h, w, cin = c.inputs[0].shape
                 d = self.eng.conv_desc((1, h, w, cin), c.filters, c.k, c.k, c.stride, c.dilation, c.padding)
                 got = bool(self.eng.conv2d_bn_in_ok(d))
@@ -1044,7 +1045,7 @@ class _Runtime:
 
     def planes_in_on(self) -> bool:
         """fp32 storage with the six-pass arithmetic, SG_ACT_PLANES != 0: activation planes are made once per tensor and step."""
-        return (self.model.compute_dtype == "float32" and os.environ.get("SG_ACT_PLANES", "1") != "0"
+        return (self.model.compute_dtype == "float32" and switches.get("SG_ACT_PLANES")
                 and int(self.eng.lib.sg_get_conv_x6()) == 1)
 
     def act_planes(self, node, x, d, make=True):
@@ -1078,7 +1079,7 @@ class _Runtime:
         if got is None:
             c = up_node.fused_into
             got = False
-            if c is not None and os.environ.get("SG_UP2_FUSE", "1") != "0" and self.model.compute_dtype == "float32":
+            if c is not None and switches.get("SG_UP2_FUSE") and self.model.compute_dtype == "float32":
                 _, h, w, cin = c.inputs[0].shape
                 d = self.eng.conv_desc((1, h, w, cin), c.filters, c.k, c.k, c.stride, c.dilation, c.padding)
                 got = bool(self.eng.conv2d_up2_ok(d))
@@ -1158,7 +1159,7 @@ class _Runtime:
         is an identity of), REMOVED from the sweep's table; None if there is none.  The node must return an input gradient
         that includes it - the table then receives the complete gradient and no separate add runs.  owned_only: only a
         buffer the sweep may write in place (not a gradient shared with another tensor) - for nodes that accumulate into it."""
-        if self._pending is None or os.environ.get("SG_GRAD_ACC", "1") != "1":
+        if self._pending is None or not switches.get("SG_GRAD_ACC"):
             return None
         cur = self._pending.get(id(sym))
         if cur is None or (owned_only and not cur[1]):

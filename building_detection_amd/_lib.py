@@ -65,7 +65,28 @@ class BnBwdIn(C.Structure):
                 ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("dz", C.c_void_p), ("relu", C.c_int32), ("rows", C.c_int64)]
 
 
+class ConvOpts(C.Structure):
+    """Mirror of `sg_conv_opts` (include/segengine.h): the optional operands of sg_conv2d_fwd / _dgrad / _wgrad (all-zero = plain)."""
+
+    _fields_ = [("ws", C.c_void_p), ("ws_bytes", C.c_size_t), ("stats", C.c_void_p), ("tiles_out", C.POINTER(C.c_int)),
+                ("a_planes", C.c_void_p), ("res", C.c_void_p), ("bn_in", C.POINTER(BnIn)), ("bnb", C.POINTER(BnBwdIn))]
+
+
+class DwBnSums(C.Structure):
+    """Mirror of `sg_dw_bnsums` (include/segengine.h): the BatchNormalization whose backward sums sg_dwconv2d_dgrad also produces."""
+
+    _fields_ = [("x", C.c_void_p), ("mean", C.c_void_p), ("invstd", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
+                ("relu", C.c_int), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
+class ConvCaps(C.Structure):
+    """Mirror of `sg_conv_caps` (include/segengine.h): what the launches of one convolution can take (sg_conv2d_caps)."""
+
+    _fields_ = [(n, C.c_int) for n in ("thin", "bn_in", "up2", "bnb", "planes_in", "wgrad_planes")]
+
+
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
+_op = C.POINTER(ConvOpts)
 _dp = C.POINTER(ConvDesc)
 _pp = C.POINTER(C.c_void_p)
 
@@ -77,12 +98,9 @@ _SIGNATURES = {
     "sg_create": (_i, [_i, _pp]),
     "sg_destroy": (_i, [_vp]),
     "sg_num_cus": (_i, [_vp]),
-    "sg_conv2d_fwd": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i]),
+    "sg_conv2d_fwd": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _op]),
     "sg_conv2d_fwd_ws_bytes": (_sz, [_dp]),
-    "sg_conv2d_fwd_ws": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _vp, _sz]),
-    "sg_conv2d_up2_supported": (_i, [_i, _dp]),
     "sg_conv2d_fwd_stats_bytes": (_sz, [_dp]),
-    "sg_conv2d_fwd_stats": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, C.POINTER(C.c_int)]),
     "sg_get_conv_x6": (_i, []),
     "sg_conv2d_planes_job": (_i, [_vp, _i, _dp, _i, C.POINTER(PlanesJob), C.POINTER(C.c_size_t)]),
     "sg_prepare_planes": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
@@ -90,33 +108,20 @@ _SIGNATURES = {
     "sg_bn_train_fwd_tiles": (_i, [_vp, _vp, _i, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _i, _vp, _sz]),
     "sg_bn_apply": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "sg_conv2d_dgrad_ws_bytes": (_sz, [_dp]),
-    "sg_conv2d_dgrad": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _vp, _sz]),
-    "sg_conv2d_dgrad_acc": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "sg_conv2d_dgrad": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _op]),
     "sg_conv2d_wgrad_ws_bytes": (_sz, [_vp, _dp]),
-    "sg_conv2d_wgrad": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _vp, _sz]),
-    "sg_conv2d_bn_in_supported": (_i, [_vp, _i, _dp]),
-    "sg_conv2d_fwd_stats_bn": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, C.POINTER(C.c_int), C.POINTER(BnIn)]),
-    "sg_conv2d_wgrad_bn": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(BnIn)]),
-    "sg_conv2d_dgrad_bnb_supported": (_i, [_vp, _i, _dp]),
-    "sg_conv2d_dgrad_bnb": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _sz, C.POINTER(BnBwdIn)]),
+    "sg_conv2d_wgrad": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _op]),
+    "sg_conv2d_caps": (_i, [_vp, _i, _dp, _i, C.POINTER(ConvCaps)]),
     "sg_split_planes": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
-    "sg_conv2d_planes_in": (_i, [_dp, _i]),
-    "sg_conv2d_fwd_stats_ap": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, C.POINTER(C.c_int), _vp]),
-    "sg_conv2d_dgrad_ap": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
-    "sg_conv2d_wgrad_planes_supported": (_i, [_vp, _dp]),
     "sg_conv2d_wgrad_planes_ws_bytes": (_sz, [_vp, _dp]),
     "sg_conv2d_wgrad_planes": (_i, [_vp, _vp, _dp, _vp, _vp, _vp, _vp, _sz]),
     "sg_bias_grad_ws_bytes": (_sz, [_vp, _i64, _i]),
     "sg_bias_grad": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _sz]),
-    "sg_dwconv2d_fwd": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _i]),
-    "sg_dwconv2d_dgrad": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i]),
-    "sg_dwconv2d_dgrad_acc": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "sg_dwconv2d_fwd": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _i, C.POINTER(BnIn)]),
+    "sg_dwconv2d_dgrad": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _vp, C.POINTER(DwBnSums)]),
     "sg_dwconv2d_dgrad_bnsums_ws_bytes": (_sz, [_vp, _dp]),
-    "sg_dwconv2d_dgrad_bnsums": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _i, _vp] + [_vp] * 5 + [_i, _vp, _vp, _vp, _sz]),
-    "sg_dwconv2d_fwd_bn": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
-    "sg_dwconv2d_wgrad_bn": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz]),
     "sg_dwconv2d_wgrad_ws_bytes": (_sz, [_vp, _dp]),
-    "sg_dwconv2d_wgrad": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _i, _vp, _sz]),
+    "sg_dwconv2d_wgrad": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _i, C.POINTER(BnIn), _vp, _sz]),
     "sg_dense_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
     "sg_bn_ws_bytes": (_sz, [_vp, _i64, _i]),
     "sg_bn_train_fwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _sz]),

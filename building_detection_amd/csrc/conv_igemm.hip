@@ -38,8 +38,8 @@ constexpr int LDA = BK + 4;  // floats; 144-byte rows
 template <int V>
 using IC = std::integral_constant<int, V>;
 
-// A BatchNormalization (+ReLU) applied to the convolution's INPUT while it is loaded (round 5: sg_conv2d_fwd_stats_bn /
-// sg_conv2d_wgrad_bn; the patch kernels and the thin 1x1 kernels): y = [relu](fmaf((x - mean) * invstd, gamma, beta)), bn_apply's own
+// A BatchNormalization (+ReLU) applied to the convolution's INPUT while it is loaded (round 5: sg_conv_opts.bn_in of
+// sg_conv2d_fwd / _wgrad; the patch kernels and the thin 1x1 kernels): y = [relu](fmaf((x - mean) * invstd, gamma, beta)), bn_apply's own
 // expression, on every pixel inside the image (the zero padding stays zero).  mean == nullptr: none.
 struct BnIn {
   const float* mean;
@@ -109,9 +109,9 @@ struct IgemmParams {
   int perm2;
   FastDiv fd_mc, fd_hcwc, fd_wc;
   // dgrad: a gradient already collected for the same tensor (y's layout, may be y itself), added in the epilogue
-  // (sg_conv2d_dgrad_acc; conv_x6_kernel / conv_b16_kernel only)
+  // (sg_conv_opts.res; conv_x6_kernel / conv_b16_kernel only)
   const float* res;
-  // the A operand already split into three bf16 planes [3][pixels][C] (sg_split_planes; sg_conv2d_fwd_stats_ap / _dgrad_ap): the
+  // the A operand already split into three bf16 planes [3][pixels][C] (sg_split_planes; sg_conv_opts.a_planes): the
   // planes-in kernel (conv_x6w.h) reads them instead of splitting x itself; ignored by every other kernel; null: none
   const unsigned short* a_planes;
   BnIn bn;   // conv_x6p_kernel only: the BatchNormalization applied in the patch loader (mean == nullptr: none)
@@ -1166,7 +1166,7 @@ int dispatch_x6(const IgemmParams& p_in, int num_cus, hipStream_t st) {
 // ---- who chooses the kernel --------------------------------------------------------------------------------------------
 // plan_conv() decides which kernel family a forward convolution or an input gradient takes and how its weight planes and the
 // scratch behind them are laid out - from the descriptor, the storage type, the arithmetic mode and the experiment switches, and
-// from nothing else: no pointers, no `res`.  The workspace queries, the `_supported` queries, sg_conv2d_planes_job and the launch
+// from nothing else: no pointers, no `res`.  The workspace queries, sg_conv2d_caps, sg_conv2d_planes_job and the launch
 // all read this one plan (the filter gradient's counterpart is plan_wgrad), so they cannot disagree.  What the descriptor does
 // not say - the alignment of the operands, the workspace a launch was handed - is checked once, at the launch, against the plan.
 enum ConvFamily {   // (from CONV_SLAB on: the kernels that read prepared weight planes, sg_planes_job.kind 1 / 2 / 3)
@@ -1194,7 +1194,7 @@ struct ConvPlan {
   bool deep = false;
   size_t a_img_bytes = 0, part_img_bytes = 0;   // scratch behind the planes per image: activation planes, split-K partial slabs
   // what the family can do
-  bool res = false;        // add a collected gradient (sg_conv2d_dgrad_acc).  Of the plane kernels only the slab family: a launch
+  bool res = false;        // add a collected gradient (sg_conv_opts.res).  Of the plane kernels only the slab family: a launch
                            // with `res` whose plan names a wide slab form takes conv_x6_kernel / conv_b16_kernel on the same planes
   bool bn_in = false;      // apply a BatchNormalization in its loader (thin; patch with 32 / 64 reduction channels per tap)
   bool up2 = false;        // the fused up-sampling forms exist for this layer (SG_PRO_UP2; with CONV_PATCH: SG_EPI_DOWN2)
@@ -1239,7 +1239,7 @@ int run_x6(const ConvPlan& pl, IgemmParams& p, const float* w, bool dgrad, int C
           SG_LAUNCH_CHECK("split3_weights_kernel");
         }
         if constexpr (NPL == 3) {
-          if (p.bnb.x)   // the BatchNormalization backward in the A path (sg_conv2d_dgrad_bnb)
+          if (p.bnb.x)   // the BatchNormalization backward in the A path (sg_conv_opts.bnb)
             return pl.wbn == 256 ? launch_pw_wide<NPL, TA, 256, true>(p, st) : launch_pw_wide<NPL, TA, 384, true>(p, st);
         }
         return pl.wbn == 256 ? launch_pw_wide<NPL, TA, 256>(p, st) : launch_pw_wide<NPL, TA, 384>(p, st);
@@ -1486,7 +1486,7 @@ __global__ __launch_bounds__(256) void thin_dgrad_kernel(const TY* __restrict__ 
     for (int o = 0; o < CO; ++o) a = fmaf(g[o], w[(4 * c + k) * CO + o], a);
     r[k] = a;
   }
-  if (res) {   // uniform: a gradient already collected for the same tensor (sg_conv2d_dgrad_acc; may be dx itself)
+  if (res) {   // uniform: a gradient already collected for the same tensor (sg_conv_opts.res; may be dx itself)
     const f32x4 t = ld4<TA>(res + pix * x_ld + 4 * c);
 #pragma unroll
     for (int k = 0; k < 4; ++k) r[k] += t[k];
@@ -1965,10 +1965,6 @@ static size_t conv_ws_scratch(const sg_conv_desc* d, bool dgrad) {
   return n ? n + 256 : 0;
 }
 
-int sg_conv2d_up2_supported(int dtype, const sg_conv_desc* d) {
-  return (d && check_desc(d, "sg_conv2d_up2_supported") == 0 && plan_conv(0, dtype, d, false, 0).up2) ? 1 : 0;
-}
-
 size_t sg_conv2d_fwd_ws_bytes(const sg_conv_desc* d) {
   if (!d) return 0;
   size_t n = x6_ws_bytes(d->KH * d->KW, d->Cin, d->Cout) + 256 + conv_ws_scratch(d, false);
@@ -1976,24 +1972,10 @@ size_t sg_conv2d_fwd_ws_bytes(const sg_conv_desc* d) {
   return n;
 }
 
-int sg_conv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
-                  const void* bias, void* y, int flags) {
-  return sg_conv2d_fwd_ws(ctx, stream, dtype, d, x, w, bias, y, flags, nullptr, 0);
-}
-
-int sg_conv2d_fwd_ws(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
-                     const void* bias, void* y, int flags, void* ws, size_t ws_bytes) {
-  return sg_conv2d_fwd_stats(ctx, stream, dtype, d, x, w, bias, y, flags, ws, ws_bytes, nullptr, nullptr);
-}
-
 size_t sg_conv2d_fwd_stats_bytes(const sg_conv_desc* d) {
   if (!d) return 0;
   return (size_t)sg_cdiv((int64_t)d->N * d->Ho * d->Wo, BM) * 2 * d->Cout * sizeof(float);
 }
-
-static int conv2d_fwd_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
-                           const void* bias, void* y, int flags, void* ws, size_t ws_bytes, void* stats, int* tiles_out,
-                           const void* x_planes, const sg_bn_in* bn = nullptr);
 
 static BnIn bn_in_of(const sg_bn_in* b) {
   BnIn o = bn_in_none();
@@ -2011,40 +1993,8 @@ static bool bn_in_geom(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
   return pl.bn_in && (pl.family == CONV_THIN || plan_wgrad(ctx->num_cus, d, false).patch != 0);
 }
 
-int sg_conv2d_bn_in_supported(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
-  return (ctx && d && check_desc(d, "sg_conv2d_bn_in_supported") == 0 && bn_in_geom(ctx, dtype, d)) ? 1 : 0;
-}
-
-int sg_conv2d_fwd_stats_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
-                           const void* bias, void* y, int flags, void* ws, size_t ws_bytes, void* stats, int* tiles_out,
-                           const sg_bn_in* bn) {
-  SG_CHECK_ARG(bn && bn->mean && bn->invstd && bn->gamma && bn->beta, "sg_conv2d_fwd_stats_bn: null BatchNormalization parameters");
-  SG_CHECK_ARG(ctx && d, "sg_conv2d_fwd_stats_bn: null argument");
-  if (check_desc(d, "sg_conv2d_fwd_stats_bn") || !bn_in_geom(ctx, dtype, d) || (flags & SG_PRO_UP2)) {
-    sg_set_error("sg_conv2d_fwd_stats_bn: this launch takes neither a thin 1x1 nor a patch kernel (3x3 s1 SAME, 32 / 64 input channels, "
-                 "fp32 storage): no kernel to apply the BatchNormalization in");
-    return SG_EUNSUPPORTED;
-  }
-  return conv2d_fwd_impl(ctx, stream, dtype, d, x, w, bias, y, flags, ws, ws_bytes, stats, tiles_out, nullptr, bn);
-}
-
-int sg_conv2d_fwd_stats(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
-                        const void* bias, void* y, int flags, void* ws, size_t ws_bytes, void* stats, int* tiles_out) {
-  return conv2d_fwd_impl(ctx, stream, dtype, d, x, w, bias, y, flags, ws, ws_bytes, stats, tiles_out, nullptr);
-}
-
-int sg_conv2d_fwd_stats_ap(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
-                           const void* bias, void* y, int flags, void* ws, size_t ws_bytes, void* stats, int* tiles_out,
-                           const void* x_planes) {
-  SG_CHECK_ARG(!x_planes || aligned16(x_planes), "sg_conv2d_fwd_stats_ap: planes must be 16-byte aligned");
-  return conv2d_fwd_impl(ctx, stream, dtype, d, x, w, bias, y, flags, ws, ws_bytes, stats, tiles_out, x_planes);
-}
-
-// does the fp32 launch of this geometry read its A operand as bf16 planes (conv_x6w.h)?  Then handing it planes that exist
-// already (sg_split_planes: shared by several consumers of one tensor, or kept for the filter gradient) saves its own split.
-int sg_conv2d_planes_in(const sg_conv_desc* d, int dgrad) {
-  return (d && check_desc(d, "sg_conv2d_planes_in") == 0 && plan_conv(0, SG_F32, d, dgrad != 0, 0).planes_in) ? 1 : 0;
-}
+// sg_conv_opts: a NULL pointer is the plain launch
+static const sg_conv_opts kNoOpts = {};
 
 // one launch of the plan: the whole batch or one sub-batch of it (`d`: its images).  The caller has checked the operands against
 // the plan: `fast` = they allow the plan's plane kernel (else: the native kernel)
@@ -2091,9 +2041,27 @@ static int conv2d_fwd_launch(sg_ctx* ctx, hipStream_t st, int dtype, const sg_co
   return dispatch_igemm(p, (d->Cin % 4 == 0) && (p.x_ld % 4 == 0) && (d->Cout % 4 == 0) && aligned16(x) && aligned16(w), ctx->num_cus, st);
 }
 
-static int conv2d_fwd_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
-                           const void* bias, void* y, int flags, void* ws, size_t ws_bytes, void* stats, int* tiles_out,
-                           const void* x_planes, const sg_bn_in* bn) {
+int sg_conv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
+                  const void* bias, void* y, int flags, const sg_conv_opts* opts) {
+  const sg_conv_opts& o = opts ? *opts : kNoOpts;
+  void* const ws = o.ws;
+  const size_t ws_bytes = o.ws_bytes;
+  void* const stats = o.stats;
+  int* const tiles_out = o.tiles_out;
+  const void* const x_planes = o.a_planes;
+  const sg_bn_in* const bn = o.bn_in;
+  SG_CHECK_ARG(!o.res && !o.bnb, "sg_conv2d_fwd: res / bnb are operands of the input gradient");
+  SG_CHECK_ARG(!(bn && x_planes), "sg_conv2d_fwd: bn_in with a_planes (the planes hold the raw tensor's split)");
+  if (bn) {
+    SG_CHECK_ARG(bn->mean && bn->invstd && bn->gamma && bn->beta, "sg_conv2d_fwd: bn_in with null BatchNormalization parameters");
+    SG_CHECK_ARG(ctx && d, "sg_conv2d_fwd: null argument");
+    if (check_desc(d, "sg_conv2d_fwd") || !bn_in_geom(ctx, dtype, d) || (flags & SG_PRO_UP2)) {
+      sg_set_error("sg_conv2d_fwd: bn_in, but this launch takes neither a thin 1x1 nor a patch kernel (3x3 s1 SAME, 32 / 64 input "
+                   "channels, fp32 storage): no kernel to apply the BatchNormalization in");
+      return SG_EUNSUPPORTED;
+    }
+  }
+  SG_CHECK_ARG(!x_planes || aligned16(x_planes), "sg_conv2d_fwd: a_planes must be 16-byte aligned");
   if (tiles_out) *tiles_out = 0;
   SG_CHECK_ARG(ctx != nullptr, "sg_conv2d_fwd: null ctx");
   SG_CHECK_ARG(dt_ok(dtype), "sg_conv2d_fwd: dtype %d", dtype);
@@ -2151,7 +2119,7 @@ static int conv2d_fwd_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_d
   }
   if (pl.family != CONV_THIN && pl.family != CONV_HEAD) {
     if (bn && bn->mean && !(fast && pl.bn_in)) {   // only the patch kernel applies it
-      sg_set_error("sg_conv2d_fwd_stats_bn: the launch does not take the patch kernel after all (alignment / workspace)");
+      sg_set_error("sg_conv2d_fwd: bn_in, but the launch does not take the patch kernel after all (alignment / workspace)");
       return SG_EUNSUPPORTED;
     }
     if (prepared && !fast) {
@@ -2248,48 +2216,9 @@ size_t sg_conv2d_dgrad_ws_bytes(const sg_conv_desc* d) {
   return native > x6 ? native : x6;
 }
 
-static int conv2d_dgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                            const void* bias, void* dx, int flags, void* ws, size_t ws_bytes, const void* res,
-                            const void* dy_planes = nullptr, const sg_bn_bwd_in* bnb = nullptr);
-
 // the input gradient of a pointwise convolution with the BatchNormalization backward apply in its A path (conv_pw.h, BNB form)
 static bool dgrad_bnb_geom(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
   return plan_conv(ctx->num_cus, dtype, d, true, 0).bnb;
-}
-
-int sg_conv2d_dgrad_bnb_supported(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
-  return (ctx && d && check_desc(d, "sg_conv2d_dgrad_bnb_supported") == 0 && dgrad_bnb_geom(ctx, dtype, d)) ? 1 : 0;
-}
-
-int sg_conv2d_dgrad_bnb(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w, void* dx,
-                        void* ws, size_t ws_bytes, const sg_bn_bwd_in* bnb) {
-  SG_CHECK_ARG(ctx && d && bnb, "sg_conv2d_dgrad_bnb: null argument");
-  SG_CHECK_ARG(bnb->x && bnb->mean && bnb->invstd && bnb->gamma && bnb->dgamma && bnb->dbeta && bnb->dz && bnb->rows > 0,
-               "sg_conv2d_dgrad_bnb: null BatchNormalization operand");
-  SG_CHECK_ARG(!bnb->relu || bnb->beta, "sg_conv2d_dgrad_bnb: a fused ReLU needs beta (the mask is recomputed from x)");
-  if (check_desc(d, "sg_conv2d_dgrad_bnb") || !dgrad_bnb_geom(ctx, dtype, d) || !aligned16(bnb->x) || !aligned16(bnb->dz)) {
-    sg_set_error("sg_conv2d_dgrad_bnb: not a launch of the wide pointwise kernel (1x1, stride 1, dense fp32 operands, >= 6144 rows, "
-                 "x6 arithmetic, default schedule)");
-    return SG_EUNSUPPORTED;
-  }
-  return conv2d_dgrad_impl(ctx, stream, dtype, d, dy, w, nullptr, dx, 0, ws, ws_bytes, nullptr, nullptr, bnb);
-}
-
-int sg_conv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                    const void* bias, void* dx, int flags, void* ws, size_t ws_bytes) {
-  return conv2d_dgrad_impl(ctx, stream, dtype, d, dy, w, bias, dx, flags, ws, ws_bytes, nullptr);
-}
-
-int sg_conv2d_dgrad_ap(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                       const void* bias, void* dx, int flags, void* ws, size_t ws_bytes, const void* dy_planes) {
-  SG_CHECK_ARG(!dy_planes || aligned16(dy_planes), "sg_conv2d_dgrad_ap: planes must be 16-byte aligned");
-  return conv2d_dgrad_impl(ctx, stream, dtype, d, dy, w, bias, dx, flags, ws, ws_bytes, nullptr, dy_planes);
-}
-
-int sg_conv2d_dgrad_acc(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                        const void* bias, void* dx, int flags, void* ws, size_t ws_bytes, const void* res) {
-  SG_CHECK_ARG(res != nullptr, "sg_conv2d_dgrad_acc: null res");
-  return conv2d_dgrad_impl(ctx, stream, dtype, d, dy, w, bias, dx, flags, ws, ws_bytes, res);
 }
 
 // one launch of the plan: the whole batch or one sub-batch of it (see conv2d_fwd_launch)
@@ -2351,9 +2280,30 @@ static int conv2d_dgrad_launch(sg_ctx* ctx, hipStream_t st, int dtype, const sg_
   return dispatch_igemm(p, (d->Cout % 4 == 0) && (p.x_ld % 4 == 0) && (d->Cin % 4 == 0) && aligned16(dy), ctx->num_cus, st);
 }
 
-static int conv2d_dgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                            const void* bias, void* dx, int flags, void* ws, size_t ws_bytes, const void* res, const void* dy_planes,
-                            const sg_bn_bwd_in* bnb) {
+int sg_conv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
+                    const void* bias, void* dx, int flags, const sg_conv_opts* opts) {
+  const sg_conv_opts& o = opts ? *opts : kNoOpts;
+  void* const ws = o.ws;
+  const size_t ws_bytes = o.ws_bytes;
+  const void* const res = o.res;
+  const void* const dy_planes = o.a_planes;
+  const sg_bn_bwd_in* const bnb = o.bnb;
+  SG_CHECK_ARG(!o.stats && !o.tiles_out && !o.bn_in, "sg_conv2d_dgrad: stats / tiles_out / bn_in are operands of the forward");
+  SG_CHECK_ARG(!(res && dy_planes), "sg_conv2d_dgrad: res with a_planes (no kernel takes both)");
+  if (bnb) {
+    SG_CHECK_ARG(!res && !dy_planes, "sg_conv2d_dgrad: bnb with res / a_planes (the wide pointwise kernel takes neither)");
+    SG_CHECK_ARG(!bias && !flags, "sg_conv2d_dgrad: bnb with a bias / flags (the BNB form has no epilogue)");
+    SG_CHECK_ARG(ctx && d, "sg_conv2d_dgrad: null argument");
+    SG_CHECK_ARG(bnb->x && bnb->mean && bnb->invstd && bnb->gamma && bnb->dgamma && bnb->dbeta && bnb->dz && bnb->rows > 0,
+                 "sg_conv2d_dgrad: bnb with a null BatchNormalization operand");
+    SG_CHECK_ARG(!bnb->relu || bnb->beta, "sg_conv2d_dgrad: bnb with a fused ReLU needs beta (the mask is recomputed from x)");
+    if (check_desc(d, "sg_conv2d_dgrad") || !dgrad_bnb_geom(ctx, dtype, d) || !aligned16(bnb->x) || !aligned16(bnb->dz)) {
+      sg_set_error("sg_conv2d_dgrad: bnb, but not a launch of the wide pointwise kernel (1x1, stride 1, dense fp32 operands, >= 6144 "
+                   "rows, x6 arithmetic, default schedule)");
+      return SG_EUNSUPPORTED;
+    }
+  }
+  SG_CHECK_ARG(!dy_planes || aligned16(dy_planes), "sg_conv2d_dgrad: a_planes must be 16-byte aligned");
   SG_CHECK_ARG(ctx != nullptr, "sg_conv2d_dgrad: null ctx");
   SG_CHECK_ARG(dt_ok(dtype), "sg_conv2d_dgrad: dtype %d", dtype);
   int rc = check_desc(d, "sg_conv2d_dgrad");
@@ -2376,7 +2326,7 @@ static int conv2d_dgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv
   SG_CHECK_ARG(!head32 || (b16 && d->Cout <= 4), "sg_conv2d_dgrad: SG_HEAD_F32 needs Cout <= 4 (a softmax head) on bf16 storage");
   hipStream_t st = (hipStream_t)stream;
   if (res && head32) {
-    sg_set_error("sg_conv2d_dgrad_acc: softmax-head launches do not add a collected gradient");
+    sg_set_error("sg_conv2d_dgrad: res, but softmax-head launches do not add a collected gradient");
     return SG_EUNSUPPORTED;
   }
   SG_CHECK_ARG(!(dtype & SG_X_UP2) && !(flags & SG_PRO_UP2), "sg_conv2d_dgrad: the up-sampling flag of the input gradient is SG_EPI_DOWN2");
@@ -2387,7 +2337,7 @@ static int conv2d_dgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv
   if (pl.family == CONV_THIN && !(aligned16(dx) && (pl.nb >= d->N || pl.nb < 1 || ((int64_t)d->H * d->W * xl * ebx) % 16 == 0)))
     pl = plan_conv(ctx->num_cus, dtype, d, true, flags | PLAN_NOT_THIN);   // (every sub-batch's dx must meet the thin kernels' alignment)
   if (pl.family == CONV_HEAD) SG_CHECK_ARG(pl.nb >= 1, "sg_conv2d_dgrad: one image of the softmax head beyond 2 GiB");
-  const int nb = (pl.nb >= 1 && pl.nb < d->N) ? pl.nb : d->N;   // sub-batches of whole images: see conv2d_fwd_impl
+  const int nb = (pl.nb >= 1 && pl.nb < d->N) ? pl.nb : d->N;   // sub-batches of whole images: see sg_conv2d_fwd
   const bool fast = pl.family >= CONV_SLAB && pl.vec && aligned16(dy);
   const bool down2 = (flags & SG_EPI_DOWN2) != 0;
   if (down2) {  // dx = the SOURCE's gradient [N, H/2, W/2, Cin]: the patch kernel's epilogue adds the 2 x 2 cells (conv_x6p.h)
@@ -2407,14 +2357,14 @@ static int conv2d_dgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv
       return SG_EINVAL;
     }
     if (res && !(fast && pl.res)) {   // of the plane kernels only the slab family adds a collected gradient (callers ask sg_conv2d_planes_job: kind 1)
-      sg_set_error("sg_conv2d_dgrad_acc: this launch takes the %s, which do not add a collected gradient (reduction channels per tap %d, "
+      sg_set_error("sg_conv2d_dgrad: res, but this launch takes the %s, which do not add a collected gradient (reduction channels per tap %d, "
                    "K %d, output columns %d, %d x %d outputs per image)",
                    !fast ? "fp32-MFMA kernels" : (pl.family == CONV_PATCH ? "patch kernels" : "wide pointwise kernels"), d->Cout,
                    d->KH * d->KW * d->Cout, d->Cin, d->H, d->W);
       return SG_EUNSUPPORTED;
     }
     if (bnb && !(fast && pl.family == CONV_WIDE && pl.bnb)) {   // only the wide pointwise kernel evaluates the BatchNormalization backward in its A path
-      sg_set_error("sg_conv2d_dgrad_bnb: this launch does not take the wide pointwise kernel");
+      sg_set_error("sg_conv2d_dgrad: bnb, but this launch does not take the wide pointwise kernel");
       return SG_EUNSUPPORTED;
     }
     if (fast && !prepared && !res && ws_bytes < pl.ws_bytes(nb)) {
@@ -2444,27 +2394,22 @@ size_t sg_conv2d_wgrad_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d) {
   return (a > b ? a : b) + 512;
 }
 
-static int conv2d_wgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy,
-                             void* dw, void* dbias, void* ws, size_t ws_bytes, const sg_bn_in* bn);
-
 int sg_conv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy,
-                    void* dw, void* dbias, void* ws, size_t ws_bytes) {
-  return conv2d_wgrad_impl(ctx, stream, dtype, d, x, dy, dw, dbias, ws, ws_bytes, nullptr);
-}
-
-int sg_conv2d_wgrad_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy,
-                       void* dw, void* dbias, void* ws, size_t ws_bytes, const sg_bn_in* bn) {
-  SG_CHECK_ARG(bn && bn->mean && bn->invstd && bn->gamma && bn->beta, "sg_conv2d_wgrad_bn: null BatchNormalization parameters");
-  SG_CHECK_ARG(ctx && d, "sg_conv2d_wgrad_bn: null argument");
-  if (check_desc(d, "sg_conv2d_wgrad_bn") || !bn_in_geom(ctx, dtype, d)) {
-    sg_set_error("sg_conv2d_wgrad_bn: this launch takes neither the thin 1x1 nor the patch filter-gradient kernel");
-    return SG_EUNSUPPORTED;
+                    void* dw, void* dbias, const sg_conv_opts* opts) {
+  const sg_conv_opts& o = opts ? *opts : kNoOpts;
+  void* const ws = o.ws;
+  const size_t ws_bytes = o.ws_bytes;
+  const sg_bn_in* const bn = o.bn_in;
+  SG_CHECK_ARG(!o.stats && !o.tiles_out && !o.a_planes && !o.res && !o.bnb,
+               "sg_conv2d_wgrad: stats / tiles_out / a_planes / res / bnb are operands of the forward and the input gradient");
+  if (bn) {
+    SG_CHECK_ARG(bn->mean && bn->invstd && bn->gamma && bn->beta, "sg_conv2d_wgrad: bn_in with null BatchNormalization parameters");
+    SG_CHECK_ARG(ctx && d, "sg_conv2d_wgrad: null argument");
+    if (check_desc(d, "sg_conv2d_wgrad") || !bn_in_geom(ctx, dtype, d)) {
+      sg_set_error("sg_conv2d_wgrad: bn_in, but this launch takes neither the thin 1x1 nor the patch filter-gradient kernel");
+      return SG_EUNSUPPORTED;
+    }
   }
-  return conv2d_wgrad_impl(ctx, stream, dtype, d, x, dy, dw, dbias, ws, ws_bytes, bn);
-}
-
-static int conv2d_wgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy,
-                             void* dw, void* dbias, void* ws, size_t ws_bytes, const sg_bn_in* bn) {
   SG_CHECK_ARG(ctx != nullptr, "sg_conv2d_wgrad: null ctx");
   SG_CHECK_ARG(dt_ok(dtype), "sg_conv2d_wgrad: dtype %d", dtype);
   int rc = check_desc(d, "sg_conv2d_wgrad");
@@ -2579,7 +2524,7 @@ static int conv2d_wgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv
       parts = S;
     }
     if (p.bn.mean) {   // (the patch branch above returned; nothing below applies a BatchNormalization to x)
-      sg_set_error("sg_conv2d_wgrad_bn: the launch does not take the patch kernel after all");
+      sg_set_error("sg_conv2d_wgrad: bn_in, but the launch does not take the patch kernel after all");
       return SG_EUNSUPPORTED;
     }
     if (pl.wide) {  // unaligned operands: the slab kernels, with the plan's share count
@@ -2688,8 +2633,22 @@ size_t sg_conv2d_wgrad_planes_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d)
   return pl.dw_part_bytes + 512;
 }
 
-int sg_conv2d_wgrad_planes_supported(const sg_ctx* ctx, const sg_conv_desc* d) {
-  return (ctx && d && check_desc(d, "sg_conv2d_wgrad_planes_supported") == 0 && wgrad_planes_geom(ctx, d, nullptr)) ? 1 : 0;
+// what the launches of `d` can take: every answer from the plans they run by
+int sg_conv2d_caps(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int dgrad, sg_conv_caps* out) {
+  SG_CHECK_ARG(ctx && d && out && dt_ok(dtype), "sg_conv2d_caps: bad argument");
+  memset(out, 0, sizeof(*out));
+  if (check_desc(d, "sg_conv2d_caps")) return 0;   // a descriptor no launch takes: no option either (the launch says why)
+  const ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, dgrad != 0, 0);
+  out->thin = pl.family == CONV_THIN;
+  out->planes_in = pl.planes_in;
+  out->wgrad_planes = dt_storage(dtype) == SG_F32 && wgrad_planes_geom(ctx, d, nullptr);   // (the filter gradient has no direction)
+  if (dgrad) {
+    out->bnb = pl.bnb;
+  } else {
+    out->bn_in = bn_in_geom(ctx, dtype, d);
+    out->up2 = pl.up2;
+  }
+  return 0;
 }
 
 int sg_conv2d_wgrad_planes(sg_ctx* ctx, void* stream, const sg_conv_desc* d, const void* x_planes, const void* dy_planes, void* dw,
@@ -2781,7 +2740,7 @@ int sg_dense_fwd(sg_ctx* ctx, void* stream, int dtype, int rows, int in, int out
   sg_conv_desc d = {};
   d.N = rows; d.H = 1; d.W = 1; d.Cin = in; d.Cout = out; d.KH = 1; d.KW = 1; d.stride = 1; d.dilation = 1;
   d.Ho = 1; d.Wo = 1;
-  return sg_conv2d_fwd(ctx, stream, dtype, &d, x, w, bias, y, flags);
+  return sg_conv2d_fwd(ctx, stream, dtype, &d, x, w, bias, y, flags, nullptr);
 }
 
 }  // extern "C"

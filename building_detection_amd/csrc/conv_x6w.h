@@ -436,7 +436,7 @@ inline int launch_x6w(const IgemmParams& p, int S, char* scratch, hipStream_t st
     sg_set_error("conv_x6w: bad launch (%lld tiles, %d shares) or an operand beyond one 2 GiB buffer descriptor", (long long)tiles, S);
     return SG_EINVAL;
   }
-  // the activation planes: the caller's (sg_conv2d_fwd_stats_ap / _dgrad_ap: made once by sg_split_planes for every consumer of
+  // the activation planes: the caller's (sg_conv_opts.a_planes: made once by sg_split_planes for every consumer of
   // the tensor and for its filter gradient) or, without them, split here into the scratch
   const unsigned short* aq = p.a_planes;
   if (!aq) {

@@ -148,7 +148,7 @@ struct DwRunParams {
   int N, H, W, C, in_ld, out_ld, mask_ld, relu_in, flip;
   // BN = true kernels: the input is the RAW output of the producing convolution and the preceding training-mode
   // BatchNormalization (+ ReLU) is applied as the window is loaded - fmaf((x - mean) * invstd, gamma, beta), the very
-  // expression of bn_apply_kernel - so that normalised tensor is never written or read (sg_dwconv2d_fwd_bn)
+  // expression of bn_apply_kernel - so that normalised tensor is never written or read (sg_dwconv2d_fwd with bn)
   const float* __restrict__ bn_gamma;
   const float* __restrict__ bn_beta;
   const float* __restrict__ bn_mean;
@@ -157,7 +157,7 @@ struct DwRunParams {
   // bs_x.  Besides writing it the kernel sums, per channel, what that layer's backward needs - sum g and sum g * xhat with
   // g = out [masked by the layer's fused ReLU, recomputed from bs_x as sg_bn_train_bwd does] and xhat = (bs_x - mean) * invstd
   // - into bs_part[blockIdx.y][2][C]: the reduction pass of BatchNormalization's backward (two tensor reads) disappears for
-  // one more read here (sg_dwconv2d_dgrad_bnsums)
+  // one more read here (sg_dwconv2d_dgrad with sums)
   const T* __restrict__ bs_x = nullptr;
   const float* __restrict__ bs_mean = nullptr;
   const float* __restrict__ bs_invstd = nullptr;
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256, SUMS ? 2 : 3) void dw_s1_run_kernel(const DwRu
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = m[k][e] > 0.f ? o[e] : 0.f;
         }
-        if (p.res) {   // uniform: the other consumer's gradient of this tensor rides along (sg_dwconv2d_dgrad_acc)
+        if (p.res) {   // uniform: the other consumer's gradient of this tensor rides along (sg_dwconv2d_dgrad with res)
           const f32x4 rv = ld4<T>(p.res + (opix + k) * p.out_ld + c);
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] += rv[e];
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(256, SUMS ? 2 : 3) void dw_s1_run_kernel(const DwRu
 // stencil above (PRE compile-time, rows / columns outside the image masked by a select): 22 loads of a run in flight
 // together instead of one at a time.
 // BN: x is the raw output of the producing convolution; the training-mode BatchNormalization (+ ReLU, PRE) in front of this
-// depthwise convolution is applied on load with bn_apply_kernel's expression (sg_dwconv2d_wgrad_bn), its four per-channel
+// depthwise convolution is applied on load with bn_apply_kernel's expression (sg_dwconv2d_wgrad with bn), its four per-channel
 // parameters loaded once per thread (the reducer's context hook).
 template <int V>
 struct DwBnCtx {
@@ -1492,17 +1492,21 @@ void dw_fill(DwParams<T>& p, const sg_conv_desc* d) {
 
 extern "C" {
 
-static int dwconv2d_fwd_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w, void* y,
-                             int pre_relu, const void* bn_gamma, const void* bn_beta, const void* bn_mean, const void* bn_invstd) {
+int sg_dwconv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w, void* y,
+                    int pre_relu, const sg_bn_in* bn) {
   int rc = dw_check(ctx, dtype, d, "sg_dwconv2d_fwd");
   if (rc) return rc;
   SG_CHECK_ARG(x && w && y, "sg_dwconv2d_fwd: null tensor");
-  if (bn_gamma) {
-    SG_CHECK_ARG(bn_beta && bn_mean && bn_invstd, "sg_dwconv2d_fwd_bn: null BatchNormalization parameter");
+  const void *bn_gamma = nullptr, *bn_beta = nullptr, *bn_mean = nullptr, *bn_invstd = nullptr;
+  if (bn) {
+    SG_CHECK_ARG(!pre_relu && !bn->infer, "sg_dwconv2d_fwd: bn with pre_relu (bn->relu has that role) / an inference-mode bn");
+    SG_CHECK_ARG(bn->gamma && bn->beta && bn->mean && bn->invstd, "sg_dwconv2d_fwd: bn with a null BatchNormalization parameter");
+    bn_gamma = bn->gamma; bn_beta = bn->beta; bn_mean = bn->mean; bn_invstd = bn->invstd;
+    pre_relu = bn->relu;
     const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
     if (!((d->Cin % 4 == 0) && (xl % 4 == 0) && (yl % 4 == 0) && sg_aligned16(x) && sg_aligned16(w) && sg_aligned16(y) &&
           sg_aligned16(bn_gamma) && sg_aligned16(bn_beta) && sg_aligned16(bn_mean) && sg_aligned16(bn_invstd) && dw_run_ok(d))) {
-      sg_set_error("sg_dwconv2d_fwd_bn: only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned) fuse the "
+      sg_set_error("sg_dwconv2d_fwd: bn, but only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned) fuse the "
                    "BatchNormalization; materialise it instead");
       return SG_EUNSUPPORTED;
     }
@@ -1531,69 +1535,6 @@ static int dwconv2d_fwd_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv
   return 0;
 }
 
-int sg_dwconv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w, void* y,
-                    int pre_relu) {
-  return dwconv2d_fwd_impl(ctx, stream, dtype, d, x, w, y, pre_relu, nullptr, nullptr, nullptr, nullptr);
-}
-
-int sg_dwconv2d_fwd_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w, void* y,
-                       const void* gamma, const void* beta, const void* mean, const void* invstd, int relu) {
-  SG_CHECK_ARG(gamma != nullptr, "sg_dwconv2d_fwd_bn: null gamma");
-  return dwconv2d_fwd_impl(ctx, stream, dtype, d, x, w, y, relu, gamma, beta, mean, invstd);
-}
-
-static int dwconv2d_dgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                              const void* x_for_mask, void* dx, int pre_relu, const void* res) {
-  int rc = dw_check(ctx, dtype, d, "sg_dwconv2d_dgrad");
-  if (rc) return rc;
-  SG_CHECK_ARG(dy && w && dx, "sg_dwconv2d_dgrad: null tensor");
-  SG_CHECK_ARG(!pre_relu || x_for_mask, "sg_dwconv2d_dgrad: pre_relu needs the forward input");
-  if (res) {
-    const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-    if (!((d->Cin % 4 == 0) && (xl % 4 == 0) && (yl % 4 == 0) && sg_aligned16(dy) && sg_aligned16(w) && sg_aligned16(dx) &&
-          sg_aligned16(res) && (!pre_relu || sg_aligned16(x_for_mask)) && dw_run_ok(d))) {
-      sg_set_error("sg_dwconv2d_dgrad_acc: only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned) add a "
-                   "collected gradient; add it afterwards instead");
-      return SG_EUNSUPPORTED;
-    }
-  }
-  SG_DTYPE_SWITCH(dtype, "sg_dwconv2d_dgrad", {
-    DwParams<T> p;
-    dw_fill(p, d);
-    p.x = (const T*)x_for_mask; p.w = (const float*)w; p.dy = (const T*)dy; p.out = (T*)dx; p.pre_relu = pre_relu;
-    const bool vec = (p.C % 4 == 0) && (p.x_ld % 4 == 0) && (p.y_ld % 4 == 0) && sg_aligned16(dy) && sg_aligned16(w) &&
-                     sg_aligned16(dx) && (!pre_relu || sg_aligned16(x_for_mask));
-    if (vec && dw_run_ok(d)) {  // stride-1 dgrad = the same stencil with the kernel flipped
-      DwRunParams<T> r;
-      r.in = (const T*)dy; r.w = (const float*)w; r.mask = pre_relu ? (const T*)x_for_mask : nullptr; r.out = (T*)dx;
-      r.res = (const T*)res;
-      r.bn_gamma = r.bn_beta = r.bn_mean = r.bn_invstd = nullptr;
-      r.N = d->N; r.H = d->H; r.W = d->W; r.C = p.C; r.in_ld = p.y_ld; r.out_ld = p.x_ld; r.mask_ld = p.x_ld;
-      r.relu_in = 0; r.flip = 1; r.runs_per_row = d->W / 4; r.nruns = (int64_t)d->N * d->H * r.runs_per_row;
-      r.fd_rpr = make_fastdiv((uint32_t)r.runs_per_row); r.fd_h = make_fastdiv((uint32_t)d->H);
-      return launch_dw_run(r, (hipStream_t)stream);
-    }
-    const int V = vec ? 4 : 1;
-    p.fd_cv = make_fastdiv((uint32_t)(p.C / V)); p.fd_w = make_fastdiv((uint32_t)p.W); p.fd_h = make_fastdiv((uint32_t)p.H);
-    const unsigned blocks = ew_blocks((int64_t)p.N * p.H * p.W * (p.C / V));
-    if (vec) hipLaunchKernelGGL((dw_dgrad_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((dw_dgrad_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-  });
-  SG_LAUNCH_CHECK("dw_dgrad_kernel");
-  return 0;
-}
-
-int sg_dwconv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                      const void* x_for_mask, void* dx, int pre_relu) {
-  return dwconv2d_dgrad_impl(ctx, stream, dtype, d, dy, w, x_for_mask, dx, pre_relu, nullptr);
-}
-
-int sg_dwconv2d_dgrad_acc(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                          const void* x_for_mask, void* dx, int pre_relu, const void* res) {
-  SG_CHECK_ARG(res != nullptr, "sg_dwconv2d_dgrad_acc: null res");
-  return dwconv2d_dgrad_impl(ctx, stream, dtype, d, dy, w, x_for_mask, dx, pre_relu, res);
-}
-
 // second stage of the BatchNormalization sums written by dw_s1_run_kernel<SUMS>: seg_finalize_kernel adds the partial rows in
 // fp64 (fixed order) and hands the two totals of a channel to this op
 struct BnSumsFinalOp {
@@ -1611,47 +1552,64 @@ size_t sg_dwconv2d_dgrad_bnsums_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* 
   return (size_t)DW_SUMS_MAX_ROWS * 2 * (size_t)d->Cin * sizeof(float) + 256;
 }
 
-int sg_dwconv2d_dgrad_bnsums(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                             const void* x_for_mask, void* dx, int pre_relu, const void* res, const void* bn_x,
-                             const void* bn_mean, const void* bn_invstd, const void* bn_gamma, const void* bn_beta, int bn_relu,
-                             void* dgamma, void* dbeta, void* ws, size_t ws_bytes) {
-  int rc = dw_check(ctx, dtype, d, "sg_dwconv2d_dgrad_bnsums");
+int sg_dwconv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
+                      const void* x_for_mask, void* dx, int pre_relu, const void* res, const sg_dw_bnsums* sums) {
+  int rc = dw_check(ctx, dtype, d, "sg_dwconv2d_dgrad");
   if (rc) return rc;
-  SG_CHECK_ARG(dy && w && dx && bn_x && bn_mean && bn_invstd && bn_gamma && bn_beta && dgamma && dbeta,
-               "sg_dwconv2d_dgrad_bnsums: null tensor");
-  SG_CHECK_ARG(!pre_relu || x_for_mask, "sg_dwconv2d_dgrad_bnsums: pre_relu needs the forward input");
-  const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-  if (!((d->Cin % 4 == 0) && (xl % 4 == 0) && (yl % 4 == 0) && sg_aligned16(dy) && sg_aligned16(w) && sg_aligned16(dx) &&
-        sg_aligned16(bn_x) && sg_aligned16(bn_mean) && sg_aligned16(bn_invstd) && sg_aligned16(bn_gamma) && sg_aligned16(bn_beta) &&
-        (!res || sg_aligned16(res)) && (!pre_relu || sg_aligned16(x_for_mask)) && dw_run_ok(d))) {
-    sg_set_error("sg_dwconv2d_dgrad_bnsums: only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned); "
-                 "use sg_dwconv2d_dgrad and sg_bn_train_bwd instead");
-    return SG_EUNSUPPORTED;
+  SG_CHECK_ARG(dy && w && dx, "sg_dwconv2d_dgrad: null tensor");
+  SG_CHECK_ARG(!sums || (sums->x && sums->mean && sums->invstd && sums->gamma && sums->beta && sums->dgamma && sums->dbeta),
+               "sg_dwconv2d_dgrad: sums with a null tensor");
+  SG_CHECK_ARG(!pre_relu || x_for_mask, "sg_dwconv2d_dgrad: pre_relu needs the forward input");
+  if (res || sums) {
+    const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
+    if (!((d->Cin % 4 == 0) && (xl % 4 == 0) && (yl % 4 == 0) && sg_aligned16(dy) && sg_aligned16(w) && sg_aligned16(dx) &&
+          (!sums || (sg_aligned16(sums->x) && sg_aligned16(sums->mean) && sg_aligned16(sums->invstd) && sg_aligned16(sums->gamma) &&
+                     sg_aligned16(sums->beta))) &&
+          (!res || sg_aligned16(res)) && (!pre_relu || sg_aligned16(x_for_mask)) && dw_run_ok(d))) {
+      sg_set_error("sg_dwconv2d_dgrad: res / sums, but only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned) add a "
+                   "collected gradient or sum for the BatchNormalization; add it afterwards / use sg_bn_train_bwd instead");
+      return SG_EUNSUPPORTED;
+    }
   }
-  if (!ws || ws_bytes < sg_dwconv2d_dgrad_bnsums_ws_bytes(ctx, d) - 256) {
-    sg_set_error("sg_dwconv2d_dgrad_bnsums: workspace %zu < %zu", ws_bytes, sg_dwconv2d_dgrad_bnsums_ws_bytes(ctx, d) - 256);
+  if (sums && (!sums->ws || sums->ws_bytes < sg_dwconv2d_dgrad_bnsums_ws_bytes(ctx, d) - 256)) {
+    sg_set_error("sg_dwconv2d_dgrad: sums workspace %zu < %zu", sums->ws_bytes, sg_dwconv2d_dgrad_bnsums_ws_bytes(ctx, d) - 256);
     return SG_EWORKSPACE;
   }
-  hipStream_t st = (hipStream_t)stream;
-  SG_DTYPE_SWITCH(dtype, "sg_dwconv2d_dgrad_bnsums", {
-    DwRunParams<T> r;
-    r.in = (const T*)dy; r.w = (const float*)w; r.mask = pre_relu ? (const T*)x_for_mask : nullptr; r.out = (T*)dx;
-    r.res = (const T*)res;
-    r.bn_gamma = r.bn_beta = r.bn_mean = r.bn_invstd = nullptr;
-    r.N = d->N; r.H = d->H; r.W = d->W; r.C = d->Cin; r.in_ld = yl; r.out_ld = xl; r.mask_ld = xl;
-    r.relu_in = 0; r.flip = 1; r.runs_per_row = d->W / 4; r.nruns = (int64_t)d->N * d->H * r.runs_per_row;
-    r.fd_rpr = make_fastdiv((uint32_t)r.runs_per_row); r.fd_h = make_fastdiv((uint32_t)d->H);
-    r.bs_x = (const T*)bn_x; r.bs_ld = d->Cin;   /* the BatchNormalization's input is a dense tensor */ r.bs_mean = (const float*)bn_mean; r.bs_invstd = (const float*)bn_invstd;
-    r.bs_gamma = (const float*)bn_gamma; r.bs_beta = (const float*)bn_beta; r.bs_relu = bn_relu ? 1 : 0;
-    r.bs_part = (float*)ws;
-    int rows = 0;
-    rc = launch_dw_run(r, st, &rows);
-    if (rc) return rc;
-    BnSumsFinalOp op;
-    op.dgamma = (float*)dgamma; op.dbeta = (float*)dbeta;
-    seg_finalize_launch(op, 1, d->Cin, rows, (const float*)ws, st);
+  SG_DTYPE_SWITCH(dtype, "sg_dwconv2d_dgrad", {
+    DwParams<T> p;
+    dw_fill(p, d);
+    p.x = (const T*)x_for_mask; p.w = (const float*)w; p.dy = (const T*)dy; p.out = (T*)dx; p.pre_relu = pre_relu;
+    const bool vec = (p.C % 4 == 0) && (p.x_ld % 4 == 0) && (p.y_ld % 4 == 0) && sg_aligned16(dy) && sg_aligned16(w) &&
+                     sg_aligned16(dx) && (!pre_relu || sg_aligned16(x_for_mask));
+    if (vec && dw_run_ok(d)) {  // stride-1 dgrad = the same stencil with the kernel flipped
+      DwRunParams<T> r;
+      r.in = (const T*)dy; r.w = (const float*)w; r.mask = pre_relu ? (const T*)x_for_mask : nullptr; r.out = (T*)dx;
+      r.res = (const T*)res;
+      r.bn_gamma = r.bn_beta = r.bn_mean = r.bn_invstd = nullptr;
+      r.N = d->N; r.H = d->H; r.W = d->W; r.C = p.C; r.in_ld = p.y_ld; r.out_ld = p.x_ld; r.mask_ld = p.x_ld;
+      r.relu_in = 0; r.flip = 1; r.runs_per_row = d->W / 4; r.nruns = (int64_t)d->N * d->H * r.runs_per_row;
+      r.fd_rpr = make_fastdiv((uint32_t)r.runs_per_row); r.fd_h = make_fastdiv((uint32_t)d->H);
+      if (!sums) return launch_dw_run(r, (hipStream_t)stream);
+      r.bs_x = (const T*)sums->x; r.bs_ld = d->Cin;   // the BatchNormalization's input is a dense tensor
+      r.bs_mean = (const float*)sums->mean; r.bs_invstd = (const float*)sums->invstd;
+      r.bs_gamma = (const float*)sums->gamma; r.bs_beta = (const float*)sums->beta; r.bs_relu = sums->relu ? 1 : 0;
+      r.bs_part = (float*)sums->ws;
+      int rows = 0;
+      rc = launch_dw_run(r, (hipStream_t)stream, &rows);
+      if (rc) return rc;
+      BnSumsFinalOp op;
+      op.dgamma = (float*)sums->dgamma; op.dbeta = (float*)sums->dbeta;
+      seg_finalize_launch(op, 1, d->Cin, rows, (const float*)sums->ws, (hipStream_t)stream);
+      SG_LAUNCH_CHECK("sg_dwconv2d_dgrad sums");
+      return 0;
+    }
+    const int V = vec ? 4 : 1;
+    p.fd_cv = make_fastdiv((uint32_t)(p.C / V)); p.fd_w = make_fastdiv((uint32_t)p.W); p.fd_h = make_fastdiv((uint32_t)p.H);
+    const unsigned blocks = ew_blocks((int64_t)p.N * p.H * p.W * (p.C / V));
+    if (vec) hipLaunchKernelGGL((dw_dgrad_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((dw_dgrad_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
   });
-  SG_LAUNCH_CHECK("sg_dwconv2d_dgrad_bnsums");
+  SG_LAUNCH_CHECK("dw_dgrad_kernel");
   return 0;
 }
 
@@ -1669,18 +1627,21 @@ size_t sg_dwconv2d_wgrad_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d) {
   return m + 256;
 }
 
-static int dwconv2d_wgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy,
-                               void* dw, int pre_relu, void* ws, size_t ws_bytes, const void* bn_gamma, const void* bn_beta,
-                               const void* bn_mean, const void* bn_invstd) {
+int sg_dwconv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy, void* dw,
+                      int pre_relu, const sg_bn_in* bn, void* ws, size_t ws_bytes) {
   int rc = dw_check(ctx, dtype, d, "sg_dwconv2d_wgrad");
   if (rc) return rc;
   SG_CHECK_ARG(x && dy && dw, "sg_dwconv2d_wgrad: null tensor");
-  if (bn_gamma) {
-    SG_CHECK_ARG(bn_beta && bn_mean && bn_invstd, "sg_dwconv2d_wgrad_bn: null BatchNormalization parameter");
+  const void *bn_gamma = nullptr, *bn_beta = nullptr, *bn_mean = nullptr, *bn_invstd = nullptr;
+  if (bn) {
+    SG_CHECK_ARG(!pre_relu && !bn->infer, "sg_dwconv2d_wgrad: bn with pre_relu (bn->relu has that role) / an inference-mode bn");
+    SG_CHECK_ARG(bn->gamma && bn->beta && bn->mean && bn->invstd, "sg_dwconv2d_wgrad: bn with a null BatchNormalization parameter");
+    bn_gamma = bn->gamma; bn_beta = bn->beta; bn_mean = bn->mean; bn_invstd = bn->invstd;
+    pre_relu = bn->relu;
     const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
     if (!((d->Cin % 4 == 0) && (xl % 4 == 0) && (yl % 4 == 0) && sg_aligned16(x) && sg_aligned16(dy) && sg_aligned16(bn_gamma) &&
           sg_aligned16(bn_beta) && sg_aligned16(bn_mean) && sg_aligned16(bn_invstd) && dw_run_ok(d))) {
-      sg_set_error("sg_dwconv2d_wgrad_bn: only the stride-1 3x3 run kernels fuse the BatchNormalization; materialise it instead");
+      sg_set_error("sg_dwconv2d_wgrad: bn, but only the stride-1 3x3 run kernels fuse the BatchNormalization; materialise it instead");
       return SG_EUNSUPPORTED;
     }
   }
@@ -1761,18 +1722,6 @@ static int dwconv2d_wgrad_impl(sg_ctx* ctx, void* stream, int dtype, const sg_co
     return seg_reduce_launch(op, pl, 1, rows, op.C, (float*)ws, (hipStream_t)stream, "dw_wgrad");
   });
   return 0;
-}
-
-int sg_dwconv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy,
-                      void* dw, int pre_relu, void* ws, size_t ws_bytes) {
-  return dwconv2d_wgrad_impl(ctx, stream, dtype, d, x, dy, dw, pre_relu, ws, ws_bytes, nullptr, nullptr, nullptr, nullptr);
-}
-
-int sg_dwconv2d_wgrad_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy, void* dw,
-                         const void* gamma, const void* beta, const void* mean, const void* invstd, int relu, void* ws,
-                         size_t ws_bytes) {
-  SG_CHECK_ARG(gamma != nullptr, "sg_dwconv2d_wgrad_bn: null gamma");
-  return dwconv2d_wgrad_impl(ctx, stream, dtype, d, x, dy, dw, relu, ws, ws_bytes, gamma, beta, mean, invstd);
 }
 
 int sg_maxpool_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int k, int stride, int pad_t,

@@ -16,7 +16,6 @@ import numpy as np
 from .graph import KTensor, Node
 from .ops import conv_out_geometry, same_pad
 from . import _lib
-from . import switches
 
 
 def _pair(v):
@@ -167,9 +166,10 @@ class _ConvNode(Node):
             # planes of the forward's activation (kept by rt.act_planes) and of dz: the planes-in filter gradient takes both as
             # they are, the planes-in dgrad shares dz's (one split of dz instead of one per launch)
             xp = None if up2 else rt.act_planes(self, x, d, make=False)
-            wg_planes = xp is not None and dz.dtype == x.dtype and e.conv2d_wgrad_planes_ok(d)
+            caps = e.conv2d_caps(d, dgrad=True)   # what the input gradient's launch and the filter gradient can take
+            wg_planes = xp is not None and dz.dtype == x.dtype and bool(caps.wgrad_planes)
             dzp = None
-            if dz.dtype == x.dtype and not up2 and (wg_planes or (rt.needs_grad(self.inputs[0]) and rt.planes_in_on() and e.conv2d_planes_in(d, True))):
+            if dz.dtype == x.dtype and not up2 and (wg_planes or (rt.needs_grad(self.inputs[0]) and rt.planes_in_on() and caps.planes_in)):
                 dzp = e.split_planes(dz)
             # the input gradient first: the chain goes on with it, the filter gradient follows on the side stream beside the
             # bandwidth-bound kernels of the next node (two MFMA kernels side by side only share the matrix pipe)
@@ -180,10 +180,8 @@ class _ConvNode(Node):
                 res = None
                 # (not for the dilated ASPP / SK convolutions: they are the roofline kernel set, timed as pure convolutions)
                 # or the thin 1x1 kernel (scSE's spatial squeeze, Cout = 1)
-                thin = (self.k == 1 and self.stride == 1 and self.filters <= 4 and x.shape[-1] % 4 == 0 and x.shape[-1] >= 16
-                        and not switches.get("SG_CONV_NOTHIN"))
                 if (self._tag is None and dz.dtype == x.dtype and not up2
-                        and (thin or (rt.plane_kind(self, "d") == 1 and rt.planes(self, "d") is not None))):
+                        and (caps.thin or (rt.plane_kind(self, "d") == 1 and rt.planes(self, "d") is not None))):
                     root = self.inputs[0]
                     while isinstance(root.node, _ActNode) and root.node.fused_away and len(root.consumers) == 1:
                         root = root.node.inputs[0]
@@ -293,7 +291,7 @@ class _SepConvNode(Node):
             res = rt.take_pending(root) if e.dwconv_dgrad_acc_ok(ddw) else None
             # this layer's input is the output of a training-mode BatchNormalization with no other consumer: dx IS that layer's
             # output gradient, and the kernel sums what its backward needs (dgamma, dbeta) while it writes dx - the
-            # BatchNormalization then only applies (Model._fuse: bnsum_src / sums_from; sg_dwconv2d_dgrad_bnsums)
+            # BatchNormalization then only applies (Model._fuse: bnsum_src / sums_from; sums of sg_dwconv2d_dgrad)
             src = self.bnsum_src
             sv = rt._saved.get(id(src)) if src is not None else None
             # (through a residual add - src.defer_add - the gradient must be complete here: nothing left in the sweep's table)

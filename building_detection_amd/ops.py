@@ -353,10 +353,17 @@ class Engine:
         ho, wo, pt, pl = conv_out_geometry(h, w, kh, kw, stride, dilation, padding)
         return ConvDesc(n, h, w, cin, cout, kh, kw, stride, dilation, pt, pl, ho, wo, x_ld, y_ld)
 
+    def conv2d_caps(self, d: ConvDesc, dgrad=False, dt=SG_F32) -> _lib.ConvCaps:
+        """What the launches of convolution `d` can take (sg_conv2d_caps: read from the plan they run by); dgrad: the input
+        gradient's launch, else the forward's and the filter gradient's."""
+        caps = _lib.ConvCaps()
+        check(self.lib.sg_conv2d_caps(self.h, dt, C.byref(d), 1 if dgrad else 0, C.byref(caps)), "sg_conv2d_caps")
+        return caps
+
     def conv2d_bn_in_ok(self, d: ConvDesc, dtype=torch.float32) -> bool:
-        """Can the launches of convolution `d` apply a BatchNormalization(+ReLU) to their input themselves (sg_conv2d_fwd_stats_bn /
-        sg_conv2d_wgrad_bn: the thin 1x1 and the patch kernels, fp32 storage)?"""
-        return dtype == torch.float32 and bool(self.lib.sg_conv2d_bn_in_supported(self.h, SG_F32, C.byref(d)))
+        """Can the launches of convolution `d` apply a BatchNormalization(+ReLU) to their input themselves (bn_in of conv2d_fwd /
+        conv2d_wgrad: the thin 1x1 and the patch kernels, fp32 storage)?"""
+        return dtype == torch.float32 and bool(self.conv2d_caps(d).bn_in)
 
     @staticmethod
     def _bn_in(bn):
@@ -369,7 +376,16 @@ class Engine:
     def conv2d_up2_ok(self, d: ConvDesc, dtype=torch.float32) -> bool:
         """Does the convolution `d` (on the up-sampled grid) take the fused UpSampling2D(2) -> Conv2D 3x3 kernels
         (SG_PRO_UP2 / SG_EPI_DOWN2 / SG_X_UP2, csrc/conv_x6p.h)?"""
-        return dtype == torch.float32 and bool(self.lib.sg_conv2d_up2_supported(SG_F32, C.byref(d)))
+        return dtype == torch.float32 and bool(self.conv2d_caps(d).up2)
+
+    def _conv_opts(self, planes, ws_bytes, **kw):
+        """The sg_conv_opts of one launch: the layer's prepared weight planes (runtime._Runtime.ensure_planes) or a workspace of
+        ws_bytes, and the optional operands.  The caller keeps what the pointers name alive until the call has returned."""
+        if planes is not None:
+            wsp, wsn = planes, _lib.SG_WS_PREPARED
+        else:
+            wsp, wsn = self.ws(ws_bytes)
+        return _lib.ConvOpts(wsp, wsn, **kw)
 
     def conv2d_fwd(self, x, w, b=None, stride=1, dilation=1, padding="same", relu=False, out=None, desc=None,
                    want_stats=False, head_f32=False, planes=None, up2=False, x_planes=None, bn_in=None):
@@ -378,10 +394,10 @@ class Engine:
         head_f32 (bf16 storage only): the output is fp32 - the softmax head, a thin 1x1 convolution (SG_HEAD_F32).
         up2: x is the SOURCE [N, H/2, W/2, Cin] of a nearest 2x up-sampling and `desc` (required) names the convolution on
         the up-sampled grid (SG_PRO_UP2: the sub-pixel kernel; the up-sampled tensor is never built).
-        x_planes: split_planes(x), when the caller has them (sg_conv2d_fwd_stats_ap: the planes-in kernel then skips its own
+        x_planes: split_planes(x), when the caller has them (sg_conv_opts.a_planes: the planes-in kernel then skips its own
         split; any other kernel ignores them).
         bn_in: (gamma, beta, mean, invstd | moving variance, relu, infer, eps) - x is the RAW input of that BatchNormalization(+ReLU)
-        and the kernel applies it while loading (sg_conv2d_fwd_stats_bn; conv2d_bn_in_ok tells which launches can)."""
+        and the kernel applies it while loading (sg_conv_opts.bn_in; conv2d_bn_in_ok tells which launches can)."""
         _chk(x, "x"); _chk32(w, "w")
         kh, kw, cin, cout = w.shape
         d = desc or self.conv_desc(x.shape, cout, kh, kw, stride, dilation, padding)
@@ -389,55 +405,40 @@ class Engine:
         if up2:
             assert desc is not None and tuple(x.shape) == (d.N, d.H // 2, d.W // 2, d.Cin), (tuple(x.shape), d.H, d.W)
             planes = None   # the summed-tap planes of the sub-pixel form are made per launch in the plain workspace
+        assert bn_in is None or (not up2 and x_planes is None)
         head_f32 = bool(head_f32) and x.dtype == torch.bfloat16
         y = out if out is not None else self.empty(d.N, d.Ho, d.Wo, cout, dtype=torch.float32 if head_f32 else x.dtype)
         dt = _dt(x) | (SG_HEAD_F32 if head_f32 else 0)
         flags = (_lib.SG_EPI_BIAS if b is not None else 0) | (_lib.SG_EPI_RELU if relu else 0) | (_lib.SG_PRO_UP2 if up2 else 0)
-        if planes is not None:  # this layer's weight planes, prepared once per step (runtime._Runtime.ensure_planes)
-            wsp, wsn = C.c_void_p(planes), C.c_size_t(_lib.SG_WS_PREPARED)
-        else:
-            wsp, wsn = self.ws(self.lib.sg_conv2d_fwd_ws_bytes(C.byref(d)))
+        o = self._conv_opts(planes, self.lib.sg_conv2d_fwd_ws_bytes(C.byref(d)), a_planes=_ptr(x_planes))
         if bn_in is not None:
-            assert not up2 and x_planes is None
             bq = self._bn_in(bn_in)
-            st = self.empty(self.lib.sg_conv2d_fwd_stats_bytes(C.byref(d)) // 4) if want_stats else None
-            tiles = C.c_int(0)
-            with self.timed(self._gemm_tag()):
-                check(self.lib.sg_conv2d_fwd_stats_bn(self.h, self.stream, dt, C.byref(d), _ptr(x), _ptr(w), _ptr(b), _ptr(y), flags,
-                                                      wsp, wsn, _ptr(st), C.byref(tiles) if want_stats else None, C.byref(bq)),
-                      "sg_conv2d_fwd_stats_bn")
-            if want_stats:
-                return y, ((st, tiles.value) if tiles.value > 0 else None)
-            return y
+            o.bn_in = C.pointer(bq)
         if want_stats:
             st = self.empty(self.lib.sg_conv2d_fwd_stats_bytes(C.byref(d)) // 4)
             tiles = C.c_int(0)
-            with self.timed(self._gemm_tag()):
-                check(self.lib.sg_conv2d_fwd_stats_ap(self.h, self.stream, dt, C.byref(d), _ptr(x), _ptr(w), _ptr(b), _ptr(y),
-                                                      flags, wsp, wsn, _ptr(st), C.byref(tiles), _ptr(x_planes)), "sg_conv2d_fwd_stats")
-            return y, ((st, tiles.value) if tiles.value > 0 else None)
+            o.stats, o.tiles_out = _ptr(st), C.pointer(tiles)
         with self.timed(self._gemm_tag()):
-            if x_planes is not None:
-                check(self.lib.sg_conv2d_fwd_stats_ap(self.h, self.stream, dt, C.byref(d), _ptr(x), _ptr(w), _ptr(b), _ptr(y), flags,
-                                                      wsp, wsn, None, None, _ptr(x_planes)), "sg_conv2d_fwd_stats_ap")
-            else:
-                check(self.lib.sg_conv2d_fwd_ws(self.h, self.stream, dt, C.byref(d), _ptr(x), _ptr(w), _ptr(b), _ptr(y), flags,
-                                                wsp, wsn), "sg_conv2d_fwd_ws")
+            check(self.lib.sg_conv2d_fwd(self.h, self.stream, dt, C.byref(d), _ptr(x), _ptr(w), _ptr(b), _ptr(y), flags, C.byref(o)),
+                  "sg_conv2d_fwd")
+        if want_stats:
+            return y, ((st, tiles.value) if tiles.value > 0 else None)
         return y
 
     def conv2d_planes_in(self, d: ConvDesc, dgrad: bool) -> bool:
         """Does the fp32 forward (dgrad) launch of `d` read its activation as bf16 planes (csrc/conv_x6w.h)?  Then planes the
         caller already has (split_planes) save the launch its own split."""
-        return bool(self.lib.sg_conv2d_planes_in(C.byref(d), 1 if dgrad else 0))
+        return bool(self.conv2d_caps(d, dgrad).planes_in)
 
     def conv2d_dgrad(self, dy, w, d: ConvDesc, bias=None, relu=False, out=None, out_dtype=None, planes=None, res=None,
-                     down2=False, dy_planes=None):
+                     down2=False, dy_planes=None, bnb=None):
         """dx of the forward conv described by `d`; also Conv2DTranspose forward (then bias/relu apply).
         out_dtype = torch.bfloat16 with an fp32 dy: the backward of the fp32 softmax head of a bf16 model (SG_HEAD_F32).
-        res: a gradient already collected for the same tensor, added in the kernel's epilogue (sg_conv2d_dgrad_acc: only for
-        launches whose prepared planes are of kind 1, the slab kernels).
+        res: a gradient already collected for the same tensor, added in the kernel's epilogue (sg_conv_opts.res: only for
+        launches whose prepared planes are of kind 1, the slab kernels); dy_planes are not used with it.
         down2: the conv's input was a nearest 2x up-sampling; dx is the gradient of its SOURCE, [N, H/2, W/2, Cin] (the 2 x 2
-        cells added in the epilogue in up-sampling's backward order: SG_EPI_DOWN2)."""
+        cells added in the epilogue in up-sampling's backward order: SG_EPI_DOWN2).
+        bnb: a _lib.BnBwdIn (see conv2d_dgrad_bnb)."""
         _chk(dy, "dy"); _chk32(w, "w")
         odt = out.dtype if out is not None else (out_dtype or dy.dtype)
         if down2:
@@ -446,50 +447,36 @@ class Engine:
         else:
             dx = out if out is not None else self.empty(d.N, d.H, d.W, d.Cin, dtype=odt)
         dt = (SG_BF16 | SG_HEAD_F32) if (odt == torch.bfloat16 and dy.dtype == torch.float32) else _dt(dy)
-        if planes is not None:
-            wsp, wsn = C.c_void_p(planes), C.c_size_t(_lib.SG_WS_PREPARED)
-        else:
-            wsp, wsn = self.ws(self.lib.sg_conv2d_dgrad_ws_bytes(C.byref(d)))
         flags = (_lib.SG_EPI_BIAS if bias is not None else 0) | (_lib.SG_EPI_RELU if relu else 0) | (_lib.SG_EPI_DOWN2 if down2 else 0)
+        o = self._conv_opts(planes, self.lib.sg_conv2d_dgrad_ws_bytes(C.byref(d)), res=_ptr(res),
+                            a_planes=_ptr(dy_planes) if res is None else None)
+        if bnb is not None:
+            o.bnb = C.pointer(bnb)
         with self.timed(self._gemm_tag()):
-            if res is not None:
-                check(self.lib.sg_conv2d_dgrad_acc(self.h, self.stream, dt, C.byref(d), _ptr(dy), _ptr(w), _ptr(bias), _ptr(dx),
-                                                   flags, wsp, wsn, _ptr(res)), "sg_conv2d_dgrad_acc")
-            elif dy_planes is not None:
-                check(self.lib.sg_conv2d_dgrad_ap(self.h, self.stream, dt, C.byref(d), _ptr(dy), _ptr(w), _ptr(bias), _ptr(dx),
-                                                  flags, wsp, wsn, _ptr(dy_planes)), "sg_conv2d_dgrad_ap")
-            else:
-                check(self.lib.sg_conv2d_dgrad(self.h, self.stream, dt, C.byref(d), _ptr(dy), _ptr(w), _ptr(bias), _ptr(dx),
-                                               flags, wsp, wsn), "sg_conv2d_dgrad")
+            check(self.lib.sg_conv2d_dgrad(self.h, self.stream, dt, C.byref(d), _ptr(dy), _ptr(w), _ptr(bias), _ptr(dx), flags,
+                                           C.byref(o)), "sg_conv2d_dgrad")
         return dx
 
     def conv2d_dgrad_bnb_ok(self, d: ConvDesc, dtype=torch.float32) -> bool:
         """Does the input gradient of pointwise convolution `d` take the wide kernel's BatchNormalization-backward form
-        (sg_conv2d_dgrad_bnb)?  Depends on the batch (the wide kernel wants >= 6144 rows)."""
-        return dtype == torch.float32 and bool(self.lib.sg_conv2d_dgrad_bnb_supported(self.h, SG_F32, C.byref(d)))
+        (sg_conv_opts.bnb)?  Depends on the batch (the wide kernel wants >= 6144 rows)."""
+        return dtype == torch.float32 and bool(self.conv2d_caps(d, True).bnb)
 
     def conv2d_dgrad_bnb(self, dy_bn, x_bn, w, d: ConvDesc, gamma, beta, mean, invstd, dgamma, dbeta, relu, planes=None):
         """dx of pointwise convolution `d` AND the BatchNormalization's applied gradient dz, from the gradient dy_bn of that
-        layer's output and its raw input x_bn (= the convolution's forward output): sg_conv2d_dgrad_bnb.  -> (dx, dz)"""
-        _chk32(dy_bn, "dy"); _chk32(x_bn, "x"); _chk32(w, "w")
+        layer's output and its raw input x_bn (= the convolution's forward output): sg_conv_opts.bnb.  -> (dx, dz)"""
+        _chk32(dy_bn, "dy"); _chk32(x_bn, "x")
         assert dy_bn.shape == x_bn.shape and dy_bn.is_contiguous() and x_bn.is_contiguous()
-        dx = self.empty(d.N, d.H, d.W, d.Cin)
         dz = torch.empty_like(dy_bn)
         rows = dy_bn.numel() // dy_bn.shape[-1]
         q = _lib.BnBwdIn(x_bn.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr() if (relu and beta is not None) else None,
                          dgamma.data_ptr(), dbeta.data_ptr(), dz.data_ptr(), int(bool(relu)), rows)
-        if planes is not None:
-            wsp, wsn = C.c_void_p(planes), C.c_size_t(_lib.SG_WS_PREPARED)
-        else:
-            wsp, wsn = self.ws(self.lib.sg_conv2d_dgrad_ws_bytes(C.byref(d)))
-        with self.timed(self._gemm_tag()):
-            check(self.lib.sg_conv2d_dgrad_bnb(self.h, self.stream, SG_F32, C.byref(d), _ptr(dy_bn), _ptr(w), _ptr(dx), wsp, wsn, C.byref(q)),
-                  "sg_conv2d_dgrad_bnb")
-        return dx, dz
+        return self.conv2d_dgrad(dy_bn, w, d, planes=planes, bnb=q), dz
 
     def conv2d_wgrad(self, x, dy, d: ConvDesc, want_bias=True, dw=None, db=None, x_up2=False, bn_in=None):
         """x_up2: x is the SOURCE [N, H/2, W/2, Cin] of the nearest 2x up-sampling the conv `d` read (SG_X_UP2: the patch
-        kernel gathers x[n, h >> 1, w >> 1]; the bits of the filter gradient on the materialised tensor)."""
+        kernel gathers x[n, h >> 1, w >> 1]; the bits of the filter gradient on the materialised tensor).
+        bn_in: x is the raw input of the BatchNormalization(+ReLU) in front of the layer (see conv2d_fwd)."""
         _chk(x, "x"); _chk(dy, "dy")
         dt = (SG_BF16 | SG_HEAD_F32) if (x.dtype == torch.bfloat16 and dy.dtype == torch.float32) else _dt(x)
         if x_up2:
@@ -499,16 +486,13 @@ class Engine:
             dw = self.empty(d.KH, d.KW, d.Cin, d.Cout)
         if want_bias and db is None:
             db = self.empty(d.Cout)
-        need = self.lib.sg_conv2d_wgrad_ws_bytes(self.h, C.byref(d))
-        wsp, wsn = self.ws(need)
+        o = self._conv_opts(None, self.lib.sg_conv2d_wgrad_ws_bytes(self.h, C.byref(d)))
+        if bn_in is not None:
+            bq = self._bn_in(bn_in)
+            o.bn_in = C.pointer(bq)
         with self.timed(self._gemm_tag()):
-            if bn_in is not None:   # x is the raw input of the BatchNormalization(+ReLU) in front of the layer (see conv2d_fwd)
-                bq = self._bn_in(bn_in)
-                check(self.lib.sg_conv2d_wgrad_bn(self.h, self.stream, dt, C.byref(d), _ptr(x), _ptr(dy), _ptr(dw),
-                                                  _ptr(db) if want_bias else None, wsp, wsn, C.byref(bq)), "sg_conv2d_wgrad_bn")
-            else:
-                check(self.lib.sg_conv2d_wgrad(self.h, self.stream, dt, C.byref(d), _ptr(x), _ptr(dy), _ptr(dw),
-                                               _ptr(db) if want_bias else None, wsp, wsn), "sg_conv2d_wgrad")
+            check(self.lib.sg_conv2d_wgrad(self.h, self.stream, dt, C.byref(d), _ptr(x), _ptr(dy), _ptr(dw),
+                                           _ptr(db) if want_bias else None, C.byref(o)), "sg_conv2d_wgrad")
         return dw, (db if want_bias else None)
 
     def split_planes(self, x, out=None):
@@ -521,7 +505,7 @@ class Engine:
         return pl
 
     def conv2d_wgrad_planes_ok(self, d: ConvDesc) -> bool:
-        return bool(self.lib.sg_conv2d_wgrad_planes_supported(self.h, C.byref(d)))
+        return bool(self.conv2d_caps(d).wgrad_planes)
 
     def conv2d_wgrad_planes(self, x_planes, dy_planes, d: ConvDesc, dw=None):
         """The fp32 filter gradient from operands that are already split into bf16 planes (sg_conv2d_wgrad_planes): the bits of
@@ -543,45 +527,41 @@ class Engine:
         return db
 
     # --------------------------------------------------------------------------------------- depthwise
+    @staticmethod
+    def _dw_bn(bn):
+        """bn = (gamma, beta, mean, invstd, relu) -> the sg_bn_in of the depthwise entry points, or None (training mode)"""
+        if bn is None:
+            return None
+        gamma, beta, mean, invstd, relu = bn
+        return C.byref(_lib.BnIn(_ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), int(relu), 0, 0.0))
+
     def dwconv_fwd(self, x, w, stride=1, pre_relu=False, out=None, desc=None, bn=None):
         """bn = (gamma, beta, mean, invstd, relu): x is the RAW input of a training-mode BatchNormalization(+ReLU) whose
-        output this depthwise convolution consumes; the normalisation is applied in the gather (sg_dwconv2d_fwd_bn)."""
+        output this depthwise convolution consumes; the normalisation is applied in the gather (bn of sg_dwconv2d_fwd)."""
         _chk(x, "x"); _chk(w, "w")
         kh, kw, c = w.shape[0], w.shape[1], w.shape[2]
         d = desc or self.conv_desc(x.shape, c, kh, kw, stride, 1, "same")
         y = out if out is not None else self.empty(d.N, d.Ho, d.Wo, c, dtype=x.dtype)
-        if bn is not None:
-            gamma, beta, mean, invstd, relu = bn
-            check(self.lib.sg_dwconv2d_fwd_bn(self.h, self.stream, _dt(x), C.byref(d), _ptr(x), _ptr(w), _ptr(y), _ptr(gamma),
-                                              _ptr(beta), _ptr(mean), _ptr(invstd), int(relu)), "sg_dwconv2d_fwd_bn")
-            return y
-        check(self.lib.sg_dwconv2d_fwd(self.h, self.stream, _dt(x), C.byref(d), _ptr(x), _ptr(w), _ptr(y), int(pre_relu)),
-              "sg_dwconv2d_fwd")
+        check(self.lib.sg_dwconv2d_fwd(self.h, self.stream, _dt(x), C.byref(d), _ptr(x), _ptr(w), _ptr(y),
+                                       int(pre_relu) if bn is None else 0, self._dw_bn(bn)), "sg_dwconv2d_fwd")
         return y
 
-    def dwconv_dgrad(self, dy, w, d: ConvDesc, x=None, pre_relu=False, out=None, res=None):
+    def dwconv_dgrad(self, dy, w, d: ConvDesc, x=None, pre_relu=False, out=None, res=None, sums=None):
         """res: a gradient already collected for the same input tensor, added to the result inside the kernel
-        (sg_dwconv2d_dgrad_acc: stride-1 3x3, W % 4 == 0, C % 4 == 0 only - dwconv_dgrad_acc_ok)."""
+        (stride-1 3x3, W % 4 == 0, C % 4 == 0 only - dwconv_dgrad_acc_ok).  sums: a _lib.DwBnSums (see dwconv_dgrad_bnsums)."""
         dx = out if out is not None else self.empty(d.N, d.H, d.W, d.Cin, dtype=dy.dtype)
-        if res is not None:
-            check(self.lib.sg_dwconv2d_dgrad_acc(self.h, self.stream, _dt(dy), C.byref(d), _ptr(dy), _ptr(w), _ptr(x), _ptr(dx),
-                                                 int(pre_relu), _ptr(res)), "sg_dwconv2d_dgrad_acc")
-            return dx
         check(self.lib.sg_dwconv2d_dgrad(self.h, self.stream, _dt(dy), C.byref(d), _ptr(dy), _ptr(w), _ptr(x), _ptr(dx),
-                                         int(pre_relu)), "sg_dwconv2d_dgrad")
+                                         int(pre_relu), _ptr(res), C.byref(sums) if sums is not None else None), "sg_dwconv2d_dgrad")
         return dx
 
     def dwconv_dgrad_bnsums(self, dy, w, d: ConvDesc, bn_x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, dgamma, dbeta,
                             x=None, pre_relu=False, res=None, out=None):
         """dwconv_dgrad whose result is the output gradient of a training-mode BatchNormalization (raw input bn_x): also writes
-        that layer's dgamma / dbeta (sg_dwconv2d_dgrad_bnsums); follow with bn_train_bwd_apply.  Geometry: dwconv_dgrad_acc_ok."""
-        dx = out if out is not None else self.empty(d.N, d.H, d.W, d.Cin, dtype=dy.dtype)
+        that layer's dgamma / dbeta (sums of sg_dwconv2d_dgrad); follow with bn_train_bwd_apply.  Geometry: dwconv_dgrad_acc_ok."""
         wsp, wsn = self.ws(self.lib.sg_dwconv2d_dgrad_bnsums_ws_bytes(self.h, C.byref(d)))
-        check(self.lib.sg_dwconv2d_dgrad_bnsums(self.h, self.stream, _dt(dy), C.byref(d), _ptr(dy), _ptr(w), _ptr(x), _ptr(dx),
-                                                int(pre_relu), _ptr(res), _ptr(bn_x), _ptr(bn_mean), _ptr(bn_invstd), _ptr(bn_gamma),
-                                                _ptr(bn_beta), int(bn_relu), _ptr(dgamma), _ptr(dbeta), wsp, wsn),
-              "sg_dwconv2d_dgrad_bnsums")
-        return dx
+        q = _lib.DwBnSums(_ptr(bn_x), _ptr(bn_mean), _ptr(bn_invstd), _ptr(bn_gamma), _ptr(bn_beta), int(bn_relu), _ptr(dgamma),
+                          _ptr(dbeta), wsp, wsn)
+        return self.dwconv_dgrad(dy, w, d, x=x, pre_relu=pre_relu, out=out, res=res, sums=q)
 
     @staticmethod
     def dwconv_dgrad_acc_ok(d: ConvDesc) -> bool:
@@ -591,15 +571,9 @@ class Engine:
     def dwconv_wgrad(self, x, dy, d: ConvDesc, pre_relu=False, dw=None, bn=None):
         if dw is None:
             dw = self.empty(d.KH, d.KW, d.Cin, 1)
-        need = self.lib.sg_dwconv2d_wgrad_ws_bytes(self.h, C.byref(d))
-        wsp, wsn = self.ws(need)
-        if bn is not None:  # see dwconv_fwd
-            gamma, beta, mean, invstd, relu = bn
-            check(self.lib.sg_dwconv2d_wgrad_bn(self.h, self.stream, _dt(x), C.byref(d), _ptr(x), _ptr(dy), _ptr(dw), _ptr(gamma),
-                                                _ptr(beta), _ptr(mean), _ptr(invstd), int(relu), wsp, wsn), "sg_dwconv2d_wgrad_bn")
-            return dw
+        wsp, wsn = self.ws(self.lib.sg_dwconv2d_wgrad_ws_bytes(self.h, C.byref(d)))
         check(self.lib.sg_dwconv2d_wgrad(self.h, self.stream, _dt(x), C.byref(d), _ptr(x), _ptr(dy), _ptr(dw),
-                                         int(pre_relu), wsp, wsn), "sg_dwconv2d_wgrad")
+                                         int(pre_relu) if bn is None else 0, self._dw_bn(bn), wsp, wsn), "sg_dwconv2d_wgrad")   # bn: see dwconv_fwd
         return dw
 
     # ---------------------------------------------------------------------------------------------- BN

@@ -124,7 +124,7 @@ class Model:
                 cons = n.output.consumers
                 if len(cons) == 1 and isinstance(cons[0], L._BNNode) and len(n.output.shape) == 4:
                     n.bias_grad_zero = True
-                    n.emit_bn_stats = True  # the conv epilogue hands BN its statistics (sg_conv2d_fwd_stats)
+                    n.emit_bn_stats = True  # the conv epilogue hands BN its statistics (stats of sg_conv2d_fwd)
         # UpSampling2D(2) -> Conv2D 3x3 'same' (the decoder's last stage, train_model/DeepLabv3plus.py:476-477): the convolution's
         # kernels read the up-sampling's source directly (sub-pixel forward with 4/9 of the products; csrc/conv_x6p.h) and the
         # 4x tensor and its gradient are never built.  Marked here for every such pair; whether a runtime takes the fused
@@ -152,7 +152,7 @@ class Model:
             if len(cons) == 1 and isinstance(cons[0], L._SepConvNode) and id(n.output) not in outs and not cons[0].pre_relu:
                 cons[0].pre_relu, n.fused_away = True, True
         # BatchNormalization (+ fused ReLU) -> SeparableConv2D, training mode: the depthwise gather applies the normalisation
-        # to the raw tensor (sg_dwconv2d_fwd_bn / _wgrad_bn), so the normalised tensor is never written or read - two of the
+        # to the raw tensor (bn of sg_dwconv2d_fwd / _wgrad), so the normalised tensor is never written or read - two of the
         # layer's seven tensor passes.  Needs the statistics from the producing convolution's epilogue (decided at run
         # time: _BNNode.forward falls back to the materialising form) and the stride-1 run kernels' geometry.
         # Default ON since round 4 (SG_BN_DEFER=0 restores the materialising form; tests/test_models_gpu.py keeps one leg on it).
@@ -187,7 +187,7 @@ class Model:
                             p_.defer_add, n.bn_src[i] = None, None
         # BatchNormalization (+ fused ReLU) -> SeparableConv2D (stride 1), the layer's only consumer: the input gradient that the
         # depthwise convolution's dgrad writes IS the BatchNormalization's output gradient.  That kernel also sums, per channel,
-        # dbeta = sum g and dgamma = sum g * xhat in its epilogue (sg_dwconv2d_dgrad_bnsums: one more read of the layer's raw
+        # dbeta = sum g and dgamma = sum g * xhat in its epilogue (sums of sg_dwconv2d_dgrad: one more read of the layer's raw
         # input), so the reduction pass of the BatchNormalization's backward - two tensor reads of its five passes - is not run
         # (round 4; conv_bn_relu / the Xception blocks, train_model/DeepLabv3plus.py:323-416,424-429; SG_BN_SUMS=0 switches it
         # off).  Decided again at run time (geometry, training mode: _SepConvNode.backward).

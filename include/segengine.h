@@ -63,14 +63,14 @@ extern "C" {
 #define SG_EPI_RELU 2
 /* UpSampling2D(size=2) -> Conv2D(3x3, 'same') fused (train_model/DeepLabv3plus.py:476-477, the decoder's last stage; round 5).
  * The descriptor always names the convolution on the UP-SAMPLED grid (H x W); the up-sampled tensor itself never exists.
- *   SG_PRO_UP2   (flags of sg_conv2d_fwd / _ws / _stats) x is the source x[N, H/2, W/2, Cin].  The "sub-pixel" kernel computes
+ *   SG_PRO_UP2   (flags of sg_conv2d_fwd) x is the source x[N, H/2, W/2, Cin].  The "sub-pixel" kernel computes
  *                the four output phases from the 2 x 2 source pixels each of them sees, with the kernel's taps summed
  *                beforehand: 4/9 of the multiplications, within fp32 rounding of the unfused pair (not bit-identical to it).
  *   SG_EPI_DOWN2 (flags of sg_conv2d_dgrad) dx is the gradient of the SOURCE, dx[N, H/2, W/2, Cin]: each 2 x 2 cell of the
  *                up-sampled tensor's gradient is added in the epilogue, in sg_upsample_nearest_bwd's order (bit-identical to
  *                the unfused pair).  No bias / ReLU / collected gradient with it.
  * Geometry: 3x3, stride 1, dilation 1, SAME, Cin = 64, Cout = 32, H % 16 = 0, W % 32 = 0, SG_F32 storage, x6 arithmetic on;
- * anything else returns SG_EUNSUPPORTED (sg_conv2d_up2_supported tells beforehand). */
+ * anything else returns SG_EUNSUPPORTED (sg_conv_caps.up2 tells beforehand). */
 #define SG_PRO_UP2   16
 #define SG_EPI_DOWN2 32
 
@@ -102,36 +102,42 @@ typedef struct sg_conv_desc {
   int32_t y_ld; /* pixel stride of y  (0 = Cout) */
 } sg_conv_desc;
 
+/* The optional operands of the three GEMM convolution launches.  All-zero = the plain launch; a NULL pointer means the same.
+ * A field that belongs to another direction, or a combination no kernel takes (res with a_planes; bnb with res or a_planes;
+ * bn_in with a_planes), is SG_EINVAL; nothing is written then. */
+typedef struct sg_bn_in sg_bn_in;
+typedef struct sg_bn_bwd_in sg_bn_bwd_in;
+typedef struct sg_conv_opts {
+  void* ws;            /* workspace of sg_conv2d_{fwd,dgrad,wgrad}_ws_bytes (16-byte aligned); dgrad and wgrad need one */
+  size_t ws_bytes;     /* SG_WS_PREPARED: ws = this layer's prepared weight planes (fwd, dgrad; sg_prepare_planes) */
+  void* stats;         /* fwd: BatchNormalization statistics from the epilogue, sg_conv2d_fwd_stats_bytes (with tiles_out) */
+  int* tiles_out;
+  const void* a_planes; /* fwd: sg_split_planes(x); dgrad: sg_split_planes(dy).  16-byte aligned, dense [3][pixels][C] */
+  const void* res;     /* dgrad: a gradient already collected for the same tensor, added in the epilogue */
+  const sg_bn_in* bn_in;    /* fwd, wgrad: a BatchNormalization (+ReLU) applied to x in the loader */
+  const sg_bn_bwd_in* bnb;  /* dgrad: a BatchNormalization's backward apply in the A path */
+} sg_conv_opts;
+
 /* Conv2D forward: implicit-GEMM on MFMA, M = N*Ho*Wo, N = Cout, K = KH*KW*Cin.
  * Replaces tf.keras.layers.Conv2D at predict_model/v3plus.py:173,177,185,289 (incl. the ASPP / SK dilated
  * 3x3 of :83-91,:298-300), predict_model/scse.py:52-95, predict_model/res34.py:33,54,147,156,
  * predict_model/hrnet.py:21, and the pointwise half of SeparableConv2D (v3plus.py:187-278).
- * flags: SG_EPI_BIAS adds bias[Cout]; SG_EPI_RELU applies max(.,0) (Conv2D(activation='relu')). */
-int sg_conv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x,
-                  const void* w, const void* bias, void* y, int flags);
-
-/* The same forward with a caller-provided workspace of sg_conv2d_fwd_ws_bytes(d) bytes (16-byte aligned).
- * With it the GEMM may run on the bf16 matrix pipe as six MFMA passes over a 3-way bf16 split of the fp32
- * operands ("x6", csrc/conv_x6.h: at least as accurate as the fp32 MFMA, measured; the workspace holds the
- * split kernel); without it (or when the shape does not qualify) the native fp32 MFMA kernel runs. */
+ * flags: SG_EPI_BIAS adds bias[Cout]; SG_EPI_RELU applies max(.,0) (Conv2D(activation='relu')).
+ * opts->ws: sg_conv2d_fwd_ws_bytes(d) bytes.  With it the GEMM may run on the bf16 matrix pipe as six MFMA passes over a
+ *   3-way bf16 split of the fp32 operands ("x6", csrc/conv_x6.h: at least as accurate as the fp32 MFMA, measured; the
+ *   workspace holds the split kernel); without it (or when the shape does not qualify) the native fp32 MFMA kernel runs.
+ * opts->stats / tiles_out: the forward also hands the following BatchNormalization its statistics (epilogue
+ *   flag bn_stats): per 128-pixel tile and output channel the sum and the centred sum of squares of y, written to
+ *   stats[tiles][2][Cout] (sg_conv2d_fwd_stats_bytes) from the accumulators.  *tiles_out = number of tiles written, or 0 when
+ *   this launch could not produce them (shape not on the x6 path): the caller then lets sg_bn_train_fwd compute its own.
+ *   sg_bn_train_fwd_tiles turns them into mean / inv-std / moving statistics (fp64 combination); the apply pass is sg_bn_apply.
+ *   Replaces Conv2D -> BatchNormalization (training) at predict_model/v3plus.py:173-179 and every SeparableConv2D ->
+ *   BatchNormalization pair (v3plus.py:187-278).
+ * opts->a_planes, opts->bn_in: see sg_split_planes and sg_bn_in below. */
 size_t sg_conv2d_fwd_ws_bytes(const sg_conv_desc* d);
-int sg_conv2d_fwd_ws(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x,
-                     const void* w, const void* bias, void* y, int flags, void* ws, size_t ws_bytes);
-/* 1 when the convolution `d` (on the up-sampled grid) takes the fused up-sampling kernels (SG_PRO_UP2 / SG_EPI_DOWN2 /
- * SG_X_UP2) with this storage type and the current arithmetic switch, else 0. */
-int sg_conv2d_up2_supported(int dtype, const sg_conv_desc* d);
-
-/* The forward that also hands the following BatchNormalization its statistics (epilogue flag
- * bn_stats): per 128-pixel tile and output channel the sum and the centred sum of squares of y, written to
- * stats[tiles][2][Cout] (sg_conv2d_fwd_stats_bytes) from the accumulators.  *tiles_out = number of tiles written,
- * or 0 when this launch could not produce them (shape not on the x6 path): the caller then lets
- * sg_bn_train_fwd compute its own.  sg_bn_train_fwd_tiles turns them into mean / inv-std / moving statistics
- * (fp64 combination); the apply pass is sg_bn_apply.  Replaces Conv2D -> BatchNormalization (training) at
- * predict_model/v3plus.py:173-179 and every SeparableConv2D -> BatchNormalization pair (v3plus.py:187-278). */
 size_t sg_conv2d_fwd_stats_bytes(const sg_conv_desc* d);
-int sg_conv2d_fwd_stats(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x,
-                        const void* w, const void* bias, void* y, int flags, void* ws, size_t ws_bytes,
-                        void* stats, int* tiles_out);
+int sg_conv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
+                  const void* bias, void* y, int flags, const sg_conv_opts* opts);
 size_t sg_bn_tiles_ws_bytes(const sg_ctx* ctx, int tiles, int C);
 int sg_bn_train_fwd_tiles(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* stats,
                           int tiles, void* moving_mean, void* moving_var, void* save_mean, void* save_invstd,
@@ -144,59 +150,65 @@ int sg_bn_apply(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const
 /* Conv2D input gradient dx[N,H,W,Cin] (pixel stride d->x_ld) from dy[N,Ho,Wo,Cout] (pixel stride d->y_ld).
  * The same routine is Conv2DTranspose *forward* (y_T = dgrad of the SAME conv that maps the upsampled grid
  * back): v3plus.py:328,335, scse.py:71-89, res34.py:144 — hence the optional epilogue
- * (bias has d->Cin entries here).  ws: sg_conv2d_dgrad_ws_bytes(d) bytes (the per-tap transposed kernel of the
- * fp32 path, or its three bf16 planes for the x6 path, whichever is larger). */
+ * (bias has d->Cin entries here).  opts->ws (required): sg_conv2d_dgrad_ws_bytes(d) bytes (the per-tap transposed kernel of
+ * the fp32 path, or its three bf16 planes for the x6 path, whichever is larger).
+ * opts->res: dx = dgrad(dy) [+ bias] [relu] + res (res in dx's layout; it may be dx itself).  Only launches that take the slab
+ *   kernels (sg_conv2d_planes_job kind 1) or the thin 1x1 kernel (Cout <= 4, not the fp32 softmax head) do this; the others
+ *   return SG_EUNSUPPORTED and launch nothing.
+ * opts->a_planes, opts->bnb: see sg_split_planes and sg_bn_bwd_in below. */
 size_t sg_conv2d_dgrad_ws_bytes(const sg_conv_desc* d);
 int sg_conv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy,
-                    const void* w, const void* bias, void* dx, int flags, void* ws, size_t ws_bytes);
-/* sg_conv2d_dgrad with a gradient already collected for the same tensor added in the epilogue: dx = dgrad(dy) [+ bias] [relu]
- * + res (res in dx's layout; it may be dx itself).  Only launches that take the slab kernels (sg_conv2d_planes_job kind 1) or
- * the thin 1x1 kernel (Cout <= 4, not the fp32 softmax head) do this; the others return SG_EUNSUPPORTED and launch nothing. */
-int sg_conv2d_dgrad_acc(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy,
-                        const void* w, const void* bias, void* dx, int flags, void* ws, size_t ws_bytes,
-                        const void* res);
+                    const void* w, const void* bias, void* dx, int flags, const sg_conv_opts* opts);
 
 /* Conv2D kernel gradient dw[KH,KW,Cin,Cout] (and dbias[Cout] if non-null) = sum over N*Ho*Wo.
  * Deterministic split-K: partial slabs in ws, then a fixed-order reduce (no float atomics: bit-reproducible run
  * to run).  Runs as six bf16 MFMA passes (x6) when the geometry is stride 1 / "same" / W % 32 == 0, else on the
- * fp32 MFMA; 1x1 kernels with Cout <= 4 take a streaming reduction.  ws: sg_conv2d_wgrad_ws_bytes. */
+ * fp32 MFMA; 1x1 kernels with Cout <= 4 take a streaming reduction.  opts->ws (required): sg_conv2d_wgrad_ws_bytes. */
 size_t sg_conv2d_wgrad_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d);
 int sg_conv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x,
-                    const void* dy, void* dw, void* dbias, void* ws, size_t ws_bytes);
+                    const void* dy, void* dw, void* dbias, const sg_conv_opts* opts);
 
-/* A training- or inference-mode BatchNormalization (+ReLU) applied to the convolution's INPUT while the kernel loads it (round 5):
- * the normalised tensor between `BatchNormalization -> [ReLU] -> Conv2D` (conv_bn_relu chains, train_model/DeepLabv3plus.py:424-429,
- * 476-480: the 512 x 512 x 32 tensors in front of the decoder's last 3x3 convolution and of the softmax head) is never written or
- * read.  x is the BatchNormalization's RAW input; the kernel evaluates bn_apply's own expression
- * [relu](fmaf((x - mean) * invstd, gamma, beta)) on every pixel inside the image (fp32 storage: the bits of the unfused pair).
- * infer: `invstd` points at the moving VARIANCE, invstd = rsqrtf(var + eps).  Covered launches: the thin 1x1 kernels (Cout <= 4) and
- * the patch kernels (3x3, stride 1, SAME, Cin 32 / 64; forward and filter gradient) - sg_conv2d_bn_in_supported; anything else
- * returns SG_EUNSUPPORTED.  The input gradient needs nothing (it is the BatchNormalization's output gradient). */
-typedef struct sg_bn_in {
+/* What the launches of convolution `d` can take, from the plans they run by, for this storage type and the current arithmetic
+ * switch.  dgrad = 0 asks about the forward, 1 about the input gradient; a field without a meaning for the asked direction is 0.
+ *   thin          the launch takes the thin 1x1 kernel (Cout <= 4)
+ *   planes_in     the launch reads opts->a_planes (others ignore them)
+ *   wgrad_planes  sg_conv2d_wgrad_planes covers the layer's filter gradient (SG_F32 storage only; either direction)
+ *   bn_in         dgrad = 0: forward and filter gradient take opts->bn_in (the thin 1x1 and the patch kernels)
+ *   up2           dgrad = 0: the fused up-sampling kernels (SG_PRO_UP2 / SG_EPI_DOWN2 / SG_X_UP2)
+ *   bnb           dgrad = 1: the input gradient takes opts->bnb (the wide pointwise kernel)
+ * A descriptor that no launch accepts answers all-zero. */
+typedef struct sg_conv_caps { int thin, bn_in, up2, bnb, planes_in, wgrad_planes; } sg_conv_caps;
+int sg_conv2d_caps(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int dgrad, sg_conv_caps* out);
+
+/* opts->bn_in: a training- or inference-mode BatchNormalization (+ReLU) applied to the convolution's INPUT while the kernel loads
+ * it (round 5): the normalised tensor between `BatchNormalization -> [ReLU] -> Conv2D` (conv_bn_relu chains,
+ * train_model/DeepLabv3plus.py:424-429, 476-480: the 512 x 512 x 32 tensors in front of the decoder's last 3x3 convolution and of
+ * the softmax head) is never written or read.  x is the BatchNormalization's RAW input; the kernel evaluates bn_apply's own
+ * expression [relu](fmaf((x - mean) * invstd, gamma, beta)) on every pixel inside the image (fp32 storage: the bits of the unfused
+ * pair).  infer: `invstd` points at the moving VARIANCE, invstd = rsqrtf(var + eps).  Covered launches: the thin 1x1 kernels
+ * (Cout <= 4) and the patch kernels (3x3, stride 1, SAME, Cin 32 / 64; forward and filter gradient) - sg_conv_caps.bn_in; anything
+ * else, SG_PRO_UP2 included, returns SG_EUNSUPPORTED.  The input gradient needs nothing (it is the BatchNormalization's output
+ * gradient). */
+struct sg_bn_in {
   const void* mean;
   const void* invstd;
   const void* gamma;
   const void* beta;
   int32_t relu, infer;
   float eps;
-} sg_bn_in;
-int sg_conv2d_bn_in_supported(const sg_ctx* ctx, int dtype, const sg_conv_desc* d);
-int sg_conv2d_fwd_stats_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
-                           const void* bias, void* y, int flags, void* ws, size_t ws_bytes, void* stats, int* tiles_out,
-                           const sg_bn_in* bn);
-int sg_conv2d_wgrad_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy,
-                       void* dw, void* dbias, void* ws, size_t ws_bytes, const sg_bn_in* bn);
+};
 
-/* The input gradient of a pointwise convolution whose forward output feeds a training-mode BatchNormalization, with that layer's
- * backward APPLY evaluated in the kernel's A path (round 5; csrc/conv_pw.h, BNB form; SeparableConv2D -> BatchNormalization,
- * train_model/DeepLabv3plus.py:323-416).  dy is the gradient of the BatchNormalization's OUTPUT, bnb->x its raw input (= this
- * convolution's output), dgamma / dbeta its FINISHED column sums (sg_dwconv2d_dgrad_bnsums / sg_bn_train_bwd), rows the pixels
- * it normalises over.  The kernel computes dz = gamma invstd ((g - dbeta / rows) - xhat dgamma / rows) on the fly (g = dy where the
- * fused ReLU passed: the mask is bn_apply's own expression on x), multiplies it with the kernel and also stores it to bnb->dz for
- * the filter gradient - what sg_bn_train_bwd_apply + sg_conv2d_dgrad do in two launches and three more tensor passes.
- * Launches of the wide pointwise kernel only (sg_conv2d_dgrad_bnb_supported: 1x1, stride 1, dense fp32, >= 6144 rows, wide
- * enough); same order of products as sg_conv2d_dgrad, the applied gradient within rounding of sg_bn_train_bwd_apply's. */
-typedef struct sg_bn_bwd_in {
+/* opts->bnb: the input gradient of a pointwise convolution whose forward output feeds a training-mode BatchNormalization, with
+ * that layer's backward APPLY evaluated in the kernel's A path (round 5; csrc/conv_pw.h, BNB form; SeparableConv2D ->
+ * BatchNormalization, train_model/DeepLabv3plus.py:323-416).  dy is the gradient of the BatchNormalization's OUTPUT, bnb->x its raw
+ * input (= this convolution's output), dgamma / dbeta its FINISHED column sums (sg_dwconv2d_dgrad with sums / sg_bn_train_bwd), rows
+ * the pixels it normalises over.  The kernel computes dz = gamma invstd ((g - dbeta / rows) - xhat dgamma / rows) on the fly (g = dy
+ * where the fused ReLU passed: the mask is bn_apply's own expression on x), multiplies it with the kernel and also stores it to
+ * bnb->dz for the filter gradient - what sg_bn_train_bwd_apply + sg_conv2d_dgrad do in two launches and three more tensor passes.
+ * Launches of the wide pointwise kernel only (sg_conv_caps.bnb: 1x1, stride 1, dense fp32, >= 6144 rows, wide enough), with no bias
+ * and no flags (SG_EINVAL); same order of products as the plain sg_conv2d_dgrad, the applied gradient within rounding of
+ * sg_bn_train_bwd_apply's. */
+struct sg_bn_bwd_in {
   const void* x;
   const void* mean;
   const void* invstd;
@@ -207,10 +219,7 @@ typedef struct sg_bn_bwd_in {
   void* dz;
   int32_t relu;
   int64_t rows;
-} sg_bn_bwd_in;
-int sg_conv2d_dgrad_bnb_supported(const sg_ctx* ctx, int dtype, const sg_conv_desc* d);
-int sg_conv2d_dgrad_bnb(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w, void* dx,
-                        void* ws, size_t ws_bytes, const sg_bn_bwd_in* bnb);
+};
 
 /* Planes-in filter gradient (round 5).  The fp32 ("x6") filter gradient splits BOTH of its operands into three bf16 planes on
  * the VALU in every launch; where the planes already exist - the forward's activation planes of a long-K convolution, kept - the
@@ -220,21 +229,14 @@ int sg_conv2d_dgrad_bnb(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc
  *   sg_conv2d_wgrad_planes   dw[KH,KW,Cin,Cout] of the convolution `d` from x_planes[3][N*H*W][Cin] and dy_planes[3][N*Ho*Wo][Cout];
  *                            same products in the same order as sg_conv2d_wgrad on the fp32 tensors (bit-identical), no bias
  *                            gradient (sg_bias_grad).  ws: sg_conv2d_wgrad_planes_ws_bytes(ctx, d).  Stride 1, SAME, Wo % 32 = 0,
- *                            channels % 8 = 0, not a layer of the wide-pointwise / patch families; _supported() tells.
- * Replaces the filter gradient of the ASPP / SK / decoder 3x3 convolutions (train_model/DeepLabv3plus.py:219-229, 431-443). */
-int sg_split_planes(sg_ctx* ctx, void* stream, const void* x, int64_t rows, int C, int ld, void* planes);
-/* The forward / input gradient with the activation's planes handed in.  The long-K multi-tap launches (csrc/conv_x6w.h: the ASPP /
- * SK / decoder 3x3 convolutions) read their A operand as sg_split_planes' planes and otherwise split it themselves in every
- * launch; x_planes / dy_planes (may be null) = the planes of the very tensor passed as x / dy, dense [3][pixels][C].  The five
+ *                            channels % 8 = 0, not a layer of the wide-pointwise / patch families; sg_conv_caps.wgrad_planes tells.
+ * Replaces the filter gradient of the ASPP / SK / decoder 3x3 convolutions (train_model/DeepLabv3plus.py:219-229, 431-443).
+ * opts->a_planes: the forward / input gradient with the activation's planes handed in.  The long-K multi-tap launches
+ * (csrc/conv_x6w.h: the ASPP / SK / decoder 3x3 convolutions) read their A operand as sg_split_planes' planes and otherwise split
+ * it themselves in every launch; a_planes = the planes of the very tensor passed as x / dy, dense [3][pixels][C].  The five
  * consumers of the ASPP input share ONE split this way, and a layer's dy planes serve its dgrad and its filter gradient.
- * Launches that take another kernel ignore the planes.  sg_conv2d_planes_in(d, dgrad): 1 if the launch reads planes. */
-int sg_conv2d_planes_in(const sg_conv_desc* d, int dgrad);
-int sg_conv2d_fwd_stats_ap(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
-                           const void* bias, void* y, int flags, void* ws, size_t ws_bytes, void* stats, int* tiles_out,
-                           const void* x_planes);
-int sg_conv2d_dgrad_ap(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                       const void* bias, void* dx, int flags, void* ws, size_t ws_bytes, const void* dy_planes);
-int sg_conv2d_wgrad_planes_supported(const sg_ctx* ctx, const sg_conv_desc* d);
+ * Launches that take another kernel ignore the planes (sg_conv_caps.planes_in: 1 if the launch reads them). */
+int sg_split_planes(sg_ctx* ctx, void* stream, const void* x, int64_t rows, int C, int ld, void* planes);
 size_t sg_conv2d_wgrad_planes_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d);
 int sg_conv2d_wgrad_planes(sg_ctx* ctx, void* stream, const sg_conv_desc* d, const void* x_planes, const void* dy_planes, void* dw,
                            void* ws, size_t ws_bytes);
@@ -248,46 +250,44 @@ int sg_bias_grad(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, int 
 
 /* Depthwise 3x3 (the first half of SeparableConv2D, depth_multiplier 1, no bias): v3plus.py:187-278.
  * d->Cout must equal d->Cin; w is [KH][KW][C].  pre_relu folds the Activation('relu') that precedes the
- * layer (v3plus.py:204,225,242,...) into the gather: y = dw(relu(x)); its dgrad masks by x > 0. */
+ * layer (v3plus.py:204,225,242,...) into the gather: y = dw(relu(x)); its dgrad masks by x > 0.
+ * The trailing operands are optional (NULL = the plain launch):
+ *   bn (fwd, wgrad)  the layer's input is BatchNormalization(+ReLU) of a tensor x_raw, in training mode (bn->infer must be 0),
+ *          with that normalisation applied as the window is loaded - fmaf((x - mean) * invstd, gamma, beta), then max(., 0) if
+ *          bn->relu - so that the normalised tensor is never written (the pattern BatchNormalization -> Activation('relu') ->
+ *          SeparableConv2D of the Xception middle flow, predict_model/v3plus.py:170-260).  x is x_raw; mean / invstd are the
+ *          batch statistics sg_bn_train_fwd / sg_bn_train_fwd_tiles saved; pre_relu must be 0 (bn->relu takes its role).  The
+ *          input gradient is the plain sg_dwconv2d_dgrad without a mask (the ReLU's mask belongs to sg_bn_train_bwd, which
+ *          recomputes it from x_raw).
+ *   res (dgrad)  a gradient already collected for the layer's input added to the result: dx = dgrad(dy) [masked] + res (res may
+ *          be dx itself).  The input of an Xception block feeds the block AND its residual add; the block's input gradient then
+ *          leaves this kernel complete instead of through a separate add (v3plus.py's `add([residual, shortcut])` blocks).
+ *   sums (dgrad)  the layer's input is the output of a training-mode BatchNormalization(+ReLU) with no other consumer
+ *          (conv_bn_relu / the Xception blocks, train_model/DeepLabv3plus.py:323-416,424-429): dx is then that layer's output
+ *          gradient, and the kernel also produces what the layer's backward sums over the pixels - dbeta = sum g, dgamma = sum
+ *          g * xhat, g = dx [masked by the fused ReLU, recomputed from sums->x as sg_bn_train_bwd does], xhat = (x - mean) *
+ *          invstd, sums->x the layer's RAW input (dense [N,H,W,C]) - in its epilogue: one more tensor read here instead of the
+ *          two-read reduction pass of sg_bn_train_bwd.  Follow with sg_bn_train_bwd_apply.  Partial sums are added in a fixed
+ *          order (deterministic); they differ from sg_bn_train_bwd's in rounding only.  sums->ws:
+ *          sg_dwconv2d_dgrad_bnsums_ws_bytes.
+ * Each of the three needs the stride-1 3x3 run kernels: W % 4 == 0, C % 4 == 0, 16-byte aligned tensors, else SG_EUNSUPPORTED
+ * (materialise the BatchNormalization with sg_bn_apply / add afterwards / use sg_bn_train_bwd instead). */
+typedef struct sg_dw_bnsums {
+  const void *x, *mean, *invstd, *gamma, *beta;
+  int relu;
+  void *dgamma, *dbeta;
+  void* ws;
+  size_t ws_bytes;
+} sg_dw_bnsums;
 int sg_dwconv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x,
-                    const void* w, void* y, int pre_relu);
-int sg_dwconv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy,
-                      const void* w, const void* x_for_mask, void* dx, int pre_relu);
-/* The same with a gradient already collected for the layer's input added to the result: dx = dgrad(dy) [masked] + res (res may
- * be dx itself).  The input of an Xception block feeds the block AND its residual add; the block's input gradient then leaves
- * this kernel complete instead of through a separate add (v3plus.py's `add([residual, shortcut])` blocks).  Stride-1 3x3,
- * W % 4 == 0, C % 4 == 0, 16-byte aligned tensors, else SG_EUNSUPPORTED. */
-int sg_dwconv2d_dgrad_acc(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy,
-                          const void* w, const void* x_for_mask, void* dx, int pre_relu, const void* res);
-/* sg_dwconv2d_dgrad[_acc] of a SeparableConv2D whose input is the output of a training-mode BatchNormalization(+ReLU) with no
- * other consumer (conv_bn_relu / the Xception blocks, train_model/DeepLabv3plus.py:323-416,424-429): dx is then that layer's
- * output gradient, and the kernel also produces what the layer's backward sums over the pixels - dbeta = sum g, dgamma = sum
- * g * xhat, g = dx [masked by the fused ReLU, recomputed from bn_x as sg_bn_train_bwd does], xhat = (bn_x - mean) * invstd,
- * bn_x the layer's RAW input (dense [N,H,W,C]) - in its epilogue: one more tensor read here instead of the two-read
- * reduction pass of sg_bn_train_bwd.  Follow with sg_bn_train_bwd_apply.  res (may be NULL) as in sg_dwconv2d_dgrad_acc.
- * Partial sums are added in a fixed order (deterministic); they differ from sg_bn_train_bwd's in rounding only.  Stride-1 3x3,
- * W % 4 == 0, C % 4 == 0, 16-byte aligned tensors, else SG_EUNSUPPORTED.  Workspace: sg_dwconv2d_dgrad_bnsums_ws_bytes. */
+                    const void* w, void* y, int pre_relu, const sg_bn_in* bn);
 size_t sg_dwconv2d_dgrad_bnsums_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d);
-int sg_dwconv2d_dgrad_bnsums(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
-                             const void* x_for_mask, void* dx, int pre_relu, const void* res, const void* bn_x,
-                             const void* bn_mean, const void* bn_invstd, const void* bn_gamma, const void* bn_beta, int bn_relu,
-                             void* dgamma, void* dbeta, void* ws, size_t ws_bytes);
-/* The depthwise convolution of a SeparableConv2D whose input is BatchNormalization(+ReLU) of a tensor x_raw, in training
- * mode, with that normalisation applied as the window is loaded - fmaf((x - mean) * invstd, gamma, beta), then max(., 0) if
- * relu - so that the normalised tensor is never written (the pattern BatchNormalization -> Activation('relu') ->
- * SeparableConv2D of the Xception middle flow, predict_model/v3plus.py:170-260).  x is x_raw; mean / invstd are the batch
- * statistics sg_bn_train_fwd / sg_bn_train_fwd_tiles saved.  Stride-1 3x3, W % 4 == 0, C % 4 == 0, 16-byte aligned tensors
- * only (SG_EUNSUPPORTED otherwise: apply sg_bn_apply and call the plain entry points).  sg_dwconv2d_wgrad_bn is the filter
- * gradient of the same layer (workspace: sg_dwconv2d_wgrad_ws_bytes); the input gradient is sg_dwconv2d_dgrad without a mask
- * (the ReLU's mask belongs to sg_bn_train_bwd, which recomputes it from x_raw). */
-int sg_dwconv2d_fwd_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w, void* y,
-                       const void* gamma, const void* beta, const void* mean, const void* invstd, int relu);
-int sg_dwconv2d_wgrad_bn(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy, void* dw,
-                         const void* gamma, const void* beta, const void* mean, const void* invstd, int relu, void* ws,
-                         size_t ws_bytes);
+int sg_dwconv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy,
+                      const void* w, const void* x_for_mask, void* dx, int pre_relu, const void* res,
+                      const sg_dw_bnsums* sums);
 size_t sg_dwconv2d_wgrad_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d);
 int sg_dwconv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x,
-                      const void* dy, void* dw, int pre_relu, void* ws, size_t ws_bytes);
+                      const void* dy, void* dw, int pre_relu, const sg_bn_in* bn, void* ws, size_t ws_bytes);
 
 /* Dense on [rows,in] x [in,out] (+bias): bam.py channel_gate, res34.py:94,98.  Tiny GEMMs. */
 int sg_dense_fwd(sg_ctx* ctx, void* stream, int dtype, int rows, int in, int out, const void* x,
@@ -304,7 +304,7 @@ int sg_dense_fwd(sg_ctx* ctx, void* stream, int dtype, int rows, int in, int out
  *                          aligned byte offset inside the planes arena) and block0 (running sum of nblocks), copies
  *                          the job table to the device, and
  *   sg_prepare_planes      converts every job of the table in ONE launch (after Adam, after set_weights);
- *   then passes `planes_arena + out_off` as `ws` with `ws_bytes = SG_WS_PREPARED` to sg_conv2d_fwd_ws / _stats /
+ *   then passes `planes_arena + out_off` as `ws` with `ws_bytes = SG_WS_PREPARED` in the sg_conv_opts of sg_conv2d_fwd /
  *   sg_conv2d_dgrad.  A launch whose operands turn out not to qualify (unaligned, strided) returns SG_EINVAL.
  * The planes depend on the arithmetic mode (sg_get_conv_x6) and the storage dtype: prepare again after changing either. */
 #define SG_WS_PREPARED ((size_t)-1)
@@ -353,7 +353,7 @@ int sg_bn_train_bwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, c
                     const void* y, const void* dy, const void* gamma, const void* beta, const void* save_mean,
                     const void* save_invstd, void* dx, void* dgamma, void* dbeta, int relu, void* ws,
                     size_t ws_bytes);
-/* The second pass of sg_bn_train_bwd on its own: dx from FINISHED column sums dgamma / dbeta (sg_dwconv2d_dgrad_bnsums wrote
+/* The second pass of sg_bn_train_bwd on its own: dx from FINISHED column sums dgamma / dbeta (sg_dwconv2d_dgrad with sums wrote
  * them).  relu: the fused ReLU's mask is recomputed from x (beta required). */
 int sg_bn_train_bwd_apply(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* dy,
                           const void* gamma, const void* beta, const void* save_mean, const void* save_invstd,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""sg_conv2d_dgrad_bnb (csrc/conv_pw.h, BNB form): the BatchNormalization backward apply evaluated in the A path of the pointwise
+"""sg_conv_opts.bnb (csrc/conv_pw.h, BNB form): the BatchNormalization backward apply evaluated in the A path of the pointwise
 dgrad, against sg_bn_train_bwd_apply + sg_conv2d_dgrad - results and time, at the middle flow's shape and two others.
 Use: python scripts/bnb_check.py"""
 import os

@@ -2,7 +2,7 @@
 """Digest of the stride-1 3x3 depthwise stencil's outputs - forward (plain, pre-activation ReLU, BatchNormalization in the gather
 with and without ReLU), dgrad (plain, ReLU mask, a collected gradient riding along) - in fp32 and bf16 storage over maps of several
 sizes.  Run once with SG_DW_FSTRIP=0 (run kernel) and once with 1 (strip kernel) and compare the lines: same products in the same
-order, the bits must agree.  (The BatchNormalization sums of sg_dwconv2d_dgrad_bnsums are added in another order: the op test
+order, the bits must agree.  (The BatchNormalization sums of sg_dwconv2d_dgrad with sums are added in another order: the op test
 holds them to the oracle.)  Use: SG_DW_FSTRIP=0|1 python scripts/dw_var_check.py"""
 import hashlib
 import os

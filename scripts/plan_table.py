@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The plan table: what the library answers about every convolution site of the five models - the planes-job fields and slot size
-(sg_conv2d_planes_job), the workspace query and the planes_in / up2_supported / bn_in_supported / dgrad_bnb_supported answers for
+(sg_conv2d_planes_job), the workspace query and the planes_in / up2 / bn_in / bnb answers of sg_conv2d_caps for
 every unique (site, storage, arithmetic mode, direction).  A change of plan_conv() (csrc/conv_igemm.hip) is diffed against its
 parent with this: every line that moved is a launch that takes another kernel, other planes or another workspace.  The sites are the
 ones tests/test_plane_sites_gpu.py sweeps (tests/_plane_sites.py enumerates them).  Needs the GPU only for the library context.
@@ -41,8 +41,7 @@ def rows():
                 st = _lib.SG_F32 if s.policy == "float32" else _lib.SG_BF16
                 out.append(Row("b16" if mode is None else f"x{mode}", s.dgrad, s.head, dict(zip(PS.desc_fields(), s.desc)), i.kind, i.npl, i.kd,
                                i.K, i.Kpad, i.N, i.Npad, i.Ck, i.Ckp, i.nblocks, i.bytes, i.ws, i.pin,
-                               e.lib.sg_conv2d_up2_supported(st, C.byref(d)), e.lib.sg_conv2d_bn_in_supported(e.h, st, C.byref(d)),
-                               e.lib.sg_conv2d_dgrad_bnb_supported(e.h, st, C.byref(d))))
+                               e.conv2d_caps(d, False, st).up2, e.conv2d_caps(d, False, st).bn_in, e.conv2d_caps(d, True, st).bnb))
     return len(uniq), out
 
 

@@ -121,9 +121,9 @@ def planes_job(engine, s):
 
 
 def planes_in(engine, s):
-    """sg_conv2d_planes_in: the launch reads its activation as split_planes' planes (fp32 storage, mode 1)."""
+    """sg_conv2d_caps' planes_in: the launch reads its activation as split_planes' planes (fp32 storage, mode 1)."""
     d = make_desc(s)
-    return int(engine.lib.sg_conv2d_planes_in(C.byref(d), s.dgrad)) if s.policy == "float32" else 0
+    return int(engine.conv2d_caps(d, s.dgrad).planes_in) if s.policy == "float32" else 0
 
 
 def ws_query(engine, s):

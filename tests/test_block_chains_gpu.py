@@ -338,7 +338,7 @@ def test_xception_middle_flow_chain(engine):
     real step (conv_pw.h: forward, dgrad and wgrad).  This is where the round-3 fusions act, all of them on here by default:
     the pre-activation ReLU in the depthwise gather, BatchNormalization statistics from the pointwise epilogue, the third
     BatchNormalization applied BY the residual add (sg_add2_bn, SG_BN_ADD), the gradient already collected for a block's
-    input added by the first depthwise dgrad (sg_dwconv2d_dgrad_acc, SG_GRAD_ACC / take_pending: the second block's input
+    input added by the first depthwise dgrad (sg_dwconv2d_dgrad with res, SG_GRAD_ACC / take_pending: the second block's input
     feeds its branch AND its add).  Calibration: the ReLUs sit on the stem's output (its bias moves), on the first two
     BatchNormalization outputs of a block (their beta) and on a block's output = the next block's input (the third beta)."""
     import os
@@ -387,7 +387,7 @@ def test_xception_middle_flow_chain(engine):
     # round-4 fusions and at 6144 or 1536 pixels; one block at 1536 pixels: 0.986).  With 384 samples per channel the gaps the
     # calibration centres are four times wider than at 1536 and most pre-activations clear bf16's noise.  One block has three
     # ReLU layers, like the deepest of the other blocks;
-    # its input still feeds the branch AND the residual add (take_pending / sg_dwconv2d_dgrad_acc) and its third
+    # its input still feeds the branch AND the residual add (take_pending / sg_dwconv2d_dgrad with res) and its third
     # BatchNormalization is applied by the add (sg_add2_bn).
     e1, o1 = make(1)
     BF16_CASES["xception_middle_flow"] = (e1, o1, (8, 8, 24), 17, 6)

@@ -704,7 +704,7 @@ def test_segmented_data_parallel_step_gloo_world2():
 
 def test_depthwise_dgrad_takes_over_the_batchnorm_backward_sums(monkeypatch):
     """Model._fuse (round 4): a 4-D BatchNormalization whose output gradient is written by the depthwise dgrad of ONE stride-1
-    SeparableConv2D has its backward column sums produced by that kernel (sg_dwconv2d_dgrad_bnsums; layers._BNNode.sums_from /
+    SeparableConv2D has its backward column sums produced by that kernel (sg_dwconv2d_dgrad with sums; layers._BNNode.sums_from /
     _SepConvNode.bnsum_src): (a) the layer's only consumer is that SeparableConv2D (through the ReLU absorbed into either of
     them): 39 layers of DeepLabv3+, 32 in the middle flow and 7 in the entry / exit flows; (b) the layer is applied by a residual
     Add (defer_add) whose output opens the next Xception block, and that block's first SeparableConv2D is the last consumer of

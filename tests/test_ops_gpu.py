@@ -420,7 +420,7 @@ def test_upsample(engine, s):
                          ids=["dilated3x3", "stride2_1x1_parity_rows", "ragged_columns", "thin_1x1_to_1"])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_conv_dgrad_adds_a_collected_gradient(engine, case, dtype):
-    """sg_conv2d_dgrad_acc: dx = dgrad(dy) + res in the epilogue of the slab kernels (conv_x6_kernel / conv_b16_kernel, also
+    """sg_conv_opts.res: dx = dgrad(dy) + res in the epilogue of the slab kernels (conv_x6_kernel / conv_b16_kernel, also
     with the stride-2 parity-class row order).  fp32: the bits of the dgrad followed by add_n, res may be the output itself;
     bf16: within one rounding of it."""
     n, h, w, cin, cout, k, stride, dil = case
@@ -459,7 +459,7 @@ def test_conv_dgrad_adds_a_collected_gradient(engine, case, dtype):
     ((6, 32, 32, 728, 728, 1, 1), 3, None),     # the wide pointwise kernel (6144 rows)
 ], ids=["long_k_256ch", "slab_dilated", "patch_two_chunks", "patch_one_chunk", "wide_pointwise"])
 def test_dgrad_kernel_choice_does_not_depend_on_a_collected_gradient(engine, case, kind_wanted, same_kernel):
-    """include/segengine.h, sg_conv2d_dgrad_acc: a launch adds `res` exactly when sg_conv2d_planes_job (which knows no `res`) says
+    """include/segengine.h, sg_conv_opts.res: a launch adds `res` exactly when sg_conv2d_planes_job (which knows no `res`) says
     kind 1 for it - the weight planes of a step are laid out from that answer, so the launch must come to the same one with `res` as
     without.  Round 5: the patch kernel's predicate asked the planes-in kernel's, which declined a launch that carried `res`; the
     decoder's 64^2 x 512 -> 256 dgrad then took the patch kernel on planes laid out for the slab kernel's family and refused (loudly)
@@ -498,7 +498,7 @@ def test_dgrad_kernel_choice_does_not_depend_on_a_collected_gradient(engine, cas
 
 @pytest.mark.parametrize("pre_relu", [False, True])
 def test_depthwise_dgrad_adds_a_collected_gradient(engine, pre_relu):
-    """sg_dwconv2d_dgrad_acc: dx = dgrad(dy) [masked by x > 0] + res inside the kernel - the bits of the dgrad followed by
+    """sg_dwconv2d_dgrad with res: dx = dgrad(dy) [masked by x > 0] + res inside the kernel - the bits of the dgrad followed by
     add_n; res may be the output buffer itself."""
     g = torch.Generator().manual_seed(5 + pre_relu)
     n, h, w, c = 2, 12, 16, 728
@@ -562,7 +562,7 @@ def test_planes_in_x6_kernel(engine, case):
 @pytest.mark.parametrize("bn_relu,pre_relu,with_res,shape", [(True, False, False, (2, 12, 16, 728)), (False, True, True, (3, 8, 8, 128)),
                                                           (False, False, False, (2, 6, 20, 36)), (True, False, True, (1, 64, 32, 64))])
 def test_depthwise_dgrad_sums_the_batchnorm_backward(engine, bn_relu, pre_relu, with_res, shape, dtype):
-    """sg_dwconv2d_dgrad_bnsums + sg_bn_train_bwd_apply (round 4): z = BatchNormalization[+ReLU](y) in training mode, t =
+    """sg_dwconv2d_dgrad with sums + sg_bn_train_bwd_apply (round 4): z = BatchNormalization[+ReLU](y) in training mode, t =
     depthwise3x3([relu](z)).  Given dt, the depthwise dgrad writes dz (+ res) AND the BatchNormalization's dgamma / dbeta; the
     apply pass then gives dy.  Against fp64 autograd of the oracle's layers (tfops.batch_norm / depthwise_conv2d) and against the
     unfused engine path (sg_dwconv2d_dgrad -> sg_bn_train_bwd: same values up to the order of the column sums).  Shapes: the
@@ -1020,7 +1020,7 @@ def test_upsampling_fused_into_the_3x3_convolution(engine, shape):
                                   (2, 32, 32, 264, 40, 3, 1), (2, 32, 32, 1280, 256, 1, 1)],
                          ids=["aspp_d6", "aspp_like_d18_b3", "decoder_512", "w64_cout136_d2", "ragged_c264_cout40", "pointwise_1280"])
 def test_activation_planes_handed_in(engine, case):
-    """Round 5: sg_split_planes + sg_conv2d_fwd_stats_ap / _dgrad_ap / sg_conv2d_wgrad_planes.  The long-K fp32 convolutions read
+    """Round 5: sg_split_planes + sg_conv_opts.a_planes / sg_conv2d_wgrad_planes.  The long-K fp32 convolutions read
     their activation as three bf16 planes (conv_x6w.h) and split it in every launch; with the planes handed in - made once per
     tensor and step - forward and dgrad skip that split and the filter gradient (wgrad_x6_kernel<.., PIN>) takes BOTH operands as
     planes instead of splitting them on the VALU.  The planes ARE the exact split the kernels make themselves, so every result
@@ -1062,7 +1062,7 @@ def test_activation_planes_handed_in(engine, case):
 @pytest.mark.parametrize("infer", [False, True], ids=["train_stats", "moving_stats"])
 def test_batchnorm_applied_in_the_convolution_loaders(engine, case, infer):
     """Round 5: BatchNormalization(+ReLU) -> Conv2D with the normalisation applied while the convolution's kernels load their
-    input (sg_conv2d_fwd_stats_bn / sg_conv2d_wgrad_bn: the patch kernels conv_x6p.h / conv_x6wp.h and the thin 1x1 kernels).  The
+    input (sg_conv_opts.bn_in: the patch kernels conv_x6p.h / conv_x6wp.h and the thin 1x1 kernels).  The
     loaders evaluate bn_apply's own expression on every pixel inside the image, so forward (with its statistics epilogue) and the
     filter gradient must have the BITS of the unfused pair of launches - the zero padding included, which is padding of the
     NORMALISED tensor and must not be normalised."""
@@ -1113,7 +1113,7 @@ def test_batchnorm_applied_in_the_convolution_loaders(engine, case, infer):
 @pytest.mark.parametrize("case", [(6, 32, 32, 728, 728, True), (6, 32, 32, 728, 728, False), (7, 32, 32, 728, 1016, True), (3, 64, 64, 1024, 728, True)],
                          ids=["middle_flow", "no_relu", "ragged_k_1016", "tiles_256_wide"])
 def test_batchnorm_backward_apply_in_the_pointwise_dgrad(engine, case):
-    """Round 5 (csrc/conv_pw.h, BNB form; sg_conv2d_dgrad_bnb): SeparableConv2D -> BatchNormalization, backward - the layer's
+    """Round 5 (csrc/conv_pw.h, BNB form; sg_conv_opts.bnb): SeparableConv2D -> BatchNormalization, backward - the layer's
     backward APPLY evaluated in the A path of the pointwise dgrad, the applied gradient also stored for the filter gradient.  Both
     outputs must have the BITS of sg_bn_train_bwd_apply + sg_conv2d_dgrad (the transformed value is fenced before the x6 split:
     left to the compiler, the split's residual was an fma of the unrounded product and the input gradient differed in the last

@@ -82,10 +82,11 @@ def _launch(e, s, d, a, w, bias, flags, wsp, wsn, want_stats=False, a_planes=Non
     if not s.dgrad:
         if want_stats:
             st = torch.full((lib.sg_conv2d_fwd_stats_bytes(C.byref(d)) // 4,), NAN, dtype=torch.float32, device=e.device)
-        rc = lib.sg_conv2d_fwd_stats_ap(e.h, e.stream, PS.abi_dtype(s), C.byref(d), _p(a), _p(w), bp, _p(out), flags, wsp, wsn, _p(st),
-                                        C.byref(tiles) if want_stats else None, _p(a_planes))
+        o = PS_lib().ConvOpts(wsp, wsn, _p(st), C.pointer(tiles) if want_stats else None, _p(a_planes))
+        rc = lib.sg_conv2d_fwd(e.h, e.stream, PS.abi_dtype(s), C.byref(d), _p(a), _p(w), bp, _p(out), flags, C.byref(o))
     else:
-        rc = lib.sg_conv2d_dgrad_ap(e.h, e.stream, PS.abi_dtype(s), C.byref(d), _p(a), _p(w), bp, _p(out), flags, wsp, wsn, _p(a_planes))
+        o = PS_lib().ConvOpts(wsp, wsn, a_planes=_p(a_planes))
+        rc = lib.sg_conv2d_dgrad(e.h, e.stream, PS.abi_dtype(s), C.byref(d), _p(a), _p(w), bp, _p(out), flags, C.byref(o))
     return int(rc), out, st, int(tiles.value)
 
 

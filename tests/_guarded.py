@@ -1,4 +1,5 @@
-"""Guarded device operands and plain float64 references for tests/test_bandwidth_variants_gpu.py.
+"""Guarded device operands and plain float64 references for tests/test_bandwidth_variants_gpu.py and
+tests/test_batchnorm_variants_gpu.py.
 
 Every operand of a launch lives in its own uint8 arena: BAND bytes of 0xFF, the operand, BAND bytes of 0xFF.  0xFF.. is a NaN
 in fp32 and in bf16, so a read outside an operand that reaches the arithmetic poisons the result, and a write outside it changes
@@ -96,6 +97,39 @@ def close(got, ref, tol, what=""):
     return err
 
 
+def close_cols(got, ref, tol, what="", extra=None, apart=(), report=None):
+    """close() for a [..][C] tensor: |got - ref| <= tol * max|ref| + extra[c].  `extra` is a per-channel absolute allowance
+    (None: 0).  The channels listed in `apart` are compared on their own max|ref| and lend it to nobody else (a channel of zero
+    variance has invstd = 1 / sqrt(eps), thirty times everyone else's).  `report(rel)` receives the largest error / scale
+    BEFORE anything is asserted; the same number is returned."""
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
+    assert torch.isfinite(got).all(), f"{what}: non-finite values in the result"
+    C = ref.shape[-1]
+    got, ref = got.reshape(-1, C), ref.reshape(-1, C)
+    over = (got - ref).abs()
+    if extra is not None:
+        over = (over - extra.detach().cpu().double().reshape(1, C)).clamp_min(0.0)
+    rest = torch.ones(C, dtype=torch.bool)
+    groups = []
+    for c in apart:
+        rest[c] = False
+        groups.append(torch.arange(C) == c)
+    groups.append(rest)
+    worst, fails = 0.0, []
+    for sel in groups:
+        if not sel.any() or not ref.numel():
+            continue
+        scale, err = ref[:, sel].abs().max().item(), over[:, sel].max().item()
+        worst = max(worst, err / scale if scale > 0 else (0.0 if err == 0 else INF))
+        if not err <= tol * scale:
+            fails.append(f"max err {err:.3e} > {tol:.3e} * {scale:.3e} (rel {err / max(scale, 1e-300):.2e})")
+    if report is not None:
+        report(worst)
+    assert not fails, f"{what}: " + "; ".join(fails)
+    return worst
+
+
 def same_outside(after, before, sl, what=""):
     """Channels outside the written slice `sl` (last axis) keep their exact prior bits."""
     keep = torch.ones(before.shape[-1], dtype=torch.bool)
@@ -110,9 +144,12 @@ def sigmoid(v):
     return 1.0 / (1.0 + torch.exp(-v))
 
 
-def seg_plan_s(cus, rows, C, vec):
-    """The row split S of seg_plan<1> (csrc/sg_reduce.h) for one segment of `rows` rows and C channels."""
+def seg_plan(cus, rows, C, vec, wide8=False, nout=1):
+    """seg_plan<NOUT> (csrc/sg_reduce.h) for one segment of `rows` rows and C channels: V, TX, TY, gx, S, part_bytes.
+    wide8: the reduced tensor is bf16 - a lane takes 8 channels when C % 8 == 0 and NOUT <= 2."""
     V = 4 if (vec and C % 4 == 0) else 1
+    if V == 4 and wide8 and C % 8 == 0 and nout <= 2:
+        V = 8
     chunks = C // V
     tx = 1
     while tx < chunks and tx < 16:
@@ -122,11 +159,34 @@ def seg_plan_s(cus, rows, C, vec):
     S = min(-(-4 * cus // gx), -(-rows // (ty * 4)))
     if rows <= ty * 16:
         S = 1
-    return max(1, min(S, 1024))
+    S = max(1, min(S, 1024))
+    return dict(V=V, TX=tx, TY=ty, gx=gx, S=S, part_bytes=S * nout * C * 4)
+
+
+def seg_plan_s(cus, rows, C, vec, wide8=False, nout=1):
+    """The row split S of seg_plan<NOUT> (csrc/sg_reduce.h) for one segment of `rows` rows and C channels."""
+    return seg_plan(cus, rows, C, vec, wide8, nout)["S"]
 
 
 def regime(S):
     return "one" if S == 1 else ("few" if S < 32 else "many")
+
+
+def short_last_slab(rows, S):
+    """The S row slabs of seg_reduce_kernel are ceil(rows / S) long: is the last one shorter?"""
+    return S > 1 and -(-rows // S) * S != rows
+
+
+def bn_cols_grid(cus, rows, cv, unroll):
+    """bn_cols_grid (csrc/norm.hip) for cv chunks per row: (prow, b0, k) = rows per period, blocks per period (grid.x), groups of
+    `unroll` periods walked in parallel (grid.y); None where the flat kernels take the launch."""
+    g = math.gcd(256, cv)
+    b0 = cv // g
+    if b0 > 16384:
+        return None
+    prow = 256 // g
+    k = min(-(-8 * cus // b0), -(-rows // (unroll * prow)), 65535)
+    return prow, b0, max(k, 1)
 
 
 def pool_geom(H, k, s, same):
@@ -234,3 +294,69 @@ def adam_ref(w, m, v, g, lr_t, b1, b2, eps, gs):
     m = b1 * m + (1 - b1) * g
     v = b2 * v + (1 - b2) * g * g
     return w - lr_t * m / (torch.sqrt(v) + eps), m, v
+
+
+# ------------------------------------------------------------------------------ BatchNormalization / column sums (float64)
+def ulp32(v):
+    """The spacing of fp32 numbers at |v| (float64 in, float64 out)."""
+    a = v.double().abs().clamp_min(2.0 ** -126)
+    return torch.exp2(torch.floor(torch.log2(a)) - 23)
+
+
+def bn_stats_ref(x):
+    """(mean, biased variance) of x[rows][C] per channel."""
+    mean = x.mean(0)
+    return mean, ((x - mean) ** 2).mean(0)
+
+
+def bn_fwd_ref(x, gamma, beta, mm, mv, momentum, eps, relu, unbiased):
+    """Training forward: y, mean, invstd, new moving mean, new moving variance (Keras: the moving variance takes the batch
+    variance, n / (n - 1) times it with `unbiased` and more than one row)."""
+    n = x.shape[0]
+    mean, var = bn_stats_ref(x)
+    invstd = 1.0 / torch.sqrt(var + eps)
+    y = gamma * ((x - mean) * invstd) + beta
+    var_u = var * (n / (n - 1.0)) if (unbiased and n > 1) else var
+    return (torch.relu(y) if relu else y), mean, invstd, mm * momentum + mean * (1 - momentum), mv * momentum + var_u * (1 - momentum)
+
+
+def bn_apply_ref(x, gamma, beta, mean, invstd, relu):
+    y = gamma * ((x - mean) * invstd) + beta
+    return torch.relu(y) if relu else y
+
+
+def bn_bwd_ref(x, dy, gamma, mean, invstd, mask=None, dgamma=None, dbeta=None):
+    """dx, dgamma, dbeta of the training forward from the saved mean / invstd; mask: the fused ReLU's [y > 0].  With dgamma and
+    dbeta given, dx is formed from them (the apply pass on its own)."""
+    n = x.shape[0]
+    g = dy if mask is None else dy * mask
+    xhat = (x - mean) * invstd
+    if dgamma is None:
+        dgamma, dbeta = (g * xhat).sum(0), g.sum(0)
+    return gamma * invstd * (g - dbeta / n - xhat * dgamma / n), dgamma, dbeta
+
+
+def add2_bn_ref(a, b, pa, pb, relu, infer, eps, a_relu, b_relu):
+    """relu?(f(a) + f(b)); p = (mean, invstd or moving variance, gamma, beta) or None (identity, and no operand ReLU)."""
+    def f(t, p, r):
+        if p is None:
+            return t
+        mean, s, gamma, beta = p
+        u = gamma * ((t - mean) * (1.0 / torch.sqrt(s + eps) if infer else s)) + beta
+        return torch.relu(u) if r else u
+    y = f(a, pa, a_relu) + f(b, pb, b_relu)
+    return torch.relu(y) if relu else y
+
+
+def colsum_ref(dy):
+    return dy.sum(0)
+
+
+def tile_stats_ref(x, bm=128):
+    """[tiles][2][C]: per tile of bm rows (the last one ragged) the sum and the sum of squares about the tile's own mean."""
+    rows, C = x.shape
+    out = []
+    for r0 in range(0, rows, bm):
+        t = x[r0:r0 + bm]
+        out.append(torch.stack([t.sum(0), ((t - t.mean(0)) ** 2).sum(0)]))
+    return torch.stack(out)

@@ -220,6 +220,9 @@ def test_depthwise_stride1_register_window_path(engine, c, h, w, pre_relu):
 @pytest.mark.parametrize("shape,relu", [((4, 16, 16, 728), True), ((2, 9, 7, 45), False), ((16, 24), True),
                                          ((2, 64, 64, 64), True)])
 def test_batchnorm(engine, shape, relu):
+    """The layer-level round trip against the oracle.  Every kernel variant behind these entry points (vector widths, row-split
+    regimes, column / flat apply forms, offset operands), inputs with a mean far from zero and guarded operands are in
+    tests/test_batchnorm_variants_gpu.py."""
     g = torch.Generator().manual_seed(sum(shape))
     c = shape[-1]
     x = rnd(g, *shape) * 2 + 0.7

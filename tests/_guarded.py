@@ -1,5 +1,5 @@
-"""Guarded device operands and plain float64 references for tests/test_bandwidth_variants_gpu.py and
-tests/test_batchnorm_variants_gpu.py.
+"""Guarded device operands and plain float64 references for tests/test_bandwidth_variants_gpu.py,
+tests/test_batchnorm_variants_gpu.py and tests/test_depthwise_variants_gpu.py.
 
 Every operand of a launch lives in its own uint8 arena: BAND bytes of 0xFF, the operand, BAND bytes of 0xFF.  0xFF.. is a NaN
 in fp32 and in bf16, so a read outside an operand that reaches the arithmetic poisons the result, and a write outside it changes
@@ -360,3 +360,82 @@ def tile_stats_ref(x, bm=128):
         t = x[r0:r0 + bm]
         out.append(torch.stack([t.sum(0), ((t - t.mean(0)) ** 2).sum(0)]))
     return torch.stack(out)
+
+
+# ------------------------------------------------------------------------------------ depthwise convolution (float64), ld views
+def dw_geom(H, W, KH, KW, s, d, same):
+    """(Ho, Wo, pad_t, pad_b, pad_l, pad_r) of a TF 'same' / 'valid' convolution with a dilated KH x KW window."""
+    def one(n, k):
+        eff = (k - 1) * d + 1
+        if not same:
+            return (n - eff) // s + 1, 0, 0
+        o = -(-n // s)
+        total = max((o - 1) * s + eff - n, 0)
+        return o, total // 2, total - total // 2
+    Ho, pt, pb = one(H, KH)
+    Wo, pl, pr = one(W, KW)
+    return Ho, Wo, pt, pb, pl, pr
+
+
+def dw_input_ref(x, pre_relu=False, bn=None):
+    """What the window multiplies: relu?(x), or z = ((x - mean) * invstd) * gamma + beta [ReLU] with bn = (mean, invstd, gamma,
+    beta, relu).  The zero padding comes AFTER this (BN(0) != 0)."""
+    if bn is not None:
+        mean, invstd, gamma, beta, relu = bn
+        z = ((x - mean) * invstd) * gamma + beta
+        return torch.relu(z) if relu else z
+    return torch.relu(x) if pre_relu else x
+
+
+def dw_conv_ref(x, w, geom, s, d, pre_relu=False, bn=None):
+    """y[N][Ho][Wo][C] of the depthwise convolution of x[N][H][W][C] with w[KH][KW][C]: F.conv2d(groups = C) on the explicitly
+    padded tensor.  geom: dw_geom()."""
+    import torch.nn.functional as F
+    Ho, Wo, pt, pb, pl, pr = geom
+    C = x.shape[-1]
+    zp = F.pad(dw_input_ref(x, pre_relu, bn).permute(0, 3, 1, 2), (pl, pr, pt, pb))
+    y = F.conv2d(zp, w.permute(2, 0, 1).unsqueeze(1), stride=s, dilation=d, groups=C).permute(0, 2, 3, 1)
+    assert y.shape[1:3] == (Ho, Wo), (tuple(y.shape), Ho, Wo)
+    return y
+
+
+def dw_grads_ref(x, w, dy, geom, s, d, pre_relu=False, bn=None, want="dx"):
+    """dx or dw of dw_conv_ref by autograd (dx never has a BatchNormalization in front)."""
+    x = x.detach().clone().requires_grad_(want == "dx")
+    w = w.detach().clone().requires_grad_(want == "dw")
+    y = dw_conv_ref(x, w, geom, s, d, pre_relu, bn)
+    (g,) = torch.autograd.grad(y, x if want == "dx" else w, dy)
+    return g.detach()
+
+
+def bn_sums_ref(g, bsx, mean, invstd, gamma, beta, relu):
+    """(dgamma, dbeta) = (sum g * xhat, sum g) per channel, g masked by z > 0 under a fused ReLU; all [..][C] float64."""
+    C = g.shape[-1]
+    xhat = ((bsx - mean) * invstd).reshape(-1, C)
+    g = g.reshape(-1, C)
+    if relu:
+        g = g * ((xhat * gamma + beta) > 0)
+    return (g * xhat).sum(0), g.sum(0)
+
+
+def widen(t, ld, mid=0):
+    """t[..][C] as the columns [mid, mid + C) of a [pixels][ld] tensor whose other bytes are 0xFF (NaN)."""
+    C = t.shape[-1]
+    t = t.detach().cpu().reshape(-1, C)
+    wide = torch.full((t.shape[0] * ld * t.element_size(),), 0xFF, dtype=torch.uint8).view(t.dtype).reshape(t.shape[0], ld)
+    wide[:, mid:mid + C] = t
+    return wide
+
+
+def gaps_keep_prefill(wide, C, mid, what="", fill=0xFF):
+    """The columns outside [mid, mid + C) of a strided output keep every prefill byte."""
+    keep = torch.ones(wide.shape[-1], dtype=torch.bool)
+    keep[mid:mid + C] = False
+    bad = _bits(wide[:, keep]) != fill
+    assert not bad.any(), f"{what}: {int(bad.sum())} bytes of the gap columns of a strided output were overwritten"
+
+
+def untouched(o, what=""):
+    """A refused launch: every byte of the output arena keeps its prefill (bands included)."""
+    o.fetch()
+    assert torch.equal(o.after, o.before), f"{what}: a refused launch wrote into an output {o.shape}"

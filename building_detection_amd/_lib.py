@@ -85,6 +85,13 @@ class ConvCaps(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("thin", "bn_in", "up2", "bnb", "planes_in", "wgrad_planes")]
 
 
+class DwPlan(C.Structure):
+    """Mirror of `sg_dw_plan` (include/segengine.h): the plan one depthwise launch runs by (sg_dwconv2d_plan)."""
+
+    _fields_ = [(n, C.c_int) for n in ("family", "V", "RR", "lc", "HS", "nhs", "count", "gx", "gy", "S", "seg_V", "seg_TX", "seg_gx",
+                                       "seg_S", "bn", "res", "sums")] + [("ws_bytes", C.c_size_t)]
+
+
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 _op = C.POINTER(ConvOpts)
 _dp = C.POINTER(ConvDesc)
@@ -122,6 +129,7 @@ _SIGNATURES = {
     "sg_dwconv2d_dgrad_bnsums_ws_bytes": (_sz, [_vp, _dp]),
     "sg_dwconv2d_wgrad_ws_bytes": (_sz, [_vp, _dp]),
     "sg_dwconv2d_wgrad": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _i, C.POINTER(BnIn), _vp, _sz]),
+    "sg_dwconv2d_plan": (_i, [_vp, _i, _dp, _i, _i, _i, C.POINTER(DwPlan)]),
     "sg_dense_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
     "sg_bn_ws_bytes": (_sz, [_vp, _i64, _i]),
     "sg_bn_train_fwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _sz]),

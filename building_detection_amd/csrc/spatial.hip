@@ -1,6 +1,8 @@
 // HBM-bound spatial kernels of the hot path (NHWC, channels innermost so every access is a coalesced run of
 // 16-byte channel chunks): depthwise 3x3 (SeparableConv2D's first half) forward / dgrad / wgrad, max / average
 // pooling, nearest and bilinear up-sampling.
+#include <algorithm>
+#include <initializer_list>
 #include "sg_reduce.h"
 
 namespace {
@@ -165,7 +167,7 @@ struct DwRunParams {
   const float* __restrict__ bs_beta = nullptr;
   float* bs_part = nullptr;
   int bs_ld = 0, bs_relu = 0;
-  int lc;                          // lanes per run along the channels (set by launch_dw_run)
+  int lc;                          // lanes per run along the channels (plan_dw)
   int runs_per_row;                // W / 4
   int64_t nruns;                   // N * H * runs_per_row
   FastDiv fd_rpr, fd_h;
@@ -476,7 +478,7 @@ __global__ __launch_bounds__(256, OCC2 ? 2 : 1) __attribute__((amdgpu_waves_per_
       const unsigned xoff0 = (xpix0 * x_ld + c) * EB, goff0 = (xpix0 * y_ld + c) * EB;
       // Offsets are sums, never selects around a load (a select feeding a load became control flow, and with more than one
       // basic block per step the FMAs were sunk out of the steps altogether): a column outside the image adds 2^30, a row
-      // outside it sets bit 31 - either way the offset is beyond num_records (< 2^30, dw_strip_ok) and the load returns 0.
+      // outside it sets bit 31 - either way the offset is beyond num_records (< 2^30, dw_wgrad_strips_ok) and the load returns 0.
       unsigned coff[6];
 #pragma unroll
       for (int b = 0; b < 6; ++b) coff[b] = (unsigned)((b - 1) * x_ld * EB);
@@ -520,7 +522,7 @@ __global__ __launch_bounds__(256, OCC2 ? 2 : 1) __attribute__((amdgpu_waves_per_
             for (int e = 0; e < 4; ++e) acc[ta * 3 + b][e] = fmaf(v[k + b][e], g[k][e], acc[ta * 3 + b][e]);
       };
       // four x-row buffers and two dy-row buffers whose roles rotate with the (unrolled) row step: no register copies - a
-      // copy of a row that is still in flight would be a use and wait for it (HS and H are multiples of 4: dw_strip_ok)
+      // copy of a row that is still in flight would be a use and wait for it (HS and H are multiples of 4: dw_wgrad_strips_ok)
       raw_t X[4][6], G[2][4];
       load_x(h0 - 1, X[0]);
       load_x(h0, X[1]);
@@ -573,57 +575,7 @@ __global__ __launch_bounds__(256, OCC2 ? 2 : 1) __attribute__((amdgpu_waves_per_
   }
 }
 
-struct DwStripPlan {
-  int HS, nhs, nstrips, gx, S;
-  size_t part_bytes;
-};
-
-inline DwStripPlan dw_strip_plan(int num_cus, const sg_conv_desc* d) {
-  DwStripPlan pl;
-  pl.HS = d->H >= 128 ? 16 : (d->H >= 16 ? 8 : d->H);   // multiples of 4 (dw_strip_ok: H % 4 == 0); the last band may be 4 short
-  pl.nhs = (int)sg_cdiv(d->H, pl.HS);
-  pl.nstrips = d->N * pl.nhs * (d->W / 4);
-  pl.gx = (int)sg_cdiv(d->Cin / 4, 16);
-  int64_t S = sg_cdiv(pl.nstrips, 16);
-  const int64_t cap = sg_cdiv((int64_t)4 * num_cus, pl.gx);
-  if (S > cap) S = cap;
-  if (S > 256) S = 256;  // few-channel maps: the finalize adds the S partial rows with 4 lanes per channel (1024 rows of a
-                         // 64-channel map took longer than the strips themselves); a lane walks several strips instead
-  if (S < 1) S = 1;
-  pl.S = (int)S;
-  pl.part_bytes = (size_t)pl.S * 9 * d->Cin * sizeof(float);
-  return pl;
-}
-
-inline bool dw_run_ok(const sg_conv_desc* d) {
-  return d->KH == 3 && d->KW == 3 && d->stride == 1 && d->dilation == 1 && d->pad_t == 1 && d->pad_l == 1 &&
-         d->Ho == d->H && d->Wo == d->W && (d->W % 4 == 0) && (d->Cin % 4 == 0);
-}
-
-inline bool dw_strip_ok(const sg_conv_desc* d) {
-  const int on = sg_switch<SW_DW_STRIP>();
-  const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-  const int64_t pix = (int64_t)d->N * d->H * d->W;
-  // byte offsets are 32-bit buffer offsets in which bit 30 / bit 31 mark a column / row outside the image: tensors below 1 GiB
-  return on && dw_run_ok(d) && d->H % 4 == 0 && pix * (xl > yl ? xl : yl) * 4 < (1ll << 30);
-}
-
-// Rows per run, measured (profiles/r01_bw_census.txt): the stencil kernels take 2 rows; the kernel-gradient reduction loses
-// more from the shrinking number of runs than it gains on small maps and takes 2 rows only from 64x64 up (64x64x728:
-// 248 -> 157 us).  SG_DW_RR = 1 / 2 forces a value.
-// (Four rows per run are gone: the four-row stencil window ran at the 168-register cap with 47 - 73 spilled registers - three
-// alternating repetitions on one box: 75.90 -> 75.04 ms per step without it, profiles/r04_ab_runs.txt - and the reduction
-// went 51 -> 65 us with it.  DESIGN.md, retired.)
-inline int dw_rows_per_run(int H, int64_t pixels, bool wgrad) {
-  const int force = sg_switch<SW_DW_RR>();  // A/B switch: 1 or 2
-  const bool small = pixels <= 32768;
-  const int want = force ? force : (wgrad ? (small ? 1 : 2) : 2);
-  return (want >= 2 && H % 2 == 0) ? 2 : 1;
-}
-
-constexpr int DW_SUMS_MAX_ROWS = 1024;
-
-// ---- the stencil as column strips (round 4; maps of 64 rows and more - dw_fstrip_ok; SG_DW_FSTRIP=0 restores the run kernel) ------
+// ---- the stencil as column strips (round 4; maps of 64 rows and more - dw_stencil_strips_ok; SG_DW_FSTRIP=0 restores the run kernel) ------
 // dw_s1_run_kernel fetches its window once per run of RR x 4 outputs: 3 loads of 16 bytes per output chunk at RR = 2 (the
 // four-row window needs more registers than three workgroups per CU leave), and was measured at 38 us (forward with the
 // BatchNormalization in the gather) / 47 us (dgrad with the BatchNormalization sums) on the 47.7 MB middle-flow tensors that a
@@ -823,125 +775,197 @@ __global__ __launch_bounds__(256, 2) void dw_strip_kernel(const DwRunParams<T> p
   }
 }
 
-template <typename T>
-inline bool dw_fstrip_ok(const DwRunParams<T>& p) {
+// ---- who chooses the depthwise kernel: plan_dw() --------------------------------------------------------------------------------
+// One DwPlan per launch, a pure function of (CU count, element size, descriptor, direction, operands aligned, sums requested) and
+// the four SG_DW_* switches.  sg_dwconv2d_fwd / _dgrad / _wgrad refuse, fill their parameters and launch from it, the two workspace
+// queries add its bytes up and sg_dwconv2d_plan hands it out (include/segengine.h: sg_dw_plan, the fields), so a query and a launch
+// cannot disagree (tests/test_depthwise_variants_gpu.py compares every launch's plan with its own mirror of the rules below).
+// The stencil directions and the filter gradient have their own rules where both have one, each set by its own measurement:
+//   strip height   stencil: 16 rows from H >= 64 (profiles/r04_dw_fstrip_ab.txt); filter gradient: 16 rows from H >= 128, 8 below
+//   1 GiB test     stencil: the INPUT's bytes at the storage's element size (in_ld: x_ld forward, y_ld dgrad); filter gradient: the
+//                  larger of x_ld / y_ld at 4 bytes an element whatever the storage
+//   grid cap       stencil: 16384 / gx workgroup rows; filter gradient: 4 * num_cus / gx partial rows and at most 256
+//   rows per run   stencil: 2; run reducer: 2 only above 32768 pixels (profiles/r01_bw_census.txt)
+struct DwPlan : sg_dw_plan { SegPlan seg; };   // seg: the segment reducer's launch where it runs (seg_V .. seg_S are its copy)
+
+constexpr int DW_SUMS_MAX_ROWS = 1024;   // partial rows of the BatchNormalization sums that the finalize launch adds per channel
+
+inline bool dw_run_ok(const sg_conv_desc* d) {
+  return d->KH == 3 && d->KW == 3 && d->stride == 1 && d->dilation == 1 && d->pad_t == 1 && d->pad_l == 1 &&
+         d->Ho == d->H && d->Wo == d->W && (d->W % 4 == 0) && (d->Cin % 4 == 0);
+}
+
+// Rows per run, measured (profiles/r01_bw_census.txt): the stencil kernels take 2 rows; the kernel-gradient reduction loses
+// more from the shrinking number of runs than it gains on small maps and takes 2 rows only from 64x64 up (64x64x728:
+// 248 -> 157 us).  SG_DW_RR = 1 / 2 forces a value.
+// (Four rows per run are gone: the four-row stencil window ran at the 168-register cap with 47 - 73 spilled registers - three
+// alternating repetitions on one box: 75.90 -> 75.04 ms per step without it, profiles/r04_ab_runs.txt - and the reduction
+// went 51 -> 65 us with it.  DESIGN.md, retired.)
+inline int dw_rows_per_run(int H, int64_t pixels, bool wgrad) {
+  const int force = sg_switch<SW_DW_RR>();  // A/B switch: 1 or 2
+  const bool small = pixels <= 32768;
+  const int want = force ? force : (wgrad ? (small ? 1 : 2) : 2);
+  return (want >= 2 && H % 2 == 0) ? 2 : 1;
+}
+
+// dw_strip_kernel instead of dw_s1_run_kernel (dw_run_ok maps; in_ld: x_ld forward, y_ld dgrad)
+inline bool dw_stencil_strips_ok(const sg_conv_desc* d, int in_ld, int esize) {
   // SG_DW_FSTRIP: 0 never, 1 (default) maps of 64 rows and more, 2 every map.  Measured (profiles/r04_dw_fstrip_ab.txt): 64x64x256
   // 34.0 -> 30.7 us, 128x128x128 62.0 -> 54.9, 256x256x64 115.0 -> 106.1 (strips of 16 rows); the 32x32 maps of the middle flow run
   // no faster (27.2 -> 31.8 us alone, +-0.1 ms in the step at any strip height): with 1.4 waves per SIMD the strips are
   // latency-bound there, and the run kernel was not load-issue bound to begin with (76 % of copy speed).
   const int on = sg_switch<SW_DW_FSTRIP>();
-  const int64_t pix = (int64_t)p.N * p.H * p.W;
-  if (!on || (on == 1 && p.H < 64)) return false;
+  const int64_t pix = (int64_t)d->N * d->H * d->W;
+  if (!on || (on == 1 && d->H < 64)) return false;
   // byte offsets are 32-bit buffer offsets in which bit 30 / bit 31 mark a column / row outside the image: inputs below 1 GiB
-  return p.H % 4 == 0 && p.W % 4 == 0 && pix * p.in_ld * (int64_t)sizeof(T) < (1ll << 30);
+  return d->H % 4 == 0 && d->W % 4 == 0 && pix * in_ld * (int64_t)esize < (1ll << 30);
 }
 
-template <typename T>
-int launch_dw_strip(const DwRunParams<T>& p, hipStream_t st, int* sums_rows) {
+// dw_wgrad_strip_kernel instead of the run reducer
+inline bool dw_wgrad_strips_ok(const sg_conv_desc* d) {
+  const int on = sg_switch<SW_DW_STRIP>();
+  const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
+  const int64_t pix = (int64_t)d->N * d->H * d->W;
+  // byte offsets are 32-bit buffer offsets in which bit 30 / bit 31 mark a column / row outside the image: tensors below 1 GiB
+  return on && dw_run_ok(d) && d->H % 4 == 0 && pix * (xl > yl ? xl : yl) * 4 < (1ll << 30);
+}
+
+// the stencil's grid: gy rows of workgroups over `per_wg` runs / strips each; with sums every row writes one partial row
+inline void plan_dw_stencil_grid(DwPlan& pl, int per_wg, bool sums) {
+  int64_t gy = sg_cdiv(pl.count, per_wg);
+  const int64_t cap = sg_cdiv(16384, pl.gx);
+  if (gy > cap) gy = cap;
+  if (gy < 1) gy = 1;
+  if (sums && gy > DW_SUMS_MAX_ROWS) gy = DW_SUMS_MAX_ROWS;
+  pl.gy = (int)gy;
+}
+
+inline void plan_dw_stencil_run(DwPlan& pl, const sg_conv_desc* d, bool sums) {
+  pl.family = SG_DWK_RUN;
+  pl.RR = dw_rows_per_run(d->H, (int64_t)d->N * d->H * d->W, false);
+  pl.count = d->N * (d->H / pl.RR) * (d->W / 4);
+  pl.lc = 1;
+  while (pl.lc < d->Cin / 4 && pl.lc < 64) pl.lc <<= 1;
+  pl.gx = (int)sg_cdiv(d->Cin / 4, pl.lc);
+  plan_dw_stencil_grid(pl, 256 / pl.lc, sums);
+}
+
+inline void plan_dw_stencil_strip(DwPlan& pl, const sg_conv_desc* d, bool sums) {
   const int hs_force = sg_switch<SW_DW_FSTRIP_HS>();
-  DwStripGeom<T> g;
-  g.HS = hs_force > 0 ? hs_force : (p.H >= 64 ? 16 : (p.H >= 16 ? 8 : p.H));
-  if (g.HS % 4 != 0 || g.HS > p.H) g.HS = 4;
-  const int nhs = (int)sg_cdiv(p.H, g.HS);
-  g.nstrips = p.N * nhs * (p.W / 4);
-  g.in_bytes = (unsigned)((int64_t)p.N * p.H * p.W * p.in_ld * (int64_t)sizeof(T));
-  g.fd_q = make_fastdiv((uint32_t)(p.W / 4));
-  g.fd_hs = make_fastdiv((uint32_t)nhs);
-  const unsigned gx = (unsigned)sg_cdiv(p.C / 4, 16);
-  int64_t gy = sg_cdiv(g.nstrips, 16);
-  const int64_t cap = sg_cdiv(16384, gx);
-  if (gy > cap) gy = cap;
-  if (gy < 1) gy = 1;
-  if (p.bs_part && gy > DW_SUMS_MAX_ROWS) gy = DW_SUMS_MAX_ROWS;
-  const dim3 grid(gx, (unsigned)gy);
-  if (p.bs_part) {
-    if (p.mask) hipLaunchKernelGGL((dw_strip_kernel<T, false, true, false, true>), grid, dim3(256), 0, st, p, g);
-    else hipLaunchKernelGGL((dw_strip_kernel<T, false, false, false, true>), grid, dim3(256), 0, st, p, g);
-    SG_LAUNCH_CHECK("dw_strip_kernel<SUMS>");
-    if (sums_rows) *sums_rows = (int)gy;
-    return 0;
-  }
-  if (p.bn_gamma) {
-    if (p.relu_in) hipLaunchKernelGGL((dw_strip_kernel<T, true, false, true, false>), grid, dim3(256), 0, st, p, g);
-    else hipLaunchKernelGGL((dw_strip_kernel<T, false, false, true, false>), grid, dim3(256), 0, st, p, g);
-  } else if (p.mask) {
-    hipLaunchKernelGGL((dw_strip_kernel<T, false, true, false, false>), grid, dim3(256), 0, st, p, g);
-  } else if (p.relu_in) {
-    hipLaunchKernelGGL((dw_strip_kernel<T, true, false, false, false>), grid, dim3(256), 0, st, p, g);
-  } else {
-    hipLaunchKernelGGL((dw_strip_kernel<T, false, false, false, false>), grid, dim3(256), 0, st, p, g);
-  }
-  SG_LAUNCH_CHECK("dw_strip_kernel");
-  return 0;
+  pl.family = SG_DWK_STRIP;
+  pl.HS = hs_force > 0 ? hs_force : (d->H >= 64 ? 16 : (d->H >= 16 ? 8 : d->H));
+  if (pl.HS % 4 != 0 || pl.HS > d->H) pl.HS = 4;
+  pl.nhs = (int)sg_cdiv(d->H, pl.HS);
+  pl.count = d->N * pl.nhs * (d->W / 4);
+  pl.gx = (int)sg_cdiv(d->Cin / 4, 16);
+  plan_dw_stencil_grid(pl, 16, sums);
 }
 
+inline void plan_dw_wgrad_strip(DwPlan& pl, int num_cus, const sg_conv_desc* d) {
+  pl.family = SG_DWK_STRIP;
+  pl.HS = d->H >= 128 ? 16 : (d->H >= 16 ? 8 : d->H);   // multiples of 4 (dw_wgrad_strips_ok: H % 4 == 0); the last band may be 4 short
+  pl.nhs = (int)sg_cdiv(d->H, pl.HS);
+  pl.count = d->N * pl.nhs * (d->W / 4);
+  pl.gx = (int)sg_cdiv(d->Cin / 4, 16);
+  int64_t S = sg_cdiv(pl.count, 16);
+  const int64_t cap = sg_cdiv((int64_t)4 * num_cus, pl.gx);
+  if (S > cap) S = cap;
+  if (S > 256) S = 256;  // few-channel maps: the finalize adds the S partial rows with 4 lanes per channel (1024 rows of a
+                         // 64-channel map took longer than the strips themselves); a lane walks several strips instead
+  if (S < 1) S = 1;
+  pl.S = (int)S;
+  pl.ws_bytes = (size_t)pl.S * 9 * d->Cin * sizeof(float);
+}
+
+// the filter gradient on the segment reducer: DwWgradOp over the pixels (SG_DWK_GENERIC), DwWgradRunOp over the runs (SG_DWK_RUN)
+inline void plan_dw_wgrad_seg(DwPlan& pl, int num_cus, int family, int64_t rows, int C, bool vec) {
+  pl.family = family;
+  pl.seg = seg_plan<9>(num_cus, 1, rows, C, vec);
+  pl.seg_V = pl.seg.V; pl.seg_TX = pl.seg.TX; pl.seg_gx = pl.seg.gx; pl.seg_S = pl.S = pl.seg.S;
+  pl.ws_bytes = pl.seg.part_bytes;
+}
+
+inline DwPlan plan_dw(int num_cus, int esize, const sg_conv_desc* d, int dir, bool aligned, bool sums) {
+  DwPlan pl = {};
+  const int C = d->Cin, xl = d->x_ld ? d->x_ld : C, yl = d->y_ld ? d->y_ld : d->Cout;
+  const bool vec = aligned && C % 4 == 0 && xl % 4 == 0 && yl % 4 == 0;
+  const bool fast = vec && dw_run_ok(d);   // only the stride-1 3x3 kernels on 16-byte chunks take a fused operand
+  pl.V = vec ? 4 : 1;
+  if (dir == SG_DW_WGRAD) {
+    const int64_t rows = (int64_t)d->N * d->Ho * d->Wo;
+    pl.bn = fast;
+    if (fast && dw_wgrad_strips_ok(d)) {
+      plan_dw_wgrad_strip(pl, num_cus, d);
+    } else if (fast) {
+      pl.RR = dw_rows_per_run(d->H, rows, true);
+      pl.count = (int)(rows / (4 * pl.RR));
+      plan_dw_wgrad_seg(pl, num_cus, SG_DWK_RUN, pl.count, C, true);
+    } else plan_dw_wgrad_seg(pl, num_cus, SG_DWK_GENERIC, rows, C, vec);
+    return pl;
+  }
+  if (dir == SG_DW_FWD) pl.bn = fast;
+  else pl.res = pl.sums = fast;
+  if (!fast) {
+    pl.family = SG_DWK_GENERIC; pl.gy = 1;
+    pl.gx = (int)ew_blocks((int64_t)d->N * (dir == SG_DW_FWD ? d->Ho * d->Wo : d->H * d->W) * (C / pl.V));
+  } else if (dw_stencil_strips_ok(d, dir == SG_DW_FWD ? xl : yl, esize)) plan_dw_stencil_strip(pl, d, sums);
+  else plan_dw_stencil_run(pl, d, sums);
+  if (dir == SG_DW_DGRAD && sums) {
+    pl.S = fast ? pl.gy : 0;
+    pl.ws_bytes = (size_t)DW_SUMS_MAX_ROWS * 2 * (size_t)C * sizeof(float);   // the row cap, whatever gy: known without the grid
+  }
+  return pl;
+}
+
+// "operands aligned" of plan_dw: every tensor the call passes (null: not passed) starts on a 16-byte boundary
+inline bool dw_aligned(std::initializer_list<const void*> ps) { return std::all_of(ps.begin(), ps.end(), sg_aligned16); }
+
+// The seven <RELU, MASK, BN, SUMS> forms of the stencil an entry point can ask for, named once: dw_s1_run_kernel<1 | 2> and
+// dw_strip_kernel are instantiated for these and no others (the forward never has a mask or sums, the dgrad never relu_in or bn).
+enum DwForm { DW_PLAIN, DW_RELU, DW_BN, DW_BN_RELU, DW_MASK, DW_SUMS, DW_MASK_SUMS };
+constexpr std::true_type dw_y{};
+constexpr std::false_type dw_n{};
+
+template <class F>
+inline void dw_with_form(DwForm form, F&& fn) {
+  switch (form) {   //                   RELU  MASK  BN    SUMS
+    case DW_PLAIN:     return fn(dw_n, dw_n, dw_n, dw_n);
+    case DW_RELU:      return fn(dw_y, dw_n, dw_n, dw_n);
+    case DW_BN:        return fn(dw_n, dw_n, dw_y, dw_n);
+    case DW_BN_RELU:   return fn(dw_y, dw_n, dw_y, dw_n);
+    case DW_MASK:      return fn(dw_n, dw_y, dw_n, dw_n);
+    case DW_SUMS:      return fn(dw_n, dw_n, dw_n, dw_y);
+    case DW_MASK_SUMS: return fn(dw_n, dw_y, dw_n, dw_y);
+  }
+}
+
+// the four <PRE, BN> forms of the two filter-gradient kernels
+template <class F>
+inline auto dw_with_pre_bn(bool pre, bool bn, F&& fn) {
+  if (bn) return pre ? fn(dw_y, dw_y) : fn(dw_n, dw_y);
+  return pre ? fn(dw_y, dw_n) : fn(dw_n, dw_n);
+}
+
+// launch what the plan says: dw_s1_run_kernel<RR> or dw_strip_kernel in `form`, on the operands in p and the plan's geometry
 template <typename T>
-int launch_dw_run(const DwRunParams<T>& p_in, hipStream_t st, int* sums_rows = nullptr) {
-  DwRunParams<T> p = p_in;
-  if (dw_fstrip_ok(p)) {
-    if (p.bs_part && (p.relu_in || p.bn_gamma)) {
-      sg_set_error("dw_s1_run: BatchNormalization sums together with relu_in / a fused BatchNormalization");
-      return SG_EINVAL;
-    }
-    if (p.mask && (p.relu_in || p.bn_gamma)) {
-      sg_set_error("dw_s1_run: mask together with relu_in / a fused BatchNormalization");
-      return SG_EINVAL;
-    }
-    return launch_dw_strip(p, st, sums_rows);
+int launch_dw_stencil(const DwPlan& pl, DwForm form, const sg_conv_desc* d, DwRunParams<T> p, hipStream_t st) {
+  p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->Cin;
+  p.lc = pl.lc; p.runs_per_row = d->W / 4; p.nruns = pl.count;
+  p.fd_rpr = make_fastdiv((uint32_t)p.runs_per_row); p.fd_h = make_fastdiv((uint32_t)(pl.RR ? d->H / pl.RR : d->H));
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+  DwStripGeom<T> g = {};
+  if (pl.family == SG_DWK_STRIP) {
+    g.HS = pl.HS; g.nstrips = pl.count;
+    g.in_bytes = (unsigned)((int64_t)p.N * p.H * p.W * p.in_ld * (int64_t)sizeof(T));
+    g.fd_q = make_fastdiv((uint32_t)(p.W / 4)); g.fd_hs = make_fastdiv((uint32_t)pl.nhs);
   }
-  const int rr = dw_rows_per_run(p.H, (int64_t)p.N * p.H * p.W, false);
-  p.nruns = (int64_t)p.N * (p.H / rr) * p.runs_per_row;
-  p.fd_h = make_fastdiv((uint32_t)(p.H / rr));
-  int lc = 1;
-  while (lc < p.C / 4 && lc < 64) lc <<= 1;
-  p.lc = lc;
-  const unsigned gx = (unsigned)sg_cdiv(p.C / 4, lc);
-  int64_t gy = sg_cdiv(p.nruns, 256 / lc);
-  const int64_t cap = sg_cdiv(16384, gx);
-  if (gy > cap) gy = cap;
-  if (gy < 1) gy = 1;
-  if (p.bs_part && gy > DW_SUMS_MAX_ROWS) gy = DW_SUMS_MAX_ROWS;   // partial rows the finalize launch adds per channel
-  const dim3 grid(gx, (unsigned)gy);
-  if (p.bs_part) {
-    if (p.relu_in || p.bn_gamma) {
-      sg_set_error("dw_s1_run: BatchNormalization sums together with relu_in / a fused BatchNormalization");
-      return SG_EINVAL;
-    }
-#define SG_DW_RUN_SUMS(RR_)                                                                                             \
-  do {                                                                                                                  \
-    if (p.mask) hipLaunchKernelGGL((dw_s1_run_kernel<RR_, T, false, true, false, true>), grid, dim3(256), 0, st, p);    \
-    else hipLaunchKernelGGL((dw_s1_run_kernel<RR_, T, false, false, false, true>), grid, dim3(256), 0, st, p);          \
-  } while (0)
-    if (rr == 2) SG_DW_RUN_SUMS(2);
-    else SG_DW_RUN_SUMS(1);
-#undef SG_DW_RUN_SUMS
-    SG_LAUNCH_CHECK("dw_s1_run_kernel<SUMS>");
-    if (sums_rows) *sums_rows = (int)gy;   // the number of partial rows written
-    return 0;
-  }
-#define SG_DW_RUN(RR_)                                                                                                  \
-  do {                                                                                                                  \
-    if (p.mask) hipLaunchKernelGGL((dw_s1_run_kernel<RR_, T, false, true>), grid, dim3(256), 0, st, p);                 \
-    else if (p.relu_in) hipLaunchKernelGGL((dw_s1_run_kernel<RR_, T, true, false>), grid, dim3(256), 0, st, p);         \
-    else hipLaunchKernelGGL((dw_s1_run_kernel<RR_, T, false, false>), grid, dim3(256), 0, st, p);                       \
-  } while (0)
-  if (p.mask && (p.relu_in || p.bn_gamma)) {
-    sg_set_error("dw_s1_run: mask together with relu_in / a fused BatchNormalization");
-    return SG_EINVAL;
-  }
-#define SG_DW_RUN_BN(RR_)                                                                                               \
-  do {                                                                                                                  \
-    if (p.relu_in) hipLaunchKernelGGL((dw_s1_run_kernel<RR_, T, true, false, true>), grid, dim3(256), 0, st, p);        \
-    else hipLaunchKernelGGL((dw_s1_run_kernel<RR_, T, false, false, true>), grid, dim3(256), 0, st, p);                 \
-  } while (0)
-  if (p.bn_gamma) {
-    if (rr == 2) SG_DW_RUN_BN(2);
-    else SG_DW_RUN_BN(1);
-  } else if (rr == 2) SG_DW_RUN(2);
-  else SG_DW_RUN(1);
-#undef SG_DW_RUN_BN
-#undef SG_DW_RUN
-  SG_LAUNCH_CHECK("dw_s1_run_kernel");
+  dw_with_form(form, [&](auto relu, auto mask, auto bn, auto sums) {
+    constexpr bool RELU = decltype(relu)::value, MASK = decltype(mask)::value, BN = decltype(bn)::value, SUMS = decltype(sums)::value;
+    if (pl.family == SG_DWK_STRIP) hipLaunchKernelGGL((dw_strip_kernel<T, RELU, MASK, BN, SUMS>), grid, dim3(256), 0, st, p, g);
+    else if (pl.RR == 2) hipLaunchKernelGGL((dw_s1_run_kernel<2, T, RELU, MASK, BN, SUMS>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((dw_s1_run_kernel<1, T, RELU, MASK, BN, SUMS>), grid, dim3(256), 0, st, p);
+  });
+  SG_LAUNCH_CHECK(pl.family == SG_DWK_STRIP ? "dw_strip_kernel" : "dw_s1_run_kernel");
   return 0;
 }
 
@@ -1480,6 +1504,8 @@ int dw_check(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, const char* wh
   return 0;
 }
 
+inline int dw_esize(int dtype) { return dtype == SG_BF16 ? 2 : 4; }
+
 template <typename T>
 void dw_fill(DwParams<T>& p, const sg_conv_desc* d) {
   p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.KH = d->KH; p.KW = d->KW;
@@ -1492,50 +1518,58 @@ void dw_fill(DwParams<T>& p, const sg_conv_desc* d) {
 
 extern "C" {
 
+int sg_dwconv2d_plan(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int direction, int aligned, int sums, sg_dw_plan* out) {
+  SG_CHECK_ARG(out, "sg_dwconv2d_plan: null out");
+  *out = sg_dw_plan{};
+  SG_CHECK_ARG(direction >= SG_DW_FWD && direction <= SG_DW_WGRAD && (!sums || direction == SG_DW_DGRAD),
+               "sg_dwconv2d_plan: bad direction / sums with another direction than the dgrad");
+  int rc = dw_check(ctx, dtype, d, "sg_dwconv2d_plan");
+  if (rc) return rc;
+  SG_CHECK_ARG(direction != SG_DW_WGRAD || (d->KH == 3 && d->KW == 3), "sg_dwconv2d_plan: only 3x3 depthwise kernels have a filter gradient");
+  *out = plan_dw(ctx->num_cus, dw_esize(dtype), d, direction, aligned != 0, sums != 0);
+  return 0;
+}
+
 int sg_dwconv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w, void* y,
                     int pre_relu, const sg_bn_in* bn) {
   int rc = dw_check(ctx, dtype, d, "sg_dwconv2d_fwd");
   if (rc) return rc;
   SG_CHECK_ARG(x && w && y, "sg_dwconv2d_fwd: null tensor");
-  const void *bn_gamma = nullptr, *bn_beta = nullptr, *bn_mean = nullptr, *bn_invstd = nullptr;
   if (bn) {
     SG_CHECK_ARG(!pre_relu && !bn->infer, "sg_dwconv2d_fwd: bn with pre_relu (bn->relu has that role) / an inference-mode bn");
     SG_CHECK_ARG(bn->gamma && bn->beta && bn->mean && bn->invstd, "sg_dwconv2d_fwd: bn with a null BatchNormalization parameter");
-    bn_gamma = bn->gamma; bn_beta = bn->beta; bn_mean = bn->mean; bn_invstd = bn->invstd;
     pre_relu = bn->relu;
-    const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-    if (!((d->Cin % 4 == 0) && (xl % 4 == 0) && (yl % 4 == 0) && sg_aligned16(x) && sg_aligned16(w) && sg_aligned16(y) &&
-          sg_aligned16(bn_gamma) && sg_aligned16(bn_beta) && sg_aligned16(bn_mean) && sg_aligned16(bn_invstd) && dw_run_ok(d))) {
-      sg_set_error("sg_dwconv2d_fwd: bn, but only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned) fuse the "
-                   "BatchNormalization; materialise it instead");
-      return SG_EUNSUPPORTED;
-    }
+  }
+  const sg_bn_in b = bn ? *bn : sg_bn_in{};   // all-null without bn
+  const DwPlan pl = plan_dw(ctx->num_cus, dw_esize(dtype), d, SG_DW_FWD,
+                            dw_aligned({x, w, y, b.gamma, b.beta, b.mean, b.invstd}), false);
+  if (bn && !pl.bn) {
+    sg_set_error("sg_dwconv2d_fwd: bn, but only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned) fuse the "
+                 "BatchNormalization; materialise it instead");
+    return SG_EUNSUPPORTED;
   }
   SG_DTYPE_SWITCH(dtype, "sg_dwconv2d_fwd", {
+    if (pl.family != SG_DWK_GENERIC) {
+      DwRunParams<T> r;
+      r.in = (const T*)x; r.w = (const float*)w; r.mask = nullptr; r.res = nullptr; r.out = (T*)y;
+      r.bn_gamma = (const float*)b.gamma; r.bn_beta = (const float*)b.beta; r.bn_mean = (const float*)b.mean; r.bn_invstd = (const float*)b.invstd;
+      r.in_ld = d->x_ld ? d->x_ld : d->Cin; r.out_ld = d->y_ld ? d->y_ld : d->Cout; r.mask_ld = 0;
+      r.relu_in = pre_relu; r.flip = 0;
+      // never a mask or sums here (DW_MASK* / DW_SUMS are the dgrad's): pre_relu with bn is refused above, bn->relu takes its place
+      return launch_dw_stencil(pl, bn ? (pre_relu ? DW_BN_RELU : DW_BN) : (pre_relu ? DW_RELU : DW_PLAIN), d, r, (hipStream_t)stream);
+    }
     DwParams<T> p;
     dw_fill(p, d);
     p.x = (const T*)x; p.w = (const float*)w; p.dy = nullptr; p.out = (T*)y; p.pre_relu = pre_relu;
-    const bool vec = (p.C % 4 == 0) && (p.x_ld % 4 == 0) && (p.y_ld % 4 == 0) && sg_aligned16(x) && sg_aligned16(w) && sg_aligned16(y);
-    if (vec && dw_run_ok(d)) {
-      DwRunParams<T> r;
-      r.in = (const T*)x; r.w = (const float*)w; r.mask = nullptr; r.res = nullptr; r.out = (T*)y;
-      r.bn_gamma = (const float*)bn_gamma; r.bn_beta = (const float*)bn_beta; r.bn_mean = (const float*)bn_mean; r.bn_invstd = (const float*)bn_invstd;
-      r.N = d->N; r.H = d->H; r.W = d->W; r.C = p.C; r.in_ld = p.x_ld; r.out_ld = p.y_ld; r.mask_ld = 0;
-      r.relu_in = pre_relu; r.flip = 0; r.runs_per_row = d->W / 4; r.nruns = (int64_t)d->N * d->H * r.runs_per_row;
-      r.fd_rpr = make_fastdiv((uint32_t)r.runs_per_row); r.fd_h = make_fastdiv((uint32_t)d->H);
-      return launch_dw_run(r, (hipStream_t)stream);
-    }
-    const int V = vec ? 4 : 1;
-    p.fd_cv = make_fastdiv((uint32_t)(p.C / V)); p.fd_w = make_fastdiv((uint32_t)p.Wo); p.fd_h = make_fastdiv((uint32_t)p.Ho);
-    const unsigned blocks = ew_blocks((int64_t)p.N * p.Ho * p.Wo * (p.C / V));
-    if (vec) hipLaunchKernelGGL((dw_fwd_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((dw_fwd_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    p.fd_cv = make_fastdiv((uint32_t)(p.C / pl.V)); p.fd_w = make_fastdiv((uint32_t)p.Wo); p.fd_h = make_fastdiv((uint32_t)p.Ho);
+    if (pl.V == 4) hipLaunchKernelGGL((dw_fwd_kernel<4, T>), dim3((unsigned)pl.gx), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((dw_fwd_kernel<1, T>), dim3((unsigned)pl.gx), dim3(256), 0, (hipStream_t)stream, p);
   });
   SG_LAUNCH_CHECK("dw_fwd_kernel");
   return 0;
 }
 
-// second stage of the BatchNormalization sums written by dw_s1_run_kernel<SUMS>: seg_finalize_kernel adds the partial rows in
+// second stage of the BatchNormalization sums written by the stencil's SUMS forms: seg_finalize_kernel adds the partial rows in
 // fp64 (fixed order) and hands the two totals of a channel to this op
 struct BnSumsFinalOp {
   static constexpr int NOUT = 2;
@@ -1547,9 +1581,10 @@ struct BnSumsFinalOp {
   }
 };
 
+// what a launch with sums requires (the plan's ws_bytes; alignment and geometry do not enter it) and 256 bytes of slack
 size_t sg_dwconv2d_dgrad_bnsums_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d) {
   if (!ctx || !d) return 0;
-  return (size_t)DW_SUMS_MAX_ROWS * 2 * (size_t)d->Cin * sizeof(float) + 256;
+  return plan_dw(ctx->num_cus, 4, d, SG_DW_DGRAD, true, true).ws_bytes + 256;
 }
 
 int sg_dwconv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
@@ -1560,71 +1595,64 @@ int sg_dwconv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* 
   SG_CHECK_ARG(!sums || (sums->x && sums->mean && sums->invstd && sums->gamma && sums->beta && sums->dgamma && sums->dbeta),
                "sg_dwconv2d_dgrad: sums with a null tensor");
   SG_CHECK_ARG(!pre_relu || x_for_mask, "sg_dwconv2d_dgrad: pre_relu needs the forward input");
-  if (res || sums) {
-    const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-    if (!((d->Cin % 4 == 0) && (xl % 4 == 0) && (yl % 4 == 0) && sg_aligned16(dy) && sg_aligned16(w) && sg_aligned16(dx) &&
-          (!sums || (sg_aligned16(sums->x) && sg_aligned16(sums->mean) && sg_aligned16(sums->invstd) && sg_aligned16(sums->gamma) &&
-                     sg_aligned16(sums->beta))) &&
-          (!res || sg_aligned16(res)) && (!pre_relu || sg_aligned16(x_for_mask)) && dw_run_ok(d))) {
-      sg_set_error("sg_dwconv2d_dgrad: res / sums, but only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned) add a "
-                   "collected gradient or sum for the BatchNormalization; add it afterwards / use sg_bn_train_bwd instead");
-      return SG_EUNSUPPORTED;
-    }
+  const sg_dw_bnsums q = sums ? *sums : sg_dw_bnsums{};   // all-null without sums
+  const DwPlan pl = plan_dw(ctx->num_cus, dw_esize(dtype), d, SG_DW_DGRAD,
+                            dw_aligned({dy, w, dx, pre_relu ? x_for_mask : nullptr, res, q.x, q.mean, q.invstd, q.gamma, q.beta}),
+                            sums != nullptr);
+  if ((res && !pl.res) || (sums && !pl.sums)) {
+    sg_set_error("sg_dwconv2d_dgrad: res / sums, but only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned) add a "
+                 "collected gradient or sum for the BatchNormalization; add it afterwards / use sg_bn_train_bwd instead");
+    return SG_EUNSUPPORTED;
   }
-  if (sums && (!sums->ws || sums->ws_bytes < sg_dwconv2d_dgrad_bnsums_ws_bytes(ctx, d) - 256)) {
-    sg_set_error("sg_dwconv2d_dgrad: sums workspace %zu < %zu", sums->ws_bytes, sg_dwconv2d_dgrad_bnsums_ws_bytes(ctx, d) - 256);
+  if (sums && (!sums->ws || sums->ws_bytes < pl.ws_bytes)) {
+    sg_set_error("sg_dwconv2d_dgrad: sums workspace %zu < %zu", sums->ws_bytes, pl.ws_bytes);
     return SG_EWORKSPACE;
   }
   SG_DTYPE_SWITCH(dtype, "sg_dwconv2d_dgrad", {
-    DwParams<T> p;
-    dw_fill(p, d);
-    p.x = (const T*)x_for_mask; p.w = (const float*)w; p.dy = (const T*)dy; p.out = (T*)dx; p.pre_relu = pre_relu;
-    const bool vec = (p.C % 4 == 0) && (p.x_ld % 4 == 0) && (p.y_ld % 4 == 0) && sg_aligned16(dy) && sg_aligned16(w) &&
-                     sg_aligned16(dx) && (!pre_relu || sg_aligned16(x_for_mask));
-    if (vec && dw_run_ok(d)) {  // stride-1 dgrad = the same stencil with the kernel flipped
+    if (pl.family != SG_DWK_GENERIC) {  // stride-1 dgrad = the same stencil with the kernel flipped
       DwRunParams<T> r;
-      r.in = (const T*)dy; r.w = (const float*)w; r.mask = pre_relu ? (const T*)x_for_mask : nullptr; r.out = (T*)dx;
-      r.res = (const T*)res;
+      r.in = (const T*)dy; r.w = (const float*)w; r.mask = pre_relu ? (const T*)x_for_mask : nullptr; r.out = (T*)dx; r.res = (const T*)res;
       r.bn_gamma = r.bn_beta = r.bn_mean = r.bn_invstd = nullptr;
-      r.N = d->N; r.H = d->H; r.W = d->W; r.C = p.C; r.in_ld = p.y_ld; r.out_ld = p.x_ld; r.mask_ld = p.x_ld;
-      r.relu_in = 0; r.flip = 1; r.runs_per_row = d->W / 4; r.nruns = (int64_t)d->N * d->H * r.runs_per_row;
-      r.fd_rpr = make_fastdiv((uint32_t)r.runs_per_row); r.fd_h = make_fastdiv((uint32_t)d->H);
-      if (!sums) return launch_dw_run(r, (hipStream_t)stream);
-      r.bs_x = (const T*)sums->x; r.bs_ld = d->Cin;   // the BatchNormalization's input is a dense tensor
-      r.bs_mean = (const float*)sums->mean; r.bs_invstd = (const float*)sums->invstd;
-      r.bs_gamma = (const float*)sums->gamma; r.bs_beta = (const float*)sums->beta; r.bs_relu = sums->relu ? 1 : 0;
-      r.bs_part = (float*)sums->ws;
-      int rows = 0;
-      rc = launch_dw_run(r, (hipStream_t)stream, &rows);
-      if (rc) return rc;
+      r.in_ld = d->y_ld ? d->y_ld : d->Cout; r.out_ld = r.mask_ld = d->x_ld ? d->x_ld : d->Cin;
+      r.relu_in = 0; r.flip = 1;
+      if (sums) {
+        r.bs_x = (const T*)sums->x; r.bs_ld = d->Cin;   // the BatchNormalization's input is a dense tensor
+        r.bs_mean = (const float*)sums->mean; r.bs_invstd = (const float*)sums->invstd;
+        r.bs_gamma = (const float*)sums->gamma; r.bs_beta = (const float*)sums->beta; r.bs_relu = sums->relu ? 1 : 0; r.bs_part = (float*)sums->ws;
+      }
+      // never relu_in or a fused BatchNormalization here (DW_RELU / DW_BN* are the forward's): this entry point has no such operand
+      rc = launch_dw_stencil(pl, sums ? (pre_relu ? DW_MASK_SUMS : DW_SUMS) : (pre_relu ? DW_MASK : DW_PLAIN), d, r, (hipStream_t)stream);
+      if (rc || !sums) return rc;
       BnSumsFinalOp op;
       op.dgamma = (float*)sums->dgamma; op.dbeta = (float*)sums->dbeta;
-      seg_finalize_launch(op, 1, d->Cin, rows, (const float*)sums->ws, (hipStream_t)stream);
+      seg_finalize_launch(op, 1, d->Cin, pl.S, (const float*)sums->ws, (hipStream_t)stream);   // pl.S = gy partial rows
       SG_LAUNCH_CHECK("sg_dwconv2d_dgrad sums");
       return 0;
     }
-    const int V = vec ? 4 : 1;
-    p.fd_cv = make_fastdiv((uint32_t)(p.C / V)); p.fd_w = make_fastdiv((uint32_t)p.W); p.fd_h = make_fastdiv((uint32_t)p.H);
-    const unsigned blocks = ew_blocks((int64_t)p.N * p.H * p.W * (p.C / V));
-    if (vec) hipLaunchKernelGGL((dw_dgrad_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((dw_dgrad_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    DwParams<T> p;
+    dw_fill(p, d);
+    p.x = (const T*)x_for_mask; p.w = (const float*)w; p.dy = (const T*)dy; p.out = (T*)dx; p.pre_relu = pre_relu;
+    p.fd_cv = make_fastdiv((uint32_t)(p.C / pl.V)); p.fd_w = make_fastdiv((uint32_t)p.W); p.fd_h = make_fastdiv((uint32_t)p.H);
+    if (pl.V == 4) hipLaunchKernelGGL((dw_dgrad_kernel<4, T>), dim3((unsigned)pl.gx), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((dw_dgrad_kernel<1, T>), dim3((unsigned)pl.gx), dim3(256), 0, (hipStream_t)stream, p);
   });
   SG_LAUNCH_CHECK("dw_dgrad_kernel");
   return 0;
 }
 
+// An upper bound of plan_dw's ws_bytes over what the query cannot know (+ 256 of slack): whether the operands will be aligned -
+// hence DwWgradOp's plan at V = 4 and at V = 1 - and, on a dw_run_ok map, which of the two fast kernels the switches pick - the strips,
+// and the run reducer at RR = 1: seg_plan's part_bytes does not decrease as the row count grows (S = min(ceil(4 CUs / gx),
+// ceil(rows / (4 TY))) and the one-workgroup rule only lowers small counts), and ceil(rows / 4) >= rows / (4 RR) for RR = 1 and 2.
 size_t sg_dwconv2d_wgrad_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d) {
   if (!ctx || !d) return 0;
   const int64_t rows = (int64_t)d->N * d->Ho * d->Wo;
-  const SegPlan a = seg_plan<9>(ctx->num_cus, 1, rows, d->Cin, true), b = seg_plan<9>(ctx->num_cus, 1, rows, d->Cin, false);
-  const SegPlan r = seg_plan<9>(ctx->num_cus, 1, sg_cdiv(rows, 4), d->Cin, true);
-  size_t m = a.part_bytes > b.part_bytes ? a.part_bytes : b.part_bytes;
-  if (r.part_bytes > m) m = r.part_bytes;
-  if (dw_run_ok(d)) {
-    const DwStripPlan sp = dw_strip_plan(ctx->num_cus, d);
-    if (sp.part_bytes > m) m = sp.part_bytes;
-  }
-  return m + 256;
+  DwPlan v4 = {}, v1 = {}, run = {}, strip = {};
+  plan_dw_wgrad_seg(v4, ctx->num_cus, SG_DWK_GENERIC, rows, d->Cin, true);
+  plan_dw_wgrad_seg(v1, ctx->num_cus, SG_DWK_GENERIC, rows, d->Cin, false);
+  plan_dw_wgrad_seg(run, ctx->num_cus, SG_DWK_RUN, sg_cdiv(rows, 4), d->Cin, true);
+  if (dw_run_ok(d)) plan_dw_wgrad_strip(strip, ctx->num_cus, d);
+  return std::max({v4.ws_bytes, v1.ws_bytes, run.ws_bytes, strip.ws_bytes}) + 256;
 }
 
 int sg_dwconv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy, void* dw,
@@ -1632,94 +1660,61 @@ int sg_dwconv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* 
   int rc = dw_check(ctx, dtype, d, "sg_dwconv2d_wgrad");
   if (rc) return rc;
   SG_CHECK_ARG(x && dy && dw, "sg_dwconv2d_wgrad: null tensor");
-  const void *bn_gamma = nullptr, *bn_beta = nullptr, *bn_mean = nullptr, *bn_invstd = nullptr;
   if (bn) {
     SG_CHECK_ARG(!pre_relu && !bn->infer, "sg_dwconv2d_wgrad: bn with pre_relu (bn->relu has that role) / an inference-mode bn");
     SG_CHECK_ARG(bn->gamma && bn->beta && bn->mean && bn->invstd, "sg_dwconv2d_wgrad: bn with a null BatchNormalization parameter");
-    bn_gamma = bn->gamma; bn_beta = bn->beta; bn_mean = bn->mean; bn_invstd = bn->invstd;
     pre_relu = bn->relu;
-    const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-    if (!((d->Cin % 4 == 0) && (xl % 4 == 0) && (yl % 4 == 0) && sg_aligned16(x) && sg_aligned16(dy) && sg_aligned16(bn_gamma) &&
-          sg_aligned16(bn_beta) && sg_aligned16(bn_mean) && sg_aligned16(bn_invstd) && dw_run_ok(d))) {
-      sg_set_error("sg_dwconv2d_wgrad: bn, but only the stride-1 3x3 run kernels fuse the BatchNormalization; materialise it instead");
-      return SG_EUNSUPPORTED;
-    }
+  }
+  const sg_bn_in b = bn ? *bn : sg_bn_in{};   // all-null without bn
+  const DwPlan pl = plan_dw(ctx->num_cus, dw_esize(dtype), d, SG_DW_WGRAD, dw_aligned({x, dy, b.gamma, b.beta, b.mean, b.invstd}), false);
+  if (bn && !pl.bn) {
+    sg_set_error("sg_dwconv2d_wgrad: bn, but only the stride-1 3x3 run kernels fuse the BatchNormalization; materialise it instead");
+    return SG_EUNSUPPORTED;
   }
   SG_CHECK_ARG(d->KH == 3 && d->KW == 3, "sg_dwconv2d_wgrad: only 3x3 depthwise kernels occur on this path");
+  if (!ws || ws_bytes < pl.ws_bytes) {
+    sg_set_error("sg_dwconv2d_wgrad: workspace %zu < %zu", ws_bytes, pl.ws_bytes);
+    return SG_EWORKSPACE;
+  }
+  const int x_ld = d->x_ld ? d->x_ld : d->Cin, y_ld = d->y_ld ? d->y_ld : d->Cout;
   SG_DTYPE_SWITCH(dtype, "sg_dwconv2d_wgrad", {
-    DwWgradOp<T> op;
-    op.x = (const T*)x; op.dy = (const T*)dy; op.dw = (float*)dw;
-    op.H = d->H; op.W = d->W; op.C = d->Cin; op.Ho = d->Ho; op.Wo = d->Wo; op.stride = d->stride; op.dil = d->dilation;
-    op.pad_t = d->pad_t; op.pad_l = d->pad_l; op.x_ld = d->x_ld ? d->x_ld : d->Cin; op.y_ld = d->y_ld ? d->y_ld : d->Cout;
-    op.pre_relu = pre_relu;
-    op.fd_w = make_fastdiv((uint32_t)d->Wo); op.fd_h = make_fastdiv((uint32_t)d->Ho);
-    const int64_t rows = (int64_t)d->N * d->Ho * d->Wo;
-    const bool vec = (op.C % 4 == 0) && (op.x_ld % 4 == 0) && (op.y_ld % 4 == 0) && sg_aligned16(x) && sg_aligned16(dy);
-    if (vec && dw_strip_ok(d)) {
-      const DwStripPlan sp = dw_strip_plan(ctx->num_cus, d);
-      if (!ws || ws_bytes < sp.part_bytes) {
-        sg_set_error("sg_dwconv2d_wgrad: workspace %zu < %zu", ws_bytes, sp.part_bytes);
-        return SG_EWORKSPACE;
-      }
-      const dim3 grid((unsigned)sp.gx, (unsigned)sp.S);
-      const FastDiv fq = make_fastdiv((uint32_t)(d->W / 4)), fh = make_fastdiv((uint32_t)sp.nhs);
-      const unsigned xb_ = (unsigned)((int64_t)d->N * d->H * d->W * op.x_ld * (int64_t)sizeof(T));
-      const unsigned yb_ = (unsigned)((int64_t)d->N * d->H * d->W * op.y_ld * (int64_t)sizeof(T));
-      auto strip = [&](auto pre_, auto bn_) {
+    if (pl.family == SG_DWK_STRIP) {
+      const dim3 grid((unsigned)pl.gx, (unsigned)pl.S);
+      const FastDiv fq = make_fastdiv((uint32_t)(d->W / 4)), fh = make_fastdiv((uint32_t)pl.nhs);
+      const unsigned xb_ = (unsigned)((int64_t)d->N * d->H * d->W * x_ld * (int64_t)sizeof(T));
+      const unsigned yb_ = (unsigned)((int64_t)d->N * d->H * d->W * y_ld * (int64_t)sizeof(T));
+      dw_with_pre_bn(pre_relu, bn != nullptr, [&](auto pre_, auto bn_) {
         constexpr bool PRE_ = decltype(pre_)::value, BN_ = decltype(bn_)::value;
         hipLaunchKernelGGL((dw_wgrad_strip_kernel<T, PRE_, BN_>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)dy,
-                           (float*)ws, d->H, d->W, op.C, op.x_ld, op.y_ld, sp.HS, sp.nstrips, sp.S, xb_, yb_, fq, fh,
-                           (const float*)bn_gamma, (const float*)bn_beta, (const float*)bn_mean, (const float*)bn_invstd);
-      };
-      if (bn_gamma) {
-        if (pre_relu) strip(std::true_type{}, std::true_type{});
-        else strip(std::false_type{}, std::true_type{});
-      } else if (pre_relu) strip(std::true_type{}, std::false_type{});
-      else strip(std::false_type{}, std::false_type{});
+                           (float*)ws, d->H, d->W, d->Cin, x_ld, y_ld, pl.HS, pl.count, pl.S, xb_, yb_, fq, fh,
+                           (const float*)b.gamma, (const float*)b.beta, (const float*)b.mean, (const float*)b.invstd);
+      });
       SG_LAUNCH_CHECK("dw_wgrad_strip_kernel");
       DwWgradRunOp<1, T, false> fin;   // finalize() only: dw[t][c] = the fp64 sum of the S partial rows
-      fin.dw = (float*)dw; fin.C = op.C;
-      seg_finalize_launch(fin, 1, op.C, sp.S, (const float*)ws, (hipStream_t)stream);
+      fin.dw = (float*)dw; fin.C = d->Cin;
+      seg_finalize_launch(fin, 1, d->Cin, pl.S, (const float*)ws, (hipStream_t)stream);
       SG_LAUNCH_CHECK("dw_wgrad_strip finalize");
       return 0;
     }
-    if (vec && dw_run_ok(d)) {
-      const int rr = dw_rows_per_run(d->H, rows, true);
-      const int64_t nruns = rows / (4 * rr);
-      const SegPlan rp = seg_plan<9>(ctx->num_cus, 1, nruns, op.C, true);
-      if (!ws || ws_bytes < rp.part_bytes) {
-        sg_set_error("sg_dwconv2d_wgrad: workspace %zu < %zu", ws_bytes, rp.part_bytes);
-        return SG_EWORKSPACE;
-      }
+    if (pl.family == SG_DWK_RUN) {
       auto run = [&](auto ro) -> int {
-        ro.x = (const T*)x; ro.dy = (const T*)dy; ro.dw = (float*)dw; ro.H = d->H; ro.W = d->W; ro.C = op.C;
-        ro.x_ld = op.x_ld; ro.y_ld = op.y_ld;
-        ro.bn_gamma = (const float*)bn_gamma; ro.bn_beta = (const float*)bn_beta; ro.bn_mean = (const float*)bn_mean;
-        ro.bn_invstd = (const float*)bn_invstd;
-        ro.fd_rpr = make_fastdiv((uint32_t)(d->W / 4)); ro.fd_h = make_fastdiv((uint32_t)(d->H / rr));
-        return seg_reduce_launch(ro, rp, 1, nruns, op.C, (float*)ws, (hipStream_t)stream, "dw_wgrad_run");
+        ro.x = (const T*)x; ro.dy = (const T*)dy; ro.dw = (float*)dw; ro.H = d->H; ro.W = d->W; ro.C = d->Cin; ro.x_ld = x_ld; ro.y_ld = y_ld;
+        ro.bn_gamma = (const float*)b.gamma; ro.bn_beta = (const float*)b.beta; ro.bn_mean = (const float*)b.mean; ro.bn_invstd = (const float*)b.invstd;
+        ro.fd_rpr = make_fastdiv((uint32_t)(d->W / 4)); ro.fd_h = make_fastdiv((uint32_t)(d->H / pl.RR));
+        return seg_reduce_launch(ro, pl.seg, 1, pl.count, d->Cin, (float*)ws, (hipStream_t)stream, "dw_wgrad_run");
       };
-      if (bn_gamma) {
-        if (pre_relu) {
-          if (rr == 2) return run(DwWgradRunOp<2, T, true, true>{});
-          return run(DwWgradRunOp<1, T, true, true>{});
-        }
-        if (rr == 2) return run(DwWgradRunOp<2, T, false, true>{});
-        return run(DwWgradRunOp<1, T, false, true>{});
-      }
-      if (pre_relu) {
-        if (rr == 2) return run(DwWgradRunOp<2, T, true>{});
-        return run(DwWgradRunOp<1, T, true>{});
-      }
-      if (rr == 2) return run(DwWgradRunOp<2, T, false>{});
-      return run(DwWgradRunOp<1, T, false>{});
+      return dw_with_pre_bn(pre_relu, bn != nullptr, [&](auto pre_, auto bn_) -> int {
+        constexpr bool PRE_ = decltype(pre_)::value, BN_ = decltype(bn_)::value;
+        return pl.RR == 2 ? run(DwWgradRunOp<2, T, PRE_, BN_>{}) : run(DwWgradRunOp<1, T, PRE_, BN_>{});
+      });
     }
-    const SegPlan pl = seg_plan<9>(ctx->num_cus, 1, rows, op.C, vec);
-    if (!ws || ws_bytes < pl.part_bytes) {
-      sg_set_error("sg_dwconv2d_wgrad: workspace %zu < %zu", ws_bytes, pl.part_bytes);
-      return SG_EWORKSPACE;
-    }
-    return seg_reduce_launch(op, pl, 1, rows, op.C, (float*)ws, (hipStream_t)stream, "dw_wgrad");
+    DwWgradOp<T> op;
+    op.x = (const T*)x; op.dy = (const T*)dy; op.dw = (float*)dw;
+    op.H = d->H; op.W = d->W; op.C = d->Cin; op.Ho = d->Ho; op.Wo = d->Wo; op.stride = d->stride; op.dil = d->dilation;
+    op.pad_t = d->pad_t; op.pad_l = d->pad_l; op.x_ld = x_ld; op.y_ld = y_ld;
+    op.pre_relu = pre_relu;
+    op.fd_w = make_fastdiv((uint32_t)d->Wo); op.fd_h = make_fastdiv((uint32_t)d->Ho);
+    return seg_reduce_launch(op, pl.seg, 1, (int64_t)d->N * d->Ho * d->Wo, d->Cin, (float*)ws, (hipStream_t)stream, "dw_wgrad");
   });
   return 0;
 }

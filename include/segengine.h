@@ -289,6 +289,34 @@ size_t sg_dwconv2d_wgrad_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d);
 int sg_dwconv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x,
                       const void* dy, void* dw, int pre_relu, const sg_bn_in* bn, void* ws, size_t ws_bytes);
 
+/* The plan one depthwise launch runs by (csrc/spatial.hip, plan_dw - the entry points above and the two workspace queries read the
+ * same one), for this storage type and the SG_DW_* switches.  direction: SG_DW_FWD / SG_DW_DGRAD / SG_DW_WGRAD.  aligned: every
+ * tensor the call passes is 16-byte aligned.  sums: the dgrad is asked for the BatchNormalization sums.
+ *   family      SG_DWK_GENERIC  dw_fwd_kernel / dw_dgrad_kernel; filter gradient: DwWgradOp on the segment reducer
+ *               SG_DWK_RUN      dw_s1_run_kernel; filter gradient: DwWgradRunOp on the segment reducer
+ *               SG_DWK_STRIP    dw_strip_kernel; filter gradient: dw_wgrad_strip_kernel
+ *   V           channels per lane (4: 16-byte chunks)
+ *   RR, lc      SG_DWK_RUN: output rows per run; stencil: lanes per run along the channels
+ *   HS, nhs     SG_DWK_STRIP: rows per strip, strips per image column
+ *   count       runs (SG_DWK_RUN) or strips (SG_DWK_STRIP) of the launch
+ *   gx, gy      the stencil's grid (generic kernels: gx workgroups); SG_DWK_STRIP filter gradient: gx column blocks
+ *   S           partial rows written to the workspace: the filter gradient's row split; the sums' rows (= gy) with sums
+ *   seg_*       the segment reducer's plan where it runs (filter gradient, SG_DWK_GENERIC and SG_DWK_RUN)
+ *   bn, res, sums   1 if the launch can take that fused operand (else the entry point answers SG_EUNSUPPORTED)
+ *   ws_bytes    the workspace the launch itself requires (the queries answer an upper bound of it + 256)
+ * A descriptor the entry point would refuse answers all-zero with the entry point's error code. */
+#define SG_DW_FWD 0
+#define SG_DW_DGRAD 1
+#define SG_DW_WGRAD 2
+#define SG_DWK_GENERIC 0
+#define SG_DWK_RUN 1
+#define SG_DWK_STRIP 2
+typedef struct sg_dw_plan {
+  int family, V, RR, lc, HS, nhs, count, gx, gy, S, seg_V, seg_TX, seg_gx, seg_S, bn, res, sums;
+  size_t ws_bytes;
+} sg_dw_plan;
+int sg_dwconv2d_plan(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int direction, int aligned, int sums, sg_dw_plan* out);
+
 /* Dense on [rows,in] x [in,out] (+bias): bam.py channel_gate, res34.py:94,98.  Tiny GEMMs. */
 int sg_dense_fwd(sg_ctx* ctx, void* stream, int dtype, int rows, int in, int out, const void* x,
                  const void* w, const void* bias, void* y, int flags);

@@ -2,9 +2,10 @@
 sg_dwconv2d_dgrad, sg_dwconv2d_wgrad) through the C ABI on tests/_guarded.py arenas, each launch against plain float64
 (F.conv2d(groups = C) on the explicitly padded tensor, autograd for dx and dw).
 
-A case states which kernel its launch takes - from the mirrors below of dw_run_ok, dw_fstrip_ok, dw_strip_ok, dw_rows_per_run,
-launch_dw_run's lc / gx / gy, launch_dw_strip, dw_strip_plan and (tests/_guarded.py) seg_plan - and asserts before launching that
-the mirrors say the same for this device's CU count as for the 256 CUs the shapes were chosen at.
+A case states which kernel its launch takes - from the mirrors below of the parts of plan_dw (csrc/spatial.hip): dw_run_ok,
+dw_stencil_strips_ok, dw_wgrad_strips_ok, dw_rows_per_run, plan_dw_stencil_run, plan_dw_stencil_strip, plan_dw_wgrad_strip and
+(tests/_guarded.py) seg_plan - and asserts before launching that the mirrors say the same for this device's CU count as for the 256
+CUs the shapes were chosen at, and that the engine's own plan (sg_dwconv2d_plan) equals plan_mirror field by field.
 
 Run as a program (`python tests/_dw_cases.py` with one of CHILD_ENVS in the environment: the switches are read once per process)
 it runs child_cases() of that environment and prints one `CASE ok|FAIL ...` line per case, then its records."""
@@ -23,7 +24,7 @@ if _ROOT not in sys.path:
 from _bn_cases import gap_beta
 from _guarded import (Guarded, assert_written, bn_sums_ref, check_all, dw_conv_ref, dw_geom, dw_grads_ref, gaps_keep_prefill,
                       regime, seg_plan, untouched, widen)
-from building_detection_amd._lib import BnIn, ConvDesc, DwBnSums
+from building_detection_amd._lib import BnIn, ConvDesc, DwBnSums, DwPlan
 from test_bandwidth_variants_gpu import BF16, DEV, F32, G, GO, SP_CAP, call, gen, rnd, sgdt
 
 REF_CUS = 256
@@ -146,7 +147,7 @@ def dw_run_ok(g):
             and g.W % 4 == 0 and g.C % 4 == 0)
 
 
-def dw_strip_ok(g, xl, yl):
+def dw_wgrad_strips_ok(g, xl, yl):
     return bool(SW["SG_DW_STRIP"]) and dw_run_ok(g) and g.H % 4 == 0 and g.N * g.H * g.W * max(xl, yl) * 4 < (1 << 30)
 
 
@@ -156,15 +157,15 @@ def dw_rows_per_run(H, pixels, wgrad):
     return 2 if (want >= 2 and H % 2 == 0) else 1
 
 
-def dw_fstrip_ok(g, in_ld, es):
+def dw_stencil_strips_ok(g, in_ld, es):
     on = SW["SG_DW_FSTRIP"]
     if not on or (on == 1 and g.H < 64):
         return False
     return g.H % 4 == 0 and g.W % 4 == 0 and g.N * g.H * g.W * in_ld * es < (1 << 30)
 
 
-def launch_dw_strip(g, sums):
-    """(HS, nstrips, gx, gy) of launch_dw_strip."""
+def plan_dw_stencil_strip(g, sums):
+    """(HS, nstrips, gx, gy) of plan_dw_stencil_strip (with plan_dw_stencil_grid)."""
     hs_force = SW["SG_DW_FSTRIP_HS"]
     HS = hs_force if hs_force > 0 else (16 if g.H >= 64 else (8 if g.H >= 16 else g.H))
     if HS % 4 != 0 or HS > g.H:
@@ -177,8 +178,8 @@ def launch_dw_strip(g, sums):
     return HS, nstrips, gx, gy
 
 
-def launch_dw_run(g, sums):
-    """(rr, lc, gx, gy, nruns) of launch_dw_run's run-kernel branch."""
+def plan_dw_stencil_run(g, sums):
+    """(rr, lc, gx, gy, nruns) of plan_dw_stencil_run (with plan_dw_stencil_grid)."""
     rr = dw_rows_per_run(g.H, g.N * g.H * g.W, False)
     nruns = g.N * (g.H // rr) * (g.W // 4)
     lc = 1
@@ -191,8 +192,8 @@ def launch_dw_run(g, sums):
     return rr, lc, gx, gy, nruns
 
 
-def dw_strip_plan(cus, g):
-    """(HS, nhs, nstrips, gx, S) of dw_strip_plan (the filter gradient's strips)."""
+def plan_dw_wgrad_strip(cus, g):
+    """(HS, nhs, nstrips, gx, S) of plan_dw_wgrad_strip (the filter gradient's strips)."""
     HS = 16 if g.H >= 128 else (8 if g.H >= 16 else g.H)
     nhs = cdiv(g.H, HS)
     nstrips = g.N * nhs * (g.W // 4)
@@ -206,12 +207,12 @@ def stencil_name(g, es, in_ld, sums):
     run.RR<rows per run>lc<lanes per run>gx<column blocks>gy<rows of workgroups>.dead<lanes past the last chunk>[.trip2]
     strip.HS<strip height>[+short last band]r<remainder of the three-step unroll in the last band>gx..gy...dead..[.trip2]"""
     chunks = g.C // 4
-    if dw_fstrip_ok(g, in_ld, es):
-        HS, nstrips, gx, gy = launch_dw_strip(g, sums)
+    if dw_stencil_strips_ok(g, in_ld, es):
+        HS, nstrips, gx, gy = plan_dw_stencil_strip(g, sums)
         last = g.H - (cdiv(g.H, HS) - 1) * HS
         name = f"strip.HS{HS}{'+short' if last != HS else ''}r{last % 3}gx{gx}gy{gy}.dead{gx * 16 - chunks}"
         return name + (".trip2" if nstrips > gy * 16 else "")
-    rr, lc, gx, gy, nruns = launch_dw_run(g, sums)
+    rr, lc, gx, gy, nruns = plan_dw_stencil_run(g, sums)
     return f"run.RR{rr}lc{lc}gx{gx}gy{gy}.dead{gx * lc - chunks}" + (".trip2" if nruns > gy * (256 // lc) else "")
 
 
@@ -235,8 +236,8 @@ def wgrad_name(cus, g, vec, xl, yl, form=""):
     run.RR<rows per run>.V4tx<TX>gx<gx>.<regime> / seg.V<V>tx<TX>gx<gx>.<regime> (the segment reducer, tests/_guarded.seg_plan)"""
     rows = g.N * g.Ho * g.Wo
     tail = f".{form}" if form else ""
-    if vec and dw_strip_ok(g, xl, yl):
-        HS, nhs, nstrips, gx, S = dw_strip_plan(cus, g)
+    if vec and dw_wgrad_strips_ok(g, xl, yl):
+        HS, nhs, nstrips, gx, S = plan_dw_wgrad_strip(cus, g)
         return (f"wgrad.strip.HS{HS}{'+short' if g.H % HS else ''}gx{gx}.{regime(S)}{'.capped' if nstrips > S * 16 else ''}" + tail)
     if vec and dw_run_ok(g):
         rr = dw_rows_per_run(g.H, rows, True)
@@ -249,8 +250,8 @@ def wgrad_name(cus, g, vec, xl, yl, form=""):
 def wgrad_need(cus, g, vec, xl, yl):
     """The bytes of workspace the launch itself asks for."""
     rows = g.N * g.Ho * g.Wo
-    if vec and dw_strip_ok(g, xl, yl):
-        return dw_strip_plan(cus, g)[4] * 9 * g.C * 4
+    if vec and dw_wgrad_strips_ok(g, xl, yl):
+        return plan_dw_wgrad_strip(cus, g)[4] * 9 * g.C * 4
     if vec and dw_run_ok(g):
         return seg_plan(cus, rows // (4 * dw_rows_per_run(g.H, rows, True)), g.C, True, nout=9)["part_bytes"]
     return seg_plan(cus, rows, g.C, vec, nout=9)["part_bytes"]
@@ -262,7 +263,7 @@ def wgrad_ws_query(cus, g):
     m = max(seg_plan(cus, rows, g.C, True, nout=9)["part_bytes"], seg_plan(cus, rows, g.C, False, nout=9)["part_bytes"],
             seg_plan(cus, cdiv(rows, 4), g.C, True, nout=9)["part_bytes"])
     if dw_run_ok(g):
-        m = max(m, dw_strip_plan(cus, g)[4] * 9 * g.C * 4)
+        m = max(m, plan_dw_wgrad_strip(cus, g)[4] * 9 * g.C * 4)
     return m + 256
 
 
@@ -275,6 +276,75 @@ def pinned(engine, fn, *a, **kw):
     here, ref = fn(num_cus(engine), *a, **kw), fn(REF_CUS, *a, **kw)
     assert here == ref, f"{num_cus(engine)} CUs take {here}, the case was chosen for {ref}"
     return here
+
+
+FWD, DGRAD, WGRAD = 0, 1, 2                      # SG_DW_FWD, SG_DW_DGRAD, SG_DW_WGRAD
+K_GENERIC, K_RUN, K_STRIP = 0, 1, 2              # SG_DWK_GENERIC, SG_DWK_RUN, SG_DWK_STRIP
+PLAN_FIELDS = tuple(n for n, _ in DwPlan._fields_)
+
+
+def plan_mirror(cus, g, dtype, direction, vec, xl, yl, sums=False):
+    """plan_dw: every field of sg_dw_plan, from the mirrors above."""
+    z = dict.fromkeys(PLAN_FIELDS, 0)
+    fast = bool(vec and dw_run_ok(g))
+    V = z["V"] = 4 if vec else 1
+    if direction == WGRAD:
+        rows = g.N * g.Ho * g.Wo
+        z["bn"] = int(fast)
+        z["ws_bytes"] = wgrad_need(cus, g, vec, xl, yl)
+        if vec and dw_wgrad_strips_ok(g, xl, yl):
+            HS, nhs, nstrips, gx, S = plan_dw_wgrad_strip(cus, g)
+            z.update(family=K_STRIP, HS=HS, nhs=nhs, count=nstrips, gx=gx, S=S)
+            return z
+        if fast:
+            z.update(family=K_RUN, RR=dw_rows_per_run(g.H, rows, True))
+            rows = z["count"] = rows // (4 * z["RR"])
+        p = seg_plan(cus, rows, g.C, vec, nout=9)
+        z.update(seg_V=p["V"], seg_TX=p["TX"], seg_gx=p["gx"], seg_S=p["S"], S=p["S"])
+        return z
+    z.update({"bn": int(fast)} if direction == FWD else {"res": int(fast), "sums": int(fast)})
+    if not fast:
+        items = g.N * (g.Ho * g.Wo if direction == FWD else g.H * g.W) * (g.C // V)
+        z.update(family=K_GENERIC, gx=max(1, min(cdiv(items, 256), 16384)), gy=1)
+    elif dw_stencil_strips_ok(g, xl if direction == FWD else yl, esize(dtype)):
+        HS, nstrips, gx, gy = plan_dw_stencil_strip(g, sums)
+        z.update(family=K_STRIP, HS=HS, nhs=cdiv(g.H, HS), count=nstrips, gx=gx, gy=gy)
+    else:
+        rr, lc, gx, gy, nruns = plan_dw_stencil_run(g, sums)
+        z.update(family=K_RUN, RR=rr, lc=lc, count=nruns, gx=gx, gy=gy)
+    if direction == DGRAD and sums:
+        z.update(S=z["gy"] if fast else 0, ws_bytes=DW_SUMS_MAX_ROWS * 2 * g.C * 4)
+    return z
+
+
+def plan_query(engine, g, dtype, direction, aligned, sums=False, xgap=0, ygap=0):
+    """(return code, fields) of sg_dwconv2d_plan."""
+    d, p = g.desc(xgap, ygap), DwPlan()
+    rc = engine.lib.sg_dwconv2d_plan(engine.h, sgdt(dtype), CT.byref(d), direction, int(bool(aligned)), int(bool(sums)), CT.byref(p))
+    return rc, {n: getattr(p, n) for n in PLAN_FIELDS}
+
+
+def checked_plan(engine, g, dtype, direction, aligned, sums=False, xgap=0, ygap=0):
+    """The engine's plan of one launch, asserted equal to plan_mirror in every field for this device's CU count.  aligned: every
+    pointer of the call is 16-byte aligned (channel count and pixel strides are the plan's own business)."""
+    rc, got = plan_query(engine, g, dtype, direction, aligned, sums, xgap, ygap)
+    what = f"sg_dwconv2d_plan {g.tag} {dname(dtype)} dir={direction} aligned={int(bool(aligned))} sums={int(bool(sums))} gaps={xgap},{ygap}"
+    if direction == WGRAD and (g.KH, g.KW) != (3, 3):      # sg_dwconv2d_wgrad refuses the descriptor: all-zero with its code
+        assert rc == SG_EINVAL and not any(got.values()), (what, rc, got)
+        return got
+    assert rc == 0, f"{what}: rc={rc}: {engine.lib.sg_last_error().decode('utf-8', 'replace')}"
+    want = plan_mirror(num_cus(engine), g, dtype, direction, is_vec(g, xgap, ygap, not aligned), g.C + xgap, g.C + ygap, sums)
+    diff = {n: (got[n], want[n]) for n in PLAN_FIELDS if got[n] != want[n]}
+    assert not diff, f"{what}: (engine, mirror) differ in {diff}"
+    return got
+
+
+FAMILY_IN_NAME = {K_GENERIC: (".V", ".seg."), K_RUN: (".run.",), K_STRIP: (".strip.",)}
+
+
+def plan_names(plan, name):
+    """The case's kernel name speaks of the family the engine planned."""
+    assert any(t in name for t in FAMILY_IN_NAME[plan["family"]]), (name, plan)
 
 
 # ================================================================================================ inputs
@@ -448,12 +518,14 @@ def fwd_launch(engine, g, dtype, pre=0, bn=None, xgap=0, ygap=0, off=None, expec
     vec = is_vec(g, xgap, ygap, off)
     name = fwd_name(g, dtype, vec, g.C + xgap, fname if (vec and dw_run_ok(g)) else "")
     what = f"dwconv2d_fwd {g.tag} {dname(dtype)} pre={pre} bn={bn} gaps={xgap},{ygap} off={off} [{name}]"
+    plan = checked_plan(engine, g, dtype, FWD, not off, False, xgap, ygap)
     rc = call(engine, "sg_dwconv2d_fwd", sgdt(dtype), CT.byref(d), vptr(X), W.ptr(), vptr(Y), pre, CT.byref(st) if st else None)
     ops = [X, W, Y] + B
     if expect:
         refused(rc, expect, what, ops, [Y])
         return name
     ok(engine, rc, what, ops)
+    plan_names(plan, name)
     ref = dw_conv_ref(x.double(), w.double(), g.geom, g.s, g.d, bool(pre), bn_ref(g.C, bn) if bn is not None else None)
     cmp(vread(Y, what), ref, etol(dtype), what, form_of(name), "y", dtype)
     return name
@@ -505,12 +577,16 @@ def dgrad_launch(engine, g, dtype, mask=0, res=0, sums=0, relu=0, xgap=0, ygap=0
     stencil = vec and dw_run_ok(g)
     name = dgrad_name(g, dtype, vec, g.C + ygap, dgrad_form(mask, res, sums, relu) if stencil else "", bool(sums))
     what = f"dwconv2d_dgrad {g.tag} {dname(dtype)} {dgrad_form(mask, res, sums, relu)} gaps={xgap},{ygap} off={off} [{name}]"
+    plan = checked_plan(engine, g, dtype, DGRAD, not off, bool(sums), xgap, ygap)
+    if sums:
+        assert nws == plan["ws_bytes"] + 256, (what, nws, plan)
     rc = call(engine, "sg_dwconv2d_dgrad", sgdt(dtype), CT.byref(d), vptr(DY), W.ptr(), vptr(Xm), vptr(DX), int(mask), rptr,
               CT.byref(q) if q else None)
     if expect:
         refused(rc, expect, what, ops, outs)
         return name
     ok(engine, rc, what, ops)
+    plan_names(plan, name)
     ref = dx_ref(g, dtype, bool(mask))
     if res:
         ref = ref + rt.double()
@@ -536,12 +612,14 @@ def wgrad_launch(engine, g, dtype, pre=0, bn=None, xgap=0, ygap=0, off=None, exp
     d, d0 = g.desc(xgap, ygap), g.desc()
     vec = is_vec(g, xgap, ygap, off in ("x", "dy"))
     fname = f"PRE{int(bool(bn)) if bn is not None else int(pre)}BN{int(bn is not None)}"
+    plan = checked_plan(engine, g, dtype, WGRAD, off not in ("x", "dy", "bn"), False, xgap, ygap)
     if g.KH == 3 and g.KW == 3:
         name = pinned(engine, wgrad_name, g, vec, g.C + xgap, g.C + ygap, fname)
         cus = num_cus(engine)
         nws = engine.lib.sg_dwconv2d_wgrad_ws_bytes(engine.h, CT.byref(d0))
         assert nws == wgrad_ws_query(cus, g), (g.tag, nws, wgrad_ws_query(cus, g))
         assert wgrad_need(cus, g, vec, g.C + xgap, g.C + ygap) <= nws - 256
+        assert plan["ws_bytes"] + 256 <= nws, (g.tag, plan, nws)
     else:
         name, nws = "wgrad.refused", 1024
     if ws_bytes is not None:
@@ -555,6 +633,7 @@ def wgrad_launch(engine, g, dtype, pre=0, bn=None, xgap=0, ygap=0, off=None, exp
         refused(rc, expect, what, ops, [DWo])
         return name
     ok(engine, rc, what, ops)
+    plan_names(plan, name)
     ref = dw_grads_ref(x.double(), taps(g).double(), dy.double(), g.geom, g.s, g.d, bool(pre), bn_ref(g.C, bn) if bn is not None else None,
                        "dw")
     got = DWo.read()

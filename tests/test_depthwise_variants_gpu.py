@@ -12,7 +12,8 @@ Inputs: N >= 2 (257 and 9 in two cap cases), uniform in [-1, 1] on every border,
 Tolerances, as max|got - ref| <= tol * max|ref| over the whole tensor: 2e-5 fp32 y / dx, 1e-4 fp32 dw / dgamma / dbeta (fp32 for
 either storage), 2^-7 bf16-stored y / dx; refusals and gap columns exact.
 
-Every case id ends in the kernel the launch takes at 256 CUs (the case asserts the same for this device before launching):
+Every case id ends in the kernel the launch takes at 256 CUs (the case asserts the same for this device before launching, and that
+the engine's own plan, sg_dwconv2d_plan, equals the mirror of the rules it was named from, tests/_dw_cases.plan_mirror):
     fwd|dgrad.V<1|4>[.cap]                                      dw_fwd_kernel / dw_dgrad_kernel; .cap: past ew_blocks' 16384 workgroups
     fwd|dgrad.run.RR<1|2>lc<lanes per run>gx<column blocks>gy<workgroup rows>.dead<lanes past the last chunk>[.trip2]
     fwd|dgrad.strip.HS<band>[+short]r<last band's rows % 3>gx..gy...dead..[.trip2]          .trip2: the run / strip loop's second trip
@@ -24,6 +25,7 @@ SUMS / MASK+SUMS / res+SUMS / SUMS under a fused ReLU / all of them at once; wgr
 
 Out of reach of a test this size and left out: the second trip of the non-SUMS run and strip loops (above ~0.5 GB per operand; the
 same loop is walked twice by the SUMS cap cases), and the uint32 index arithmetic near 2^32."""
+import ctypes as CT
 import os
 import subprocess
 import sys
@@ -54,7 +56,7 @@ def _wgrad_params(shapes):
 
 # ================================================================================================ self-checks (CPU)
 def test_dispatch_mirrors_agree_with_hand_computed_values_at_256_cus():
-    run = lambda *a, sums=False: D.launch_dw_run(Geom(*a), sums)
+    run = lambda *a, sums=False: D.plan_dw_stencil_run(Geom(*a), sums)
     # lc: the power of two that covers C / 4 chunks, at most 64; a workgroup holds 256 / lc runs
     assert run(2, 6, 8, 4) == (2, 1, 1, 1, 12)            # 2 images x 3 row pairs x 2 runs per row
     assert run(2, 6, 8, 20) == (2, 8, 1, 1, 12)           # 5 chunks on 8 lanes: 3 dead
@@ -64,15 +66,15 @@ def test_dispatch_mirrors_agree_with_hand_computed_values_at_256_cus():
     assert D.dw_rows_per_run(66, 33792, True) == 2 and D.dw_rows_per_run(64, 32768, True) == 1 and D.dw_rows_per_run(9, 10 ** 6, True) == 1
     assert D.dw_rows_per_run(1, 8, False) == 1 and D.dw_rows_per_run(2, 8, False) == 2
     # the strips of the stencil: HS 16 from 64 rows on; gy = ceil(strips / 16)
-    assert D.launch_dw_strip(Geom(2, 64, 8, 4), False) == (16, 16, 1, 1) and D.launch_dw_strip(Geom(2, 68, 12, 68), False) == (16, 30, 2, 2)
-    assert D.launch_dw_strip(Geom(257, 64, 64, 4), False) == (16, 16448, 1, 1028) and D.launch_dw_strip(Geom(257, 64, 64, 4), True)[3] == 1024
-    assert D.dw_fstrip_ok(Geom(2, 64, 8, 4), 4, 4) and not D.dw_fstrip_ok(Geom(2, 66, 8, 4), 4, 4) and not D.dw_fstrip_ok(Geom(2, 60, 8, 4), 4, 4)
-    assert not D.dw_fstrip_ok(Geom(64, 1024, 1024, 4), 4, 4)      # 1 GiB: bit 30 is a flag
+    assert D.plan_dw_stencil_strip(Geom(2, 64, 8, 4), False) == (16, 16, 1, 1) and D.plan_dw_stencil_strip(Geom(2, 68, 12, 68), False) == (16, 30, 2, 2)
+    assert D.plan_dw_stencil_strip(Geom(257, 64, 64, 4), False) == (16, 16448, 1, 1028) and D.plan_dw_stencil_strip(Geom(257, 64, 64, 4), True)[3] == 1024
+    assert D.dw_stencil_strips_ok(Geom(2, 64, 8, 4), 4, 4) and not D.dw_stencil_strips_ok(Geom(2, 66, 8, 4), 4, 4) and not D.dw_stencil_strips_ok(Geom(2, 60, 8, 4), 4, 4)
+    assert not D.dw_stencil_strips_ok(Geom(64, 1024, 1024, 4), 4, 4)      # 1 GiB: bit 30 is a flag
     # the strips of the filter gradient: HS = H below 16 rows, 8 below 128, 16 from there; S = min(ceil(strips / 16), 1024 / gx, 256)
-    P = lambda *a: D.dw_strip_plan(256, Geom(*a))
+    P = lambda *a: D.plan_dw_wgrad_strip(256, Geom(*a))
     assert P(2, 12, 8, 4) == (12, 1, 4, 1, 1) and P(2, 20, 12, 68) == (8, 3, 18, 2, 2) and P(2, 128, 128, 4) == (16, 8, 512, 1, 32)
     assert P(2, 132, 8, 20) == (16, 9, 36, 1, 3) and P(9, 64, 256, 4) == (8, 8, 4608, 1, 256)
-    assert D.dw_strip_ok(Geom(2, 8, 8, 4), 4, 4) and not D.dw_strip_ok(Geom(2, 6, 8, 4), 4, 4) and not D.dw_strip_ok(Geom(2, 8, 8, 4, s=2), 4, 4)
+    assert D.dw_wgrad_strips_ok(Geom(2, 8, 8, 4), 4, 4) and not D.dw_wgrad_strips_ok(Geom(2, 6, 8, 4), 4, 4) and not D.dw_wgrad_strips_ok(Geom(2, 8, 8, 4, s=2), 4, 4)
     assert D.dw_run_ok(Geom(2, 5, 8, 4)) and not D.dw_run_ok(Geom(2, 5, 6, 4)) and not D.dw_run_ok(Geom(2, 5, 8, 5))
     assert not D.dw_run_ok(Geom(2, 5, 8, 4, d=2)) and not D.dw_run_ok(Geom(2, 5, 8, 4, KH=5)) and not D.dw_run_ok(Geom(2, 5, 8, 4, same=False))
     # geometry: stride 2 'same' pads (0, 1) on even and (1, 1) on odd maps; dilation 3 on three rows: (3, 3)
@@ -116,7 +118,7 @@ def test_case_tables_contain_every_form_by_name():
     for part in ("strip.HS4gx1.one", "strip.HS12gx", "strip.HS8+short", "strip.HS16gx", "strip.HS16+short", "gx2.few", ".many", ".many.capped",
                  "run.RR1.V4tx1gx1", "run.RR1.V4tx8gx1", "run.RR1.V4tx16gx2", "run.RR2."):
         assert any(part in n for n in wg), part
-    # the forms a case runs: every <RELU, MASK, BN, SUMS> instantiation launch_dw_run / launch_dw_strip can launch, every <PRE, BN>
+    # the forms a case runs: every <RELU, MASK, BN, SUMS> instantiation launch_dw_stencil can launch (DwForm), every <PRE, BN>
     assert {(bool(p), b is not None) for _, p, b in D.FWD_FORMS} == {(False, False), (True, False), (False, True)}
     assert {b for _, p, b in D.FWD_FORMS if b is not None} == {0, 1}
     assert {(bool(m), bool(s)) for m, r, s, q in D.DGRAD_FORMS} == {(False, False), (True, False), (False, True), (True, True)}
@@ -291,6 +293,33 @@ def test_wgrad_run_reducer(engine, g, dtype):
                                     for k, g in D.CAPS])
 def test_grid_cap_of_the_generic_kernels(engine, kind, g):
     assert D.cap_case(engine, kind, g).endswith(".cap")
+
+
+@gpu
+def test_plan_query_equals_the_mirrors(engine):
+    """No launch: sg_dwconv2d_plan against plan_mirror over every shape of the case tables, both storages, the three directions,
+    operands aligned or not, the dgrad with and without sums; and the two workspace queries against the plan's bytes."""
+    shapes = [(g, 0) for g in D.RUN_SHAPES + D.STRIP_SHAPES + D.SUMS_CAP + D.WSTRIP_SHAPES + D.WSTRIP_MORE + D.WRUN_SHAPES + D.WRUN_MORE]
+    shapes += [(g, gap) for g, gap, _ in D.GENERIC] + [(g, 0) for _, g in D.CAPS]
+    families = set()
+    for g, gap in dict.fromkeys(shapes):
+        d = g.desc(gap, gap)
+        wq = engine.lib.sg_dwconv2d_wgrad_ws_bytes(engine.h, CT.byref(d))
+        sq = engine.lib.sg_dwconv2d_dgrad_bnsums_ws_bytes(engine.h, CT.byref(d))
+        for dtype in DT:
+            for direction in (D.FWD, D.DGRAD, D.WGRAD):
+                for aligned in (0, 1):
+                    for sums in ((0, 1) if direction == D.DGRAD else (0,)):
+                        plan = D.checked_plan(engine, g, dtype, direction, aligned, sums, gap, gap)
+                        families.add((direction, plan["family"]))
+                        if direction == D.WGRAD and (g.KH, g.KW) == (3, 3):
+                            assert wq >= plan["ws_bytes"] + 256, (g.tag, gap, aligned, wq, plan)
+                        if sums:
+                            assert sq == plan["ws_bytes"] + 256, (g.tag, gap, aligned, sq, plan)
+    assert families == {(k, f) for k in (D.FWD, D.DGRAD, D.WGRAD) for f in (D.K_GENERIC, D.K_RUN, D.K_STRIP)}
+    # a descriptor the entry points refuse: all-zero with their code
+    rc, got = D.plan_query(engine, Geom(2, 6, 8, 8, KH=5), F32, D.WGRAD, 1)
+    assert rc == D.SG_EINVAL and not any(got.values())
 
 
 @gpu

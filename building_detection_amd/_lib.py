@@ -20,6 +20,7 @@ SG_PRO_UP2, SG_EPI_DOWN2 = 16, 32   # UpSampling2D(2) -> Conv2D 3x3 fused: forwa
 SG_X_UP2 = 0x200                   # ... and the dtype flag of its filter gradient
 SG_ACT_RELU, SG_ACT_SIGMOID = 0, 1
 SG_LOSS_CE2, SG_LOSS_FOCAL, SG_LOSS_EDGE_FOCAL = 0, 1, 2
+SG_MAX_CLASSES = 32   # the C-class head: sg_softmax_*, sg_lossn_*, sg_confusion_matrix, sg_argmax_max_u8
 SG_AUGMENT_MAX_ITEMS = 64
 SG_AUG_FLIP_UD, SG_AUG_FLIP_LR, SG_AUG_SWAP_RB, SG_AUG_THRESHOLD = 1, 2, 4, 8
 
@@ -96,6 +97,7 @@ _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 _op = C.POINTER(ConvOpts)
 _dp = C.POINTER(ConvDesc)
 _pp = C.POINTER(C.c_void_p)
+_fp = C.POINTER(C.c_float)
 
 # name -> (restype, argtypes).  Kept in the order of include/segengine.h.
 _SIGNATURES = {
@@ -143,6 +145,8 @@ _SIGNATURES = {
     "sg_copy_channels": (_i, [_vp, _vp, _i, _i64, _i, _vp, _i, _i, _vp, _i, _i, _i]),
     "sg_softmax2_fwd": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
     "sg_softmax2_bwd": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "sg_softmax_fwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp]),
+    "sg_softmax_bwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp]),
     "sg_softmax_branch_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sg_softmax_branch_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sg_bcast_mul_fwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _i]),
@@ -169,12 +173,17 @@ _SIGNATURES = {
     "sg_loss_fwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _sz]),
     "sg_loss_bwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _f]),
     "sg_confusion_counts": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "sg_lossn_ws_bytes": (_sz, [_vp, _i64]),
+    "sg_lossn_fwd": (_i, [_vp, _vp, _i, _i64, _i, _i, _fp, _vp, _vp, _vp, _vp, _sz]),
+    "sg_lossn_bwd": (_i, [_vp, _vp, _i, _i64, _i, _i, _fp, _vp, _vp, _vp, _f]),
+    "sg_confusion_matrix": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "sg_adam_step": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f]),
     "sg_adam_step_lr": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f]),
     "sg_edge_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sg_resize_linear_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "sg_augment_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     "sg_argmax_accumulate_i8": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i]),
+    "sg_argmax_max_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i]),
     "sg_vote_ge": (_i, [_vp, _vp, _i, _pp, _i64, _i, _vp]),
     "sg_mask_objects_ws_bytes": (_sz, [_i, _i]),
     "sg_mask_objects": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp]),

@@ -25,6 +25,22 @@ AREA_OBJECT = 1000  # model_fuse.py:22  `if area <= 1000`
 AREA_PIECE = 500    # model_fuse.py:57  `if area <= 500`
 
 
+def require_binary(mask, who: str):
+    """The vote and the clean-up are binary morphology on 0/255 masks.  A class map (what pipeline.detection returns for a
+    model of more than two classes: uint8 class indices 0 ... C-1) would pass as a mask of all its non-zero pixels, or vote
+    as all background: refuse it by name.  Host arrays only - a device tensor is not read back for this.
+
+    The test is a heuristic on the values, not a type: a uint8 array whose largest value lies in 1 ... SG_MAX_CLASSES - 1 counts as a
+    class map.  An all-zero array passes (an empty mask and an all-background class map are the same picture), and a mask that is
+    not 0/255 but holds only such small values - outside this module's documented contract - is refused where it used to
+    count as background in the vote."""
+    if isinstance(mask, np.ndarray) and mask.dtype == np.uint8 and mask.size:
+        top = int(mask.max())
+        if 0 < top < _lib.SG_MAX_CLASSES:
+            raise ValueError(f"{who}: a class map (uint8 class indices up to {top}), not a 0/255 mask - the ensemble vote and "
+                             "the contour clean-up are binary; take one class first, e.g. np.where(class_map == c, 255, 0)")
+
+
 def _dev(mask, eng):
     import torch
     if isinstance(mask, torch.Tensor):
@@ -47,6 +63,7 @@ def fill_and_delete(mask, engine=None, max_objs: int = 1 << 16):
     """-> (gray_label u8 device tensor, labels i32 device tensor, object table as a numpy array [n, 8])."""
     import torch
     from .ops import get_engine
+    require_binary(mask, "fill_and_delete")
     eng = engine or get_engine(0)
     m = _dev(mask, eng)
     h, w = m.shape
@@ -103,6 +120,8 @@ def clean(mask, engine=None):
 def model_confuse(masks: Sequence, engine=None):
     """model_fuse.py:271-350 on five masks (arrays or device tensors, 0/255): clean each, vote >= 3, clean the vote."""
     from .ops import get_engine
+    for m in masks:
+        require_binary(m, "model_confuse")
     eng = engine or get_engine(0)
     if len(masks) != 5:
         raise ValueError("no five images")  # model_fuse.py:283-285 prints this and returns

@@ -34,6 +34,15 @@ void sg_set_error(const char* fmt, ...);
 
 static inline int64_t sg_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// partial sums (= workgroups of 256 threads, four rows each, capped) of the first stage of the loss reductions: one rule for
+// sg_loss_fwd / sg_lossn_fwd and their workspace queries
+static inline int sg_loss_parts(int64_t rows) {
+  int64_t b = sg_cdiv(rows, 256 * 4);
+  if (b > 2048) b = 2048;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
 // ---- unsigned division by a runtime-constant divisor (n < 2^31), precomputed on the host -------------
 struct FastDiv {
   uint32_t mul;

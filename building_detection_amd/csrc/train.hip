@@ -409,18 +409,11 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(const unsigned char* __
   }
 }
 
-inline int loss_parts(int64_t rows) {
-  int64_t b = sg_cdiv(rows, 256 * 4);
-  if (b > 2048) b = 2048;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace
 
 extern "C" {
 
-size_t sg_loss_ws_bytes(const sg_ctx*, int64_t rows) { return (size_t)loss_parts(rows) * sizeof(float) + 256; }
+size_t sg_loss_ws_bytes(const sg_ctx*, int64_t rows) { return (size_t)sg_loss_parts(rows) * sizeof(float) + 256; }
 
 int sg_loss_fwd(sg_ctx* ctx, void* stream, int kind, int64_t rows, int y_cols, const void* p, const void* y_true,
                 void* loss_out, void* ws, size_t ws_bytes) {
@@ -428,7 +421,7 @@ int sg_loss_fwd(sg_ctx* ctx, void* stream, int kind, int64_t rows, int y_cols, c
   SG_CHECK_ARG(kind >= SG_LOSS_CE2 && kind <= SG_LOSS_EDGE_FOCAL, "sg_loss_fwd: unknown loss %d", kind);
   SG_CHECK_ARG(y_cols == 2 || y_cols == 4, "sg_loss_fwd: y_true must have 2 or 4 columns");
   SG_CHECK_ARG(kind != SG_LOSS_EDGE_FOCAL || y_cols == 4, "sg_loss_fwd: edge_focal_loss needs y_true[...,4]");
-  const int parts = loss_parts(rows);
+  const int parts = sg_loss_parts(rows);
   if (!ws || ws_bytes < (size_t)parts * sizeof(float)) {
     sg_set_error("sg_loss_fwd: workspace %zu < %zu", ws_bytes, (size_t)parts * sizeof(float));
     return SG_EWORKSPACE;

@@ -6,6 +6,9 @@ y: [N,H,W,4] = one-hot(background, building), f_edge weight, p_edge weight, buil
 iterations, restated with scipy min/max filters (OpenCV is not available): cv.erode pads with +inf, cv.dilate
 with -inf; p_edge = 2 where mask - erode == 1 (inner building rim), f_edge = 2 where dilate - mask == 1 (outer
 rim), else 1; channel order (one_hot, f_edge, p_edge) as in `np.concatenate` at :100.
+
+`num_classes=C` > 2: every rectangle gets a class in 1 ... C-1 and y is [N,H,W,2C] = one-hot C, then one edge weight per class
+(class_edge_weights: 2 on a pixel of class c whose 11 x 11 window holds another class - the same rule, said per class).
 """
 from __future__ import annotations
 
@@ -24,7 +27,42 @@ def edge_weight_channels(mask: np.ndarray):
     return f_edge, p_edge
 
 
-def synthetic_batch(n: int, h: int = 512, w: int = 512, seed: int = 1103):
+def class_edge_weights(class_map: np.ndarray, num_classes: int) -> np.ndarray:
+    """[H,W] integer class map -> [H,W,C] edge weights: w_c = 2 where the pixel is of class c and its 11 x 11 in-image window
+    (five 3 x 3 iterations) holds a pixel of another class, else 1.  At C = 2 this is (f_edge, p_edge) of
+    edge_weight_channels: `dilate(fg) - fg == 1` says the same of class 0 as `fg - erode(fg) == 1` says of class 1."""
+    from scipy import ndimage
+    cm = np.asarray(class_map)
+    w = np.ones(cm.shape + (num_classes,), np.float32)
+    for c in range(num_classes):
+        other = ndimage.maximum_filter((cm != c).astype(np.uint8), size=11, mode="constant", cval=0)
+        w[..., c] = np.where((cm == c) & (other == 1), 2.0, 1.0)
+    return w
+
+
+def _synthetic_multiclass(n, h, w, seed, num_classes):
+    rng = np.random.default_rng(seed)
+    x = rng.integers(0, 256, size=(n, h, w, 3), dtype=np.uint8).astype(np.float32) / 127.5 - 1.0
+    y = np.empty((n, h, w, 2 * num_classes), np.float32)
+    for i in range(n):
+        cm = np.zeros((h, w), np.int64)
+        for _ in range(int(rng.integers(3, 13))):
+            rh = int(rng.integers(max(h // 32, 2), max(h // 4, 3)))
+            rw = int(rng.integers(max(w // 32, 2), max(w // 4, 3)))
+            r0, c0 = int(rng.integers(0, h - rh)), int(rng.integers(0, w - rw))
+            cm[r0:r0 + rh, c0:c0 + rw] = int(rng.integers(1, num_classes))   # a later rectangle covers an earlier one
+        y[i, ..., :num_classes] = np.eye(num_classes, dtype=np.float32)[cm]
+        y[i, ..., num_classes:] = class_edge_weights(cm, num_classes)
+    return x.astype(np.float32), y
+
+
+def synthetic_batch(n: int, h: int = 512, w: int = 512, seed: int = 1103, num_classes: int = 2):
+    """num_classes > 2: every rectangle gets a class in 1 ... C-1 and y is [N,H,W,2C] = one-hot C, then the per-class edge
+    weights of class_edge_weights.  The default draws exactly what it always drew."""
+    if num_classes != 2:
+        if num_classes < 2:
+            raise ValueError(f"num_classes = {num_classes}")
+        return _synthetic_multiclass(n, h, w, seed, num_classes)
     rng = np.random.default_rng(seed)
     x = rng.integers(0, 256, size=(n, h, w, 3), dtype=np.uint8).astype(np.float32) / 127.5 - 1.0
     y = np.empty((n, h, w, 4), np.float32)

@@ -67,8 +67,8 @@ class _ConvNode(Node):
         ho, wo, _, _ = conv_out_geometry(h, w, self.k, self.k, self.stride, self.dilation, self.padding)
         self.w = self.add_param("kernel", (self.k, self.k, cin, self.filters), self.kinit)
         self.b = self.add_param("bias", (self.filters,), "zeros", kind="bias") if self.use_bias else None
-        if self.activation == "softmax" and self.filters != 2:
-            raise ValueError("softmax heads on this path have 2 classes")
+        if self.activation == "softmax" and not 2 <= self.filters <= _lib.SG_MAX_CLASSES:
+            raise ValueError(f"softmax heads on this path have 2 ... {_lib.SG_MAX_CLASSES} classes, not {self.filters}")
         return self.connect([x], (None, ho, wo, self.filters))
 
     def desc(self, rt, x):
@@ -145,7 +145,7 @@ class _ConvNode(Node):
         if self.activation == "sigmoid":
             y = rt.eng.act_fwd(y, _lib.SG_ACT_SIGMOID, out=y)
         elif self.activation == "softmax":
-            y = rt.eng.softmax2_fwd(y, out=y)
+            y = rt.eng.softmax2_fwd(y, out=y) if self.filters == 2 else rt.eng.softmax_fwd(y, out=y)
         return y
 
     def backward(self, rt, xs, y, dy):
@@ -156,7 +156,7 @@ class _ConvNode(Node):
         elif self.activation == "sigmoid":
             dz = e.act_bwd(y, dy, _lib.SG_ACT_SIGMOID)
         elif self.activation == "softmax":
-            dz = e.softmax2_bwd(y, dy)
+            dz = e.softmax2_bwd(y, dy) if self.filters == 2 else e.softmax_bwd(y, dy)
         else:
             dz = dy
         up2 = self._up2(rt)
@@ -554,7 +554,8 @@ class _ActNode(Node):
             ax = self.axis if self.axis >= 0 else len(x.shape) + self.axis
             self.sm_axis = ax
             if ax == len(x.shape) - 1:
-                assert x.shape[-1] == 2, "last-axis softmax on this path has 2 classes"
+                if not 2 <= x.shape[-1] <= _lib.SG_MAX_CLASSES:
+                    raise ValueError(f"last-axis softmax on this path has 2 ... {_lib.SG_MAX_CLASSES} classes, not {x.shape[-1]}")
             else:
                 assert len(x.shape) == 4 and ax == 2 and x.shape[1] == 1, "branch softmax expects [N,1,B,C]"
         return self.connect([x], x.shape)
@@ -569,7 +570,7 @@ class _ActNode(Node):
         if self.act == "sigmoid":
             return e.act_fwd(x, _lib.SG_ACT_SIGMOID)
         if self.sm_axis == len(x.shape) - 1:
-            return e.softmax2_fwd(x)
+            return e.softmax2_fwd(x) if x.shape[-1] == 2 else e.softmax_fwd(x)
         n, _, b, c = x.shape
         return e.softmax_branch_fwd(x.view(n, b, c)).view(x.shape)
 
@@ -582,7 +583,7 @@ class _ActNode(Node):
         if self.act == "sigmoid":
             return [e.act_bwd(y, dy, _lib.SG_ACT_SIGMOID)]
         if self.sm_axis == len(y.shape) - 1:
-            return [e.softmax2_bwd(y, dy)]
+            return [e.softmax2_bwd(y, dy) if y.shape[-1] == 2 else e.softmax_bwd(y, dy)]
         n, _, b, c = y.shape
         return [e.softmax_branch_bwd(y.view(n, b, c), dy.view(n, b, c)).view(y.shape)]
 

@@ -4,6 +4,10 @@
 Python callables.  The engine does not trace tf ops: it recognises the three losses and four metrics of the
 reference by name (these objects, or any callable with the same `__name__`, e.g. the reference's own
 functions) and runs the fused HIP kernels `sg_loss_fwd/bwd` and `sg_confusion_counts` instead.
+
+A model of C > 2 classes runs `sg_lossn_fwd/bwd` and `sg_confusion_matrix`: the focal losses then carry one weight per
+class (`focal_loss.with_alpha([...])`, `edge_focal_loss.with_alpha([...])`), and the four metrics come from the C x C
+matrix (`metrics_from_matrix`).
 """
 from __future__ import annotations
 
@@ -37,9 +41,27 @@ class _Named:
         return f"<building_detection_amd {self.__name__}>"
 
 
-binary_crossentropy = _Named("binary_crossentropy", "2-class CE on softmax probabilities (DeepLabv3plus.py:490-499)")
-focal_loss = _Named("focal_loss", "focal loss, alpha=(.5,.5), gamma=2 (DeepLabv3plus.py:502-512)")
-edge_focal_loss = _Named("edge_focal_loss", "edge-weighted focal loss (DeepLabv3plus.py:515-527)")
+class _FocalLoss(_Named):
+    """A focal loss that may carry its per-class weights: `with_alpha(seq)` returns an object of the same `__name__`
+    (compile() selects the kernel by it, as ever) whose `alpha` the model reads - nothing global changes."""
+
+    alpha = None
+
+    def with_alpha(self, alpha):
+        a = tuple(float(v) for v in alpha)
+        if not a or any(not np.isfinite(v) for v in a):
+            raise ValueError(f"{self.__name__}.with_alpha: {alpha!r} is not a list of finite class weights")
+        out = _FocalLoss(self.__name__, self.__doc__)
+        out.alpha = a
+        return out
+
+    def __repr__(self):
+        return f"<building_detection_amd {self.__name__}{'' if self.alpha is None else ' alpha=' + repr(self.alpha)}>"
+
+
+binary_crossentropy = _Named("binary_crossentropy", "CE on softmax probabilities (DeepLabv3plus.py:490-499)")
+focal_loss = _FocalLoss("focal_loss", "focal loss, alpha = .5 for every class, gamma=2 (DeepLabv3plus.py:502-512)")
+edge_focal_loss = _FocalLoss("edge_focal_loss", "edge-weighted focal loss, alpha=(.35,.65) at 2 classes (DeepLabv3plus.py:515-527)")
 PA = _Named("PA", "pixel accuracy (DeepLabv3plus.py:530-553)")
 IoU = _Named("IoU", "foreground IoU (DeepLabv3plus.py:556-575)")
 MIoU = _Named("MIoU", "mean of foreground / background IoU (DeepLabv3plus.py:578-598)")
@@ -70,6 +92,26 @@ def resolve_loss(loss) -> int:
     return _LOSS_KINDS[name]
 
 
+def resolve_alpha(loss, num_classes: int):
+    """The per-class weights `loss` trains a `num_classes` model with: None = what the 2-class kernels have built in
+    (no weights given, 2 classes; cross-entropy has none at all), else a tuple of `num_classes` floats."""
+    kind = _LOSS_KINDS[loss if isinstance(loss, str) else getattr(loss, "__name__", None)]
+    alpha = getattr(loss, "alpha", None)
+    if kind == SG_LOSS_CE2:
+        return None
+    if alpha is None:
+        if num_classes == 2:
+            return None
+        if kind == SG_LOSS_EDGE_FOCAL:
+            raise ValueError(f"edge_focal_loss has class weights for 2 classes only ((.35, .65), DeepLabv3plus.py:515-527): "
+                             f"compile a {num_classes}-class model with loss=edge_focal_loss.with_alpha([...{num_classes} weights])")
+        return (0.5,) * num_classes
+    alpha = tuple(float(a) for a in alpha)
+    if len(alpha) != num_classes:
+        raise ValueError(f"the loss carries {len(alpha)} class weights, the model has {num_classes} classes")
+    return alpha
+
+
 def resolve_metric(metric) -> str:
     name = metric if isinstance(metric, str) else getattr(metric, "__name__", None)
     if name not in _METRICS:
@@ -89,3 +131,60 @@ def metrics_from_counts(tp: int, tn: int, fp: int, fn: int) -> dict:
     recall, precision = tp / (tp + fn + e), tp / (tp + fp + e)
     f1 = (f(2.0) * precision * recall) / (precision + recall + e)
     return {"PA": float(pa), "IoU": float(iou), "MIoU": float(miou), "F1_score": float(f1)}
+
+
+def metrics_from_matrix(M) -> dict:
+    """The four metrics from the C x C count matrix M[truth][prediction], in the float32 arithmetic with +epsilon of
+    metrics_from_counts (to which every one of them reduces bit for bit at C = 2, where M = [[TN, FP], [FN, TP]]):
+
+        PA = trace / total;  per class  IoU_c = M_cc / (row_c + col_c - M_cc + e),  recall_c = M_cc / (row_c + e),
+        precision_c = M_cc / (col_c + e),  F1_c = 2 precision_c recall_c / (precision_c + recall_c + e);
+        IoU = mean of IoU_c over the foreground classes 1 ... C-1,  F1_score = mean of F1_c over the same,
+        MIoU = mean of IoU_c over all classes.  `IoU_per_class` and `F1_per_class` hold the lists.
+
+    Sums run diagonal first, then the cells above it, then those below it (each in row-major order): the order in which
+    the reference adds TP, TN, FP, FN."""
+    f = np.float32
+    M = np.asarray(M)
+    if M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] < 2:
+        raise ValueError(f"metrics_from_matrix: a C x C matrix with C >= 2, not {M.shape}")
+    C = M.shape[0]
+    m = [[f(int(M[t][q])) for q in range(C)] for t in range(C)]
+    e = f(K_EPSILON)
+
+    def fsum(vals):
+        s = f(0.0)
+        for v in vals:
+            s = s + v
+        return s
+
+    trace = fsum([m[c][c] for c in reversed(range(C))])      # TP + TN at two classes
+    upper = [m[t][q] for t in range(C) for q in range(t + 1, C)]
+    lower = [m[t][q] for t in range(C) for q in range(t)]
+    total = trace
+    for v in upper + lower:
+        total = total + v
+    pa = trace / (total + e)
+    iou, f1 = [], []
+    for c in range(C):
+        up = [m[t][c] for t in range(c)] + [m[c][q] for q in range(c + 1, C)]        # cells above the diagonal that involve c
+        lo = [m[c][q] for q in range(c)] + [m[t][c] for t in range(c + 1, C)]        # ... and below it
+        den = m[c][c]
+        for v in up + lo:
+            den = den + v
+        iou.append(m[c][c] / (den + e))
+        row = m[c][c]
+        for q in range(C):
+            if q != c:
+                row = row + m[c][q]
+        col = m[c][c]
+        for t in range(C):
+            if t != c:
+                col = col + m[t][c]
+        recall, precision = m[c][c] / (row + e), m[c][c] / (col + e)
+        f1.append((f(2.0) * precision * recall) / (precision + recall + e))
+    fg = list(reversed(range(1, C)))
+    miou = fsum([iou[c] for c in reversed(range(C))]) / f(C)
+    return {"PA": float(pa), "IoU": float(fsum([iou[c] for c in fg]) / f(len(fg))), "MIoU": float(miou),
+            "F1_score": float(fsum([f1[c] for c in fg]) / f(len(fg))),
+            "IoU_per_class": [float(v) for v in iou], "F1_per_class": [float(v) for v in f1]}

@@ -701,6 +701,22 @@ class Engine:
               "sg_softmax2_bwd")
         return dz
 
+    def softmax_fwd(self, z, out=None):
+        """Softmax over a last axis of 2 ... SG_MAX_CLASSES classes (fp32; `out=z` runs in place)."""
+        _chk32(z, "z")
+        c = z.shape[-1]
+        p = out if out is not None else torch.empty_like(z)
+        check(self.lib.sg_softmax_fwd(self.h, self.stream, SG_F32, z.numel() // c, c, _ptr(z), _ptr(p)), "sg_softmax_fwd")
+        return p
+
+    def softmax_bwd(self, p, dp, out=None):
+        _chk32(p, "p"); _chk32(dp, "dp")
+        c = p.shape[-1]
+        dz = out if out is not None else torch.empty_like(p)
+        check(self.lib.sg_softmax_bwd(self.h, self.stream, SG_F32, p.numel() // c, c, _ptr(p), _ptr(dp), _ptr(dz)),
+              "sg_softmax_bwd")
+        return dz
+
     def softmax_branch_fwd(self, z):
         n, b, c = z.shape
         p = torch.empty_like(z)
@@ -867,6 +883,44 @@ class Engine:
                                            C.c_void_p(out.data_ptr())), "sg_confusion_counts")
         return out
 
+    @staticmethod
+    def _alpha(alpha, c):
+        """The C class weights as the host float array sg_lossn_* read at the call (None -> NULL: cross-entropy only)."""
+        if alpha is None:
+            return None
+        if len(alpha) != c:
+            raise ValueError(f"{len(alpha)} class weights for {c} classes")
+        return (C.c_float * c)(*[float(a) for a in alpha])
+
+    def lossn_fwd(self, kind, p, y_true, alpha=None):
+        """The loss of `kind` on p [..., C] and y_true [..., C or 2C]; alpha: C per-class weights (focal kinds)."""
+        _chk32(p, "p"); _chk32(y_true, "y_true")
+        c = p.shape[-1]
+        rows = p.numel() // c
+        out = self.empty(1)
+        wsp, wsn = self.ws(self.lib.sg_lossn_ws_bytes(self.h, rows))
+        check(self.lib.sg_lossn_fwd(self.h, self.stream, kind, rows, c, y_true.shape[-1], self._alpha(alpha, c), _ptr(p),
+                                    _ptr(y_true), _ptr(out), wsp, wsn), "sg_lossn_fwd")
+        return out
+
+    def lossn_bwd(self, kind, p, y_true, alpha=None, scale=1.0, out=None):
+        _chk32(p, "p"); _chk32(y_true, "y_true")
+        c = p.shape[-1]
+        dp = out if out is not None else torch.empty_like(p)
+        check(self.lib.sg_lossn_bwd(self.h, self.stream, kind, p.numel() // c, c, y_true.shape[-1], self._alpha(alpha, c),
+                                    _ptr(p), _ptr(y_true), _ptr(dp), float(scale)), "sg_lossn_bwd")
+        return dp
+
+    def confusion_matrix(self, p, y_true, out=None):
+        """out[t * C + q] += rows whose truth is class t and prediction class q (int64 [C * C], zeroed when created here)."""
+        _chk32(p, "p"); _chk32(y_true, "y_true")
+        c = p.shape[-1]
+        if out is None:
+            out = torch.zeros(c * c, dtype=torch.int64, device=self.device)
+        check(self.lib.sg_confusion_matrix(self.h, self.stream, p.numel() // c, c, y_true.shape[-1], _ptr(p), _ptr(y_true),
+                                           C.c_void_p(out.data_ptr())), "sg_confusion_matrix")
+        return out
+
     def adam_step(self, w, m, v, g, lr_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, lr_dev=None):
         """lr_dev: a one-float device tensor holding lr_t (a captured training step; lr_t is then ignored)."""
         if lr_dev is not None:
@@ -891,6 +945,15 @@ class Engine:
         assert canvas.dtype == torch.int8
         check(self.lib.sg_argmax_accumulate_i8(self.h, self.stream, _ptr(p), th, tw, C.c_void_p(canvas.data_ptr()), ch, cw,
                                                y0, x0), "sg_argmax_accumulate_i8")
+
+    def argmax_max(self, p, canvas, y0, x0):
+        """canvas[y0:, x0:] = max(canvas, argmax of the tile p [TH, TW, C]) on a uint8 class-map canvas, clipped to it."""
+        _chk32(p, "p")
+        th, tw, c = p.shape[-3], p.shape[-2], p.shape[-1]
+        ch, cw = canvas.shape
+        assert canvas.dtype == torch.uint8 and canvas.is_contiguous()
+        check(self.lib.sg_argmax_max_u8(self.h, self.stream, _ptr(p), c, th, tw, C.c_void_p(canvas.data_ptr()), ch, cw,
+                                        y0, x0), "sg_argmax_max_u8")
 
     def vote_ge(self, masks: Sequence[torch.Tensor], k: int):
         arr = (C.c_void_p * len(masks))(*[m.data_ptr() for m in masks])

@@ -51,7 +51,11 @@ def read_rgb(path: str) -> np.ndarray:
 
 def detection(img, user_path=None, model=None, save_name="model", batch: int = 8, reference_jloop: bool = True):
     """predict.py:90-116 for one model.  `img`: path or uint8 RGB array [h,w,3].  Returns the uint8 mask
-    (0/255) of shape [h,w]; writes `<user_path>/<save_name>.png` when user_path is given."""
+    (0/255) of shape [h,w]; writes `<user_path>/<save_name>.png` when user_path is given.
+
+    A model of C > 2 classes: the canvas is a uint8 class map and a tile's argmax is merged into it by MAXIMUM
+    (sg_argmax_max_u8: where tiles overlap the higher class index wins, whatever the order of the tiles; at two
+    classes that is the reference's OR).  The returned array and the PNG then hold class indices 0 ... C-1."""
     import torch
     from .ops import get_engine
     if isinstance(img, (str, os.PathLike)):
@@ -64,14 +68,21 @@ def detection(img, user_path=None, model=None, save_name="model", batch: int = 8
     canvas_img[:h, :w, :] = x
     rt = model._runtime()
     eng = rt.eng
-    pred = torch.zeros(ch, cw, dtype=torch.int8, device=eng.device)
+    class_map = model.num_classes > 2
+    pred = torch.zeros(ch, cw, dtype=torch.uint8 if class_map else torch.int8, device=eng.device)
     for s in range(0, len(origins), batch):
         chunk = origins[s:s + batch]
         tiles = np.stack([canvas_img[i:i + TILE, j:j + TILE, :] for i, j in chunk]).astype(np.float32)
         p = model.predict_device(torch.from_numpy(tiles).to(eng.device))
         for k, (i, j) in enumerate(chunk):
-            eng.argmax_accumulate(p[k], pred, i, j)             # argmax (ties -> 0) and int8 `+=` (:110-113)
-    out = np.where(pred.cpu().numpy() >= 1, 255, 0).astype(np.uint8)[:h, :w]   # :114
+            if class_map:
+                eng.argmax_max(p[k], pred, i, j)                # argmax (ties -> lowest index), merged by maximum
+            else:
+                eng.argmax_accumulate(p[k], pred, i, j)         # argmax (ties -> 0) and int8 `+=` (:110-113)
+    if class_map:
+        out = np.ascontiguousarray(pred.cpu().numpy()[:h, :w])
+    else:
+        out = np.where(pred.cpu().numpy() >= 1, 255, 0).astype(np.uint8)[:h, :w]   # :114
     if user_path is not None:
         from PIL import Image
         os.makedirs(user_path, exist_ok=True)
@@ -82,7 +93,10 @@ def detection(img, user_path=None, model=None, save_name="model", batch: int = 8
 def vote(masks: Sequence[np.ndarray], k: int = 3) -> np.ndarray:
     """model_fuse.py:315-323: `final = sum(l_i // 255)`; `np.where(final >= 3, 255, 0)` as one HIP kernel."""
     import torch
+    from . import cleanup
     from .ops import get_engine
+    for m in masks:
+        cleanup.require_binary(np.asarray(m), "vote")
     eng = get_engine(0)
     dev = [torch.from_numpy(np.ascontiguousarray(m, dtype=np.uint8)).to(eng.device) for m in masks]
     return eng.vote_ge(dev, k).cpu().numpy()

@@ -102,6 +102,16 @@ class Model:
         self._rt = None
         from . import mixed_precision
         self.compute_dtype = mixed_precision.resolve(dtype)   # "float32" | "bfloat16"
+        if self.compute_dtype == "bfloat16":
+            # the fp32 head of a bf16 model (SG_HEAD_F32) is a convolution of at most 4 output channels: the library
+            # refuses any wider one, so say so here and not at the first batch
+            for n in self.nodes:
+                if isinstance(n, L._ConvNode) and n.activation == "softmax" and n.filters > 4:
+                    _, h, w, cin = n.inputs[0].shape
+                    raise ValueError(
+                        f"softmax head {n.k}x{n.k} on [{h},{w},{cin}] with {n.filters} classes: under bf16 storage the "
+                        "convolution code keeps an fp32 head of at most 4 output channels (SG_HEAD_F32); build this model "
+                        "with dtype='float32'")
         self._fuse()
         self._layout_params()
         self.dist = None  # set by dist.DataParallel
@@ -379,14 +389,42 @@ class Model:
             optimizer = Optimizer()
         self.optimizer = optimizer
         self.loss_kind = LS.resolve_loss(loss)
+        # per-class weights of the focal losses (loss.with_alpha(...)); None: the 2-class kernels' built-in ones.  A wrong
+        # count, or edge_focal_loss without weights on more than two classes, is a ValueError here
+        self.loss_alpha = LS.resolve_alpha(loss, self.num_classes)
         self.metric_names = [LS.resolve_metric(m) for m in (metrics or [])]
         self.jit_compile = bool(jit_compile)
         self._train_graphs = {}
         self._train_graph_seen = {}
 
+    @property
+    def num_classes(self) -> int:
+        """C of the softmax head: the last axis of the model's output."""
+        return int(self.outputs[0].shape[-1])
+
+    # The head side of a step.  Two classes with the reference's weights: the 2-class entry points and the four counts
+    # {TP, TN, FP, FN}, as ever.  Otherwise sg_lossn_* with the per-class weights, and for C > 2 the C x C count matrix.
+    def _two_class(self):
+        return self.num_classes == 2 and getattr(self, "loss_alpha", None) is None
+
+    def _loss_fwd(self, eng, p, y):
+        if self._two_class():
+            return eng.loss_fwd(self.loss_kind, p, y)
+        return eng.lossn_fwd(self.loss_kind, p, y, self.loss_alpha)
+
+    def _loss_bwd(self, eng, p, y):
+        if self._two_class():
+            return eng.loss_bwd(self.loss_kind, p, y, 1.0)
+        return eng.lossn_bwd(self.loss_kind, p, y, self.loss_alpha, 1.0)
+
+    def _counts(self, eng, p, y):
+        if not self.metric_names:
+            return None
+        return eng.confusion_counts(p, y) if self.num_classes == 2 else eng.confusion_matrix(p, y)
+
     # ------------------------------------------------------------------------------------------ predict
     def predict(self, x, batch_size=32, verbose=0, **kw):
-        """numpy [N,H,W,3] (any float dtype; predict.py feeds float64) -> numpy float32 probabilities."""
+        """numpy [N,H,W,3] (any float dtype; predict.py feeds float64) -> numpy float32 probabilities [N,H,W,C]."""
         import torch
         rt = self._runtime()
         x = np.asarray(x)
@@ -453,9 +491,9 @@ class Model:
                     loss, counts = g.run(xd, yd)
                     return (loss, counts) if return_device_scalars else self._logs(loss, counts)
             p = rt.forward(xd, training=True)
-            loss = rt.eng.loss_fwd(self.loss_kind, p, yd)
-            counts = rt.eng.confusion_counts(p, yd) if self.metric_names else None
-            dp = rt.eng.loss_bwd(self.loss_kind, p, yd, 1.0)
+            loss = self._loss_fwd(rt.eng, p, yd)
+            counts = self._counts(rt.eng, p, yd)
+            dp = self._loss_bwd(rt.eng, p, yd)
             rt.backward(dp)
             grad_scale = 1.0
             if self.dist is not None:
@@ -478,8 +516,8 @@ class Model:
         with rt.eng.lock:
             xd, yd = rt.to_device(x), rt.to_device(y)
             p = rt.forward(xd, training=False)
-            loss = rt.eng.loss_fwd(self.loss_kind, p, yd)
-            counts = rt.eng.confusion_counts(p, yd) if self.metric_names else None
+            loss = self._loss_fwd(rt.eng, p, yd)
+            counts = self._counts(rt.eng, p, yd)
             if self.dist is not None:  # val_* logs describe the GLOBAL validation batch on every rank, as the training
                 loss, counts = self.dist.reduce_step_scalars(loss, counts)  # logs do: callbacks then decide alike
             rt.release()
@@ -488,8 +526,11 @@ class Model:
     def _logs(self, loss, counts):
         logs = {"loss": float(loss.item())}
         if counts is not None:
-            tp, tn, fp, fn = [int(v) for v in counts.cpu().tolist()]
-            m = LS.metrics_from_counts(tp, tn, fp, fn)
+            c = [int(v) for v in counts.cpu().tolist()]
+            if len(c) == 4 and self.num_classes == 2:
+                m = LS.metrics_from_counts(*c)          # tp, tn, fp, fn
+            else:
+                m = LS.metrics_from_matrix(np.asarray(c, np.int64).reshape(self.num_classes, self.num_classes))
             for name in self.metric_names:
                 logs[name] = m[name]
         return logs
@@ -743,9 +784,9 @@ class GraphedTrainStep:
                 eng.lane = lane
                 begin()
                 p = rt.forward(self.x, training=True)
-                self.loss = eng.loss_fwd(model.loss_kind, p, self.y)
-                self.counts = eng.confusion_counts(p, self.y) if model.metric_names else None
-                dp = eng.loss_bwd(model.loss_kind, p, self.y, 1.0)
+                self.loss = model._loss_fwd(eng, p, self.y)
+                self.counts = model._counts(eng, p, self.y)   # zeroed inside the graph, four counts or C x C
+                dp = model._loss_bwd(eng, p, self.y)
                 rt.backward(dp)
                 if not segmented:  # Adam rides in the same graph
                     eng.adam_step(rt.w_train, rt.adam_m, rt.adam_v, rt.g_train, 0.0, opt.beta_1, opt.beta_2, opt.epsilon, 1.0,

@@ -411,6 +411,12 @@ int sg_copy_channels(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, 
 int sg_softmax2_fwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, const void* z, void* p);
 int sg_softmax2_bwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, const void* p, const void* dp,
                     void* dz);
+/* The same for a last axis of C classes, 2 <= C <= SG_MAX_CLASSES (SG_F32 only; z, p [rows,C] dense, 4-byte alignment is
+ * enough): p = exp(z - max z) / sum, in place allowed (p == z); dz_c = p_c (dp_c - sum_k dp_k p_k).  Another C is
+ * SG_EINVAL.  At C = 2 the bits of the two calls above. */
+int sg_softmax_fwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* z, void* p);
+int sg_softmax_bwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* p, const void* dp,
+                   void* dz);
 /* Softmax(axis=-2) over the B stacked SK branch logits z[N,B,C] (v3plus.py:120-121), and backward. */
 int sg_softmax_branch_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int B, int C, const void* z,
                           void* p);
@@ -510,6 +516,26 @@ int sg_loss_bwd(sg_ctx* ctx, void* stream, int kind, int64_t rows, int y_cols, c
  * class 0) vs argmax of y_true[:, :2]; out[4] = int64 {TP, TN, FP, FN}, accumulated (caller zeroes). */
 int sg_confusion_counts(sg_ctx* ctx, void* stream, int64_t rows, int y_cols, const void* p,
                         const void* y_true, void* out_i64x4);
+/* The same losses and counts for C classes, 2 <= C <= SG_MAX_CLASSES: p[rows,C], y_true[rows,y_cols] with y_cols = C
+ * (one-hot) or 2C (one-hot C, then one edge weight per class); all fp32, dense, 4-byte alignment is enough.
+ *   kind 0: a_c = y_c (alpha is not read, NULL allowed);  kind 1: a_c = alpha_c * y_c;
+ *   kind 2: a_c = alpha_c * w_c * y_c with w = y_true[:, C:2C] (y_cols = 2C only);  f and L as above.
+ * alpha is a HOST array of C floats, read at the call and carried in the kernel arguments (a captured graph keeps
+ * it).  sg_lossn_fwd reduces as sg_loss_fwd does (no float atomics, the same bits run to run; ws of sg_lossn_ws_bytes);
+ * sg_lossn_bwd writes dL/dp[rows,C] scaled by grad_scale.  sg_confusion_matrix adds to out[t*C + q] (int64, the caller
+ * zeroes) the number of rows with argmax(y_true[:, :C]) == t and argmax(p) == q, ties to the lowest index; exact (a workgroup
+ * counts in 32 bits: up to 2^32 rows per workgroup, i.e. rows / 2048 < 2^32, as for the 2-class counts).
+ * C outside the range, another y_cols, kind 2 without the weight columns, a null pointer or rows <= 0 is SG_EINVAL
+ * and nothing is launched or written.  At C = 2 with alpha (.5,.5) / (.35,.65) these compute what the 2-class calls
+ * do, in the same order (the loss scalar within the rounding of its per-row sum; out = {TN, FP, FN, TP}). */
+#define SG_MAX_CLASSES 32
+size_t sg_lossn_ws_bytes(const sg_ctx* ctx, int64_t rows);
+int sg_lossn_fwd(sg_ctx* ctx, void* stream, int kind, int64_t rows, int C, int y_cols, const float* alpha,
+                 const void* p, const void* y_true, void* loss_out, void* ws, size_t ws_bytes);
+int sg_lossn_bwd(sg_ctx* ctx, void* stream, int kind, int64_t rows, int C, int y_cols, const float* alpha,
+                 const void* p, const void* y_true, void* dp, float grad_scale);
+int sg_confusion_matrix(sg_ctx* ctx, void* stream, int64_t rows, int C, int y_cols, const void* p,
+                        const void* y_true, void* out_i64);
 /* Keras-2 Adam (compile(optimizer='adam'), DeepLabv3plus.py:835) on one flat fp32
  * parameter arena: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; w -= lr_t * m / (sqrt(v) + eps) with
  * lr_t = lr*sqrt(1-b2^t)/(1-b1^t) precomputed by the host.  g is scaled by grad_scale first (1/world). */
@@ -562,6 +588,11 @@ int sg_augment_u8(sg_ctx* ctx, void* stream, int S, int H, int W, int C, const v
  * [CH,CW] canvas; tile is [TH,TW] probabilities p[TH*TW,2]. */
 int sg_argmax_accumulate_i8(sg_ctx* ctx, void* stream, const void* p, int TH, int TW, void* canvas,
                             int CH, int CW, int y0, int x0);
+/* The class-map form for C classes (2 <= C <= SG_MAX_CLASSES, p[TH*TW,C] fp32): canvas[y0+r, x0+c] = max(canvas[...],
+ * argmax_c p[r,c,:]) on a uint8 [CH,CW] canvas, clipped to it, ties to the lowest index.  The maximum does not depend
+ * on the order of the tiles; at C = 2 `canvas > 0` is the reference's OR of the tile masks. */
+int sg_argmax_max_u8(sg_ctx* ctx, void* stream, const void* p, int C, int TH, int TW, void* canvas_u8,
+                     int CH, int CW, int y0, int x0);
 /* model_fuse.py:315,323: out = 255 where sum_i (masks[i] // 255) >= k else 0; masks are u8 [n]. */
 int sg_vote_ge(sg_ctx* ctx, void* stream, int nmasks, const void* const* masks, int64_t n, int k,
                void* out_u8);

@@ -23,6 +23,8 @@ SG_LOSS_CE2, SG_LOSS_FOCAL, SG_LOSS_EDGE_FOCAL = 0, 1, 2
 SG_MAX_CLASSES = 32   # the C-class head: sg_softmax_*, sg_lossn_*, sg_confusion_matrix, sg_argmax_max_u8
 SG_AUGMENT_MAX_ITEMS = 64
 SG_AUG_FLIP_UD, SG_AUG_FLIP_LR, SG_AUG_SWAP_RB, SG_AUG_THRESHOLD = 1, 2, 4, 8
+SG_SCENE_MAX_ITEMS = 64
+SG_SYM_FLIP_UD, SG_SYM_FLIP_LR, SG_SYM_TRANSPOSE = 1, 2, 4
 
 
 class SgError(RuntimeError):
@@ -42,6 +44,11 @@ SG_WS_PREPARED = C.c_size_t(-1).value
 class AugmentItem(C.Structure):
     """Mirror of `sg_augment_item` (include/segengine.h): one output tile of sg_augment_u8."""
     _fields_ = [(n, C.c_int32) for n in ("src", "n", "shift", "flags")]
+
+
+class SceneItem(C.Structure):
+    """Mirror of `sg_scene_item` (include/segengine.h): one tile window of sg_scene_tiles_u8 / sg_prob_accumulate."""
+    _fields_ = [(n, C.c_int32) for n in ("y0", "x0", "sym", "reserved")]
 
 
 class ConvDesc(C.Structure):
@@ -184,6 +191,9 @@ _SIGNATURES = {
     "sg_augment_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     "sg_argmax_accumulate_i8": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i]),
     "sg_argmax_max_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i]),
+    "sg_scene_tiles_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "sg_prob_accumulate": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i]),
+    "sg_prob_finalize": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "sg_vote_ge": (_i, [_vp, _vp, _i, _pp, _i64, _i, _vp]),
     "sg_mask_objects_ws_bytes": (_sz, [_i, _i]),
     "sg_mask_objects": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp]),

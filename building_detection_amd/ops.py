@@ -955,6 +955,76 @@ class Engine:
         check(self.lib.sg_argmax_max_u8(self.h, self.stream, _ptr(p), c, th, tw, C.c_void_p(canvas.data_ptr()), ch, cw,
                                         y0, x0), "sg_argmax_max_u8")
 
+    @staticmethod
+    def _scene_chunks(items):
+        """(first index, ctypes table) per launch of an item list [(y0, x0, sym), ...]: SG_SCENE_MAX_ITEMS at a time, in order."""
+        items = [tuple(int(v) for v in it) for it in items]
+        cap = _lib.SG_SCENE_MAX_ITEMS
+        for i0 in range(0, len(items), cap):
+            chunk = items[i0:i0 + cap]
+            yield i0, (_lib.SceneItem * len(chunk))(*[_lib.SceneItem(y0, x0, sym, 0) for y0, x0, sym in chunk])
+
+    def _chk_dev(self, t, dtype, name):
+        if not t.is_cuda:
+            raise _lib.SgError(f"{name}: expected a CUDA (HIP) tensor - this engine has no CPU path")
+        if t.dtype != dtype:
+            raise _lib.SgError(f"{name}: expected {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise _lib.SgError(f"{name}: tensor must be contiguous")
+
+    def scene_tiles(self, scene_u8, items, tile):
+        """sg_scene_tiles_u8: uint8 scene [H,W,3] -> float32 tiles [N,tile,tile,3], tile n cut at items[n] = (y0, x0, sym) with
+        the symmetry applied and `float32(float64(s) / 127.5 - 1)` as the value (0.0 outside the scene).  More than
+        SG_SCENE_MAX_ITEMS items take several launches."""
+        self._chk_dev(scene_u8, torch.uint8, "scene_u8")
+        if scene_u8.dim() != 3 or scene_u8.shape[2] != 3:
+            raise _lib.SgError(f"scene_u8: expected [H,W,3], got {tuple(scene_u8.shape)}")
+        h, w = scene_u8.shape[:2]
+        items = list(items)
+        tile = int(tile)
+        dst = torch.empty((len(items), tile, tile, 3), dtype=torch.float32, device=self.device)
+        for i0, table in self._scene_chunks(items):
+            check(self.lib.sg_scene_tiles_u8(self.h, self.stream, h, w, _ptr(scene_u8), len(table), table, tile,
+                                             _ptr(dst[i0:i0 + len(table)])), "sg_scene_tiles_u8")
+        return dst
+
+    def prob_accumulate(self, p, items, win, acc, wsum, scale=1.0):
+        """sg_prob_accumulate: acc[CH,CW,C] += w * p[N,T,T,C] and wsum[CH,CW] += w at the windows items[n] = (y0, x0, sym),
+        w = scale * win[u] * win[v]; item by item in list order, bitwise the same however the list is split into launches.
+        fp32 only: a model that returns another storage type is cast first (Engine.cast)."""
+        _chk32(p, "p")
+        _chk32(win, "win")
+        _chk32(acc, "acc")
+        _chk32(wsum, "wsum")
+        items = list(items)
+        if p.dim() != 4 or p.shape[0] != len(items) or p.shape[1] != p.shape[2]:
+            raise _lib.SgError(f"p: expected [{len(items)},T,T,C], got {tuple(p.shape)}")
+        t, c = int(p.shape[1]), int(p.shape[3])
+        if acc.dim() != 3 or acc.shape[2] != c or tuple(wsum.shape) != tuple(acc.shape[:2]) or tuple(win.shape) != (t,):
+            raise _lib.SgError(f"acc {tuple(acc.shape)} / wsum {tuple(wsum.shape)} / win {tuple(win.shape)} do not fit "
+                               f"p {tuple(p.shape)}")
+        ch, cw = acc.shape[:2]
+        for i0, table in self._scene_chunks(items):
+            check(self.lib.sg_prob_accumulate(self.h, self.stream, c, t, _ptr(p[i0:i0 + len(table)]), len(table), table, _ptr(win),
+                                              float(scale), _ptr(acc), _ptr(wsum), ch, cw), "sg_prob_accumulate")
+
+    def prob_finalize(self, acc, wsum, out_scale, probs_out=None):
+        """sg_prob_finalize: uint8 map [CH,CW] = out_scale * argmax of acc (ties -> lowest index, 0 where wsum == 0); probs_out
+        (may be `acc`) receives acc / wsum."""
+        _chk32(acc, "acc")
+        _chk32(wsum, "wsum")
+        if acc.dim() != 3 or tuple(wsum.shape) != tuple(acc.shape[:2]):
+            raise _lib.SgError(f"acc {tuple(acc.shape)} / wsum {tuple(wsum.shape)}: expected [CH,CW,C] and [CH,CW]")
+        if probs_out is not None:
+            _chk32(probs_out, "probs_out")
+            if tuple(probs_out.shape) != tuple(acc.shape):
+                raise _lib.SgError(f"probs_out {tuple(probs_out.shape)} is not acc's {tuple(acc.shape)}")
+        ch, cw, c = acc.shape
+        out = torch.empty((ch, cw), dtype=torch.uint8, device=self.device)
+        check(self.lib.sg_prob_finalize(self.h, self.stream, c, _ptr(acc), _ptr(wsum), ch, cw, _ptr(probs_out), int(out_scale),
+                                        _ptr(out)), "sg_prob_finalize")
+        return out
+
     def vote_ge(self, masks: Sequence[torch.Tensor], k: int):
         arr = (C.c_void_p * len(masks))(*[m.data_ptr() for m in masks])
         out = torch.empty_like(masks[0])

@@ -3,6 +3,7 @@
     load_model()                 -> (res_model, hr_model, v3_model, unet_model, bam_model)   predict.py:17-54
     detection(img, user_path, model, save_name)  sliding 512-px window, stride 360, argmax, OR-merge   :90-116
     vote(masks, k=3)             -> 255 where at least k of the 5 cleaned masks agree          model_fuse.py:315-323
+    detection_soft(img, user_path, models, ...)  probability-domain counterpart (no reference: SoftScene below)
 
 What changes against the reference: tiles of one image are predicted in batches on the GPU instead of one
 `model.predict` per tile (BatchNorm runs on moving statistics in inference, so per-tile results do not depend
@@ -88,6 +89,137 @@ def detection(img, user_path=None, model=None, save_name="model", batch: int = 8
         os.makedirs(user_path, exist_ok=True)
         Image.fromarray(out).save(os.path.join(user_path, f"{save_name}.png"), compress_level=0)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ soft scene inference
+# Beside the reference's hard-decision loop above: tiles are cut from the uint8 scene on the device (sg_scene_tiles_u8),
+# their probabilities are averaged where tiles overlap, optionally under a window and over the symmetries of the square
+# (sg_prob_accumulate), and several models meet as a weighted mean of probabilities (sg_prob_finalize takes the argmax).
+TTA_PRESETS = {1: [0], 2: [0, 2], 4: [0, 1, 2, 3], 8: list(range(8))}
+
+
+def scene_origins(h: int, w: int, tile: int = TILE, stride: int = STRIDE):
+    """((ch, cw), [(y0, x0), ...]) row-major: per axis num = max(1, ceil((dim - overlap) / stride)) tiles at multiples of
+    `stride`, overlap = tile - stride.  At 512/360 these are tile_origins(h, w, reference_jloop=False) for axes longer than
+    the overlap (a shorter axis gets no tile there and one tile here)."""
+    tile, stride = int(tile), int(stride)
+    if not 0 < stride <= tile:
+        raise ValueError(f"stride {stride} outside (0, tile = {tile}]")
+    overlap = tile - stride
+    nums = [max(1, math.ceil((d - overlap) / stride)) for d in (h, w)]
+    ch, cw = (max(n * stride + overlap, tile) for n in nums)
+    rows, cols = (range(0, n * stride, stride) for n in nums)
+    return (ch, cw), [(i, j) for i in rows for j in cols]
+
+
+def make_window(window, tile: int) -> np.ndarray:
+    """float32 [tile]: "flat" = ones, "pyramid" = min(i+1, tile-i) / ceil(tile/2), or a positive array of length `tile`."""
+    if isinstance(window, str):
+        if window == "flat":
+            return np.ones(tile, np.float32)
+        if window == "pyramid":
+            i = np.arange(tile)
+            return (np.minimum(i + 1, tile - i) / math.ceil(tile / 2)).astype(np.float32)
+        raise ValueError(f"window={window!r}: 'flat', 'pyramid' or an array of {tile} positive weights")
+    win = np.asarray(window, dtype=np.float32)
+    if win.shape != (tile,):
+        raise ValueError(f"window of shape {win.shape}, expected ({tile},)")
+    if not (win > 0).all():       # also refuses NaN
+        raise ValueError("window entries must be positive")
+    return np.ascontiguousarray(win)
+
+
+def tta_symmetries(tta) -> List[int]:
+    """The symmetry codes of a `tta` argument: a preset (1, 2, 4, 8) or an iterable of codes 0 ... 7."""
+    if isinstance(tta, (int, np.integer)):
+        if int(tta) not in TTA_PRESETS:
+            raise ValueError(f"tta={tta}: presets are {sorted(TTA_PRESETS)}; pass a list for other symmetry sets")
+        return list(TTA_PRESETS[int(tta)])
+    syms = [int(s) for s in tta]
+    if not syms or any(not 0 <= s < 8 for s in syms):
+        raise ValueError(f"tta={tta!r}: symmetry codes are 0 ... 7 (SG_SYM_FLIP_UD | _FLIP_LR | _TRANSPOSE)")
+    return syms
+
+
+class SoftScene:
+    """Probability canvases of one scene: `acc` [h,w,C] = sum of w * p and `wsum` [h,w] = sum of w on the device, filled by
+    add() model by model and read by result().  The image is uploaded once as uint8; overhanging tiles are clipped by the
+    kernels (no padded canvas)."""
+
+    def __init__(self, img, num_classes: int, tile: int = TILE, stride: int = STRIDE, window="flat", engine=None):
+        import torch
+        from .ops import get_engine
+        if isinstance(img, (str, os.PathLike)):
+            img = read_rgb(str(img))
+        arr = np.ascontiguousarray(img)
+        if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
+            raise ValueError(f"img: expected a uint8 RGB array [h,w,3], got {arr.dtype} {arr.shape}")
+        self.eng = engine if engine is not None else get_engine(0)
+        self.num_classes, self.tile, self.stride = int(num_classes), int(tile), int(stride)
+        self.h, self.w = arr.shape[:2]
+        _, self.origins = scene_origins(self.h, self.w, self.tile, self.stride)
+        dev = self.eng.device
+        self.scene = torch.from_numpy(arr).to(dev)
+        self.win = torch.from_numpy(make_window(window, self.tile)).to(dev)
+        self.acc = torch.zeros(self.h, self.w, self.num_classes, dtype=torch.float32, device=dev)
+        self.wsum = torch.zeros(self.h, self.w, dtype=torch.float32, device=dev)
+
+    def work_list(self, tta=1):
+        """[(y0, x0, sym), ...]: origins-major, then symmetries."""
+        syms = tta_symmetries(tta)
+        return [(i, j, s) for i, j in self.origins for s in syms]
+
+    def add(self, model, tta=1, weight: float = 1.0, batch: int = 8):
+        import torch
+        shape = tuple(model.inputs[0].shape[1:])
+        if shape != (self.tile, self.tile, 3):
+            raise ValueError(f"model input {shape} is not the scene's tile {(self.tile, self.tile, 3)}")
+        if model.num_classes != self.num_classes:
+            raise ValueError(f"model has {model.num_classes} classes, the scene {self.num_classes}")
+        eng = self.eng
+        work = self.work_list(tta)
+        for s in range(0, len(work), batch):
+            chunk = work[s:s + batch]
+            p = model.predict_device(eng.scene_tiles(self.scene, chunk, self.tile))
+            if p.dtype != torch.float32:
+                p = eng.cast(p, torch.float32)
+            eng.prob_accumulate(p, chunk, self.win, self.acc, self.wsum, scale=weight)
+        return self
+
+    def result(self, return_probs: bool = False):
+        """The uint8 array [h,w] (0/255 at two classes, class indices otherwise); with return_probs also acc / wsum as
+        float32 [h,w,C]."""
+        import torch
+        probs = torch.empty_like(self.acc) if return_probs else None
+        out = self.eng.prob_finalize(self.acc, self.wsum, 255 if self.num_classes == 2 else 1, probs).cpu().numpy()
+        return (out, probs.cpu().numpy()) if return_probs else out
+
+
+def detection_soft(img, user_path=None, models=None, save_name="model", batch: int = 8, tta=1, window="flat", weights=None,
+                   tile=None, stride=None, return_probs: bool = False):
+    """Soft counterpart of detection(): `models` is one model or a sequence (the soft ensemble: the mean of the models'
+    probabilities under `weights`, default all 1).  tile defaults to the model's input height; stride to 360 at tile 512.
+    Returns the uint8 array (and the probabilities with return_probs); writes `<user_path>/<save_name>.png` when given."""
+    models = list(models) if isinstance(models, (list, tuple)) else [models]
+    if not models or models[0] is None:
+        raise ValueError("detection_soft: no model")
+    weights = [1.0] * len(models) if weights is None else [float(v) for v in weights]
+    if len(weights) != len(models):
+        raise ValueError(f"{len(weights)} weights for {len(models)} models")
+    tile = int(models[0].inputs[0].shape[1]) if tile is None else int(tile)
+    if stride is None:
+        if tile != TILE:
+            raise ValueError(f"tile {tile}: give a stride (only {TILE} has the default {STRIDE})")
+        stride = STRIDE
+    scene = SoftScene(img, models[0].num_classes, tile, stride, window, engine=models[0]._runtime().eng)
+    for m, wt in zip(models, weights):
+        scene.add(m, tta=tta, weight=wt, batch=batch)
+    res = scene.result(return_probs)
+    if user_path is not None:
+        from PIL import Image
+        os.makedirs(user_path, exist_ok=True)
+        Image.fromarray(res[0] if return_probs else res).save(os.path.join(user_path, f"{save_name}.png"), compress_level=0)
+    return res
 
 
 def vote(masks: Sequence[np.ndarray], k: int = 3) -> np.ndarray:

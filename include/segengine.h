@@ -593,6 +593,42 @@ int sg_argmax_accumulate_i8(sg_ctx* ctx, void* stream, const void* p, int TH, in
  * on the order of the tiles; at C = 2 `canvas > 0` is the reference's OR of the tile masks. */
 int sg_argmax_max_u8(sg_ctx* ctx, void* stream, const void* p, int C, int TH, int TW, void* canvas_u8,
                      int CH, int CW, int y0, int x0);
+/* Soft scene inference (no counterpart in the reference, which stitches arg-maxed tiles): tiles are cut from the uint8
+ * scene on the device, and their probabilities are averaged on fp32 canvases, optionally under a window and over the 8
+ * symmetries of the square.  One table item places one T x T tile: for tile coordinate (r, c)
+ *     (a, b) = (sym & SG_SYM_TRANSPOSE) ? (c, r) : (r, c)
+ *     u = (sym & SG_SYM_FLIP_UD) ? T-1-a : a,   v = (sym & SG_SYM_FLIP_LR) ? T-1-b : b
+ * and tile element (r, c) corresponds to scene / canvas pixel (y0+u, x0+v).  0 <= sym < 8, |y0|, |x0| < 2^30 (an origin
+ * may be negative or lie past the image: both kernels clip), reserved = 0, 1 <= N <= SG_SCENE_MAX_ITEMS; the table is
+ * checked on the host before anything is launched (SG_EINVAL otherwise).
+ *   sg_scene_tiles_u8   scene_u8[H,W,3] -> tiles_f32[N,T,T,3]: tiles[n,r,c,k] = (float)((double)scene[y0+u,x0+v,k] / 127.5
+ *                       - 1.0) (predict.py:93 in float64, rounded once), 0.0f where the pixel lies outside the scene
+ *                       (predict.py:102's zero canvas).  H*W*3 < 2^31, N*T*T*3*4 < 2^31.
+ *   sg_prob_accumulate  p_f32[N,T,T,C] -> acc_f32[CH,CW,C], wsum_f32[CH,CW]: for every item n in table order and every
+ *                       (r, c) whose canvas pixel (y, x) lies inside the canvas, w = (scale * win[u]) * win[v];
+ *                       acc[y,x,k] = fmaf(w, p[n,r,c,k], acc[y,x,k]); wsum[y,x] += w.  win_f32[T] is indexed by the
+ *                       canvas-relative position.  No float atomics: one thread owns a canvas element and adds its items in
+ *                       table order to what the canvas held, so the result is bitwise reproducible and does not depend on
+ *                       how a list of items is split into launches.  2 <= C <= SG_MAX_CLASSES, T*T*C < 2^31, CH, CW < 2^30;
+ *                       the canvases are indexed in 64 bits.
+ *   sg_prob_finalize    map_u8[CH,CW] = out_scale * argmax_k acc[y,x,k] (ties -> lowest index; out_scale >= 1 and
+ *                       out_scale * (C-1) <= 255), probs_out_f32[CH,CW,C] = acc / wsum when given (may be acc itself);
+ *                       where wsum == 0 both are 0. */
+#define SG_SCENE_MAX_ITEMS 64
+#define SG_SYM_FLIP_UD   1      /* same bits as SG_AUG_FLIP_UD / _LR */
+#define SG_SYM_FLIP_LR   2
+#define SG_SYM_TRANSPOSE 4
+typedef struct sg_scene_item {
+  int32_t y0, x0;    /* scene / canvas pixel of the tile window's corner */
+  int32_t sym;       /* SG_SYM_* */
+  int32_t reserved;  /* must be 0 */
+} sg_scene_item;
+int sg_scene_tiles_u8(sg_ctx* ctx, void* stream, int H, int W, const void* scene_u8, int N, const sg_scene_item* items,
+                      int T, void* tiles_f32);
+int sg_prob_accumulate(sg_ctx* ctx, void* stream, int C, int T, const void* p_f32, int N, const sg_scene_item* items,
+                       const void* win_f32, float scale, void* acc_f32, void* wsum_f32, int CH, int CW);
+int sg_prob_finalize(sg_ctx* ctx, void* stream, int C, const void* acc_f32, const void* wsum_f32, int CH, int CW,
+                     void* probs_out_f32, int out_scale, void* map_u8);
 /* model_fuse.py:315,323: out = 255 where sum_i (masks[i] // 255) >= k else 0; masks are u8 [n]. */
 int sg_vote_ge(sg_ctx* ctx, void* stream, int nmasks, const void* const* masks, int64_t n, int k,
                void* out_u8);

@@ -1,0 +1,132 @@
+#!/usr/bin/env python
+"""Times whole-scene inference of one DeepLabv3+ (fp32, 512-px tiles, stride 360, batch 8) on random 2048^2 and 4096^2
+scenes: pipeline.detection(reference_jloop=False) - the hard-decision loop with its host-side tile preparation - against
+pipeline.detection_soft at tta 1 / flat window and at tta 8 / pyramid window.
+
+Per scene size it reports
+  * the time per scene of the three paths: a host clock around the call, which ends in the device-to-host copy of the
+    result; the median, minimum and maximum of --reps calls after one warm-up call each, detection and the tta-1 soft path
+    alternating;
+  * the host-cut + upload part of detection(): ITS statements (float64 canvas, slice + stack + float32 cast, upload) run on
+    their own without a model, host clock, synchronised after every upload - and its share of detection()'s time;
+  * the device time of all sg_scene_tiles_u8 launches and of all sg_prob_accumulate launches of one scene, each set run
+    back-to-back between two device events (launch gaps included), and their shares of the soft path's time.
+Imports the engine only; needs the GPU (no time is reported without one).  One JSON line per row, then the file.
+
+    python scripts/bench_scene.py [--sizes 2048 4096] [--reps 3] [--batch 8] [--out profiles/scene_bench.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from building_detection_amd import pipeline as PL, zoo   # noqa: E402
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def stats(ms):
+    return {"ms": round(statistics.median(ms), 2), "ms_min": round(min(ms), 2), "ms_max": round(max(ms), 2), "reps": len(ms)}
+
+
+def host_prep(img, batch, device):
+    """detection()'s tile preparation (pipeline.py, the statements around model.predict_device) without the model."""
+    h, w = img.shape[:2]
+    x = img.astype(np.float64) / 127.5 - 1
+    (ch, cw), origins = PL.tile_origins(h, w, False)
+    canvas = np.zeros((ch, cw, 3))
+    canvas[:h, :w, :] = x
+    for s in range(0, len(origins), batch):
+        chunk = origins[s:s + batch]
+        tiles = np.stack([canvas[i:i + PL.TILE, j:j + PL.TILE, :] for i, j in chunk]).astype(np.float32)
+        torch.from_numpy(tiles).to(device)
+        torch.cuda.synchronize()
+
+
+def device_ms(fn, runs=5):
+    """Median device time of fn() (a set of launches) between two events, after one warm-up."""
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(runs):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return round(statistics.median(out), 3)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[2048, 4096])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_scene: no GPU - times are measured on the device or not at all")
+    model = zoo.Xception_DeepLabV3_Plus((512, 512, 3))
+    eng = model._runtime().eng
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    for size in a.sizes:
+        img = np.random.default_rng(size).integers(0, 256, size=(size, size, 3), dtype=np.uint8)
+        paths = {"detection": lambda: PL.detection(img, None, model, batch=a.batch, reference_jloop=False),
+                 "soft_tta1_flat": lambda: PL.detection_soft(img, None, model, batch=a.batch, tta=1, window="flat"),
+                 "soft_tta8_pyramid": lambda: PL.detection_soft(img, None, model, batch=a.batch, tta=8, window="pyramid")}
+        times = {k: [] for k in paths}
+        for fn in paths.values():            # warm-up: every shape of the timed windows
+            fn()
+        for _ in range(a.reps):              # the two comparable paths alternate
+            for k in ("detection", "soft_tta1_flat"):
+                times[k].append(wall(paths[k]))
+        for _ in range(a.reps):
+            times["soft_tta8_pyramid"].append(wall(paths["soft_tta8_pyramid"]))
+        ntiles = len(PL.scene_origins(size, size)[1])
+        for k, ms in times.items():
+            emit({"scene": size, "what": k, "tiles": ntiles * (8 if "tta8" in k else 1), **stats(ms)})
+        host_prep(img, a.batch, eng.device)
+        prep = stats([wall(lambda: host_prep(img, a.batch, eng.device)) for _ in range(a.reps)])
+        emit({"scene": size, "what": "detection: host cut + upload", **prep,
+              "share_of_detection": round(prep["ms"] / statistics.median(times["detection"]), 4)})
+        for name, tta, window in (("soft_tta1_flat", 1, "flat"), ("soft_tta8_pyramid", 8, "pyramid")):
+            sc = PL.SoftScene(img, 2, window=window, engine=eng)
+            work = sc.work_list(tta)
+            chunks = [work[s:s + a.batch] for s in range(0, len(work), a.batch)]
+            p = torch.rand(a.batch, 512, 512, 2, device=eng.device)
+            cut = device_ms(lambda: [eng.scene_tiles(sc.scene, c, 512) for c in chunks])
+            acc = device_ms(lambda: [eng.prob_accumulate(p[:len(c)], c, sc.win, sc.acc, sc.wsum) for c in chunks])
+            total = statistics.median(times[name])
+            emit({"scene": size, "what": f"{name}: sg_scene_tiles_u8, all launches", "launches": len(chunks), "device_ms": cut,
+                  "share_of_path": round(cut / total, 4)})
+            emit({"scene": size, "what": f"{name}: sg_prob_accumulate, all launches", "launches": len(chunks), "device_ms": acc,
+                  "share_of_path": round(acc / total, 4)})
+            del sc, p
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -51,6 +51,13 @@ class SceneItem(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("y0", "x0", "sym", "reserved")]
 
 
+class RegionDesc(C.Structure):
+    """Mirror of `sg_region_desc` (include/segengine.h): a region-overlap loss, alone or added to a pointwise loss."""
+    _fields_ = ([(n, C.c_int32) for n in ("C", "y_cols", "images", "point_kind")] + [("rows_per_image", C.c_int64)] +
+                [(n, C.c_float) for n in ("a", "b", "smooth", "gamma", "point_weight", "region_weight")] +
+                [("class_w", C.c_float * SG_MAX_CLASSES), ("point_alpha", C.c_float * SG_MAX_CLASSES)])
+
+
 class ConvDesc(C.Structure):
     """Mirror of `sg_conv_desc` (include/segengine.h)."""
 
@@ -184,6 +191,9 @@ _SIGNATURES = {
     "sg_lossn_fwd": (_i, [_vp, _vp, _i, _i64, _i, _i, _fp, _vp, _vp, _vp, _vp, _sz]),
     "sg_lossn_bwd": (_i, [_vp, _vp, _i, _i64, _i, _i, _fp, _vp, _vp, _vp, _f]),
     "sg_confusion_matrix": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "sg_loss_region_ws_bytes": (_sz, [_vp, C.POINTER(RegionDesc)]),
+    "sg_loss_region_fwd": (_i, [_vp, _vp, C.POINTER(RegionDesc), _vp, _vp, _vp, _vp, _vp, _sz]),
+    "sg_loss_region_bwd": (_i, [_vp, _vp, C.POINTER(RegionDesc), _vp, _vp, _vp, _vp, _f]),
     "sg_adam_step": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f]),
     "sg_adam_step_lr": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f]),
     "sg_edge_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -8,6 +8,10 @@ functions) and runs the fused HIP kernels `sg_loss_fwd/bwd` and `sg_confusion_co
 A model of C > 2 classes runs `sg_lossn_fwd/bwd` and `sg_confusion_matrix`: the focal losses then carry one weight per
 class (`focal_loss.with_alpha([...])`, `edge_focal_loss.with_alpha([...])`), and the four metrics come from the C x C
 matrix (`metrics_from_matrix`).
+
+Beyond the reference: the region-overlap losses `dice_loss`, `jaccard_loss`, `tversky_loss(alpha, beta)` and
+`compound(pointwise, region)`, which adds one of them to one of the three losses above (`sg_loss_region_fwd/bwd`, at 2 ... 32
+classes).
 """
 from __future__ import annotations
 
@@ -62,6 +66,93 @@ class _FocalLoss(_Named):
 binary_crossentropy = _Named("binary_crossentropy", "CE on softmax probabilities (DeepLabv3plus.py:490-499)")
 focal_loss = _FocalLoss("focal_loss", "focal loss, alpha = .5 for every class, gamma=2 (DeepLabv3plus.py:502-512)")
 edge_focal_loss = _FocalLoss("edge_focal_loss", "edge-weighted focal loss, alpha=(.35,.65) at 2 classes (DeepLabv3plus.py:515-527)")
+
+
+def _finite(v):
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        return None
+    return v if np.isfinite(v) else None
+
+
+class _RegionLoss(_Named):
+    """A region-overlap loss (no counterpart in the reference).  Per group g - the batch, or one image with
+    `per_image` - and class c, with I = sum p y, P = sum p, Y = sum y over the group's pixels:
+
+        T = (I + smooth) / (I + alpha (P - I) + beta (Y - I) + smooth),   l[g,c] = (1 - T)^gamma,
+        L = sum_g sum_c w_c l[g,c] / (G * sum_c w_c).
+
+    alpha = beta = .5 is Dice, T = (2 I + 2 smooth) / (P + Y + 2 smooth): `smooth` here is HALF the smoothing constant of the
+    usual Dice notation.  alpha = beta = 1 is Jaccard (soft IoU); gamma > 1 is the focal-Tversky form."""
+
+    smooth, gamma, class_weights, per_image = 1.0, 1.0, None, False
+
+    def __init__(self, name, doc, alpha, beta):
+        super().__init__(name, doc)
+        a, b = _finite(alpha), _finite(beta)
+        if a is None or b is None or a < 0 or b < 0:
+            raise ValueError(f"{name}: alpha = {alpha!r}, beta = {beta!r} must be finite and >= 0")
+        self.alpha, self.beta = a, b
+
+    def with_options(self, smooth=1.0, gamma=1.0, class_weights=None, per_image=False):
+        s, g = _finite(smooth), _finite(gamma)
+        if s is None or s <= 0:
+            raise ValueError(f"{self.__name__}.with_options: smooth = {smooth!r} must be finite and > 0")
+        if g is None or g < 1:
+            raise ValueError(f"{self.__name__}.with_options: gamma = {gamma!r} must be finite and >= 1")
+        w = None
+        if class_weights is not None:
+            w = tuple(_finite(v) for v in class_weights)
+            if not w or any(v is None or v < 0 for v in w) or not sum(w) > 0:
+                raise ValueError(f"{self.__name__}.with_options: class_weights = {class_weights!r} must be finite, >= 0 and "
+                                 "have a positive sum")
+        out = _RegionLoss(self.__name__, self.__doc__, self.alpha, self.beta)
+        out.smooth, out.gamma, out.class_weights, out.per_image = s, g, w, bool(per_image)
+        return out
+
+    def __repr__(self):
+        return (f"<building_detection_amd {self.__name__} alpha={self.alpha} beta={self.beta} smooth={self.smooth} "
+                f"gamma={self.gamma} class_weights={self.class_weights} per_image={self.per_image}>")
+
+
+dice_loss = _RegionLoss("dice_loss", "soft Dice loss: 1 - (2 I + 2 smooth) / (P + Y + 2 smooth) per class", 0.5, 0.5)
+jaccard_loss = _RegionLoss("jaccard_loss", "soft Jaccard (IoU) loss: 1 - (I + smooth) / (P + Y - I + smooth) per class", 1.0, 1.0)
+
+
+def tversky_loss(alpha, beta):
+    """Tversky loss: alpha weighs the false positives P - I, beta the false negatives Y - I."""
+    return _RegionLoss("tversky_loss", "Tversky loss: 1 - (I + smooth) / (I + alpha (P - I) + beta (Y - I) + smooth) per class",
+                       alpha, beta)
+
+
+class _CompoundLoss(_Named):
+    """pointwise_weight * pointwise + region_weight * region, evaluated by ONE forward and ONE backward pass."""
+
+    def __init__(self, pointwise, region, region_weight, pointwise_weight):
+        super().__init__(f"{pointwise.__name__}+{region.__name__}", self.__doc__)
+        self.pointwise, self.region, self.region_weight, self.pointwise_weight = pointwise, region, region_weight, pointwise_weight
+
+    def __repr__(self):
+        return f"<building_detection_amd {self.pointwise_weight} * {self.pointwise!r} + {self.region_weight} * {self.region!r}>"
+
+
+def compound(pointwise, region, region_weight=1.0, pointwise_weight=1.0):
+    """`pointwise` is binary_crossentropy, focal_loss or edge_focal_loss (with or without with_alpha), `region` one of
+    dice_loss / jaccard_loss / tversky_loss(...).  The weights are >= 0 and not both 0."""
+    if not isinstance(pointwise, _Named) or pointwise.__name__ not in _LOSS_KINDS:
+        raise ValueError(f"compound: pointwise = {pointwise!r} is not one of {sorted(_LOSS_KINDS)}")
+    if not isinstance(region, _RegionLoss):
+        raise ValueError(f"compound: region = {region!r} is not dice_loss, jaccard_loss or a tversky_loss(...)")
+    wr, wp = _finite(region_weight), _finite(pointwise_weight)
+    if wr is None or wp is None or wr < 0 or wp < 0 or wr + wp == 0:
+        raise ValueError(f"compound: region_weight = {region_weight!r}, pointwise_weight = {pointwise_weight!r} must be finite, "
+                         ">= 0 and not both 0")
+    return _CompoundLoss(pointwise, region, wr, wp)
+
+
+NO_POINTWISE = -1   # sg_region_desc.point_kind of a region loss on its own
+
 PA = _Named("PA", "pixel accuracy (DeepLabv3plus.py:530-553)")
 IoU = _Named("IoU", "foreground IoU (DeepLabv3plus.py:556-575)")
 MIoU = _Named("MIoU", "mean of foreground / background IoU (DeepLabv3plus.py:578-598)")
@@ -85,16 +176,54 @@ def _warn_foreign(fn, what, lines):
 
 
 def resolve_loss(loss) -> int:
+    """The pointwise kind of `loss`: SG_LOSS_* for the reference's three names (and for the pointwise part of a compound),
+    NO_POINTWISE for a region loss on its own."""
+    if isinstance(loss, _CompoundLoss):
+        return _LOSS_KINDS[loss.pointwise.__name__]
+    if isinstance(loss, _RegionLoss):
+        return NO_POINTWISE
     name = loss if isinstance(loss, str) else getattr(loss, "__name__", None)
     if name not in _LOSS_KINDS:
-        raise ValueError(f"loss {loss!r}: the engine implements {sorted(_LOSS_KINDS)} (train_model/DeepLabv3plus.py:490-527)")
+        raise ValueError(f"loss {loss!r}: the engine implements {sorted(_LOSS_KINDS)} (train_model/DeepLabv3plus.py:490-527), "
+                         "dice_loss, jaccard_loss, tversky_loss(alpha, beta) and compound(pointwise, region)")
     _warn_foreign(loss, "loss", "490-527")
     return _LOSS_KINDS[name]
+
+
+_TWO_CLASS_ALPHA = {SG_LOSS_FOCAL: (0.5, 0.5), SG_LOSS_EDGE_FOCAL: (0.35, 0.65)}   # what the 2-class kernels have built in
+
+
+def resolve_region(loss, num_classes: int):
+    """The fields of `sg_region_desc` that `loss` fixes for a `num_classes` model, or None for a loss without a region term:
+    dict(a, b, smooth, gamma, class_w, per_image, point_kind, point_alpha, point_weight, region_weight).  class_w has
+    `num_classes` entries (ones when none were given); point_alpha is None (no pointwise term, or cross-entropy) or
+    `num_classes` weights - at two classes without with_alpha the reference's own, passed explicitly."""
+    if isinstance(loss, _CompoundLoss):
+        region, kind = loss.region, _LOSS_KINDS[loss.pointwise.__name__]
+        alpha = resolve_alpha(loss.pointwise, num_classes)
+        if alpha is None and kind != SG_LOSS_CE2:
+            alpha = _TWO_CLASS_ALPHA[kind]
+        wp, wr = loss.pointwise_weight, loss.region_weight
+    elif isinstance(loss, _RegionLoss):
+        region, kind, alpha, wp, wr = loss, NO_POINTWISE, None, 0.0, 1.0
+    else:
+        return None
+    w = region.class_weights
+    if w is None:
+        w = (1.0,) * num_classes
+    elif len(w) != num_classes:
+        raise ValueError(f"the loss carries {len(w)} class weights, the model has {num_classes} classes")
+    return dict(a=region.alpha, b=region.beta, smooth=region.smooth, gamma=region.gamma, class_w=tuple(w),
+                per_image=region.per_image, point_kind=kind, point_alpha=alpha, point_weight=wp, region_weight=wr)
 
 
 def resolve_alpha(loss, num_classes: int):
     """The per-class weights `loss` trains a `num_classes` model with: None = what the 2-class kernels have built in
     (no weights given, 2 classes; cross-entropy has none at all), else a tuple of `num_classes` floats."""
+    if isinstance(loss, _CompoundLoss):
+        return resolve_alpha(loss.pointwise, num_classes)
+    if isinstance(loss, _RegionLoss):
+        return None
     kind = _LOSS_KINDS[loss if isinstance(loss, str) else getattr(loss, "__name__", None)]
     alpha = getattr(loss, "alpha", None)
     if kind == SG_LOSS_CE2:

@@ -911,6 +911,49 @@ class Engine:
                                     _ptr(p), _ptr(y_true), _ptr(dp), float(scale)), "sg_lossn_bwd")
         return dp
 
+    @staticmethod
+    def region_desc(region, p, y_true):
+        """`sg_region_desc` of `region` (the dict of losses.resolve_region) for p [N, ..., C] and y_true [N, ..., C or 2C]:
+        one group per image of the leading axis with per_image, else one for the batch."""
+        c, y_cols = int(p.shape[-1]), int(y_true.shape[-1])
+        rows = p.numel() // c
+        if y_true.numel() != rows * y_cols or y_cols not in (c, 2 * c):
+            raise ValueError(f"y_true {tuple(y_true.shape)} does not go with p {tuple(p.shape)}: C or 2C columns per pixel")
+        if region["point_kind"] == _lib.SG_LOSS_EDGE_FOCAL and y_cols != 2 * c:
+            raise ValueError(f"edge_focal_loss needs y_true[..., {2 * c}] (one-hot, then one edge weight per class), got {y_cols} columns")
+        if len(region["class_w"]) != c or (region["point_alpha"] is not None and len(region["point_alpha"]) != c):
+            raise ValueError(f"the loss carries class weights for another class count than {c}")
+        images = int(p.shape[0]) if region["per_image"] and p.dim() > 1 else 1
+        d = _lib.RegionDesc(C=c, y_cols=y_cols, images=images, point_kind=int(region["point_kind"]), rows_per_image=rows // images,
+                            a=region["a"], b=region["b"], smooth=region["smooth"], gamma=region["gamma"],
+                            point_weight=region["point_weight"], region_weight=region["region_weight"])
+        for i in range(c):
+            d.class_w[i] = region["class_w"][i]
+            d.point_alpha[i] = 1.0 if region["point_alpha"] is None else region["point_alpha"][i]
+        return d
+
+    def loss_region_fwd(self, region, p, y_true):
+        """A region-overlap loss, alone or with its pointwise term, in one pass (sg_loss_region_fwd).  Returns (loss, coef):
+        loss = {L, L_point, L_region}, coef [images, 2C] = the per-class {A, B} loss_region_bwd forms the gradient from."""
+        _chk32(p, "p"); _chk32(y_true, "y_true")
+        d = self.region_desc(region, p, y_true)
+        out, coef = self.empty(3), self.empty(d.images, 2 * d.C)
+        wsp, wsn = self.ws(self.lib.sg_loss_region_ws_bytes(self.h, C.byref(d)))
+        check(self.lib.sg_loss_region_fwd(self.h, self.stream, C.byref(d), _ptr(p), _ptr(y_true), _ptr(out), _ptr(coef), wsp, wsn),
+              "sg_loss_region_fwd")
+        return out, coef
+
+    def loss_region_bwd(self, region, p, y_true, coef, scale=1.0, out=None):
+        """dL/dp of loss_region_fwd's L, times `scale`; `coef` is what the forward call returned for the same p and y_true."""
+        _chk32(p, "p"); _chk32(y_true, "y_true"); _chk32(coef, "coef")
+        d = self.region_desc(region, p, y_true)
+        if tuple(coef.shape) != (d.images, 2 * d.C):
+            raise ValueError(f"coef {tuple(coef.shape)} is not the forward call's [{d.images}, {2 * d.C}]")
+        dp = out if out is not None else torch.empty_like(p)
+        check(self.lib.sg_loss_region_bwd(self.h, self.stream, C.byref(d), _ptr(p), _ptr(y_true), _ptr(coef), _ptr(dp), float(scale)),
+              "sg_loss_region_bwd")
+        return dp
+
     def confusion_matrix(self, p, y_true, out=None):
         """out[t * C + q] += rows whose truth is class t and prediction class q (int64 [C * C], zeroed when created here)."""
         _chk32(p, "p"); _chk32(y_true, "y_true")

@@ -382,7 +382,12 @@ class Model:
     def compile(self, optimizer="adam", loss=None, metrics=None, jit_compile=False, **kw):
         """jit_compile (tf.keras's name for "compile the train step"): capture the whole training step - forward, loss,
         metric counts, backward, Adam - into one hipGraph per input shape and replay it (GraphedTrainStep).  Same
-        kernels, same order: bit-identical to the eager step; ~1800 launches per step become one."""
+        kernels, same order: bit-identical to the eager step; ~1800 launches per step become one.
+
+        loss: one of the reference's three, or a region-overlap loss (losses.dice_loss, jaccard_loss, tversky_loss(a, b)) or
+        losses.compound(pointwise, region); logs["loss"] is then L = pointwise_weight * L_point + region_weight * L_region.
+        Under data parallelism (model.dist) every rank computes the region term on its own batch; the gradients are averaged
+        as ever and the logged loss is the mean over the ranks."""
         if isinstance(optimizer, str):
             if optimizer.lower() != "adam":
                 raise ValueError("the reference compiles with optimizer='adam' (DeepLabv3plus.py:835)")
@@ -392,6 +397,11 @@ class Model:
         # per-class weights of the focal losses (loss.with_alpha(...)); None: the 2-class kernels' built-in ones.  A wrong
         # count, or edge_focal_loss without weights on more than two classes, is a ValueError here
         self.loss_alpha = LS.resolve_alpha(loss, self.num_classes)
+        # a region-overlap loss or a compound: the descriptor fields sg_loss_region_* run by, else None.  (Under data
+        # parallelism the sums I, P, Y are not exchanged: the mean of the ranks' region losses is not the region loss of the
+        # global batch.)
+        self.loss_region = LS.resolve_region(loss, self.num_classes)
+        self._loss_coef = None
         self.metric_names = [LS.resolve_metric(m) for m in (metrics or [])]
         self.jit_compile = bool(jit_compile)
         self._train_graphs = {}
@@ -407,12 +417,19 @@ class Model:
     def _two_class(self):
         return self.num_classes == 2 and getattr(self, "loss_alpha", None) is None
 
+    # A region loss: one forward call leaves {L, L_point, L_region} and the per-class gradient coefficients `coef`, which the
+    # backward call of the same step reads (self._loss_coef; a captured step keeps the tensor, GraphedTrainStep.coef).
     def _loss_fwd(self, eng, p, y):
+        if getattr(self, "loss_region", None) is not None:
+            out, self._loss_coef = eng.loss_region_fwd(self.loss_region, p, y)
+            return out[:1]
         if self._two_class():
             return eng.loss_fwd(self.loss_kind, p, y)
         return eng.lossn_fwd(self.loss_kind, p, y, self.loss_alpha)
 
     def _loss_bwd(self, eng, p, y):
+        if getattr(self, "loss_region", None) is not None:
+            return eng.loss_region_bwd(self.loss_region, p, y, self._loss_coef, 1.0)
         if self._two_class():
             return eng.loss_bwd(self.loss_kind, p, y, 1.0)
         return eng.lossn_bwd(self.loss_kind, p, y, self.loss_alpha, 1.0)
@@ -785,6 +802,7 @@ class GraphedTrainStep:
                 begin()
                 p = rt.forward(self.x, training=True)
                 self.loss = model._loss_fwd(eng, p, self.y)
+                self.coef = getattr(model, "_loss_coef", None)   # a region loss: the graph's backward pass reads this tensor
                 self.counts = model._counts(eng, p, self.y)   # zeroed inside the graph, four counts or C x C
                 dp = model._loss_bwd(eng, p, self.y)
                 rt.backward(dp)

@@ -536,6 +536,45 @@ int sg_lossn_bwd(sg_ctx* ctx, void* stream, int kind, int64_t rows, int C, int y
                  const void* p, const void* y_true, void* dp, float grad_scale);
 int sg_confusion_matrix(sg_ctx* ctx, void* stream, int64_t rows, int C, int y_cols, const void* p,
                         const void* y_true, void* out_i64);
+/* Region-overlap losses on the C-class head (no counterpart in the reference): Dice / Jaccard / Tversky, focal-Tversky with
+ * gamma > 1, alone or added to one of the three pointwise losses above.  A group g is the whole batch (images = 1) or one
+ * image of rows_per_image rows (images = N: rows g * rows_per_image ... of p and y_true).  Per group and class, with
+ * y = y_true[:, c] (the one-hot columns only; the weight columns of a 2C-wide y_true belong to the pointwise term):
+ *   I = sum p y,  P = sum p,  Y = sum y,  D = I + a (P - I) + b (Y - I) + smooth,  T = (I + smooth) / D,
+ *   l[g,c] = (1 - T)^gamma,  L_region = sum_g sum_c class_w[c] l[g,c] / (images * sum_c class_w[c]),
+ *   L = point_weight * L_point + region_weight * L_region,
+ * L_point being what sg_lossn_fwd computes over all images * rows_per_image rows for kind point_kind with point_alpha
+ * (point_kind = -1: no pointwise term, L = region_weight * L_region, L_point is reported as 0).  a = b = .5 is Dice with
+ * T = (2I + 2 smooth) / (P + Y + 2 smooth) - the smoothing of the usual Dice notation is 2 * smooth -, a = b = 1 Jaccard.
+ * The gradient of the region term is A[g,c] * y + B[g,c] at every pixel:
+ *   k = -region_weight class_w[c] gamma (1 - T)^(gamma - 1) / (images * sum_w * D^2)      ((1 - T)^0 = 1 also at T = 1)
+ *   A = k (D - (I + smooth)(1 - a - b)),   B = -k (I + smooth) a        (region_weight is folded into both).
+ * Domain: 2 <= C <= SG_MAX_CLASSES; y_cols = C or 2C (2C with point_kind 2); 1 <= images <= 65535; rows_per_image > 0;
+ * a, b >= 0; smooth > 0; gamma >= 1; class_w >= 0 with a positive sum; point_weight, region_weight >= 0 and not both 0
+ * (region_weight > 0 without a pointwise term); everything finite.  The descriptor is a HOST struct, read at the call and
+ * carried in the kernel arguments (a captured graph keeps it).
+ *   fwd  one pass over p and y_true (images * sg_loss_parts workgroups, each leaving 1 + 3C partial sums in ws), then a fixed-order
+ *        sum in double: loss_out[3] = {L, L_point, L_region}, coef_out[images][2C] = {A[C], B[C]}, all fp32.
+ *   bwd  one pass: dp = grad_scale * (point_weight * the gradient sg_lossn_bwd writes + A y + B), coef = fwd's coef_out
+ *        (device memory).  With region_weight = 0 and point_weight = 1 the bits of sg_lossn_bwd.
+ * fp32, dense, 4-byte alignment is enough for every pointer.  No allocation, no synchronisation, no float atomics: two calls
+ * on the same inputs give the same bits.  A descriptor outside the domain, a null pointer or a short workspace is SG_EINVAL /
+ * SG_EWORKSPACE and nothing is launched or written; the workspace query then returns 0. */
+typedef struct sg_region_desc {
+  int32_t C, y_cols;
+  int32_t images;             /* 1: one group, the whole batch */
+  int32_t point_kind;         /* -1, or SG_LOSS_* */
+  int64_t rows_per_image;
+  float a, b, smooth, gamma;
+  float point_weight, region_weight;
+  float class_w[SG_MAX_CLASSES];
+  float point_alpha[SG_MAX_CLASSES]; /* read for point_kind 1 and 2 */
+} sg_region_desc;
+size_t sg_loss_region_ws_bytes(const sg_ctx* ctx, const sg_region_desc* desc);
+int sg_loss_region_fwd(sg_ctx* ctx, void* stream, const sg_region_desc* desc, const void* p, const void* y_true,
+                       void* loss_out, void* coef_out, void* ws, size_t ws_bytes);
+int sg_loss_region_bwd(sg_ctx* ctx, void* stream, const sg_region_desc* desc, const void* p, const void* y_true,
+                       const void* coef, void* dp, float grad_scale);
 /* Keras-2 Adam (compile(optimizer='adam'), DeepLabv3plus.py:835) on one flat fp32
  * parameter arena: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; w -= lr_t * m / (sqrt(v) + eps) with
  * lr_t = lr*sqrt(1-b2^t)/(1-b1^t) precomputed by the host.  g is scaled by grad_scale first (1/world). */

@@ -1,0 +1,346 @@
+"""sg_loss_region_* on the GPU against the float64 restatement (tests/_region_loss_ref.py): every operand between guard bands
+(tests/_guarded.py), outputs NaN-prefilled, the workspace exactly as long as the query says, at the 16-byte aligned start and
+ONE ELEMENT further; reproducibility; the pointwise part against sg_lossn_*; what the calls refuse; and a compound loss inside
+a model, eager and captured.
+
+Tolerances are the project's (tests/test_bandwidth_variants_gpu.py): 2e-5 of max|ref| for the element-wise gradient, 1e-4 for
+the reduced scalars and the coefficients formed from reduced sums."""
+import ctypes as C_
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+import _multiclass_ref as MR
+import _region_loss_ref as RR
+from _guarded import Guarded, assert_written, check_all, close, untouched
+
+pytestmark = pytest.mark.gpu
+
+SG_EINVAL, SG_EWORKSPACE = -1, -2
+DEV = "cuda"
+F32 = torch.float32
+TOL, TOL_RED = 2e-5, 1e-4
+OFFS = [pytest.param(False, id="aligned"), pytest.param(True, id="offset")]
+RED_CAP = 2048 * 1024                 # rows per image after which the 2048 workgroups of an image take a second trip
+PARAMS = ((1.0, 0.5, 0.5), (2.0, 1.0, 1.0), (1.0, 0.3, 0.7), (2.0, 0.3, 0.7))      # gamma, a, b
+
+
+def gen(tag):
+    return torch.Generator().manual_seed(zlib.crc32(tag.encode()) % (2 ** 31))
+
+
+def G(t, off=False, role="in"):
+    return Guarded(t, DEV, off=off, role=role)
+
+
+def GO(shape, off=False):
+    return Guarded.out(shape, F32, DEV, off=off)
+
+
+def c_desc(d, C, y_cols, rows_per_image):
+    """The ctypes descriptor of a reference descriptor (tests/_region_loss_ref.desc)."""
+    from building_detection_amd._lib import RegionDesc
+    cd = RegionDesc(C=C, y_cols=y_cols, images=d["images"], point_kind=d["point_kind"], rows_per_image=rows_per_image, a=d["a"],
+                    b=d["b"], smooth=d["smooth"], gamma=d["gamma"], point_weight=d["point_weight"], region_weight=d["region_weight"])
+    for c in range(min(C, len(cd.class_w))):
+        cd.class_w[c] = d["class_w"][c]
+        cd.point_alpha[c] = 1.0 if d["point_alpha"] is None else d["point_alpha"][c]
+    return cd
+
+
+def rounded(d):
+    """The descriptor with the fp32 values the C struct carries (0.3 is not a float): what the reference is evaluated at."""
+    f = lambda v: float(np.float32(v))
+    out = dict(d)
+    for k in ("a", "b", "smooth", "gamma", "point_weight", "region_weight"):
+        out[k] = f(d[k])
+    out["class_w"] = tuple(f(v) for v in d["class_w"])
+    out["point_alpha"] = None if d["point_alpha"] is None else tuple(f(v) for v in d["point_alpha"])
+    return out
+
+
+def ws_bytes(engine, cd):
+    return engine.lib.sg_loss_region_ws_bytes(engine.h, C_.byref(cd))
+
+
+def fwd(engine, cd, P, Y, L, K, W, nws):
+    return engine.lib.sg_loss_region_fwd(engine.h, engine.stream, C_.byref(cd), P.ptr(), Y.ptr(), L.ptr(), K.ptr(), W.ptr(), nws)
+
+
+def bwd(engine, cd, P, Y, K, D, scale):
+    return engine.lib.sg_loss_region_bwd(engine.h, engine.stream, C_.byref(cd), P.ptr(), Y.ptr(), K.ptr(), D.ptr(), scale)
+
+
+def done(engine, rc, what, *ops):
+    assert rc == 0, f"{what}: rc={rc}: {engine.lib.sg_last_error().decode('utf-8', 'replace')}"
+    check_all(ops, what)
+
+
+def run_case(engine, rows_per_image, C, y_cols, d, off, scales=(1.0,), p=None, yt=None, tag=""):
+    """Forward twice, backward once per scale; everything against float64 on the same fp32 inputs."""
+    images = d["images"]
+    rows = rows_per_image * images
+    what = f"region rpi={rows_per_image} images={images} C={C} y_cols={y_cols} kind={d['point_kind']} off={off} {tag}"
+    if p is None:
+        g = gen(f"rg{rows}{C}{y_cols}{tag}")
+        p, yt = MR.class_probs(g, rows, C), MR.class_labels(g, rows, C, y_cols)
+    cd, dr = c_desc(d, C, y_cols, rows_per_image), rounded(d)
+    p64, y64 = p.double(), yt.double()
+    nws = ws_bytes(engine, cd)
+    parts = min(max(-(-rows_per_image // 1024), 1), 2048)
+    assert nws == 4 * (images * parts * (1 + 3 * C) + (2 * images if images > 1 else 0)), what
+    P, Y, L, K, W = G(p, off), G(yt, off), GO((3,), off), GO((images, 2 * C), off), Guarded.ws(nws, DEV)
+    done(engine, fwd(engine, cd, P, Y, L, K, W, nws), what, P, Y, L, K, W)
+    loss, coef = L.read(), K.read()
+    assert_written(loss, what + " loss"); assert_written(coef, what + " coef")
+    ref_l, ref_k = RR.loss_ref(dr, p64, y64), RR.coef_ref(dr, p64, y64)
+    print(f"{what}: loss {loss.tolist()} ref {ref_l.tolist()}")
+    close(loss, ref_l, TOL_RED, what + " loss")
+    close(coef, ref_k, TOL_RED, what + " coef")
+    if d["point_kind"] < 0:
+        assert loss[1] == 0, what
+    L2, K2, W2 = GO((3,), off), GO((images, 2 * C), off), Guarded.ws(nws, DEV)
+    done(engine, fwd(engine, cd, P, Y, L2, K2, W2, nws), what + " again", L2, K2, W2)
+    assert torch.equal(L2.read(), loss) and torch.equal(K2.read(), coef), what + ": the forward call is not reproducible"
+    for gs in scales:
+        KI, D = G(coef, off), GO((rows, C), off)
+        done(engine, bwd(engine, cd, P, Y, KI, D, gs), what + " bwd", P, Y, KI, D)
+        dp = D.read()
+        assert_written(dp, what + " bwd")
+        close(dp, RR.grad_ref(dr, p64, y64, gs), TOL, what + f" bwd scale={gs}")
+        D2 = GO((rows, C), off)
+        done(engine, bwd(engine, cd, P, Y, KI, D2, gs), what + " bwd again", D2)
+        assert torch.equal(D2.read(), dp), what + ": the backward call is not reproducible"
+    return loss, coef
+
+
+def alpha_for(C):
+    return tuple(round(0.35 + 0.3 * c / (C - 1), 4) for c in range(C))
+
+
+# ================================================================================================ rows, classes, widths, parameters
+@pytest.mark.parametrize("off", OFFS)
+@pytest.mark.parametrize("C", (2, 3, 5, 32))
+def test_row_tails_classes_and_parameter_sets(engine, C, off):
+    for n, rows in enumerate((1, 63, 255, 257, 1023, 1025)):                 # 1025: two parts
+        gamma, a, b = PARAMS[n % len(PARAMS)]
+        kind = (2, 1, 0)[n % 3]
+        d = RR.desc(C, a=a, b=b, gamma=gamma, point_kind=kind, point_alpha=None if kind == 0 else alpha_for(C),
+                    point_weight=0.75, region_weight=1.5)
+        run_case(engine, rows, C, 2 * C if kind == 2 or n % 2 else C, d, off, scales=(1.0, 0.25))
+        gamma, a, b = PARAMS[(n + 1) % len(PARAMS)]
+        d = RR.desc(C, a=a, b=b, gamma=gamma, smooth=0.5 + n, class_w=[0.5 + (c % 3) for c in range(C)])
+        run_case(engine, rows, C, C if n % 2 else 2 * C, d, off, scales=(1.0, 0.25), tag="only")
+
+
+@pytest.mark.parametrize("gamma,a,b", PARAMS[:3])
+def test_every_parameter_set_with_every_pointwise_kind(engine, gamma, a, b):
+    C, rows = 3, 257
+    for kind in (-1, 0, 1, 2):
+        d = RR.desc(C, a=a, b=b, gamma=gamma, point_kind=kind, point_alpha=alpha_for(C) if kind > 0 else None)
+        run_case(engine, rows, C, 2 * C, d, False, scales=(1.0, 0.25), tag=f"k{kind}")
+        if kind != 2:
+            run_case(engine, rows, C, C, d, True, tag=f"k{kind}c")
+
+
+def test_many_parts(engine):
+    d = RR.desc(3, a=0.3, b=0.7, gamma=2.0, point_kind=2, point_alpha=alpha_for(3))       # 586 parts, a ragged last one
+    run_case(engine, 600001, 3, 6, d, True)
+
+
+@pytest.mark.parametrize("kind", (-1, 2), ids=("only", "compound"))
+def test_part_cap_and_second_trip(engine, kind):
+    rows = RED_CAP + 1027
+    d = RR.desc(2, point_kind=kind, point_alpha=(0.35, 0.65) if kind == 2 else None)
+    cd = c_desc(d, 2, 4, rows)
+    assert ws_bytes(engine, cd) == 2048 * 7 * 4 == ws_bytes(engine, c_desc(d, 2, 4, RED_CAP))
+    assert ws_bytes(engine, c_desc(d, 2, 4, RED_CAP - 1024)) == 2047 * 7 * 4
+    run_case(engine, rows, 2, 4, d, kind == 2, tag="cap")
+
+
+# ================================================================================================ groups
+@pytest.mark.parametrize("off", OFFS)
+@pytest.mark.parametrize("rpi", (63, 1023, 1031))
+def test_per_image_groups(engine, rpi, off):
+    """Three images; the boundary between two of them lies inside what one workgroup of a batch-wide launch would walk."""
+    for C, kind, y_cols in ((2, 2, 4), (5, -1, 5), (3, 1, 3)):
+        d = RR.desc(C, images=3, a=0.3, b=0.7, gamma=2.0 if C == 5 else 1.0, point_kind=kind,
+                    point_alpha=alpha_for(C) if kind > 0 else None, class_w=[1.0 + c for c in range(C)])
+        g = gen(f"img{rpi}{C}")
+        p, yt = MR.class_probs(g, 3 * rpi, C), MR.class_labels(g, 3 * rpi, C, y_cols)
+        p[rpi:2 * rpi] = MR.class_probs(g, rpi, C, -1.0, 1.0)                  # the middle image is unlike its neighbours
+        loss, coef = run_case(engine, rpi, C, y_cols, d, off, scales=(1.0, 0.25), p=p, yt=yt)
+        assert not torch.equal(coef[0], coef[1]) and not torch.equal(coef[1], coef[2])
+        # ... and every image on its own, batch-wide, gives that image's coefficients (times the 3 of G) and the mean loss
+        d1 = dict(d, images=1)
+        each = [run_case(engine, rpi, C, y_cols, d1, off, p=p[i * rpi:(i + 1) * rpi].contiguous(),
+                         yt=yt[i * rpi:(i + 1) * rpi].contiguous(), tag=f"img{i}") for i in range(3)]
+        close(coef, torch.cat([e[1] for e in each]) / 3, TOL_RED, "per-image coefficients")
+        close(loss[2:], torch.stack([e[0][2] for e in each]).mean().reshape(1), TOL_RED, "per-image region loss")
+
+
+# ================================================================================================ absent class, zero weight
+@pytest.mark.parametrize("off", OFFS)
+def test_absent_class_and_zero_class_weight(engine, off):
+    C, rows = 5, 1025
+    g = gen("absent")
+    p, yt = MR.class_probs(g, rows, C), MR.class_labels(g, rows, C, 2 * C)
+    hit = yt[:, 3] == 1
+    yt[hit, 3], yt[hit, 0] = 0.0, 1.0                                          # class 3 is in no pixel: Y = I = 0
+    assert yt[:, 3].sum() == 0 and hit.any()
+    for gamma in (1.0, 2.0):
+        d = RR.desc(C, a=0.3, b=0.7, gamma=gamma, class_w=(1.0, 0.0, 2.0, 1.0, 0.5), point_kind=2, point_alpha=alpha_for(C))
+        _, coef = run_case(engine, rows, C, 2 * C, d, off, scales=(1.0,), p=p, yt=yt, tag=f"absent g{gamma}")
+        assert coef[0, 1] == 0 and coef[0, C + 1] == 0                         # the class of weight 0 has no region gradient
+        assert coef[0, C + 3] > 0                                              # the absent class is pushed down everywhere
+        d = RR.desc(C, gamma=gamma, class_w=(0.0, 0.0, 0.0, 1.0, 0.0))          # only the absent class counts
+        run_case(engine, rows, C, C, d, off, p=p, yt=yt[:, :C].contiguous(), tag=f"absent-only g{gamma}")
+
+
+# ================================================================================================ the pointwise part is sg_lossn_*
+@pytest.mark.parametrize("off", OFFS)
+@pytest.mark.parametrize("C", (2, 3, 5, 32))
+def test_without_region_weight_the_pointwise_calls(engine, C, off):
+    for rows, y_cols in ((257, 2 * C), (1025, C), (4099, 2 * C)):
+        g = gen(f"pw{rows}{C}")
+        p, yt = MR.class_probs(g, rows, C), MR.class_labels(g, rows, C, y_cols)
+        alpha = alpha_for(C)
+        al = (C_.c_float * C)(*alpha)
+        for kind in ((0, 1, 2) if y_cols == 2 * C else (0, 1)):
+            what = f"pointwise kind={kind} rows={rows} C={C} y_cols={y_cols}"
+            d = RR.desc(C, gamma=2.0, point_kind=kind, point_alpha=alpha, point_weight=1.0, region_weight=0.0)
+            cd = c_desc(d, C, y_cols, rows)
+            nws = ws_bytes(engine, cd)
+            P, Y, L, K, W = G(p, off), G(yt, off), GO((3,)), GO((1, 2 * C)), Guarded.ws(nws, DEV)
+            done(engine, fwd(engine, cd, P, Y, L, K, W, nws), what, P, Y, L, K, W)
+            assert torch.equal(K.read(), torch.zeros(1, 2 * C)), what
+            nwn = engine.lib.sg_lossn_ws_bytes(engine.h, rows)
+            Ln, Wn = GO((1,)), Guarded.ws(nwn, DEV)
+            rc = engine.lib.sg_lossn_fwd(engine.h, engine.stream, kind, rows, C, y_cols, al, P.ptr(), Y.ptr(), Ln.ptr(), Wn.ptr(), nwn)
+            done(engine, rc, what + " lossn_fwd", Ln, Wn)
+            loss = L.read()
+            close(loss[1:2], Ln.read().double(), TOL_RED, what + " L_point")
+            assert loss[0] == loss[1] and loss[2] > 0, what
+            for gs in (1.0, 0.25):
+                D, Dn = GO((rows, C), off), GO((rows, C), off)
+                done(engine, bwd(engine, cd, P, Y, K, D, gs), what + " bwd", P, Y, K, D)
+                rc = engine.lib.sg_lossn_bwd(engine.h, engine.stream, kind, rows, C, y_cols, al, P.ptr(), Y.ptr(), Dn.ptr(), gs)
+                done(engine, rc, what + " lossn_bwd", Dn)
+                assert torch.equal(D.read(), Dn.read()), what + f": dp differs from sg_lossn_bwd's at scale {gs}"
+
+
+# ================================================================================================ refusals
+def test_refusals_write_nothing(engine):
+    C, rows = 3, 65
+    g = gen("refuse")
+    p, yt = MR.class_probs(g, rows, C), MR.class_labels(g, rows, C, 2 * C)
+    ok = RR.desc(C, point_kind=2, point_alpha=alpha_for(C))
+    nan, inf = float("nan"), float("inf")
+    bad = [("C=1", dict(), dict(C=1)), ("C=33", dict(), dict(C=33)), ("y_cols", dict(), dict(y_cols=4)),
+           ("edge without weights", dict(), dict(y_cols=3)), ("images=0", dict(images=0), {}), ("images<0", dict(images=-1), {}),
+           ("images>65535", dict(images=65536), {}), ("rows=0", dict(), dict(rows_per_image=0)), ("rows<0", dict(), dict(rows_per_image=-5)),
+           ("a<0", dict(a=-0.1), {}), ("b nan", dict(b=nan), {}), ("smooth=0", dict(smooth=0.0), {}), ("smooth<0", dict(smooth=-1.0), {}),
+           ("smooth inf", dict(smooth=inf), {}), ("gamma<1", dict(gamma=0.5), {}), ("gamma nan", dict(gamma=nan), {}),
+           ("w<0", dict(class_w=(1.0, -1.0, 1.0)), {}), ("w=0", dict(class_w=(0.0, 0.0, 0.0)), {}), ("w nan", dict(class_w=(1.0, nan, 1.0)), {}),
+           ("kind=3", dict(point_kind=3), {}), ("kind=-2", dict(point_kind=-2), {}), ("lambda<0", dict(region_weight=-1.0), {}),
+           ("lambda_p nan", dict(point_weight=nan), {}), ("both 0", dict(point_weight=0.0, region_weight=0.0), {}),
+           ("region 0 alone", dict(point_kind=-1, region_weight=0.0), {}), ("alpha inf", dict(point_alpha=(0.5, inf, 0.5)), {})]
+    P, Y = G(p), G(yt)
+    good = c_desc(ok, C, 2 * C, rows)
+    nws = ws_bytes(engine, good)
+    assert nws == 10 * 4
+    L, K, W, D = GO((3,)), GO((1, 2 * C)), Guarded.ws(nws, DEV), GO((rows, C))
+    KI = G(torch.zeros(1, 2 * C))
+    for name, dkw, ckw in bad:
+        cd = c_desc(dict(ok, **dkw), C, 2 * C, rows)
+        for k, v in ckw.items():
+            setattr(cd, k, v)
+        assert ws_bytes(engine, cd) == 0, name
+        assert fwd(engine, cd, P, Y, L, K, W, nws) == SG_EINVAL, name
+        assert bwd(engine, cd, P, Y, KI, D, 1.0) == SG_EINVAL, name
+    null = type("Null", (), {"ptr": staticmethod(lambda: None)})
+    for i in range(5):                                                        # a null pointer in every position
+        ops = [P, Y, L, K, W]
+        ops[i] = null
+        assert fwd(engine, good, *ops, nws) == (SG_EWORKSPACE if i == 4 else SG_EINVAL), i
+    for i in range(4):
+        ops = [P, Y, KI, D]
+        ops[i] = null
+        assert bwd(engine, good, *ops, 1.0) == SG_EINVAL, i
+    assert engine.lib.sg_loss_region_fwd(engine.h, engine.stream, None, P.ptr(), Y.ptr(), L.ptr(), K.ptr(), W.ptr(), nws) == SG_EINVAL
+    assert engine.lib.sg_loss_region_bwd(engine.h, engine.stream, None, P.ptr(), Y.ptr(), KI.ptr(), D.ptr(), 1.0) == SG_EINVAL
+    assert engine.lib.sg_loss_region_ws_bytes(engine.h, None) == 0
+    assert fwd(engine, good, P, Y, L, K, W, nws - 1) == SG_EWORKSPACE          # one byte short
+    per = c_desc(dict(ok, images=5), C, 2 * C, 13)                            # 5 images: 5 * 10 + 2 * 5 floats
+    assert ws_bytes(engine, per) == 60 * 4
+    Wp = Guarded.ws(60 * 4 - 4, DEV)
+    assert fwd(engine, per, P, Y, L, GO((5, 2 * C)), Wp, Wp.nb) == SG_EWORKSPACE
+    torch.cuda.synchronize()
+    for o in (L, K, W, D, Wp):
+        untouched(o, "refusals")
+    check_all((P, Y, KI), "refusals")
+    # ... and the same operands are taken once the descriptor is right
+    done(engine, fwd(engine, good, P, Y, L, K, W, nws), "good", P, Y, L, K, W)
+    assert_written(L.read(), "good")
+
+
+def test_engine_wrappers(engine):
+    from building_detection_amd import losses as LS
+    C, n, hw = 3, 2, 33
+    g = gen("wrap")
+    p, yt = MR.class_probs(g, n * hw * hw, C).reshape(n, hw, hw, C), MR.class_labels(g, n * hw * hw, C, 2 * C).reshape(n, hw, hw, 2 * C)
+    pd, yd = p.to(DEV), yt.to(DEV)
+    for loss, images in ((LS.compound(LS.edge_focal_loss.with_alpha(alpha_for(C)), LS.dice_loss.with_options(per_image=True)), n),
+                         (LS.tversky_loss(0.3, 0.7).with_options(gamma=2.0, class_weights=[1, 2, 3]), 1)):
+        r = LS.resolve_region(loss, C)
+        out, coef = engine.loss_region_fwd(r, pd, yd)
+        dp = engine.loss_region_bwd(r, pd, yd, coef, 0.5)
+        d = rounded(RR.desc(C, a=r["a"], b=r["b"], smooth=r["smooth"], gamma=r["gamma"], class_w=r["class_w"], images=images,
+                            point_kind=r["point_kind"], point_alpha=r["point_alpha"], point_weight=r["point_weight"],
+                            region_weight=r["region_weight"]))
+        p64, y64 = p.reshape(-1, C).double(), yt.reshape(-1, 2 * C).double()
+        assert tuple(out.shape) == (3,) and tuple(coef.shape) == (images, 2 * C) and dp.shape == pd.shape
+        close(out, RR.loss_ref(d, p64, y64), TOL_RED, "wrapper loss")
+        close(coef, RR.coef_ref(d, p64, y64), TOL_RED, "wrapper coef")
+        close(dp.reshape(-1, C), RR.grad_ref(d, p64, y64, 0.5), TOL, "wrapper dp")
+        with pytest.raises(ValueError, match="coef"):
+            engine.loss_region_bwd(r, pd, yd, coef[:, :C].contiguous())
+
+
+# ================================================================================================ inside a model
+def build(C):
+    from building_detection_amd import zoo
+    return zoo.BUILDERS["hrnet"]((32, 32, 3), C)
+
+
+@pytest.mark.parametrize("C", (2, 3))
+def test_compound_loss_in_a_model_eager_and_captured(engine, C):
+    from building_detection_amd import losses as LS
+    from building_detection_amd.data import synthetic_batch
+    from building_detection_amd.runtime import GraphedTrainStep
+    alpha = (0.35, 0.65) if C == 2 else alpha_for(C)
+    loss = LS.compound(LS.edge_focal_loss if C == 2 else LS.edge_focal_loss.with_alpha(alpha), LS.dice_loss, region_weight=0.5)
+    ma, mb = build(C), build(C)
+    mb.set_weights(ma.get_weights())
+    ma.compile(optimizer="adam", loss=loss, metrics=[LS.PA, LS.IoU, LS.MIoU, LS.F1_score])
+    mb.compile(optimizer="adam", loss=loss, metrics=[LS.PA, LS.IoU, LS.MIoU, LS.F1_score], jit_compile=True)
+    x, y = synthetic_batch(2, 32, 32, seed=41, num_classes=C)
+    logs = ma.test_on_batch(x, y)
+    p = torch.from_numpy(ma.predict(x)).reshape(-1, C).double()
+    d = rounded(RR.desc(C, point_kind=2, point_alpha=alpha, region_weight=0.5))
+    ref = RR.loss_ref(d, p, torch.from_numpy(y).reshape(-1, 2 * C).double())
+    print(f"C={C}: test_on_batch loss {logs['loss']:.7f}, float64 on predict's probabilities {ref.tolist()}")
+    close(torch.tensor([logs["loss"]]), ref[:1], TOL_RED, "test_on_batch loss")
+    assert ref[1] > 0 and ref[2] > 0 and set(logs) == {"loss", "PA", "IoU", "MIoU", "F1_score"}
+    for i in range(5):
+        x, y = synthetic_batch(2, 32, 32, seed=80 + i, num_classes=C)
+        (la, ca), (lb, cb) = ma.train_on_batch(x, y, return_device_scalars=True), mb.train_on_batch(x, y, return_device_scalars=True)
+        assert la.numel() == 1 and torch.equal(la, lb) and torch.equal(ca, cb), (i, la, lb, ca, cb)     # steps 3 and 4 are replays
+        assert ma._logs(la, ca) == mb._logs(lb, cb) and np.isfinite(la.item())
+    assert len(mb._train_graphs) == 1 and isinstance(next(iter(mb._train_graphs.values())), GraphedTrainStep)
+    assert next(iter(mb._train_graphs.values())).coef is not None and not getattr(ma, "_train_graphs", None)
+    for wa, wb in zip(ma.get_weights(), mb.get_weights()):
+        assert np.array_equal(wa, wb)
+    assert any(not np.array_equal(w0, w1) for w0, w1 in zip(build(C).get_weights(), ma.get_weights()))

@@ -107,6 +107,19 @@ class DwPlan(C.Structure):
                                        "seg_S", "bn", "res", "sums")] + [("ws_bytes", C.c_size_t)]
 
 
+class BnPlan(C.Structure):
+    """Mirror of `sg_bn_plan_t` (include/segengine.h): the plan one BatchNormalization call runs by (sg_bn_plan)."""
+
+    _fields_ = [(n, C.c_int) for n in ("V", "cols", "prow", "gx", "gy", "seg_V", "seg_TX", "seg_TY", "seg_gx", "seg_S", "fused",
+                                       "fin_lanes")] + [("ws_bytes", C.c_size_t)]
+
+
+class SegPlan(C.Structure):
+    """Mirror of `sg_seg_plan_t` (include/segengine.h): the segment reducer's plan (sg_seg_plan)."""
+
+    _fields_ = [(n, C.c_int) for n in ("V", "TX", "TY", "gx", "S")] + [("part_bytes", C.c_size_t)]
+
+
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 _op = C.POINTER(ConvOpts)
 _dp = C.POINTER(ConvDesc)
@@ -153,6 +166,8 @@ _SIGNATURES = {
     "sg_bn_train_bwd_apply": (_i, [_vp, _vp, _i, _i64, _i] + [_vp] * 9 + [_i]),
     "sg_bn_infer": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i]),
     "sg_add2_bn": (_i, [_vp, _vp, _i, _i64, _i] + [_vp] * 11 + [_i, _i, _f, _i, _i]),
+    "sg_bn_plan": (_i, [_vp, _i, _i64, _i, _i, _i, C.POINTER(BnPlan)]),
+    "sg_seg_plan": (_i, [_vp, _i, _i, _i64, _i, _i, _i, C.POINTER(SegPlan)]),
     "sg_act_fwd": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp]),
     "sg_act_bwd": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _i]),
     "sg_add_n": (_i, [_vp, _vp, _i, _i, _pp, _i64, _vp, _i]),

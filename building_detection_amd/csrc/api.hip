@@ -1,5 +1,5 @@
 // libsegengine: context, error reporting and small utility entry points of the C ABI (include/segengine.h).
-#include "sg_common.h"
+#include "sg_reduce.h"
 #include <string.h>
 
 static thread_local char g_err[512] = "";
@@ -83,6 +83,15 @@ int sg_destroy(sg_ctx* ctx) {
 }
 
 int sg_num_cus(const sg_ctx* ctx) { return ctx ? ctx->num_cus : 0; }
+
+// the segment reducer's plan (sg_reduce.h) as its users in every translation unit compute it
+int sg_seg_plan(const sg_ctx* ctx, int nout, int nseg, int64_t rows, int C, int vec, int wide8, sg_seg_plan_t* out) {
+  SG_CHECK_ARG(out, "sg_seg_plan: null out");
+  *out = sg_seg_plan_t{};
+  SG_CHECK_ARG(ctx && nout > 0 && nseg > 0 && rows > 0 && C > 0, "sg_seg_plan: bad argument");
+  *out = seg_plan_n(nout, ctx->num_cus, nseg, rows, C, vec != 0, wide8 != 0);
+  return 0;
+}
 
 int sg_fill_f32(sg_ctx* ctx, void* stream, void* p, int64_t n, float value) {
   SG_CHECK_ARG(ctx && (p || n == 0), "sg_fill_f32: null argument");

@@ -16,12 +16,7 @@ struct ClassAlpha {
   float a[SG_MAX_CLASSES];
 };
 
-inline unsigned ew_blocks(int64_t total) {
-  int64_t b = sg_cdiv(total, 256);
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+constexpr int64_t EW_CAP = 8192;   // ew_blocks: workgroups of this file's element-wise launches
 
 // CM: the unrolled trip count; EX: C == CM is known at compile time
 #define MC_FOR(c) _Pragma("unroll") for (int c = 0; c < CM; ++c) if (EX || c < C)
@@ -256,7 +251,7 @@ int sg_softmax_fwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, co
   SG_CHECK_ARG(classes_ok(C), "sg_softmax_fwd: C = %d outside [2, %d]", C, SG_MAX_CLASSES);
   if (rows == 0) return 0;
 #define L(CM, EX)                                                                                                     \
-  hipLaunchKernelGGL((softmax_fwd_kernel<CM, EX>), dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, (const float*)z, \
+  hipLaunchKernelGGL((softmax_fwd_kernel<CM, EX>), dim3(ew_blocks(rows, EW_CAP)), dim3(256), 0, (hipStream_t)stream, (const float*)z, \
                      (float*)p, rows, C)
   MC_DISPATCH(C, L);
 #undef L
@@ -269,7 +264,7 @@ int sg_softmax_bwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, co
   SG_CHECK_ARG(classes_ok(C), "sg_softmax_bwd: C = %d outside [2, %d]", C, SG_MAX_CLASSES);
   if (rows == 0) return 0;
 #define L(CM, EX)                                                                                                     \
-  hipLaunchKernelGGL((softmax_bwd_kernel<CM, EX>), dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, (const float*)p, \
+  hipLaunchKernelGGL((softmax_bwd_kernel<CM, EX>), dim3(ew_blocks(rows, EW_CAP)), dim3(256), 0, (hipStream_t)stream, (const float*)p, \
                      (const float*)dp, (float*)dz, rows, C)
   MC_DISPATCH(C, L);
 #undef L

@@ -6,6 +6,27 @@
 
 namespace {
 
+// The per-element expressions, each written once: what makes mask modes 1 and 2, and the flat and column forms, bit-identical
+__device__ __forceinline__ float bn_affine(float x, float mean, float invstd, float gamma, float beta) {
+  return fmaf((x - mean) * invstd, gamma, beta);
+}
+// MODE: 0 = no fused ReLU, 1 = ReLU mask read from y, 2 = ReLU mask recomputed from x (gamma, beta given)
+template <int MODE, int V>
+__device__ __forceinline__ void bn_mask(float (&g)[V], const float (&x)[V], const float (&y)[V], const float (&mean)[V],
+                                        const float (&invstd)[V], const float (&gamma)[V], const float (&beta)[V]) {
+  if constexpr (MODE == 2) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) g[i] = bn_affine(x[i], mean[i], invstd[i], gamma[i], beta[i]) > 0.f ? g[i] : 0.f;
+  } else if constexpr (MODE == 1) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) g[i] = y[i] > 0.f ? g[i] : 0.f;
+  }
+}
+__device__ __forceinline__ float bn_dx(float x, float g, float mean, float invstd, float gamma, float dgamma, float dbeta, float inv_n) {
+  const float xh = (x - mean) * invstd;
+  return gamma * invstd * (g - dbeta * inv_n - xh * dgamma * inv_n);
+}
+
 template <typename T>
 struct BnStatsOp {
   static constexpr int NOUT = 2;
@@ -45,9 +66,8 @@ struct BnStatsOp {
   }
 };
 
-// MODE: 0 = no fused ReLU, 1 = ReLU mask read from y, 2 = ReLU mask recomputed from x (gamma, beta given).  Compile-time,
-// and the per-channel parameters are loaded once per thread (BnCtx): the row loop is two loads (three in mode 1) and
-// arithmetic, four rows in flight.
+// MODE as in bn_mask.  Compile-time, and the per-channel parameters are loaded once per thread (BnCtx): the row loop is two
+// loads (three in mode 1) and arithmetic, four rows in flight.
 template <int V>
 struct BnCtx {
   float mv[V], iv[V], gm[V], bt[V];
@@ -80,18 +100,11 @@ struct BnBwdOp {
   }
   template <int V>
   __device__ __forceinline__ void accum(int, int64_t r, int c, float (&acc)[2][V], const BnCtx<V>& k) const {
-    float xv[V], gv[V];
+    float xv[V], gv[V], yv[V];
     ldv<V>(x + r * C + c, xv);
     ldv<V>(dy + r * C + c, gv);
-    if constexpr (MODE == 2) {
-#pragma unroll
-      for (int i = 0; i < V; ++i) gv[i] = fmaf((xv[i] - k.mv[i]) * k.iv[i], k.gm[i], k.bt[i]) > 0.f ? gv[i] : 0.f;
-    } else if constexpr (MODE == 1) {
-      float yv[V];
-      ldv<V>(y + r * C + c, yv);
-#pragma unroll
-      for (int i = 0; i < V; ++i) gv[i] = yv[i] > 0.f ? gv[i] : 0.f;
-    }
+    if constexpr (MODE == 1) ldv<V>(y + r * C + c, yv);
+    bn_mask<MODE>(gv, xv, yv, k.mv, k.iv, k.gm, k.bt);
 #pragma unroll
     for (int i = 0; i < V; ++i) {
       acc[0][i] += gv[i];
@@ -124,7 +137,7 @@ __global__ void bn_apply_kernel(const T* __restrict__ x, const float* __restrict
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       const float is = infer ? rsqrtf(iv[k] + eps) : iv[k];
-      float t = fmaf((xv[k] - mv[k]) * is, gv[k], bv[k]);  // the backward re-evaluates exactly this for the ReLU mask
+      float t = bn_affine(xv[k], mv[k], is, gv[k], bv[k]);
       if (relu) t = fmaxf(t, 0.f);
       o[k] = t;
     }
@@ -155,11 +168,12 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict
     ldv<V>(gamma + c, gam);
     ldv<V>(dgamma + c, dg);
     ldv<V>(dbeta + c, db);
+    // bn_mask and bn_dx written out: through the helpers this kernel alone (V = 4, 8) comes out in another instruction order
     if constexpr (MODE == 2) {
       float bt[V];
       ldv<V>(beta + c, bt);
 #pragma unroll
-      for (int k = 0; k < V; ++k) gv[k] = fmaf((xv[k] - mv[k]) * iv[k], gam[k], bt[k]) > 0.f ? gv[k] : 0.f;
+      for (int k = 0; k < V; ++k) gv[k] = bn_affine(xv[k], mv[k], iv[k], gam[k], bt[k]) > 0.f ? gv[k] : 0.f;
     } else if constexpr (MODE == 1) {
       float yv[V];
       ldv<V>(y + r * C + c, yv);
@@ -205,7 +219,7 @@ __global__ __launch_bounds__(256) void bn_apply_cols_kernel(const T* __restrict_
     float o[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      float t = fmaf((xv[k] - mv[k]) * is[k], gv[k], bv[k]);  // the backward re-evaluates exactly this for the ReLU mask
+      float t = bn_affine(xv[k], mv[k], is[k], gv[k], bv[k]);
       if (relu) t = fmaxf(t, 0.f);
       o[k] = t;
     }
@@ -229,6 +243,7 @@ __global__ __launch_bounds__(256) void bn_apply_cols_kernel(const T* __restrict_
     }
   }
 }
+constexpr int BN_APPLY_PERIODS = 4;   // bn_cols_grid's `unroll`: the periods of prow rows a group (blockIdx.y) owns per trip - four consecutive ones
 
 template <int V, typename T, int MODE>
 __global__ __launch_bounds__(256) void bn_bwd_apply_cols_kernel(const T* __restrict__ x, const T* __restrict__ y,
@@ -250,18 +265,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cols_kernel(const T* __restr
   const float inv_n = 1.0f / (float)rows;
   auto one = [&](const float (&xv)[V], float (&gv)[V], const float (&yv)[V], int64_t r) {
     float o[V];
-    if constexpr (MODE == 2) {
+    bn_mask<MODE>(gv, xv, yv, mv, iv, gam, bt);
 #pragma unroll
-      for (int k = 0; k < V; ++k) gv[k] = fmaf((xv[k] - mv[k]) * iv[k], gam[k], bt[k]) > 0.f ? gv[k] : 0.f;
-    } else if constexpr (MODE == 1) {
-#pragma unroll
-      for (int k = 0; k < V; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      const float xh = (xv[k] - mv[k]) * iv[k];
-      o[k] = gam[k] * iv[k] * (gv[k] - db[k] * inv_n - xh * dg[k] * inv_n);
-    }
+    for (int k = 0; k < V; ++k) o[k] = bn_dx(xv[k], gv[k], mv[k], iv[k], gam[k], dg[k], db[k], inv_n);
     stv<V>(dx + r * C + c, o);
   };
   // (two rows a whole grid apart: measured 2 - 5 % faster here than two adjacent periods, the opposite of the forward kernel)
@@ -288,6 +294,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cols_kernel(const T* __restr
     }
   }
 }
+constexpr int BN_BWD_PERIODS = 1;   // ONE: this kernel's two rows lie a whole grid apart, so a group owns a single period per trip
 
 // y = [relu]( f_a(a) + f_b(b) ), f = BatchNormalization's apply (training: saved mean / invstd; inference: moving mean /
 // variance) for an operand whose parameter pointers are given, the identity otherwise: the residual add of an Xception block
@@ -331,8 +338,8 @@ __global__ __launch_bounds__(256) void add2_bn_kernel(const T* __restrict__ a, c
     float o[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      float ta = on[0] ? fmaf((xa[k] - mv[0][k]) * is[0][k], gv[0][k], bv[0][k]) : xa[k];
-      float tb = on[1] ? fmaf((xb[k] - mv[1][k]) * is[1][k], gv[1][k], bv[1][k]) : xb[k];
+      float ta = on[0] ? bn_affine(xa[k], mv[0][k], is[0][k], gv[0][k], bv[0][k]) : xa[k];
+      float tb = on[1] ? bn_affine(xb[k], mv[1][k], is[1][k], gv[1][k], bv[1][k]) : xb[k];
       if (q.relu_op[0]) ta = fmaxf(ta, 0.f);
       if (q.relu_op[1]) tb = fmaxf(tb, 0.f);
       float t = ta + tb;
@@ -359,265 +366,258 @@ __global__ __launch_bounds__(256) void add2_bn_kernel(const T* __restrict__ a, c
     }
   }
 }
+constexpr int BN_ADD2_PERIODS = 2;   // two consecutive periods
 
-// grid of the column-stationary kernels: x = the blocks of one period (b0 x 256 threads = prow whole rows), y = groups of
+// ---- who chooses the kernels: plan_bn() ---------------------------------------------------------------------------------
+// One BnPlan per call, a pure function of (CU count, storage type, rows, C, pass, operands aligned) and the SG_BN_COLS / SG_SEG_FUSED /
+// SG_FINALIZE_LANES switches.  The six entry points refuse and launch from it, sg_bn_ws_bytes adds its bytes up and sg_bn_plan hands it
+// out (include/segengine.h: sg_bn_plan_t), so a query and a launch cannot disagree (tests/_bn_cases.py compares each with its mirror).
+struct BnPlan : sg_bn_plan_t { SegPlan seg; int refused; };   // seg: the reduction (seg_V .. seg_S are its copy); refused: add2's code
+
+// grid of the column-stationary kernels: gx = the blocks of one period (b0 x 256 threads = prow whole rows), gy = groups of
 // `unroll` consecutive periods; a thread walks groups gridDim.y apart.  Returns false when no such grid of a sensible size
 // exists (the flat kernels take the launch).
-inline bool bn_cols_grid(int num_cus, int64_t rows, int cv, int unroll, int& prow, dim3& grid) {
+inline bool bn_cols_grid(int num_cus, int64_t rows, int cv, int unroll, sg_bn_plan_t& pl) {
   int g = 256, a = cv;
   while (a) { const int t_ = g % a; g = a; a = t_; }   // g = gcd(256, cv)
   const int64_t b0 = cv / g;
   if (b0 > 16384) return false;
-  prow = 256 / g;
+  pl.prow = 256 / g;
   int64_t k = sg_cdiv((int64_t)8 * num_cus, b0);
-  const int64_t maxk = sg_cdiv(rows, (int64_t)unroll * prow);
+  const int64_t maxk = sg_cdiv(rows, (int64_t)unroll * pl.prow);
   if (k > maxk) k = maxk;
   if (k > 65535) k = 65535;
   if (k < 1) k = 1;
-  grid = dim3((unsigned)b0, (unsigned)k);
+  pl.gx = (int)b0; pl.gy = (int)k;
   return true;
 }
 
-inline unsigned ew_blocks(int64_t total) {
-  int64_t b = sg_cdiv(total, 256);
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (unsigned)b;
+inline BnPlan plan_bn(int num_cus, int dtype, int64_t rows, int C, int pass, bool aligned) {
+  BnPlan pl = {};
+  const bool vec = aligned && C % 4 == 0, add2 = pass == SG_BN_ADD2;   // sg_add2_bn has column kernels only, whatever SG_BN_COLS
+  pl.V = (vec && dtype == SG_BF16 && C % 8 == 0) ? 8 : (vec ? 4 : 1);   // bf16: 8 channels = one 16-byte access
+  const int unroll = add2 ? BN_ADD2_PERIODS : ((pass == SG_BN_BWD || pass == SG_BN_BWD_APPLY) ? BN_BWD_PERIODS : BN_APPLY_PERIODS);
+  pl.cols = vec && (add2 || sg_switch<SW_BN_COLS>()) && bn_cols_grid(num_cus, rows, C / pl.V, unroll, pl);
+  if (!pl.cols && add2) { pl = {}; pl.refused = SG_EUNSUPPORTED; }
+  else if (!pl.cols) { pl.gx = (int)ew_blocks(rows * (C / pl.V), 8192); pl.gy = 1; }
+  if (pass == SG_BN_FWD || pass == SG_BN_BWD) {
+    pl.seg = seg_plan<2>(num_cus, 1, rows, C, vec, dtype == SG_BF16);
+    pl.seg_V = pl.seg.V; pl.seg_TX = pl.seg.TX; pl.seg_TY = pl.seg.TY; pl.seg_gx = pl.seg.gx; pl.seg_S = pl.seg.S;
+    pl.fused = seg_fused_alone(pl.seg.S);
+    pl.fin_lanes = pl.fused ? 0 : seg_finalize_lanes(pl.seg.S);
+    pl.ws_bytes = pl.seg.part_bytes;
+  }
+  return pl;
 }
 
-template <typename T>
-int launch_bn_apply(hipStream_t st, bool vec, const T* x, const float* mean, const float* invstd, const float* gamma,
-                    const float* beta, T* y, int64_t rows, int C, int relu, float eps, int infer, int num_cus) {
-  const bool wide = vec && sizeof(T) == 2 && C % 8 == 0;  // bf16: 8 channels = one 16-byte access
-  const int V = wide ? 8 : (vec ? 4 : 1);
-  const int cols_on = sg_switch<SW_BN_COLS>();
-  int prow = 0;
-  dim3 cgrid;
-  if (vec && cols_on && bn_cols_grid(num_cus, rows, C / V, 4, prow, cgrid)) {
-    const FastDiv fd = make_fastdiv((uint32_t)(C / V));
-    if (wide)
-      hipLaunchKernelGGL((bn_apply_cols_kernel<8, T>), cgrid, dim3(256), 0, st, x, mean, invstd, gamma, beta, y, rows, C, relu, eps,
-                         infer, prow, fd);
-    else
-      hipLaunchKernelGGL((bn_apply_cols_kernel<4, T>), cgrid, dim3(256), 0, st, x, mean, invstd, gamma, beta, y, rows, C, relu, eps,
-                         infer, prow, fd);
-    SG_LAUNCH_CHECK("bn_apply_cols_kernel");
-    return 0;
+// every entry point's and the query's first checks (chunked: sg_add2_bn walks 2^31 elements and more in row chunks) ...
+inline int bn_check(const sg_ctx* ctx, int dtype, int64_t rows, int C, bool chunked, const char* who) {
+  SG_CHECK_ARG(ctx && (dtype == SG_F32 || dtype == SG_BF16), "%s: bad ctx/dtype", who);
+  SG_CHECK_ARG(rows > 0 && C > 0, "%s: bad argument", who);
+  SG_CHECK_ARG(chunked || rows * C < (1ll << 31), "%s: tensor exceeds 2^31 elements", who);
+  return 0;
+}
+
+// ... and their last: the plan's refusal, then the workspace the plan asks for
+inline int bn_refuse(const BnPlan& pl, const char* who, const void* ws, size_t ws_bytes) {
+  if (pl.refused) {
+    sg_set_error("%s: needs C %% 4 == 0, 16-byte aligned tensors and a column grid; apply the BatchNormalization and add instead", who);
+    return pl.refused;
   }
-  const unsigned blocks = ew_blocks(rows * (C / V));
-  if (wide)
-    hipLaunchKernelGGL((bn_apply_kernel<8, T>), dim3(blocks), dim3(256), 0, st, x, mean, invstd, gamma, beta, y, rows, C, relu, eps,
-                       infer, make_fastdiv((uint32_t)(C / V)));
-  else if (vec)
-    hipLaunchKernelGGL((bn_apply_kernel<4, T>), dim3(blocks), dim3(256), 0, st, x, mean, invstd, gamma, beta, y, rows, C, relu, eps,
-                       infer, make_fastdiv((uint32_t)(C / V)));
-  else
-    hipLaunchKernelGGL((bn_apply_kernel<1, T>), dim3(blocks), dim3(256), 0, st, x, mean, invstd, gamma, beta, y, rows, C, relu, eps,
-                       infer, make_fastdiv((uint32_t)(C / V)));
-  SG_LAUNCH_CHECK("bn_apply_kernel");
+  if (pl.ws_bytes && (!ws || ws_bytes < pl.ws_bytes)) {
+    sg_set_error("%s: workspace %zu < %zu", who, ws_bytes, pl.ws_bytes);
+    return SG_EWORKSPACE;
+  }
+  return 0;
+}
+
+// The template forms, named once: the plan's five <V, column form> (there is no scalar column kernel) and the backward's mask mode
+template <class F>
+inline void bn_with_form(const BnPlan& pl, F&& fn) {
+  constexpr std::integral_constant<int, 8> v8{}; constexpr std::integral_constant<int, 4> v4{};
+  if (pl.V == 8) pl.cols ? fn(v8, std::true_type{}) : fn(v8, std::false_type{});
+  else if (pl.V == 4) pl.cols ? fn(v4, std::true_type{}) : fn(v4, std::false_type{});
+  else fn(std::integral_constant<int, 1>{}, std::false_type{});
+}
+template <class F>
+inline int bn_with_mode(int relu, const void* beta, F&& fn) {   // with beta the ReLU mask is recomputed from x instead of read from y
+  if (!relu) return fn(std::integral_constant<int, 0>{});
+  return beta ? fn(std::integral_constant<int, 2>{}) : fn(std::integral_constant<int, 1>{});
+}
+
+// launch what the plan says: bn_apply_cols_kernel or bn_apply_kernel (infer: `invstd` holds the moving variance)
+template <typename T>
+int launch_bn_apply(hipStream_t st, const BnPlan& pl, const T* x, const float* mean, const float* invstd, const float* gamma,
+                    const float* beta, T* y, int64_t rows, int C, int relu, float eps, int infer) {
+  const FastDiv fd = make_fastdiv((uint32_t)(C / pl.V));
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+  bn_with_form(pl, [&](auto v, auto cols) {
+    constexpr int V = decltype(v)::value;
+    if constexpr (decltype(cols)::value)
+      hipLaunchKernelGGL((bn_apply_cols_kernel<V, T>), grid, dim3(256), 0, st, x, mean, invstd, gamma, beta, y, rows, C, relu, eps,
+                         infer, pl.prow, fd);
+    else
+      hipLaunchKernelGGL((bn_apply_kernel<V, T>), grid, dim3(256), 0, st, x, mean, invstd, gamma, beta, y, rows, C, relu, eps, infer, fd);
+  });
+  SG_LAUNCH_CHECK(pl.cols ? "bn_apply_cols_kernel" : "bn_apply_kernel");
+  return 0;
+}
+
+// dx of a training-mode BatchNormalization from its finished column sums (dbeta = sum g, dgamma = sum g * xhat) on the operands
+// of q: the apply pass of sg_bn_train_bwd, also entered on its own by sg_bn_train_bwd_apply
+template <typename T, int MODE>
+int launch_bn_bwd_apply(hipStream_t st, const BnPlan& pl, const BnBwdOp<T, MODE>& q, T* dx, int64_t rows) {
+  const FastDiv fd = make_fastdiv((uint32_t)(q.C / pl.V));
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+  bn_with_form(pl, [&](auto v, auto cols) {
+    constexpr int V = decltype(v)::value;
+    if constexpr (decltype(cols)::value)
+      hipLaunchKernelGGL((bn_bwd_apply_cols_kernel<V, T, MODE>), grid, dim3(256), 0, st, q.x, q.y, q.dy, q.mean, q.invstd, q.gamma,
+                         q.beta, q.dgamma, q.dbeta, dx, rows, q.C, pl.prow, fd);
+    else
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<V, T, MODE>), grid, dim3(256), 0, st, q.x, q.y, q.dy, q.mean, q.invstd, q.gamma, q.beta,
+                         q.dgamma, q.dbeta, dx, rows, q.C, fd);
+  });
+  SG_LAUNCH_CHECK(pl.cols ? "bn_bwd_apply_cols_kernel" : "bn_bwd_apply_kernel");
+  return 0;
+}
+
+// rows per launch of sg_add2_bn: its kernel indexes with 32 bits, so a tensor of 2^31 elements or more (the BatchNormalization
+// in front of this add has already handed its RAW input on: there is no unfused form to fall back to) is walked in row chunks
+// below that, each an even number of rows so that a chunk starts 16-byte aligned with bf16 storage too.  Element-wise: same bits.
+inline int64_t add2_chunk_rows(int64_t rows, int C) { return rows * C < (1ll << 31) ? rows : (((1ll << 31) - 1) / C) & ~1ll; }
+
+// sg_bn_apply (given mean / invstd) and sg_bn_infer (moving mean / variance, eps under the root in the kernel)
+int bn_apply_entry(const char* who, sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* gamma,
+                   const void* beta, const void* mean, const void* invstd, void* y, int relu, float eps, int infer) {
+  if (int e = bn_check(ctx, dtype, rows, C, false, who)) return e;
+  SG_CHECK_ARG(x && gamma && beta && mean && invstd && y, "%s: bad argument", who);
+  const BnPlan pl = plan_bn(ctx->num_cus, dtype, rows, C, SG_BN_APPLY, sg_all_aligned16({x, y}));
+  SG_DTYPE_SWITCH(dtype, who, {
+    return launch_bn_apply<T>((hipStream_t)stream, pl, (const T*)x, (const float*)mean, (const float*)invstd, (const float*)gamma,
+                              (const float*)beta, (T*)y, rows, C, relu, eps, infer);
+  });
   return 0;
 }
 
 }  // namespace
 
-// dx of a training-mode BatchNormalization from its finished column sums (dbeta = sum g, dgamma = sum g * xhat): the apply
-// pass of sg_bn_train_bwd, also entered on its own by sg_bn_train_bwd_apply
-template <typename T>
-static void bn_bwd_apply_launch(sg_ctx* ctx, hipStream_t st, bool vec, int64_t rows, int C, const void* x, const void* y,
-                                const void* dy, const void* gamma, const void* beta, const void* save_mean,
-                                const void* save_invstd, void* dx, const void* dgamma, const void* dbeta, int relu) {
-    const bool wide = vec && sizeof(T) == 2 && C % 8 == 0;
-    const int V = wide ? 8 : (vec ? 4 : 1);
-    const unsigned blocks = ew_blocks(rows * (C / V));
-    const int mode = !relu ? 0 : (beta ? 2 : 1);
-    const int cols_on = sg_switch<SW_BN_COLS>();
-    auto apply = [&](auto vt, auto mt) {
-      constexpr int V_ = decltype(vt)::value, M_ = decltype(mt)::value;
-      if constexpr (V_ > 1) {
-        int prow = 0;
-        dim3 cgrid;
-        if (cols_on && bn_cols_grid(ctx->num_cus, rows, C / V_, 1, prow, cgrid)) {
-          hipLaunchKernelGGL((bn_bwd_apply_cols_kernel<V_, T, M_>), cgrid, dim3(256), 0, st, (const T*)x, (const T*)y,
-                             (const T*)dy, (const float*)save_mean, (const float*)save_invstd, (const float*)gamma,
-                             (const float*)beta, (const float*)dgamma, (const float*)dbeta, (T*)dx, rows, C, prow,
-                             make_fastdiv((uint32_t)(C / V_)));
-          return;
-        }
-      }
-      hipLaunchKernelGGL((bn_bwd_apply_kernel<V_, T, M_>), dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)y, (const T*)dy,
-                         (const float*)save_mean, (const float*)save_invstd, (const float*)gamma, (const float*)beta,
-                         (const float*)dgamma, (const float*)dbeta, (T*)dx, rows, C, make_fastdiv((uint32_t)(C / V)));
-    };
-    auto apply_v = [&](auto vt) {
-      if (mode == 0) apply(vt, std::integral_constant<int, 0>{});
-      else if (mode == 1) apply(vt, std::integral_constant<int, 1>{});
-      else apply(vt, std::integral_constant<int, 2>{});
-    };
-    if (wide) apply_v(std::integral_constant<int, 8>{});
-    else if (vec) apply_v(std::integral_constant<int, 4>{});
-    else apply_v(std::integral_constant<int, 1>{});
-}
-
 extern "C" {
 
+int sg_bn_plan(const sg_ctx* ctx, int dtype, int64_t rows, int C, int pass, int aligned, sg_bn_plan_t* out) {
+  SG_CHECK_ARG(out, "sg_bn_plan: null out");
+  *out = sg_bn_plan_t{};
+  SG_CHECK_ARG(pass >= SG_BN_FWD && pass <= SG_BN_ADD2, "sg_bn_plan: bad pass");
+  if (int e = bn_check(ctx, dtype, rows, C, pass == SG_BN_ADD2, "sg_bn_plan")) return e;
+  if (pass == SG_BN_ADD2) rows = add2_chunk_rows(rows, C);
+  SG_CHECK_ARG(rows > 0, "sg_bn_plan: a single row exceeds 2^31 elements");
+  const BnPlan pl = plan_bn(ctx->num_cus, dtype, rows, C, pass, aligned != 0);
+  if (int e = bn_refuse(pl, "sg_bn_plan", out, pl.ws_bytes)) return e;   // (a query brings no workspace: that check passes)
+  *out = pl;
+  return 0;
+}
+
+// the largest ws_bytes over what the query cannot know - the storage type and whether the operands will be aligned - + 256
 size_t sg_bn_ws_bytes(const sg_ctx* ctx, int64_t rows, int C) {
   if (!ctx) return 0;
-  SegPlan pl = seg_plan<2>(ctx->num_cus, 1, rows, C, true);
-  // scalar plan can only be smaller or equal in part_bytes (same formula, S differs): take the max of both
-  SegPlan pls = seg_plan<2>(ctx->num_cus, 1, rows, C, false);
-  SegPlan plw = seg_plan<2>(ctx->num_cus, 1, rows, C, true, true);
-  size_t m = pl.part_bytes > pls.part_bytes ? pl.part_bytes : pls.part_bytes;
-  if (plw.part_bytes > m) m = plw.part_bytes;
+  size_t m = 0;
+  for (int dtype : {SG_F32, SG_BF16})
+    for (bool aligned : {false, true}) m = std::max(m, plan_bn(ctx->num_cus, dtype, rows, C, SG_BN_FWD, aligned).ws_bytes);
   return m + 256;
 }
 
-int sg_bn_train_fwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* gamma,
-                    const void* beta, void* moving_mean, void* moving_var, void* y, void* save_mean,
-                    void* save_invstd, float momentum, float eps, int relu, int unbiased_update, void* ws,
-                    size_t ws_bytes) {
-  SG_CHECK_ARG(ctx && (dtype == SG_F32 || dtype == SG_BF16), "sg_bn_train_fwd: bad ctx/dtype");
-  SG_CHECK_ARG(rows > 0 && C > 0 && x && gamma && beta && moving_mean && moving_var && y && save_mean && save_invstd,
-               "sg_bn_train_fwd: bad argument");
-  SG_CHECK_ARG(rows * C < (1ll << 31), "sg_bn_train_fwd: tensor exceeds 2^31 elements");
-  const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
-  const SegPlan pl = seg_plan<2>(ctx->num_cus, 1, rows, C, vec, dtype == SG_BF16);
-  if (!ws || ws_bytes < pl.part_bytes) {
-    sg_set_error("sg_bn_train_fwd: workspace %zu < %zu", ws_bytes, pl.part_bytes);
-    return SG_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
+int sg_bn_train_fwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* gamma, const void* beta,
+                    void* moving_mean, void* moving_var, void* y, void* save_mean, void* save_invstd, float momentum, float eps,
+                    int relu, int unbiased_update, void* ws, size_t ws_bytes) {
+  if (int e = bn_check(ctx, dtype, rows, C, false, "sg_bn_train_fwd")) return e;
+  SG_CHECK_ARG(x && gamma && beta && moving_mean && moving_var && y && save_mean && save_invstd, "sg_bn_train_fwd: bad argument");
+  const BnPlan pl = plan_bn(ctx->num_cus, dtype, rows, C, SG_BN_FWD, sg_all_aligned16({x, y}));
+  if (int e = bn_refuse(pl, "sg_bn_train_fwd", ws, ws_bytes)) return e;
   SG_DTYPE_SWITCH(dtype, "sg_bn_train_fwd", {
-    BnStatsOp<T> op;
-    op.x = (const T*)x; op.C = C; op.rows = rows;
-    op.moving_mean = (float*)moving_mean; op.moving_var = (float*)moving_var;
-    op.save_mean = (float*)save_mean; op.save_invstd = (float*)save_invstd;
-    op.momentum = momentum; op.eps = eps; op.unbiased = unbiased_update;
-    int rc = seg_reduce_launch(op, pl, 1, rows, C, (float*)ws, st, "bn_stats");
-    if (rc) return rc;
-    return launch_bn_apply<T>(st, vec, (const T*)x, (const float*)save_mean, (const float*)save_invstd, (const float*)gamma,
-                              (const float*)beta, (T*)y, rows, C, relu, eps, 0, ctx->num_cus);
+    const BnStatsOp<T> op = {(const T*)x, C, rows, (float*)moving_mean, (float*)moving_var, (float*)save_mean, (float*)save_invstd,
+                             momentum, eps, unbiased_update};
+    if (int e = seg_reduce_launch(op, pl.seg, 1, rows, C, (float*)ws, (hipStream_t)stream, "bn_stats")) return e;
+    return launch_bn_apply<T>((hipStream_t)stream, pl, op.x, op.save_mean, op.save_invstd, (const float*)gamma, (const float*)beta, (T*)y, rows, C, relu,
+                              eps, 0);
   });
   return 0;
 }
 
-int sg_bn_train_bwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* y,
-                    const void* dy, const void* gamma, const void* beta, const void* save_mean, const void* save_invstd,
-                    void* dx, void* dgamma, void* dbeta, int relu, void* ws, size_t ws_bytes) {
-  SG_CHECK_ARG(ctx && (dtype == SG_F32 || dtype == SG_BF16), "sg_bn_train_bwd: bad ctx/dtype");
-  SG_CHECK_ARG(rows > 0 && C > 0 && x && dy && gamma && save_mean && save_invstd && dx && dgamma && dbeta,
-               "sg_bn_train_bwd: bad argument");
+int sg_bn_train_bwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* y, const void* dy,
+                    const void* gamma, const void* beta, const void* save_mean, const void* save_invstd, void* dx, void* dgamma,
+                    void* dbeta, int relu, void* ws, size_t ws_bytes) {
+  if (int e = bn_check(ctx, dtype, rows, C, false, "sg_bn_train_bwd")) return e;
+  SG_CHECK_ARG(x && dy && gamma && save_mean && save_invstd && dx && dgamma && dbeta, "sg_bn_train_bwd: bad argument");
   SG_CHECK_ARG(!relu || y || beta, "sg_bn_train_bwd: relu set but neither y nor beta given");
-  SG_CHECK_ARG(rows * C < (1ll << 31), "sg_bn_train_bwd: tensor exceeds 2^31 elements");
-  const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(dy) && sg_aligned16(dx) && (!relu || sg_aligned16(y));
-  const SegPlan pl = seg_plan<2>(ctx->num_cus, 1, rows, C, vec, dtype == SG_BF16);
-  if (!ws || ws_bytes < pl.part_bytes) {
-    sg_set_error("sg_bn_train_bwd: workspace %zu < %zu", ws_bytes, pl.part_bytes);
-    return SG_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
+  const BnPlan pl = plan_bn(ctx->num_cus, dtype, rows, C, SG_BN_BWD, sg_all_aligned16({x, dy, dx, relu ? y : nullptr}));
+  if (int e = bn_refuse(pl, "sg_bn_train_bwd", ws, ws_bytes)) return e;
   SG_DTYPE_SWITCH(dtype, "sg_bn_train_bwd", {
-    auto reduce = [&](auto op) -> int {
-      op.x = (const T*)x; op.y = (const T*)y; op.dy = (const T*)dy;
-      op.mean = (const float*)save_mean; op.invstd = (const float*)save_invstd;
-      op.gamma = (const float*)gamma; op.beta = (const float*)beta;
-      op.dgamma = (float*)dgamma; op.dbeta = (float*)dbeta; op.C = C;
-      return seg_reduce_launch(op, pl, 1, rows, C, (float*)ws, st, "bn_bwd_reduce");
-    };
-    int rc = !relu ? reduce(BnBwdOp<T, 0>{}) : (beta ? reduce(BnBwdOp<T, 2>{}) : reduce(BnBwdOp<T, 1>{}));
-    if (rc) return rc;
-    bn_bwd_apply_launch<T>(ctx, st, vec, rows, C, x, y, dy, gamma, beta, save_mean, save_invstd, dx, dgamma, dbeta, relu);
-    SG_LAUNCH_CHECK("bn_bwd_apply_kernel");
+    return bn_with_mode(relu, beta, [&](auto m) -> int {
+      const BnBwdOp<T, decltype(m)::value> op = {(const T*)x, (const T*)y, (const T*)dy, (const float*)save_mean, (const float*)save_invstd,
+                                                 (const float*)gamma, (const float*)beta, (float*)dgamma, (float*)dbeta, C};
+      if (int e = seg_reduce_launch(op, pl.seg, 1, rows, C, (float*)ws, (hipStream_t)stream, "bn_bwd_reduce")) return e;
+      return launch_bn_bwd_apply((hipStream_t)stream, pl, op, (T*)dx, rows);
+    });
   });
   return 0;
 }
 
-int sg_bn_train_bwd_apply(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* dy,
-                          const void* gamma, const void* beta, const void* save_mean, const void* save_invstd,
-                          const void* dgamma, const void* dbeta, void* dx, int relu) {
-  SG_CHECK_ARG(ctx && (dtype == SG_F32 || dtype == SG_BF16), "sg_bn_train_bwd_apply: bad ctx/dtype");
-  SG_CHECK_ARG(rows > 0 && C > 0 && x && dy && gamma && save_mean && save_invstd && dx && dgamma && dbeta,
-               "sg_bn_train_bwd_apply: bad argument");
+int sg_bn_train_bwd_apply(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* dy, const void* gamma,
+                          const void* beta, const void* save_mean, const void* save_invstd, const void* dgamma, const void* dbeta,
+                          void* dx, int relu) {
+  if (int e = bn_check(ctx, dtype, rows, C, false, "sg_bn_train_bwd_apply")) return e;
+  SG_CHECK_ARG(x && dy && gamma && save_mean && save_invstd && dx && dgamma && dbeta, "sg_bn_train_bwd_apply: bad argument");
   SG_CHECK_ARG(!relu || beta, "sg_bn_train_bwd_apply: relu needs beta (the mask is recomputed from x)");
-  SG_CHECK_ARG(rows * C < (1ll << 31), "sg_bn_train_bwd_apply: tensor exceeds 2^31 elements");
-  const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(dy) && sg_aligned16(dx);
+  const BnPlan pl = plan_bn(ctx->num_cus, dtype, rows, C, SG_BN_BWD_APPLY, sg_all_aligned16({x, dy, dx}));
   SG_DTYPE_SWITCH(dtype, "sg_bn_train_bwd_apply", {
-    bn_bwd_apply_launch<T>(ctx, (hipStream_t)stream, vec, rows, C, x, nullptr, dy, gamma, beta, save_mean, save_invstd, dx, dgamma,
-                           dbeta, relu);
+    return bn_with_mode(relu, beta, [&](auto m) -> int {   // (the finished sums are only read: the casts drop a const the kernels put back)
+      const BnBwdOp<T, decltype(m)::value> op = {(const T*)x, nullptr, (const T*)dy, (const float*)save_mean, (const float*)save_invstd,
+                                                 (const float*)gamma, (const float*)beta, (float*)dgamma, (float*)dbeta, C};
+      return launch_bn_bwd_apply((hipStream_t)stream, pl, op, (T*)dx, rows);
+    });
   });
-  SG_LAUNCH_CHECK("bn_bwd_apply_kernel");
   return 0;
 }
 
 int sg_bn_apply(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* gamma,
                 const void* beta, const void* mean, const void* invstd, void* y, int relu) {
-  SG_CHECK_ARG(ctx && (dtype == SG_F32 || dtype == SG_BF16), "sg_bn_apply: bad ctx/dtype");
-  SG_CHECK_ARG(rows > 0 && C > 0 && x && gamma && beta && mean && invstd && y, "sg_bn_apply: bad argument");
-  SG_CHECK_ARG(rows * C < (1ll << 31), "sg_bn_apply: tensor exceeds 2^31 elements");
-  const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
-  SG_DTYPE_SWITCH(dtype, "sg_bn_apply", {
-    return launch_bn_apply<T>((hipStream_t)stream, vec, (const T*)x, (const float*)mean, (const float*)invstd, (const float*)gamma,
-                              (const float*)beta, (T*)y, rows, C, relu, 0.f, 0, ctx->num_cus);
-  });
-  return 0;
+  return bn_apply_entry("sg_bn_apply", ctx, stream, dtype, rows, C, x, gamma, beta, mean, invstd, y, relu, 0.f, 0);
+}
+
+int sg_bn_infer(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* gamma,
+                const void* beta, const void* moving_mean, const void* moving_var, void* y, float eps, int relu) {
+  return bn_apply_entry("sg_bn_infer", ctx, stream, dtype, rows, C, x, gamma, beta, moving_mean, moving_var, y, relu, eps, 1);
 }
 
 int sg_add2_bn(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* a, const void* b, const void* a_mean,
                const void* a_invstd, const void* a_gamma, const void* a_beta, const void* b_mean, const void* b_invstd,
                const void* b_gamma, const void* b_beta, void* y, int relu, int infer, float eps, int a_relu, int b_relu) {
-  SG_CHECK_ARG(ctx && (dtype == SG_F32 || dtype == SG_BF16), "sg_add2_bn: bad ctx/dtype");
-  SG_CHECK_ARG(rows > 0 && C > 0 && a && b && y, "sg_add2_bn: bad argument");
+  if (int e = bn_check(ctx, dtype, rows, C, true, "sg_add2_bn")) return e;
+  SG_CHECK_ARG(a && b && y, "sg_add2_bn: bad argument");
   SG_CHECK_ARG((a_mean != nullptr) == (a_invstd != nullptr && a_gamma != nullptr && a_beta != nullptr) &&
                    (b_mean != nullptr) == (b_invstd != nullptr && b_gamma != nullptr && b_beta != nullptr),
                "sg_add2_bn: an operand's four BatchNormalization parameters come together or not at all");
-  if (!((C % 4 == 0) && sg_aligned16(a) && sg_aligned16(b) && sg_aligned16(y))) {
-    sg_set_error("sg_add2_bn: needs C %% 4 == 0 and 16-byte aligned tensors; apply the BatchNormalization and add instead");
-    return SG_EUNSUPPORTED;
-  }
-  Add2BnArgs q;
-  q.mean[0] = (const float*)a_mean; q.invstd[0] = (const float*)a_invstd; q.gamma[0] = (const float*)a_gamma; q.beta[0] = (const float*)a_beta;
-  q.mean[1] = (const float*)b_mean; q.invstd[1] = (const float*)b_invstd; q.gamma[1] = (const float*)b_gamma; q.beta[1] = (const float*)b_beta;
-  q.relu_op[0] = (a_mean && a_relu) ? 1 : 0;
-  q.relu_op[1] = (b_mean && b_relu) ? 1 : 0;
-  // The kernel indexes with 32 bits: a tensor of 2^31 elements or more (the BatchNormalization in front of this add has
-  // already handed its RAW input on, so there is no unfused form to fall back to) is walked in row chunks below that, each
-  // an even number of rows so that a chunk starts 16-byte aligned with bf16 storage too.  Element-wise: same bits.
-  const int64_t chunk_rows = rows * C < (1ll << 31) ? rows : (((1ll << 31) - 1) / C) & ~1ll;
+  const bool aligned = sg_all_aligned16({a, b, y});
+  const int64_t chunk_rows = add2_chunk_rows(rows, C);
   SG_CHECK_ARG(chunk_rows > 0, "sg_add2_bn: a single row exceeds 2^31 elements");
+  const Add2BnArgs q = {{(const float*)a_mean, (const float*)b_mean}, {(const float*)a_invstd, (const float*)b_invstd},
+                        {(const float*)a_gamma, (const float*)b_gamma}, {(const float*)a_beta, (const float*)b_beta},
+                        {(a_mean && a_relu) ? 1 : 0, (b_mean && b_relu) ? 1 : 0}};
   SG_DTYPE_SWITCH(dtype, "sg_add2_bn", {
-    const bool wide = sizeof(T) == 2 && C % 8 == 0;
-    const int V = wide ? 8 : 4;
     for (int64_t r0 = 0; r0 < rows; r0 += chunk_rows) {
       const int64_t nr = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
-      const T* ca = (const T*)a + r0 * C;
-      const T* cb = (const T*)b + r0 * C;
-      T* cy = (T*)y + r0 * C;
-      int prow = 0;
-      dim3 grid;
-      if (!bn_cols_grid(ctx->num_cus, nr, C / V, 2, prow, grid)) {
-        sg_set_error("sg_add2_bn: no column-stationary grid for C = %d", C);
-        return SG_EUNSUPPORTED;
-      }
-      const FastDiv fd = make_fastdiv((uint32_t)(C / V));
-      if (wide)
-        hipLaunchKernelGGL((add2_bn_kernel<8, T>), grid, dim3(256), 0, (hipStream_t)stream, ca, cb, q, cy, nr, C, relu, eps, infer, prow, fd);
-      else
-        hipLaunchKernelGGL((add2_bn_kernel<4, T>), grid, dim3(256), 0, (hipStream_t)stream, ca, cb, q, cy, nr, C, relu, eps, infer, prow, fd);
+      const BnPlan pl = plan_bn(ctx->num_cus, dtype, nr, C, SG_BN_ADD2, aligned);
+      if (int e = bn_refuse(pl, "sg_add2_bn", nullptr, 0)) return e;   // (whatever the rows: the first chunk refuses, before any launch)
+      bn_with_form(pl, [&](auto v, auto cols) {
+        constexpr int V = decltype(v)::value;
+        if constexpr (decltype(cols)::value)   // (the plan refuses what has no column grid)
+          hipLaunchKernelGGL((add2_bn_kernel<V, T>), dim3((unsigned)pl.gx, (unsigned)pl.gy), dim3(256), 0, (hipStream_t)stream,
+                             (const T*)a + r0 * C, (const T*)b + r0 * C, q, (T*)y + r0 * C, nr, C, relu, eps, infer, pl.prow,
+                             make_fastdiv((uint32_t)(C / V)));
+      });
     }
   });
   SG_LAUNCH_CHECK("add2_bn_kernel");
-  return 0;
-}
-
-int sg_bn_infer(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* gamma,
-                const void* beta, const void* moving_mean, const void* moving_var, void* y, float eps, int relu) {
-  SG_CHECK_ARG(ctx && (dtype == SG_F32 || dtype == SG_BF16), "sg_bn_infer: bad ctx/dtype");
-  SG_CHECK_ARG(rows > 0 && C > 0 && x && gamma && beta && moving_mean && moving_var && y, "sg_bn_infer: bad argument");
-  SG_CHECK_ARG(rows * C < (1ll << 31), "sg_bn_infer: tensor exceeds 2^31 elements");
-  const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
-  SG_DTYPE_SWITCH(dtype, "sg_bn_infer", {
-    return launch_bn_apply<T>((hipStream_t)stream, vec, (const T*)x, (const float*)moving_mean, (const float*)moving_var,
-                              (const float*)gamma, (const float*)beta, (T*)y, rows, C, relu, eps, 1, ctx->num_cus);
-  });
   return 0;
 }
 

@@ -6,12 +6,7 @@
 
 namespace {
 
-inline unsigned ew_blocks(int64_t total) {
-  int64_t b = sg_cdiv(total, 256);
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+constexpr int64_t EW_CAP = 8192;   // ew_blocks: workgroups of this file's element-wise launches
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
 
@@ -166,7 +161,7 @@ __global__ void rowcol_kernel(const F f, int64_t rows, int C, FastDiv fd_cv, Fas
 template <class F>
 int launch_rowcol(const F& f, int64_t rows, int64_t HW, int C, bool vec, hipStream_t st, const char* name) {
   const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks(rows * (C / V));
+  const unsigned blocks = ew_blocks(rows * (C / V), EW_CAP);
   if (vec)
     hipLaunchKernelGGL((rowcol_kernel<F, 4>), dim3(blocks), dim3(256), 0, st, f, rows, C, make_fastdiv((uint32_t)(C / 4)),
                        make_fastdiv((uint32_t)HW));
@@ -473,9 +468,9 @@ int sg_act_fwd(sg_ctx* ctx, void* stream, int dtype, int act, int64_t n, const v
   hipStream_t st = (hipStream_t)stream;
   SG_DTYPE_SWITCH(dtype, "sg_act_fwd", {
     if (n % 4 == 0 && sg_aligned16(x) && sg_aligned16(y))
-      hipLaunchKernelGGL((act_fwd_kernel<4, T>), dim3(ew_blocks(n / 4)), dim3(256), 0, st, (const T*)x, (T*)y, n, act);
+      hipLaunchKernelGGL((act_fwd_kernel<4, T>), dim3(ew_blocks(n / 4, EW_CAP)), dim3(256), 0, st, (const T*)x, (T*)y, n, act);
     else
-      hipLaunchKernelGGL((act_fwd_kernel<1, T>), dim3(ew_blocks(n)), dim3(256), 0, st, (const T*)x, (T*)y, n, act);
+      hipLaunchKernelGGL((act_fwd_kernel<1, T>), dim3(ew_blocks(n, EW_CAP)), dim3(256), 0, st, (const T*)x, (T*)y, n, act);
   });
   SG_LAUNCH_CHECK("act_fwd_kernel");
   return 0;
@@ -489,13 +484,13 @@ int sg_act_bwd(sg_ctx* ctx, void* stream, int dtype, int act, int64_t n, const v
   hipStream_t st = (hipStream_t)stream;
   SG_DTYPE_SWITCH(dtype, "sg_act_bwd", {
     if (sizeof(T) == 2 && n % 8 == 0 && sg_aligned16(y) && sg_aligned16(dy) && sg_aligned16(dx))
-      hipLaunchKernelGGL((act_bwd_kernel<8, T>), dim3(ew_blocks(n / 8)), dim3(256), 0, st, (const T*)y, (const T*)dy, (T*)dx, n,
+      hipLaunchKernelGGL((act_bwd_kernel<8, T>), dim3(ew_blocks(n / 8, EW_CAP)), dim3(256), 0, st, (const T*)y, (const T*)dy, (T*)dx, n,
                          act, accumulate);
     else if (n % 4 == 0 && sg_aligned16(y) && sg_aligned16(dy) && sg_aligned16(dx))
-      hipLaunchKernelGGL((act_bwd_kernel<4, T>), dim3(ew_blocks(n / 4)), dim3(256), 0, st, (const T*)y, (const T*)dy, (T*)dx, n,
+      hipLaunchKernelGGL((act_bwd_kernel<4, T>), dim3(ew_blocks(n / 4, EW_CAP)), dim3(256), 0, st, (const T*)y, (const T*)dy, (T*)dx, n,
                          act, accumulate);
     else
-      hipLaunchKernelGGL((act_bwd_kernel<1, T>), dim3(ew_blocks(n)), dim3(256), 0, st, (const T*)y, (const T*)dy, (T*)dx, n, act,
+      hipLaunchKernelGGL((act_bwd_kernel<1, T>), dim3(ew_blocks(n, EW_CAP)), dim3(256), 0, st, (const T*)y, (const T*)dy, (T*)dx, n, act,
                          accumulate);
   });
   SG_LAUNCH_CHECK("act_bwd_kernel");
@@ -519,11 +514,11 @@ int sg_add_n(sg_ctx* ctx, void* stream, int dtype, int k, const void* const* xs,
   hipStream_t st = (hipStream_t)stream;
   SG_DTYPE_SWITCH(dtype, "sg_add_n", {
     if (vec && sizeof(T) == 2 && n % 8 == 0)
-      hipLaunchKernelGGL((add_n_kernel<8, T>), dim3(ew_blocks(n / 8)), dim3(256), 0, st, a, (T*)y, n, relu);
+      hipLaunchKernelGGL((add_n_kernel<8, T>), dim3(ew_blocks(n / 8, EW_CAP)), dim3(256), 0, st, a, (T*)y, n, relu);
     else if (vec)
-      hipLaunchKernelGGL((add_n_kernel<4, T>), dim3(ew_blocks(n / 4)), dim3(256), 0, st, a, (T*)y, n, relu);
+      hipLaunchKernelGGL((add_n_kernel<4, T>), dim3(ew_blocks(n / 4, EW_CAP)), dim3(256), 0, st, a, (T*)y, n, relu);
     else
-      hipLaunchKernelGGL((add_n_kernel<1, T>), dim3(ew_blocks(n)), dim3(256), 0, st, a, (T*)y, n, relu);
+      hipLaunchKernelGGL((add_n_kernel<1, T>), dim3(ew_blocks(n, EW_CAP)), dim3(256), 0, st, a, (T*)y, n, relu);
   });
   SG_LAUNCH_CHECK("add_n_kernel");
   return 0;
@@ -541,13 +536,13 @@ int sg_copy_channels(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, 
   hipStream_t st = (hipStream_t)stream;
   SG_DTYPE_SWITCH(dtype, "sg_copy_channels", {
     if (vec && sizeof(T) == 2 && (C % 8 == 0) && (src_ld % 8 == 0) && (dst_ld % 8 == 0) && (src_off % 8 == 0) && (dst_off % 8 == 0))
-      hipLaunchKernelGGL((copy_channels_kernel<8, T>), dim3(ew_blocks(rows * (C / 8))), dim3(256), 0, st, (const T*)src, src_ld,
+      hipLaunchKernelGGL((copy_channels_kernel<8, T>), dim3(ew_blocks(rows * (C / 8), EW_CAP)), dim3(256), 0, st, (const T*)src, src_ld,
                          src_off, (T*)dst, dst_ld, dst_off, rows, C, accumulate, make_fastdiv((uint32_t)(C / 8)));
     else if (vec)
-      hipLaunchKernelGGL((copy_channels_kernel<4, T>), dim3(ew_blocks(rows * (C / 4))), dim3(256), 0, st, (const T*)src, src_ld,
+      hipLaunchKernelGGL((copy_channels_kernel<4, T>), dim3(ew_blocks(rows * (C / 4), EW_CAP)), dim3(256), 0, st, (const T*)src, src_ld,
                          src_off, (T*)dst, dst_ld, dst_off, rows, C, accumulate, make_fastdiv((uint32_t)(C / 4)));
     else
-      hipLaunchKernelGGL((copy_channels_kernel<1, T>), dim3(ew_blocks(rows * C)), dim3(256), 0, st, (const T*)src, src_ld,
+      hipLaunchKernelGGL((copy_channels_kernel<1, T>), dim3(ew_blocks(rows * C, EW_CAP)), dim3(256), 0, st, (const T*)src, src_ld,
                          src_off, (T*)dst, dst_ld, dst_off, rows, C, accumulate, make_fastdiv((uint32_t)C));
   });
   SG_LAUNCH_CHECK("copy_channels_kernel");
@@ -557,7 +552,7 @@ int sg_copy_channels(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, 
 int sg_softmax2_fwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, const void* z, void* p) {
   SG_CHECK_ARG(ctx && dtype == SG_F32 && z && p && rows >= 0, "sg_softmax2_fwd: bad argument");
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(softmax2_fwd_kernel, dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, (const float*)z,
+  hipLaunchKernelGGL(softmax2_fwd_kernel, dim3(ew_blocks(rows, EW_CAP)), dim3(256), 0, (hipStream_t)stream, (const float*)z,
                      (float*)p, rows);
   SG_LAUNCH_CHECK("softmax2_fwd_kernel");
   return 0;
@@ -566,7 +561,7 @@ int sg_softmax2_fwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, const vo
 int sg_softmax2_bwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, const void* p, const void* dp, void* dz) {
   SG_CHECK_ARG(ctx && dtype == SG_F32 && p && dp && dz && rows >= 0, "sg_softmax2_bwd: bad argument");
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(softmax2_bwd_kernel, dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, (const float*)p,
+  hipLaunchKernelGGL(softmax2_bwd_kernel, dim3(ew_blocks(rows, EW_CAP)), dim3(256), 0, (hipStream_t)stream, (const float*)p,
                      (const float*)dp, (float*)dz, rows);
   SG_LAUNCH_CHECK("softmax2_bwd_kernel");
   return 0;

@@ -34,6 +34,14 @@ void sg_set_error(const char* fmt, ...);
 
 static inline int64_t sg_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// workgroups of 256 threads for `total` items of a grid-stride element-wise kernel, at most `cap` (each file's own, measured)
+static inline unsigned ew_blocks(int64_t total, int64_t cap) {
+  int64_t b = sg_cdiv(total, 256);
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (unsigned)b;
+}
+
 // partial sums (= workgroups of 256 threads, four rows each, capped) of the first stage of the loss reductions: one rule for
 // sg_loss_fwd / sg_lossn_fwd and their workspace queries
 static inline int sg_loss_parts(int64_t rows) {

@@ -10,7 +10,9 @@
 // (grid.z) the S partial rows are added in fixed order (in fp64) by the finalize kernel.  Results are
 // therefore bit-reproducible run to run (no float atomics).
 #pragma once
+#include <algorithm>
 #include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 #include <type_traits>
 #include <utility>
@@ -210,26 +212,25 @@ __global__ __launch_bounds__(256) void seg_finalize_kernel(const Op op, const in
   }
 }
 
-// the finalize launch: 16 lanes per channel where there are many partial rows
+// lanes per channel of the finalize launch: 16 where there are many partial rows (A/B switch: 4 = rounds 1 - 3)
+static inline int seg_finalize_lanes(int S) { return (S >= 32 && sg_switch<SW_FINALIZE_LANES>() == 16) ? 16 : 4; }
+
 template <class Op>
 static inline void seg_finalize_launch(const Op& op, int nseg, int C, int S, const float* part, hipStream_t st) {
-  if (S >= 32 && sg_switch<SW_FINALIZE_LANES>() == 16)   // A/B switch: 4 = rounds 1 - 3
+  if (seg_finalize_lanes(S) == 16)
     hipLaunchKernelGGL((seg_finalize_kernel<Op, 16>), dim3((unsigned)sg_cdiv(C, 16), (unsigned)nseg), dim3(256), 0, st, op, nseg, C, S, part);
   else
     hipLaunchKernelGGL((seg_finalize_kernel<Op, 4>), dim3((unsigned)sg_cdiv(C, 64), (unsigned)nseg), dim3(256), 0, st, op, nseg, C, S, part);
 }
 
-struct SegPlan {
-  int V, TX, TY, gx, S;
-  size_t part_bytes;
-};
+using SegPlan = sg_seg_plan_t;   // V, TX, TY, gx, S, part_bytes (include/segengine.h: the sg_seg_plan query hands it out)
 
-// wide8: the reduced tensor is bf16 and C % 8 == 0: a lane takes 8 channels (one 16-byte access) instead of 4 (8 bytes)
-template <int NOUT>
-static inline SegPlan seg_plan(int num_cus, int nseg, int64_t rows, int C, bool vec_ok, bool wide8 = false) {
+// wide8: the reduced tensor is bf16 and C % 8 == 0: a lane takes 8 channels (one 16-byte access) instead of 4 (8 bytes).
+// nout = the Op's NOUT: a plain argument, so that the sg_seg_plan query hands out this very function (seg_plan<NOUT> forwards).
+static inline SegPlan seg_plan_n(int nout, int num_cus, int nseg, int64_t rows, int C, bool vec_ok, bool wide8 = false) {
   SegPlan pl;
   pl.V = (vec_ok && C % 4 == 0) ? 4 : 1;
-  if (pl.V == 4 && wide8 && C % 8 == 0 && NOUT <= 2) pl.V = 8;
+  if (pl.V == 4 && wide8 && C % 8 == 0 && nout <= 2) pl.V = 8;
   const int chunks = C / pl.V;
   // 16 lanes x 16 B = one 256-byte run per row; narrow blocks keep gx (and so the block count) high without
   // a large row split S, which the second stage would have to add up again
@@ -251,9 +252,16 @@ static inline SegPlan seg_plan(int num_cus, int nseg, int64_t rows, int C, bool 
                            // for occupancy: 1024 workgroups = 4 per CU
   if (S < 1) S = 1;
   pl.S = (int)S;
-  pl.part_bytes = (size_t)nseg * pl.S * NOUT * C * sizeof(float);
+  pl.part_bytes = (size_t)nseg * pl.S * nout * C * sizeof(float);
   return pl;
 }
+template <int NOUT>
+static inline SegPlan seg_plan(int num_cus, int nseg, int64_t rows, int C, bool vec_ok, bool wide8 = false) {
+  return seg_plan_n(NOUT, num_cus, nseg, rows, C, vec_ok, wide8);
+}
+
+// the reduce kernel finalises itself without any hand-off between workgroups (SG_SEG_FUSED >= 1): one row slab
+static inline bool seg_fused_alone(int S) { return sg_switch<SW_SEG_FUSED>() >= 1 && S == 1; }
 
 // Arrival counters of the fused second stage: n zeroed words out of a per-device ring (this translation unit's own).
 // The kernels leave their words zero again, and launches that may overlap (different streams, captured graphs) sit at
@@ -300,7 +308,7 @@ static inline int seg_reduce_launch(const Op& op, const SegPlan& pl, int nseg, i
   const int fused_mode = sg_switch<SW_SEG_FUSED>();
   unsigned* cnt = nullptr;
   int fuse = 0;
-  if (fused_mode >= 1 && pl.S == 1) fuse = 1;
+  if (seg_fused_alone(pl.S)) fuse = 1;
   else if (fused_mode >= 2 && (cnt = seg_counters((int64_t)nseg * pl.gx)) != nullptr) fuse = fused_mode >= 3 ? 3 : 2;
   const size_t lds1 = (size_t)256 * Op::NOUT * pl.V * sizeof(float), lds2 = (size_t)4 * 64 * Op::NOUT * sizeof(double);
   const size_t lds = lds1 > lds2 ? lds1 : lds2;
@@ -374,3 +382,5 @@ __device__ __forceinline__ void stv(bf16_t* __restrict__ p, const float (&o)[V])
 }
 
 static inline bool sg_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// "operands aligned" of plan_dw / plan_bn: every tensor the call passes (null: not passed) starts on a 16-byte boundary
+static inline bool sg_all_aligned16(std::initializer_list<const void*> ps) { return std::all_of(ps.begin(), ps.end(), sg_aligned16); }

@@ -7,12 +7,7 @@
 
 namespace {
 
-inline unsigned ew_blocks(int64_t total) {
-  int64_t b = sg_cdiv(total, 256);
-  if (b > 16384) b = 16384;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+constexpr int64_t EW_CAP = 16384;   // ew_blocks: workgroups of this file's element-wise launches
 
 template <typename T>
 struct DwParams {
@@ -907,7 +902,7 @@ inline DwPlan plan_dw(int num_cus, int esize, const sg_conv_desc* d, int dir, bo
   else pl.res = pl.sums = fast;
   if (!fast) {
     pl.family = SG_DWK_GENERIC; pl.gy = 1;
-    pl.gx = (int)ew_blocks((int64_t)d->N * (dir == SG_DW_FWD ? d->Ho * d->Wo : d->H * d->W) * (C / pl.V));
+    pl.gx = (int)ew_blocks((int64_t)d->N * (dir == SG_DW_FWD ? d->Ho * d->Wo : d->H * d->W) * (C / pl.V), EW_CAP);
   } else if (dw_stencil_strips_ok(d, dir == SG_DW_FWD ? xl : yl, esize)) plan_dw_stencil_strip(pl, d, sums);
   else plan_dw_stencil_run(pl, d, sums);
   if (dir == SG_DW_DGRAD && sums) {
@@ -916,9 +911,6 @@ inline DwPlan plan_dw(int num_cus, int esize, const sg_conv_desc* d, int dir, bo
   }
   return pl;
 }
-
-// "operands aligned" of plan_dw: every tensor the call passes (null: not passed) starts on a 16-byte boundary
-inline bool dw_aligned(std::initializer_list<const void*> ps) { return std::all_of(ps.begin(), ps.end(), sg_aligned16); }
 
 // The seven <RELU, MASK, BN, SUMS> forms of the stencil an entry point can ask for, named once: dw_s1_run_kernel<1 | 2> and
 // dw_strip_kernel are instantiated for these and no others (the forward never has a mask or sums, the dgrad never relu_in or bn).
@@ -1542,7 +1534,7 @@ int sg_dwconv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d,
   }
   const sg_bn_in b = bn ? *bn : sg_bn_in{};   // all-null without bn
   const DwPlan pl = plan_dw(ctx->num_cus, dw_esize(dtype), d, SG_DW_FWD,
-                            dw_aligned({x, w, y, b.gamma, b.beta, b.mean, b.invstd}), false);
+                            sg_all_aligned16({x, w, y, b.gamma, b.beta, b.mean, b.invstd}), false);
   if (bn && !pl.bn) {
     sg_set_error("sg_dwconv2d_fwd: bn, but only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned) fuse the "
                  "BatchNormalization; materialise it instead");
@@ -1597,7 +1589,7 @@ int sg_dwconv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* 
   SG_CHECK_ARG(!pre_relu || x_for_mask, "sg_dwconv2d_dgrad: pre_relu needs the forward input");
   const sg_dw_bnsums q = sums ? *sums : sg_dw_bnsums{};   // all-null without sums
   const DwPlan pl = plan_dw(ctx->num_cus, dw_esize(dtype), d, SG_DW_DGRAD,
-                            dw_aligned({dy, w, dx, pre_relu ? x_for_mask : nullptr, res, q.x, q.mean, q.invstd, q.gamma, q.beta}),
+                            sg_all_aligned16({dy, w, dx, pre_relu ? x_for_mask : nullptr, res, q.x, q.mean, q.invstd, q.gamma, q.beta}),
                             sums != nullptr);
   if ((res && !pl.res) || (sums && !pl.sums)) {
     sg_set_error("sg_dwconv2d_dgrad: res / sums, but only the stride-1 3x3 run kernels (W %% 4 == 0, C %% 4 == 0, 16-byte aligned) add a "
@@ -1666,7 +1658,7 @@ int sg_dwconv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* 
     pre_relu = bn->relu;
   }
   const sg_bn_in b = bn ? *bn : sg_bn_in{};   // all-null without bn
-  const DwPlan pl = plan_dw(ctx->num_cus, dw_esize(dtype), d, SG_DW_WGRAD, dw_aligned({x, dy, b.gamma, b.beta, b.mean, b.invstd}), false);
+  const DwPlan pl = plan_dw(ctx->num_cus, dw_esize(dtype), d, SG_DW_WGRAD, sg_all_aligned16({x, dy, b.gamma, b.beta, b.mean, b.invstd}), false);
   if (bn && !pl.bn) {
     sg_set_error("sg_dwconv2d_wgrad: bn, but only the stride-1 3x3 run kernels fuse the BatchNormalization; materialise it instead");
     return SG_EUNSUPPORTED;
@@ -1732,7 +1724,7 @@ int sg_maxpool_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, in
     const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
     const int V = vec ? 4 : 1;
     p.fd_cv = make_fastdiv((uint32_t)(C / V)); p.fd_w = make_fastdiv((uint32_t)Wo); p.fd_h = make_fastdiv((uint32_t)Ho);
-    const unsigned blocks = ew_blocks((int64_t)N * Ho * Wo * (C / V));
+    const unsigned blocks = ew_blocks((int64_t)N * Ho * Wo * (C / V), EW_CAP);
     if (vec) hipLaunchKernelGGL((maxpool_fwd_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((maxpool_fwd_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
   });
@@ -1753,7 +1745,7 @@ int sg_maxpool_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, in
     const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(y) && sg_aligned16(dy) && sg_aligned16(dx);
     const int V = vec ? 4 : 1;
     p.fd_cv = make_fastdiv((uint32_t)(C / V)); p.fd_w = make_fastdiv((uint32_t)W); p.fd_h = make_fastdiv((uint32_t)H);
-    const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V));
+    const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V), EW_CAP);
     if (vec) hipLaunchKernelGGL((maxpool_bwd_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((maxpool_bwd_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
   });
@@ -1774,7 +1766,7 @@ int sg_maxpool_fwd_idx(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W
     const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(y) && sg_aligned16(idx);
     const int V = vec ? 4 : 1;
     p.fd_cv = make_fastdiv((uint32_t)(C / V)); p.fd_w = make_fastdiv((uint32_t)Wo); p.fd_h = make_fastdiv((uint32_t)Ho);
-    const unsigned blocks = ew_blocks((int64_t)N * Ho * Wo * (C / V));
+    const unsigned blocks = ew_blocks((int64_t)N * Ho * Wo * (C / V), EW_CAP);
     if (vec) hipLaunchKernelGGL((maxpool_fwd_idx_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, (unsigned char*)idx);
     else hipLaunchKernelGGL((maxpool_fwd_idx_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, (unsigned char*)idx);
   });
@@ -1795,7 +1787,7 @@ int sg_maxpool_bwd_idx(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W
     const bool vec = (C % 4 == 0) && sg_aligned16(dy) && sg_aligned16(dx) && sg_aligned16(idx);
     const int V = vec ? 4 : 1;
     p.fd_cv = make_fastdiv((uint32_t)(C / V)); p.fd_w = make_fastdiv((uint32_t)W); p.fd_h = make_fastdiv((uint32_t)H);
-    const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V));
+    const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V), EW_CAP);
     if (vec) hipLaunchKernelGGL((maxpool_bwd_idx_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, (const unsigned char*)idx);
     else hipLaunchKernelGGL((maxpool_bwd_idx_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, (const unsigned char*)idx);
   });
@@ -1839,7 +1831,7 @@ int sg_avgpool_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, in
   SG_CHECK_ARG((int64_t)N * H * W * C < (1ll << 31), "sg_avgpool_bwd: tensor exceeds 2^31 elements");
   const bool vec = (C % 4 == 0) && sg_aligned16(dy) && sg_aligned16(dx);
   const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V));
+  const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V), EW_CAP);
   const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)W), c = make_fastdiv((uint32_t)H);
   SG_DTYPE_SWITCH(dtype, "sg_avgpool_bwd", {
     if (vec)
@@ -1862,7 +1854,7 @@ int sg_upsample_nearest_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, 
   SG_CHECK_ARG((int64_t)N * H * sh * W * sw * y_ld < (1ll << 31), "sg_upsample_nearest_fwd: tensor exceeds 2^31 elements");
   const bool vec = (C % 4 == 0) && (y_ld % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
   const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks((int64_t)N * H * sh * W * sw * (C / V));
+  const unsigned blocks = ew_blocks((int64_t)N * H * sh * W * sw * (C / V), EW_CAP);
   const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)(W * sw)), c = make_fastdiv((uint32_t)(H * sh));
   SG_DTYPE_SWITCH(dtype, "sg_upsample_nearest_fwd", {
     if (vec)
@@ -1885,7 +1877,7 @@ int sg_upsample_nearest_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, 
   SG_CHECK_ARG((int64_t)N * H * sh * W * sw * dy_ld < (1ll << 31), "sg_upsample_nearest_bwd: tensor exceeds 2^31 elements");
   const bool vec = (C % 4 == 0) && (dy_ld % 4 == 0) && sg_aligned16(dy) && sg_aligned16(dx);
   const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V));
+  const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V), EW_CAP);
   const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)W), c = make_fastdiv((uint32_t)H);
   SG_DTYPE_SWITCH(dtype, "sg_upsample_nearest_bwd", {
     if (vec && sh * sw >= 64 && (int64_t)N * H * W < 65536) {
@@ -1917,7 +1909,7 @@ int sg_upsample_bilinear_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H,
   // the vector form under sg_upsample_nearest_fwd's conditions
   const bool vec = (C % 4 == 0) && (y_ld % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
   const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks((int64_t)N * H * sh * W * sw * (C / V));
+  const unsigned blocks = ew_blocks((int64_t)N * H * sh * W * sw * (C / V), EW_CAP);
   const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)(W * sw)), c = make_fastdiv((uint32_t)(H * sh));
   const FastDiv dh = make_fastdiv((uint32_t)sh), dw = make_fastdiv((uint32_t)sw);
   const size_t lds = (size_t)(sh + sw) * sizeof(float);
@@ -1943,7 +1935,7 @@ int sg_upsample_bilinear_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H,
   SG_CHECK_ARG((int64_t)N * H * sh * W * sw * dy_ld < (1ll << 31), "sg_upsample_bilinear_bwd: tensor exceeds 2^31 elements");
   const bool vec = (C % 4 == 0) && (dy_ld % 4 == 0) && sg_aligned16(dy) && sg_aligned16(dx);
   const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V));
+  const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V), EW_CAP);
   const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)W), c = make_fastdiv((uint32_t)H);
   const size_t lds = (size_t)2 * (sh + sw) * sizeof(float);
   SG_DTYPE_SWITCH(dtype, "sg_upsample_bilinear_bwd", {

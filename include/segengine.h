@@ -390,6 +390,46 @@ int sg_bn_infer(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const
                 const void* gamma, const void* beta, const void* moving_mean, const void* moving_var,
                 void* y, float eps, int relu);
 
+/* The plan one BatchNormalization call runs by (csrc/norm.hip, plan_bn - the six entry points above and sg_bn_ws_bytes read the same
+ * one), for this storage type and the SG_BN_COLS / SG_SEG_FUSED / SG_FINALIZE_LANES switches.  pass: SG_BN_FWD (sg_bn_train_fwd:
+ * statistics and apply), SG_BN_APPLY (sg_bn_apply, sg_bn_infer), SG_BN_BWD (sg_bn_train_bwd: reduce and apply), SG_BN_BWD_APPLY,
+ * SG_BN_ADD2 (sg_add2_bn; past 2^31 elements: the plan of one full chunk of rows).  aligned: every TENSOR the call passes is
+ * 16-byte aligned (y of sg_bn_train_bwd counts only with relu; the fp32 parameter vectors never count).
+ *   V           channels per lane of the apply pass (8: bf16 storage and C % 8 == 0; 4: 16-byte chunks of fp32; 1: scalar)
+ *   cols        1 if a column-stationary kernel takes the apply pass (bn_apply_cols_kernel, bn_bwd_apply_cols_kernel, add2_bn_kernel)
+ *   prow        cols: rows per period (a period = gx workgroups = prow whole rows); 0 for the flat kernels
+ *   gx, gy      cols: workgroups per period, groups of periods walked in parallel; flat kernels: gx workgroups, gy = 1
+ *   seg_*       SG_BN_FWD, SG_BN_BWD: the segment reducer's plan (channels per lane, block shape TX x TY, column blocks, row slabs)
+ *   fused       1 if the reduce kernel finalises its channels itself: seg_S == 1 with SG_SEG_FUSED >= 1.  (SG_SEG_FUSED = 2 / 3 fuse
+ *               every split IF the launch gets its arrival counters - an allocation at run time, which a plan cannot report.)
+ *   fin_lanes   lanes per channel of the separate finalize launch (4 or 16); 0 with fused, and without a reduction
+ *   ws_bytes    the workspace the call itself requires (sg_bn_ws_bytes answers an upper bound of it + 256)
+ * An input the entry point would refuse answers all-zero with the entry point's error code (sg_add2_bn with C % 4 != 0 or an
+ * unaligned tensor: SG_EUNSUPPORTED).  The type is sg_bn_plan_t because C keeps functions and typedefs in one name space. */
+#define SG_BN_FWD 0
+#define SG_BN_APPLY 1
+#define SG_BN_BWD 2
+#define SG_BN_BWD_APPLY 3
+#define SG_BN_ADD2 4
+typedef struct sg_bn_plan_t {
+  int V, cols, prow, gx, gy, seg_V, seg_TX, seg_TY, seg_gx, seg_S, fused, fin_lanes;
+  size_t ws_bytes;
+} sg_bn_plan_t;
+int sg_bn_plan(const sg_ctx* ctx, int dtype, int64_t rows, int C, int pass, int aligned, sg_bn_plan_t* out);
+
+/* The segment reducer's plan itself (csrc/sg_reduce.h, seg_plan): what sg_bias_grad, sg_bn_train_fwd_tiles, the pooled and gate
+ * reductions and the depthwise filter gradient launch by, and what their workspace queries add up.  nout: sums per channel (the
+ * Op's NOUT), nseg: segments, rows: rows of one segment, vec: 16-byte chunks allowed (C % 4 == 0 is the plan's own business),
+ * wide8: bf16 tensor (8 channels per lane where C % 8 == 0 and nout <= 2).
+ *   V, TX, TY   channels per lane; lanes along the channels and along the rows of a 256-thread block
+ *   gx, S       column blocks; row slabs per segment (grid = gx x nseg x S)
+ *   part_bytes  the partial sums' bytes: nseg * S * nout * C floats */
+typedef struct sg_seg_plan_t {
+  int V, TX, TY, gx, S;
+  size_t part_bytes;
+} sg_seg_plan_t;
+int sg_seg_plan(const sg_ctx* ctx, int nout, int nseg, int64_t rows, int C, int vec, int wide8, sg_seg_plan_t* out);
+
 /* ------------------------------------------------------------------------------------- element-wise
  * Activation('relu'|'sigmoid'), n-ary add, channel concat / slice copies. act: 0 relu, 1 sigmoid. */
 #define SG_ACT_RELU 0

@@ -1,24 +1,32 @@
 """The cases of tests/test_batchnorm_variants_gpu.py: one function per entry point of csrc/norm.hip and of the column sums built
 on csrc/sg_reduce.h in csrc/conv_igemm.hip (sg_bias_grad, sg_bn_train_fwd_tiles), each against plain float64 (tests/_guarded.py).
 
-A case states which kernels its launch takes - plan(): the reduction's V / TX / gx / row-split regime / finalize lanes and the
-apply pass's form, from the mirrors of seg_plan and bn_cols_grid - and asserts before launching that the mirrors say the same
-for this device's CU count as for the 256 CUs the shapes were chosen at.
+A case states which kernels its launch takes - the reduction's V / TX / gx / row-split regime / finalize lanes and the apply
+pass's form - from the ENGINE's plan (sg_bn_plan; sg_seg_plan for the column sums), after checked_plan() has asserted that
+plan equal in every field to plan_mirror() (the mirrors of plan_bn, seg_plan and bn_cols_grid) for this device's CU count,
+and its name equal to the one at the 256 CUs the shapes were chosen at.
 
 Run as a program (`python tests/_bn_cases.py`, SG_BN_COLS=0 SG_FINALIZE_LANES=4 in the environment: the switches are read once
-per process) it runs child_cases() - the aligned, vectorisable subset - and prints one line per case."""
+per process) it runs child_cases() - the aligned, vectorisable subset - asserts on the engine's plans that the switches took
+effect, and prints one line per case."""
+import ctypes as CT
 import functools
 import os
 import sys
 
 import torch
 
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
+
 from _guarded import (Guarded, add2_bn_ref, assert_written, bn_apply_ref, bn_bwd_ref, bn_cols_grid, bn_fwd_ref, bn_stats_ref,
                       check_all, close_cols, colsum_ref, regime, seg_plan, short_last_slab, tile_stats_ref, ulp32)
+from building_detection_amd._lib import BnPlan, SegPlan
 from test_bandwidth_variants_gpu import BF16, DEV, F32, G, GO, call, done, gen, rnd, sgdt, tol
 
 REF_CUS = 256            # the CU count the shapes below were chosen at (MI355X)
-SG_EUNSUPPORTED = -3
+SG_EINVAL, SG_EUNSUPPORTED = -1, -3
 MOMENTUM, EPS = 0.5, 1e-3
 BM = 128                 # rows per statistics tile of the producing convolution (csrc/conv_igemm.hip)
 COLS_ON = os.environ.get("SG_BN_COLS", "1") != "0"
@@ -45,28 +53,106 @@ def apply_v(C, dtype, vec):
     return 8 if (vec and dtype == BF16 and C % 8 == 0) else (4 if vec else 1)
 
 
-def plan(cus, rows, C, dtype, off, nout=2, unroll=4, wide_ok=True, apply=True):
-    """The names of the kernels one launch takes.  off: some tensor operand is not 16-byte aligned."""
-    vec = C % 4 == 0 and not off
-    p = seg_plan(cus, rows, C, vec, wide8=(wide_ok and dtype == BF16), nout=nout)
-    S = p["S"]
-    fin = "fused" if S == 1 else ("fin16" if (S >= 32 and LANES16) else "fin4")
-    name = f"V{p['V']}tx{p['TX']}gx{p['gx']}.{regime(S)}{'+short' if short_last_slab(rows, S) else ''}.{fin}"
-    if apply:
-        va = apply_v(C, dtype, vec)
-        grid = bn_cols_grid(cus, rows, C // va, unroll) if (vec and COLS_ON) else None
-        name += f".cols{va}p{grid[0]}b{grid[1]}k{grid[2]}" if grid else f".flat{va}"
-    return name
+FWD, APPLY, BWD, BWD_APPLY, ADD2 = range(5)                     # SG_BN_FWD .. SG_BN_ADD2
+PERIODS = {FWD: 4, APPLY: 4, BWD: 1, BWD_APPLY: 1, ADD2: 2}     # BN_APPLY_PERIODS / BN_BWD_PERIODS / BN_ADD2_PERIODS (csrc/norm.hip)
+EW_CAP = 8192
+BN_FIELDS = tuple(n for n, _ in BnPlan._fields_)
+SEG_FIELDS = tuple(n for n, _ in SegPlan._fields_)
+PLANS = []               # every engine plan checked_plan() has handed out, in order (the child looks at its cases')
+
+
+def fin_lanes(S):
+    """(fused, lanes of the separate finalize launch) of a reduction with S row slabs, SG_SEG_FUSED at its default 1."""
+    return (1, 0) if S == 1 else (0, 16 if (S >= 32 and LANES16) else 4)
+
+
+def plan_mirror(cus, rows, C, dtype, pass_, aligned):
+    """plan_bn: every field of sg_bn_plan_t; None where sg_add2_bn refuses."""
+    z = dict.fromkeys(BN_FIELDS, 0)
+    vec = bool(aligned) and C % 4 == 0
+    V = z["V"] = apply_v(C, dtype, vec)
+    grid = bn_cols_grid(cus, rows, C // V, PERIODS[pass_]) if (vec and (COLS_ON or pass_ == ADD2)) else None
+    if grid:
+        z.update(cols=1, prow=grid[0], gx=grid[1], gy=grid[2])
+    elif pass_ == ADD2:
+        return None
+    else:
+        z.update(gx=max(1, min(-(-(rows * (C // V)) // 256), EW_CAP)), gy=1)
+    if pass_ in (FWD, BWD):
+        p = seg_plan(cus, rows, C, vec, wide8=(dtype == BF16), nout=2)
+        fused, lanes = fin_lanes(p["S"])
+        z.update(seg_V=p["V"], seg_TX=p["TX"], seg_TY=p["TY"], seg_gx=p["gx"], seg_S=p["S"], fused=fused, fin_lanes=lanes,
+                 ws_bytes=p["part_bytes"])
+    return z
+
+
+def reduce_name(V, TX, gx, S, rows, fused, lanes):
+    return f"V{V}tx{TX}gx{gx}.{regime(S)}{'+short' if short_last_slab(rows, S) else ''}.{'fused' if fused else f'fin{lanes}'}"
+
+
+def name_of(z, rows, pass_=FWD):
+    """The kernels of one call, from the fields of a plan (the engine's or the mirror's)."""
+    if pass_ == ADD2:
+        return f"add2.V{z['V']}p{z['prow']}b{z['gx']}k{z['gy']}"
+    form = f"cols{z['V']}p{z['prow']}b{z['gx']}k{z['gy']}" if z["cols"] else f"flat{z['V']}"
+    if not z["seg_V"]:
+        return "apply." + form
+    return reduce_name(z["seg_V"], z["seg_TX"], z["seg_gx"], z["seg_S"], rows, z["fused"], z["fin_lanes"]) + "." + form
+
+
+def plan(cus, rows, C, dtype, off, pass_=FWD):
+    """The names of the kernels one call takes, from the mirror.  off: some tensor operand is not 16-byte aligned."""
+    return name_of(plan_mirror(cus, rows, C, dtype, pass_, not off), rows, pass_)
+
+
+def seg_name(p, rows):
+    return reduce_name(p["V"], p["TX"], p["gx"], p["S"], rows, *fin_lanes(p["S"]))
 
 
 def num_cus(engine):
     return engine.lib.sg_num_cus(engine.h)
 
 
-def pinned(engine, rows, C, dtype, off, **kw):
-    """The predicate of a case, asserted: this device takes the kernels the case was written for."""
-    here, ref = plan(num_cus(engine), rows, C, dtype, off, **kw), plan(REF_CUS, rows, C, dtype, off, **kw)
-    assert here == ref, f"rows={rows} C={C} {dname(dtype)} off={off}: {num_cus(engine)} CUs take {here}, the case was chosen for {ref}"
+def plan_query(engine, rows, C, dtype, pass_, aligned):
+    """(return code, fields) of sg_bn_plan."""
+    p = BnPlan()
+    rc = engine.lib.sg_bn_plan(engine.h, sgdt(dtype), rows, C, pass_, int(bool(aligned)), CT.byref(p))
+    return rc, {n: getattr(p, n) for n in BN_FIELDS}
+
+
+def seg_query(engine, nout, rows, C, vec, wide8=False, nseg=1):
+    """(return code, fields) of sg_seg_plan."""
+    p = SegPlan()
+    rc = engine.lib.sg_seg_plan(engine.h, nout, nseg, rows, C, int(bool(vec)), int(bool(wide8)), CT.byref(p))
+    return rc, {n: getattr(p, n) for n in SEG_FIELDS}
+
+
+def _same(what, got, want):
+    diff = {n: (got[n], want[n]) for n in want if got[n] != want[n]}
+    assert not diff, f"{what}: (engine, mirror) differ in {diff}"
+
+
+def checked_plan(engine, rows, C, dtype, pass_, aligned):
+    """The predicate of a case, asserted before it launches: the engine's plan equals plan_mirror in every field for this device's
+    CU count, and names the kernels the case was written for (at REF_CUS).  Returns that name, built from the engine's fields."""
+    what = f"sg_bn_plan rows={rows} C={C} {dname(dtype)} pass={pass_} aligned={int(bool(aligned))}"
+    rc, got = plan_query(engine, rows, C, dtype, pass_, aligned)
+    assert rc == 0, f"{what}: rc={rc}: {engine.lib.sg_last_error().decode('utf-8', 'replace')}"
+    _same(what, got, plan_mirror(num_cus(engine), rows, C, dtype, pass_, aligned))
+    here, ref = name_of(got, rows, pass_), plan(REF_CUS, rows, C, dtype, not aligned, pass_)
+    assert here == ref, f"{what}: {num_cus(engine)} CUs take {here}, the case was chosen for {ref}"
+    PLANS.append(got)
+    return here
+
+
+def checked_seg_plan(engine, nout, rows, C, vec):
+    """The same for a column sum on the segment reducer alone (sg_bias_grad, sg_bn_train_fwd_tiles: fp32 sums, never V = 8)."""
+    what = f"sg_seg_plan nout={nout} rows={rows} C={C} vec={int(bool(vec))}"
+    rc, got = seg_query(engine, nout, rows, C, vec)
+    assert rc == 0, f"{what}: rc={rc}: {engine.lib.sg_last_error().decode('utf-8', 'replace')}"
+    _same(what, got, seg_plan(num_cus(engine), rows, C, vec, nout=nout))
+    here, ref = seg_name(got, rows), seg_name(seg_plan(REF_CUS, rows, C, vec, nout=nout), rows)
+    assert here == ref, f"{what}: {num_cus(engine)} CUs take {here}, the case was chosen for {ref}"
     return here
 
 
@@ -223,7 +309,7 @@ def bn_ws(engine, rows, C):
 def fwd_case(engine, C, rows, dtype, off, kind, off_only=None):
     """sg_bn_train_fwd: (relu, unbiased_update) = (0, 1) and (1, 0).  off_only: only that operand ("x" or "y") is offset."""
     I, dt = inputs(C, rows, dtype, kind), sgdt(dtype)
-    name = pinned(engine, rows, C, dtype, off or bool(off_only))
+    name = checked_plan(engine, rows, C, dtype, FWD, not (off or off_only))
     nws = bn_ws(engine, rows, C)
     po = off and not off_only           # the fp32 vectors move with the tensors
     for relu, unb in ((0, 1), (1, 0)):
@@ -248,7 +334,7 @@ def _bits_equal(a, b):
 def bwd_case(engine, C, rows, dtype, off, kind, off_only=None):
     """sg_bn_train_bwd in its three mask modes; mean / invstd / y are the float64 reference's, rounded to their storage."""
     I, dt = inputs(C, rows, dtype, kind), sgdt(dtype)
-    name = pinned(engine, rows, C, dtype, off or bool(off_only), unroll=1)
+    name = checked_plan(engine, rows, C, dtype, BWD, not (off or off_only))
     nws = bn_ws(engine, rows, C)
     po = off and not off_only
     g64, m64, i64 = I.gamma.double(), I.mean32.double(), I.invstd32.double()
@@ -282,7 +368,7 @@ def bwd_case(engine, C, rows, dtype, off, kind, off_only=None):
 def bwd_apply_case(engine, C, rows, dtype, off, kind):
     """sg_bn_train_bwd_apply: dgamma / dbeta are the reference's column sums (fp32); relu = 1 recomputes the mask from x."""
     I, dt = inputs(C, rows, dtype, kind), sgdt(dtype)
-    name = pinned(engine, rows, C, dtype, off, unroll=1)
+    name = checked_plan(engine, rows, C, dtype, BWD_APPLY, not off)
     g64, m64, i64 = I.gamma.double(), I.mean32.double(), I.invstd32.double()
     for relu in (0, 1):
         what = f"bn_train_bwd_apply relu={relu} C={C} rows={rows} {dname(dtype)} off={off} {kind} [{name}]"
@@ -303,7 +389,7 @@ def bwd_apply_case(engine, C, rows, dtype, off, kind):
 def apply_case(engine, C, rows, dtype, off, kind):
     """sg_bn_apply (given mean / invstd) and sg_bn_infer (moving mean / variance, eps inside the kernel), relu 0 and 1."""
     I, dt = inputs(C, rows, dtype, kind), sgdt(dtype)
-    name = pinned(engine, rows, C, dtype, off)
+    name = checked_plan(engine, rows, C, dtype, APPLY, not off)
     g64, b64 = I.gamma.double(), I.beta.double()
     g = gen(f"infer{C}.{rows}.{kind}")
     mm = (I.mean + 0.1 * (2 * torch.rand(C, generator=g).double() - 1)).float()     # moving values near, not at, the batch's
@@ -326,9 +412,7 @@ def apply_case(engine, C, rows, dtype, off, kind):
 
 
 def add2_plan(cus, rows, C, dtype):
-    va = 8 if (dtype == BF16 and C % 8 == 0) else 4
-    prow, b0, k = bn_cols_grid(cus, rows, C // va, 2)
-    return f"add2.V{va}p{prow}b{b0}k{k}"
+    return plan(cus, rows, C, dtype, False, ADD2)
 
 
 ADD2_COMBOS = [(na, nb, infer, rl) for na in (0, 1) for nb in (0, 1) for infer in (0, 1) for rl in ((1, 0, 1), (0, 1, 0))]
@@ -337,8 +421,7 @@ ADD2_COMBOS = [(na, nb, infer, rl) for na in (0, 1) for nb in (0, 1) for infer i
 def add2_case(engine, C, rows, dtype, kind):
     """sg_add2_bn: normalise a, b, both or neither; operand ReLUs and the outer one; training and inference parameters."""
     I, dt = inputs(C, rows, dtype, kind), sgdt(dtype)
-    name = add2_plan(num_cus(engine), rows, C, dtype)
-    assert name == add2_plan(REF_CUS, rows, C, dtype), (name, num_cus(engine))
+    name = checked_plan(engine, rows, C, dtype, ADD2, True)
     g = gen(f"add2{C}.{rows}.{dtype}")
     b = rnd(g, rows, C, dtype=dtype, lo=-2, hi=2)
     pb32 = (rnd(g, C), rnd(g, C, lo=0.5, hi=2.0), rnd(g, C) + 1.5, rnd(g, C))       # mean, invstd | variance, gamma, beta
@@ -378,7 +461,7 @@ def bias_case(engine, C, rows, dtype, form):
     ld, mid = {"dense": (C, 0), "slice": (C + 16, 8), "odd": (C + 3, 1), "offset": (C, 0)}[form]
     off = form == "offset"
     vec = C % 4 == 0 and ld % 4 == 0 and not off
-    name = pinned(engine, rows, C, dtype, not vec, nout=1, wide_ok=False, apply=False)
+    name = checked_seg_plan(engine, 1, rows, C, vec)
     cus = num_cus(engine)
     nws = engine.lib.sg_bias_grad_ws_bytes(engine.h, rows, C)
     assert nws == max(seg_plan(cus, rows, C, True)["part_bytes"], seg_plan(cus, rows, C, False)["part_bytes"]) + 256
@@ -419,7 +502,7 @@ def tiles_case(engine, C, rows, dtype, off, kind):
     tiles = -(-rows // BM)
     stats, mean, var = tile_inputs(C, rows, kind)
     assert stats.shape == (tiles, 2, C)
-    name = pinned(engine, tiles, C, F32, off, apply=False) + (".ragged" if rows % BM else "")
+    name = checked_seg_plan(engine, 2, tiles, C, C % 4 == 0 and not off) + (".ragged" if rows % BM else "")
     cus = num_cus(engine)
     nws = engine.lib.sg_bn_tiles_ws_bytes(engine.h, tiles, C)
     assert nws == seg_plan(cus, tiles, C, True, nout=2)["part_bytes"] + seg_plan(cus, tiles, C, False, nout=2)["part_bytes"]
@@ -462,9 +545,6 @@ def child_cases():
 
 
 def main():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if root not in sys.path:
-        sys.path.insert(0, root)
     global QUIET
     QUIET = True
     assert not COLS_ON and not LANES16, "run with SG_BN_COLS=0 SG_FINALIZE_LANES=4"
@@ -472,7 +552,12 @@ def main():
     engine = get_engine(0)
     lines = []
     for label, fn, args in child_cases():
+        seen = len(PLANS)
         name = fn(engine, *args)
+        # the ENGINE's plan of this case: the switches took effect in the library, not only in this file's reading of them
+        mine = PLANS[seen:]
+        assert mine and all(p["cols"] == 0 and p["fin_lanes"] in (0, 4) for p in mine), (label, mine)
+        assert all(p["fin_lanes"] == 4 for p in mine if p["seg_S"] >= 32), (label, mine)
         assert ".flat" in name and "fin16" not in name, name
         lines.append(f"CASE ok {label} [{name}]")
     many = [ln for ln in lines if ".many" in ln]

@@ -146,7 +146,9 @@ def sigmoid(v):
 
 def seg_plan(cus, rows, C, vec, wide8=False, nout=1):
     """seg_plan<NOUT> (csrc/sg_reduce.h) for one segment of `rows` rows and C channels: V, TX, TY, gx, S, part_bytes.
-    wide8: the reduced tensor is bf16 - a lane takes 8 channels when C % 8 == 0 and NOUT <= 2."""
+    wide8: the reduced tensor is bf16 - a lane takes 8 channels when C % 8 == 0 and NOUT <= 2.
+    Held to the engine's own answer (sg_seg_plan) by tests/_bn_cases.py: checked_seg_plan before the column-sum launches, and
+    test_plan_queries_equal_the_mirrors over every shape of its tables."""
     V = 4 if (vec and C % 4 == 0) else 1
     if V == 4 and wide8 and C % 8 == 0 and nout <= 2:
         V = 8
@@ -179,7 +181,8 @@ def short_last_slab(rows, S):
 
 def bn_cols_grid(cus, rows, cv, unroll):
     """bn_cols_grid (csrc/norm.hip) for cv chunks per row: (prow, b0, k) = rows per period, blocks per period (grid.x), groups of
-    `unroll` periods walked in parallel (grid.y); None where the flat kernels take the launch."""
+    `unroll` periods walked in parallel (grid.y); None where the flat kernels take the launch.  Held to the engine's plan
+    (sg_bn_plan: prow, gx, gy) by tests/_bn_cases.checked_plan before every BatchNormalization launch."""
     g = math.gcd(256, cv)
     b0 = cv // g
     if b0 > 16384:

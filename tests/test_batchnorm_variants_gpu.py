@@ -5,10 +5,11 @@ bands, NaN-prefilled outputs, inputs whose bits must survive, workspaces of exac
 aligned or one element further.  The cases themselves are tests/_bn_cases.py (also run as a program, for the forms behind
 process-wide switches).
 
-Every case id ends in the kernels the launch takes at 256 CUs, from the mirrors of seg_plan and bn_cols_grid:
+Every case id ends in the kernels the launch takes at 256 CUs, from the mirrors of plan_bn, seg_plan and bn_cols_grid:
     V<lanes' channels>tx<TX>gx<column blocks>.<one|few|many row slabs>[+short last slab].<fused|fin4|fin16 finalize>
     .<cols|flat><V of the apply pass>[p<rows per period>b<blocks per period>k<period groups>]
-and the case asserts the same string for this device's CU count (sg_num_cus) before it launches.  Where to find what:
+and before it launches the case asserts (B.checked_plan) that the ENGINE's plan for this device's CU count - sg_bn_plan, or
+sg_seg_plan for the column sums - equals the mirror in every field and spells the same string.  Where to find what:
     V = 1 / 4 / 8 in reduce and apply          c45 / c64-f32 / c64-bf16, c72-bf16; bf16 V = 4-not-8: c20-bf16
     column and flat apply forms                 cols*: every C % 4 == 0 case; flat1: c1, c45, every "-off"; flat4 / flat8: the child
     mask modes 0 / 1 / 2                        every test_train_bwd case runs the three (1 and 2 bit-identical)
@@ -23,6 +24,7 @@ Tolerances, as max|got - ref| <= tol * max|ref|: 2e-5 fp32 element-wise and stat
 bias gradient, tile statistics, everything at the 16-sigma pivot), 2^-7 bf16-stored; y of the training forward may add
 |gamma| invstd ulp32(mean) / 2 per channel (save_mean is an fp32 number).  The constant channel (invstd = 1 / sqrt(eps)) is
 compared on its own scale where it would otherwise set everyone's."""
+import ctypes as CT
 import os
 import subprocess
 import sys
@@ -47,7 +49,7 @@ def _params(shapes, off, **kw):
 
 
 FWD = _params(B.SHAPES, False) + _params(B.OFF_SHAPES, True)
-BWD = _params(B.SHAPES, False, unroll=1) + _params(B.OFF_SHAPES, True, unroll=1)
+BWD = _params(B.SHAPES, False, pass_=B.BWD) + _params(B.OFF_SHAPES, True, pass_=B.BWD)
 
 
 # ================================================================================================ harness self-checks (CPU)
@@ -249,7 +251,8 @@ def _tile_params():
     out = []
     for C, rows in B.TILE_SHAPES:
         for off in (False, True):
-            name = B.plan(B.REF_CUS, -(-rows // B.BM), C, F32, off, apply=False)
+            tiles = -(-rows // B.BM)
+            name = B.seg_name(seg_plan(B.REF_CUS, tiles, C, C % 4 == 0 and not off, nout=2), tiles)
             out.append(pytest.param(C, rows, off, id=f"c{C}r{rows}{'-off' if off else ''}-{name}"))
     return out
 
@@ -278,3 +281,61 @@ def test_forms_behind_switches_in_a_child_process(engine):
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("CASE ")]
     assert len(lines) == len(B.child_cases()) and all(ln.startswith("CASE ok ") for ln in lines), r.stdout[-4000:]
     assert any(".flat4" in ln for ln in lines) and any(".flat8" in ln for ln in lines) and any(".many" in ln and ".fin4" in ln for ln in lines)
+
+
+@gpu
+def test_plan_queries_equal_the_mirrors(engine):
+    """sg_bn_plan and sg_seg_plan against the mirrors over every shape of the tables, both storage types, every pass, aligned or not;
+    the three workspace queries against what the engine's own plans add up to; the refusals.  Launches nothing."""
+    cus, lib, h = B.num_cus(engine), engine.lib, engine.h
+    tiles = [(C, -(-rows // B.BM)) for C, rows in B.TILE_SHAPES]
+    shapes = sorted(set(B.SHAPES + B.OFF_SHAPES + B.ADD2_SHAPES + B.BIAS_SHAPES + B.TILE_SHAPES + tiles + PIVOT_SHAPES))
+    for C, rows in shapes:
+        bn_need = 0
+        for dtype in (F32, BF16):
+            for aligned in (False, True):
+                for pass_ in (B.FWD, B.APPLY, B.BWD, B.BWD_APPLY, B.ADD2):
+                    what = f"sg_bn_plan rows={rows} C={C} {B.dname(dtype)} pass={pass_} aligned={int(aligned)}"
+                    rc, got = B.plan_query(engine, rows, C, dtype, pass_, aligned)
+                    want = B.plan_mirror(cus, rows, C, dtype, pass_, aligned)
+                    if want is None:          # sg_add2_bn refuses: all-zero with its code
+                        assert pass_ == B.ADD2 and (C % 4 != 0 or not aligned), what
+                        assert rc == B.SG_EUNSUPPORTED and not any(got.values()), (what, rc, got)
+                        continue
+                    assert rc == 0, (what, rc)
+                    B._same(what, got, want)
+                    if pass_ == B.FWD:
+                        bn_need = max(bn_need, got["ws_bytes"])
+                    assert (got["ws_bytes"] > 0) == (pass_ in (B.FWD, B.BWD)), (what, got)
+        assert lib.sg_bn_ws_bytes(h, rows, C) == bn_need + 256, (rows, C)
+        part = {}
+        for nout in (1, 2, 9):
+            for vec in (False, True):
+                for wide8 in (False, True):
+                    what = f"sg_seg_plan nout={nout} rows={rows} C={C} vec={int(vec)} wide8={int(wide8)}"
+                    rc, got = B.seg_query(engine, nout, rows, C, vec, wide8)
+                    assert rc == 0, (what, rc)
+                    B._same(what, got, seg_plan(cus, rows, C, vec, wide8, nout))
+                    part[nout, vec, wide8] = got["part_bytes"]
+        assert lib.sg_bias_grad_ws_bytes(h, rows, C) == max(part[1, True, False], part[1, False, False]) + 256, (rows, C)
+        assert lib.sg_bn_tiles_ws_bytes(h, rows, C) == part[2, True, False] + part[2, False, False], (rows, C)
+        rc, got = B.seg_query(engine, 2, rows, C, True, nseg=3)
+        assert rc == 0 and got["part_bytes"] == 3 * seg_plan(cus, rows, C, True, nout=2)["part_bytes"]
+    # what the entry points answer SG_EINVAL to: all-zero with that code
+    p = B.BnPlan()
+    bad = [(h, 0, 0, 64, B.FWD), (h, 0, 130, 0, B.BWD), (h, 0, -1, 64, B.APPLY), (h, 7, 130, 64, B.FWD), (h, 0, 130, 64, 5),
+           (h, 0, 130, 64, -1), (None, 0, 130, 64, B.FWD), (h, 0, 1 << 25, 64, B.FWD), (h, 1, 1 << 25, 64, B.BWD_APPLY)]
+    for ctx, dt, rows, C, pass_ in bad:
+        CT.memset(CT.byref(p), 0xFF, CT.sizeof(p))
+        assert lib.sg_bn_plan(ctx, dt, rows, C, pass_, 1, CT.byref(p)) == B.SG_EINVAL, (dt, rows, C, pass_)
+        assert not any(getattr(p, n) for n in B.BN_FIELDS), (dt, rows, C, pass_)
+    # ... which sg_add2_bn walks in row chunks: the plan of one full chunk (an even number of rows below 2^31 elements)
+    rc, got = B.plan_query(engine, 1 << 25, 64, F32, B.ADD2, True)
+    assert rc == 0
+    B._same("add2 chunk", got, B.plan_mirror(cus, (((1 << 31) - 1) // 64) & ~1, 64, F32, B.ADD2, True))
+    assert lib.sg_bn_plan(h, 0, 130, 64, B.FWD, 1, None) == B.SG_EINVAL
+    s = B.SegPlan()
+    for ctx, nout, nseg, rows, C in ((None, 1, 1, 130, 64), (h, 0, 1, 130, 64), (h, 1, 0, 130, 64), (h, 1, 1, 0, 64), (h, 1, 1, 130, 0)):
+        CT.memset(CT.byref(s), 0xFF, CT.sizeof(s))
+        assert lib.sg_seg_plan(ctx, nout, nseg, rows, C, 1, 0, CT.byref(s)) == B.SG_EINVAL
+        assert not any(getattr(s, n) for n in B.SEG_FIELDS)

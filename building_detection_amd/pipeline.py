@@ -4,6 +4,7 @@
     detection(img, user_path, model, save_name)  sliding 512-px window, stride 360, argmax, OR-merge   :90-116
     vote(masks, k=3)             -> 255 where at least k of the 5 cleaned masks agree          model_fuse.py:315-323
     detection_soft(img, user_path, models, ...)  probability-domain counterpart (no reference: SoftScene below)
+    evaluate_objects(pred, truth, iou=0.5)       per-building TP / FP / FN, precision, recall, F1 of a scene (objects.py)
 
 What changes against the reference: tiles of one image are predicted in batches on the GPU instead of one
 `model.predict` per tile (BatchNorm runs on moving statistics in inference, so per-tile results do not depend
@@ -255,6 +256,25 @@ def model_confuse(path, name: str = ""):
         print("no five images")
         return None
     return cleanup.model_confuse(list(path))
+
+
+def evaluate_objects(pred, truth, iou=0.5, clean: bool = False, **kw):
+    """Scores a whole-scene result (what detection, detection_soft or model_confuse return: a 0/255 mask or a class map, array
+    or device tensor) against the ground-truth scene building by building: objects.ObjectScores(iou, **kw) over this one
+    scene -> its result() (tp / fp / fn, precision, recall, f1, mean IoU of the matches, recall per truth-area bin, per-class
+    figures for a class map).  clean=True passes a binary prediction through cleanup.clean first; a class map is refused."""
+    from . import cleanup, objects
+    if clean:
+        import torch
+        if isinstance(pred, torch.Tensor):   # require_binary reads host arrays only: hand it the one value it judges by
+            if pred.dtype == torch.uint8 and pred.numel():
+                cleanup.require_binary(np.array([int(pred.max())], np.uint8), "evaluate_objects(clean=True)")
+        else:
+            cleanup.require_binary(np.asarray(pred), "evaluate_objects(clean=True)")
+        pred = cleanup.clean(pred, kw.get("engine"))
+    scores = objects.ObjectScores(iou, **kw)
+    scores.update(pred, truth)
+    return scores.result()
 
 
 def load_model(weight_dir: str = ".", shape=(512, 512, 3)):

@@ -734,6 +734,31 @@ int sg_mask_objects(sg_ctx* ctx, void* stream, int H, int W, const void* mask_u8
 int64_t sg_mask_split_words(int H, int W, int x0, int y0, int x1, int y1);
 int sg_mask_split(sg_ctx* ctx, void* stream, int H, int W, const void* labels_i32, const void* table_i32, const void* objs_i32,
                   const void* offsets_i64, int nobj, int piece_area2, void* ws, void* out_u8);
+/* Per-building evaluation (no counterpart in the reference, which scores pixels only; model_fuse.py and edge_3.py decide object
+ * by object): objects of a u8 map and the overlaps of two labelled maps, in exact integers (csrc/objects.hip).  The matching
+ * and the scores built on them are host code (building_detection_amd/objects.py).
+ *   sg_objects_label    map_u8[H][W] -> labels_i32[H][W], table_i32[max_objs][8], count_i32[1].  An object is a connected set
+ *                       of pixels of EQUAL non-zero value (a building of a 0/255 mask, a building of one class of a class
+ *                       map: neighbours of different value never join); conn8 = 1: 8-connected, 0: 4-connected (anything
+ *                       else is SG_EINVAL); holes are NOT filled.  Objects are numbered 0 ... n-1 by ascending raster index
+ *                       of their first pixel - the same numbers in every run.  labels[i] = object number or -1, whatever
+ *                       max_objs is; table[k] = {first pixel, area in pixels, x0, y0, x1, y1 (inclusive), value, 0} for
+ *                       k < max_objs only (rows at and beyond max_objs are not touched); *count = n, which may exceed
+ *                       max_objs: enlarge the table and repeat.  H*W < 2^31 - 2.  ws: sg_objects_label_ws_bytes(H, W).
+ *   sg_objects_overlap  labels_a_i32[H][W], labels_b_i32[H][W] (what sg_objects_label wrote) -> pairs_i32[n_pairs][3] =
+ *                       {a, b, pixels with labels a and b}, every pair with a non-empty intersection once, in no particular
+ *                       order; stat_i32[2] = {n_pairs, lost}.  Pixels with a < 0 or b < 0 count nowhere.  The counts are
+ *                       collected in a hash table of `slots` entries inside ws (slots: a power of two, 1 ... 2^30; ws:
+ *                       sg_objects_overlap_ws_bytes(slots)); pairs must have room for `slots` rows.  Probing is bounded: a
+ *                       pixel run that finds no slot after `slots` probes adds its length to `lost`.  lost > 0: the list is
+ *                       unspecified (n_pairs <= slots rows are written, never more) - repeat with twice the slots.
+ * Neither call allocates or synchronises; a bad argument or a short workspace launches and writes nothing. */
+size_t sg_objects_label_ws_bytes(int H, int W);
+int sg_objects_label(sg_ctx* ctx, void* stream, int H, int W, const void* map_u8, int conn8, void* ws, size_t ws_bytes,
+                     void* labels_i32, void* table_i32, int max_objs, void* count_i32);
+size_t sg_objects_overlap_ws_bytes(int64_t slots);
+int sg_objects_overlap(sg_ctx* ctx, void* stream, int H, int W, const void* labels_a_i32, const void* labels_b_i32, int64_t slots,
+                       void* ws, size_t ws_bytes, void* pairs_i32, void* stat_i32);
 /* dst[i] = (float)src[i] / div - sub: decode_img's `np.array(img, np.float32) / 127.5 - 1` and decode_lbel's `/ 255`
  * (train_model/DeepLabv3plus.py:36-37, 48) on the GPU, so the input pipeline ships uint8 pixels over PCIe (a quarter of
  * the fp32 bytes) and converts on the device; bit-identical to the numpy float32 arithmetic. */

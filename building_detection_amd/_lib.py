@@ -114,6 +114,25 @@ class BnPlan(C.Structure):
                                        "fin_lanes")] + [("ws_bytes", C.c_size_t)]
 
 
+class WgradLaunch(C.Structure):
+    """Mirror of `sg_wgrad_launch` (include/segengine.h): one launch of a filter-gradient plan."""
+
+    _fields_ = [(n, C.c_int) for n in ("family", "bn", "vec", "fast", "planes", "skip_slabs", "tap_inner", "stagger", "S", "steps",
+                                       "step_px")]
+
+
+class WgradPlan(C.Structure):
+    """Mirror of `sg_wgrad_plan` (include/segengine.h): the plan one filter-gradient call runs by (sg_conv2d_wgrad_plan)."""
+
+    _fields_ = ([("main", WgradLaunch), ("tail", WgradLaunch)] +
+                [(n, C.c_int) for n in ("chunks", "nb", "tail_n", "max_parts", "bn_in", "up2")] +
+                [(n, C.c_size_t) for n in ("dw_part_bytes", "bias_part_bytes", "bias_off", "ws_bytes")])
+
+
+SG_WG_THIN, SG_WG_WIDE, SG_WG_PATCH, SG_WG_SLAB_X6, SG_WG_SLAB_NATIVE, SG_WG_HEAD32, SG_WG_PLANES = range(1, 8)
+WG_FAMILY_NAMES = {0: "none", 1: "thin", 2: "wide", 3: "patch", 4: "slab-x6", 5: "slab-native", 6: "head32", 7: "planes-in"}
+
+
 class SegPlan(C.Structure):
     """Mirror of `sg_seg_plan_t` (include/segengine.h): the segment reducer's plan (sg_seg_plan)."""
 
@@ -151,6 +170,7 @@ _SIGNATURES = {
     "sg_split_planes": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "sg_conv2d_wgrad_planes_ws_bytes": (_sz, [_vp, _dp]),
     "sg_conv2d_wgrad_planes": (_i, [_vp, _vp, _dp, _vp, _vp, _vp, _vp, _sz]),
+    "sg_conv2d_wgrad_plan": (_i, [_vp, _i, _dp, _i, _i, C.POINTER(WgradPlan)]),
     "sg_bias_grad_ws_bytes": (_sz, [_vp, _i64, _i]),
     "sg_bias_grad": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _sz]),
     "sg_dwconv2d_fwd": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _i, C.POINTER(BnIn)]),

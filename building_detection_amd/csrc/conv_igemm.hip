@@ -1335,50 +1335,7 @@ int launch_wgrad_f(const WgradParams& p, int S, hipStream_t st) {
   return 0;
 }
 
-template <int BN, int WGM, int WGN, int PF, bool VEC>
-int launch_wgrad(const WgradParams& p, int S, hipStream_t st) {
-  if constexpr (VEC && PF == 2) {
-    const bool fast = p.stride == 1 && p.OH == p.H && p.OW == p.W && p.x_bytes != 0 && p.dy_bytes != 0;
-    const bool force1 = sg_switch<SW_WGRAD_FAST1>();  // A/B switch
-    const bool aligned = fast && !force1 && (p.OW % BK == 0) && (p.KH_KW == 1 || p.Cin % BM == 0) &&
-                         ((int64_t)p.x_bytes + 2 * 32 * (int64_t)p.x_ld * 4 < (1ll << 31));
-    if (aligned) return launch_wgrad_f<BN, WGM, WGN, PF, true, 2>(p, S, st);
-    if (fast) return launch_wgrad_f<BN, WGM, WGN, PF, true, 1>(p, S, st);
-  }
-  return launch_wgrad_f<BN, WGM, WGN, PF, VEC, 0>(p, S, st);
-}
-
 inline int wgrad_bn(int cout) { return cout > 64 ? 128 : (cout > 32 ? 64 : 32); }
-
-int dispatch_wgrad(const WgradParams& p_in, int S, bool vec, hipStream_t st) {
-  WgradParams p = p_in;
-  p.KH_KW = p.K / p.Cin;
-  p.skip_slabs = (!sg_switch<SW_CONV_NOSKIP>() && p.dil > 1 && p.KH_KW > 1) ? 1 : 0;
-  p.tap_inner = ((conv_l2() & 4) && p.KH_KW > 1 && p.Cin % BM == 0) ? 1 : 0;
-  const int bn = wgrad_bn(p.Cout);
-  p.stagger = 1;
-  if (wgrad_x6_ok(p, vec)) {
-    p.tap_inner = ((conv_l2(true) & 4) && p.KH_KW > 1 && p.Cin % BM == 0) ? 1 : 0;
-    p.stagger = sg_switch<SW_X6_ABLATE>() & 7;  // the x6 wgrad kernel has no stagger; the field carries the ablation mask
-    if (x6_mode() == 2) {  // bf16 products in one pass on fp32 storage
-      if (bn == 128) return launch_wgrad_x6<128, 2, 4, 1, 1, float>(p, S, st);
-      if (bn == 64) return launch_wgrad_x6<64, 4, 2, 1, 1, float>(p, S, st);
-      return launch_wgrad_x6<32, 4, 1, 1, 1, float>(p, S, st);
-    }
-    if (bn == 128) return launch_wgrad_x6<128, 2, 4, 1>(p, S, st);
-    if (bn == 64) return launch_wgrad_x6<64, 4, 2, 1>(p, S, st);
-    return launch_wgrad_x6<32, 4, 1, 1>(p, S, st);
-  }
-  if (!vec) {
-    if (bn == 128) return launch_wgrad<128, 2, 4, 1, false>(p, S, st);
-    if (bn == 64) return launch_wgrad<64, 4, 2, 1, false>(p, S, st);
-    return launch_wgrad<32, 4, 1, 1, false>(p, S, st);
-  }
-  if (bn == 128) return launch_wgrad<128, 2, 4, 2, true>(p, S, st);
-  if (bn == 64) return launch_wgrad<64, 4, 2, 2, true>(p, S, st);
-  return launch_wgrad<32, 4, 1, 2, true>(p, S, st);
-}
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int check_desc(const sg_conv_desc* d, const char* who) {
@@ -1626,92 +1583,6 @@ inline int images_per_2gib_mixed(const sg_conv_desc* d, int ebx, int eby) {
   return (int)(nb < 1 ? 0 : nb);
 }
 
-struct WgradPlan {
-  int S;
-  int slabs_per_split;
-  size_t dw_part_bytes;
-  size_t bias_part_bytes;
-  int chunks = 1;  // > 1: activations beyond 2 GiB are reduced as sub-batches of nb whole images, each with S splits
-  int nb = 0;
-  int patch = 0;   // the patch form (conv_x6wp.h): S = its workgroup count, every workgroup writes one partial slab
-  int wide = 0;    // the wide pointwise form (conv_pw.h): slabs_per_split counts 16-pixel k-steps
-};
-
-// Split of the pixel reduction over S workgroups per tile.  Modelled time = MFMA work / (fraction of the
-// 2*CUs workgroup slots kept busy over whole waves) + the traffic of writing and re-adding S partial slabs;
-// the S with the smallest modelled time wins (e.g. ASPP: 288 tiles -> S = 7: 2016 workgroups = 3.94 waves).
-WgradPlan plan_wgrad(int num_cus, const sg_conv_desc* d, bool b16 = false) {
-  WgradPlan pl;
-  const int64_t K = (int64_t)d->KH * d->KW * d->Cin;
-  const int64_t P = (int64_t)d->N * d->Ho * d->Wo;
-  {
-    const int nb = images_per_2gib(d);
-    if (nb >= 1 && nb < d->N && !thin_ok(d)) {
-      sg_conv_desc sub = *d;
-      sub.N = nb;
-      pl = plan_wgrad(num_cus, &sub, b16);
-      pl.nb = nb;
-      pl.chunks = (int)sg_cdiv(d->N, nb);
-      pl.dw_part_bytes = (size_t)pl.chunks * pl.S * K * d->Cout * 4;  // every chunk writes partial slabs
-      pl.bias_part_bytes = colsum_ws_bytes(num_cus, P, d->Cout);
-      return pl;
-    }
-  }
-  if (thin_ok(d)) {
-    pl.S = 1;
-    pl.slabs_per_split = 0;
-    pl.dw_part_bytes = thin_part_bytes(num_cus, d);
-    pl.bias_part_bytes = colsum_ws_bytes(num_cus, P, d->Cout);
-    return pl;
-  }
-  if ((b16 || x6_mode() == 1) && wgrad_pw_wide_geom(d, b16 ? 2 : 4)) {   // 1x1, stride 1, wide enough: 128 x 384 tiles of dw (conv_pw.h)
-    pl.wide = 1;
-    wgrad_pw_wide_plan(num_cus, d, pl.S, pl.slabs_per_split, b16 ? WPB_KP : 16);
-    pl.dw_part_bytes = pl.S > 1 ? (size_t)pl.S * K * d->Cout * 4 : 0;
-    pl.bias_part_bytes = colsum_ws_bytes(num_cus, P, d->Cout);
-    return pl;
-  }
-  if (x6wp_geom(d) && (b16 || x6_enabled()) && (d->x_ld ? d->x_ld : d->Cin) % (b16 ? 8 : 4) == 0 &&
-      (d->y_ld ? d->y_ld : d->Cout) % (b16 ? 8 : 4) == 0) {
-    pl.patch = 1;
-    pl.S = x6wp_grid(num_cus, d);
-    pl.slabs_per_split = (int)sg_cdiv(sg_cdiv(P, BK), pl.S);  // for the slab kernels, should the launch fall back to them
-    pl.dw_part_bytes = pl.S > 1 ? (size_t)pl.S * K * d->Cout * 4 : 0;
-    pl.bias_part_bytes = colsum_ws_bytes(num_cus, P, d->Cout);
-    return pl;
-  }
-  const int bn = wgrad_bn(d->Cout);
-  const int64_t tiles = sg_cdiv(K, BM) * sg_cdiv(d->Cout, bn);
-  const int64_t nslab = sg_cdiv(P, BK);
-  const int64_t slots = 2 * (int64_t)num_cus;
-  const double flops = 2.0 * (double)tiles * BM * bn * (double)P;  // padded tile work
-  // sustained rate of the kernel that will run: the x6 wgrad (geometry test as in wgrad_x6_ok) or the fp32 MFMA one
-  const double rate_x6 = sg_switch_f<SW_WGRAD_PLAN_RATE>() * 1e12;
-  const bool x6_geom = ((d->stride == 1 && d->Ho == d->H && d->Wo == d->W) || (d->stride == 2 && d->dilation == 1)) &&
-                      d->Wo % 32 == 0 && d->Cout >= 16 && d->Cin % 4 == 0;
-  // the one-pass bf16 kernel multiplies ~4x faster than the six-pass one: the split's partial-slab traffic weighs more
-  const double rate_b16 = sg_switch_f<SW_WGRAD_PLAN_RATE_B16>() * 1e12;  // measured 110 / 250 / 450 / 900: no gain from a higher rate (profiles/r02_b16_deep_ab.txt)
-  const double rate = x6_geom ? (b16 ? rate_b16 : rate_x6) : 110e12;
-  int64_t maxS = nslab / 8;  // at least 8 slabs per split
-  if (maxS < 1) maxS = 1;
-  if (maxS > 512) maxS = 512;
-  double best_t = 1e300;
-  int64_t best_S = 1;
-  for (int64_t S = 1; S <= maxS; ++S) {
-    const int64_t wgs = tiles * S;
-    const double eff = (double)wgs / (double)(sg_cdiv(wgs, slots) * slots);
-    const double part_bytes = S > 1 ? (double)S * (double)K * d->Cout * 4.0 : 0.0;
-    if (part_bytes > (double)(384ll << 20)) break;
-    const double t = flops / (eff * rate) + 2.0 * part_bytes / 3.0e12 + (S > 1 ? 3e-6 : 0.0);
-    if (t < best_t * 0.999) { best_t = t; best_S = S; }
-  }
-  pl.slabs_per_split = (int)sg_cdiv(nslab, best_S);
-  pl.S = (int)sg_cdiv(nslab, pl.slabs_per_split);
-  pl.dw_part_bytes = pl.S > 1 ? (size_t)pl.S * K * d->Cout * 4 : 0;
-  pl.bias_part_bytes = colsum_ws_bytes(num_cus, P, d->Cout);
-  return pl;
-}
-
 // ---- storage-type plumbing of the entry points ---------------------------------------------------------------------
 // dtype = SG_F32 or SG_BF16 (activation storage), optionally | SG_HEAD_F32: the few-channel side of a thin 1x1
 // convolution (y of the forward, dy of dgrad / wgrad) is fp32 although the activations are bf16 - the softmax head,
@@ -1802,48 +1673,6 @@ int dispatch_igemm_mixed(const IgemmParams& p_in, bool vec, int num_cus, hipStre
 }
 int dispatch_igemm_b16(const IgemmParams& p, bool vec, int num_cus, hipStream_t st) {
   return dispatch_igemm_mixed<bf16_t, bf16_t>(p, vec, num_cus, st);
-}
-
-// x bf16, dy fp32: the kernel gradient of a (non-thin) softmax head of a bf16 model
-int dispatch_wgrad_head32(const WgradParams& p_in, int S, bool vec4, hipStream_t st) {
-  WgradParams p = p_in;
-  p.KH_KW = p.K / p.Cin;
-  p.skip_slabs = 0;
-  p.tap_inner = 0;
-  p.stagger = 0;
-  const int bn = wgrad_bn(p.Cout);
-  if (vec4) {
-    if (bn == 128) return launch_wgrad_f<128, 2, 4, 1, true, 0, bf16_t, float>(p, S, st);
-    if (bn == 64) return launch_wgrad_f<64, 4, 2, 1, true, 0, bf16_t, float>(p, S, st);
-    return launch_wgrad_f<32, 4, 1, 1, true, 0, bf16_t, float>(p, S, st);
-  }
-  if (bn == 128) return launch_wgrad_f<128, 2, 4, 1, false, 0, bf16_t, float>(p, S, st);
-  if (bn == 64) return launch_wgrad_f<64, 4, 2, 1, false, 0, bf16_t, float>(p, S, st);
-  return launch_wgrad_f<32, 4, 1, 1, false, 0, bf16_t, float>(p, S, st);
-}
-
-int dispatch_wgrad_b16(const WgradParams& p_in, int S, bool vec8, bool vec4, hipStream_t st) {
-  WgradParams p = p_in;
-  p.KH_KW = p.K / p.Cin;
-  p.skip_slabs = (!sg_switch<SW_CONV_NOSKIP>() && p.dil > 1 && p.KH_KW > 1) ? 1 : 0;
-  p.stagger = 0;
-  const int bn = wgrad_bn(p.Cout);
-  if (wgrad_x6_ok(p, vec8, true)) {
-    p.tap_inner = ((conv_l2(true) & 4) && p.KH_KW > 1 && p.Cin % BM == 0) ? 1 : 0;
-    if (bn == 128) return launch_wgrad_x6<128, 2, 4, 1, 1, bf16_t>(p, S, st);
-    if (bn == 64) return launch_wgrad_x6<64, 4, 2, 1, 1, bf16_t>(p, S, st);
-    return launch_wgrad_x6<32, 4, 1, 1, 1, bf16_t>(p, S, st);
-  }
-  p.tap_inner = 0;
-  p.skip_slabs = 0;
-  if (vec4) {
-    if (bn == 128) return launch_wgrad_f<128, 2, 4, 1, true, 0, bf16_t>(p, S, st);
-    if (bn == 64) return launch_wgrad_f<64, 4, 2, 1, true, 0, bf16_t>(p, S, st);
-    return launch_wgrad_f<32, 4, 1, 1, true, 0, bf16_t>(p, S, st);
-  }
-  if (bn == 128) return launch_wgrad_f<128, 2, 4, 1, false, 0, bf16_t>(p, S, st);
-  if (bn == 64) return launch_wgrad_f<64, 4, 2, 1, false, 0, bf16_t>(p, S, st);
-  return launch_wgrad_f<32, 4, 1, 1, false, 0, bf16_t>(p, S, st);
 }
 
 // ---- plan_conv(): fills the ConvPlan that every query and launch reads (the struct and run_x6: above, behind dispatch_x6) ----
@@ -1946,6 +1775,218 @@ ConvPlan plan_conv(int num_cus, int dtype, const sg_conv_desc* d, bool dgrad, in
   return plan_conv_mode(x6_mode(), dtype, d, dgrad, flags);
 }
 
+// ---- plan_wgrad(): the filter gradient's counterpart of plan_conv() -----------------------------------------------------
+// Everything a filter-gradient call decides - the kernel family, the slab kernel's form, the pixel split, the sub-batches, the
+// workspace layout, the fused operands it can take - from what a call knows: the CU count, the storage type (SG_HEAD_F32 and
+// SG_X_UP2 included), the descriptor, the alignment CLASS of x and of dy (16, 8 or 0 bytes; never the pointers) and whether the
+// operands are bf16 planes.  sg_conv2d_wgrad, sg_conv2d_wgrad_planes, both workspace queries, sg_conv2d_caps and
+// sg_conv2d_wgrad_plan read this one plan; run_wgrad() launches what it names and decides nothing.
+typedef sg_wgrad_launch WgradLaunch;
+typedef sg_wgrad_plan WgradPlan;
+
+// WgradParams' x_bytes / dy_bytes for a launch of `d`: the operands' extents, 0 = beyond the 2 GiB of a buffer descriptor
+inline void wgrad_extents(int dtype, const sg_conv_desc* d, uint32_t& x_bytes, uint32_t& dy_bytes) {
+  const int up = (dtype & SG_X_UP2) ? 1 : 0, eb = dt_bytes(dtype), eby = (dtype & SG_HEAD_F32) ? 4 : eb;
+  const int64_t xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
+  const int64_t xb = (((int64_t)d->N * (d->H >> up) * (d->W >> up) - 1) * xl + d->Cin) * eb;
+  const int64_t yb = (((int64_t)d->N * d->Ho * d->Wo - 1) * yl + d->Cout) * eby;
+  x_bytes = xb < (1ll << 31) ? (uint32_t)xb : 0;
+  dy_bytes = yb < (1ll << 31) ? (uint32_t)yb : 0;
+}
+
+// Split of the pixel reduction over S workgroups per tile of the slab kernels.  Modelled time = MFMA work / (fraction of the
+// 2*CUs workgroup slots kept busy over whole waves) + the traffic of writing and re-adding S partial slabs; the S with the
+// smallest modelled time wins (e.g. ASPP: 288 tiles -> S = 7: 2016 workgroups = 3.94 waves).  It knows the descriptor and the
+// storage type, no pointers and no byte limits.
+static int wgrad_slab_split(int num_cus, const sg_conv_desc* d, bool b16) {
+  const int64_t K = (int64_t)d->KH * d->KW * d->Cin, P = (int64_t)d->N * d->Ho * d->Wo;
+  const int bn = wgrad_bn(d->Cout);
+  const int64_t tiles = sg_cdiv(K, BM) * sg_cdiv(d->Cout, bn);
+  const int64_t nslab = sg_cdiv(P, BK);
+  const int64_t slots = 2 * (int64_t)num_cus;
+  const double flops = 2.0 * (double)tiles * BM * bn * (double)P;  // padded tile work
+  // Sustained rate of the kernel that will run: wgrad_x6_kernel's or the fp32 MFMA one's.  The test is wgrad_x6_geom, the
+  // geometry half of wgrad_x6_ok, loosened in two ways that stay because S - and with it the order of the sum - hangs on them:
+  // a stride-2 layer counts whatever its padding (wgrad_x6_ok also wants Ho = ceil(H / 2)), and of the launch's 16-byte test
+  // only Cin % 4 is asked, not the pixel strides, Cout % 4, the alignment or the arithmetic switch.
+  const bool x6_rate = (wgrad_x6_geom(d) || (d->stride == 2 && d->dilation == 1 && d->Wo % BK == 0 && d->Cout >= 16)) && d->Cin % 4 == 0;
+  const double rate_x6 = sg_switch_f<SW_WGRAD_PLAN_RATE>() * 1e12;
+  // the one-pass bf16 kernel multiplies ~4x faster than the six-pass one: the split's partial-slab traffic weighs more
+  const double rate_b16 = sg_switch_f<SW_WGRAD_PLAN_RATE_B16>() * 1e12;  // measured 110 / 250 / 450 / 900: no gain from a higher rate (profiles/r02_b16_deep_ab.txt)
+  const double rate = x6_rate ? (b16 ? rate_b16 : rate_x6) : 110e12;
+  int64_t maxS = nslab / 8;  // at least 8 slabs per split
+  if (maxS < 1) maxS = 1;
+  if (maxS > 512) maxS = 512;
+  double best_t = 1e300;
+  int64_t best_S = 1;
+  for (int64_t S = 1; S <= maxS; ++S) {
+    const int64_t wgs = tiles * S;
+    const double eff = (double)wgs / (double)(sg_cdiv(wgs, slots) * slots);
+    const double part_bytes = S > 1 ? (double)S * (double)K * d->Cout * 4.0 : 0.0;
+    if (part_bytes > (double)(384ll << 20)) break;
+    const double t = flops / (eff * rate) + 2.0 * part_bytes / 3.0e12 + (S > 1 ? 3e-6 : 0.0);
+    if (t < best_t * 0.999) { best_t = t; best_S = S; }
+  }
+  return (int)best_S;
+}
+
+// One launch of the plan: `n` images of `dm`, the descriptor of the whole batch or of a full sub-batch (n < dm->N: the last,
+// smaller sub-batch).  The family and the share count S0 come from dm, so that the last sub-batch takes the kernel of the others
+// and never writes more partial slabs than one of them; its own size only shortens the shares.  ax / ay: alignment class of x / dy.
+static WgradLaunch plan_wgrad_launch(int num_cus, int dtype, const sg_conv_desc* dm, int n, int ax, int ay) {
+  WgradLaunch f = {};
+  const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0;
+  sg_conv_desc dd = *dm;
+  dd.N = n;
+  const sg_conv_desc* d = &dd;
+  const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout, taps = d->KH * d->KW;
+  const int64_t P = (int64_t)n * d->Ho * d->Wo, nslab = sg_cdiv(P, BK);
+  const bool thin = thin_ok(dm);
+  if (thin && ax == 16) {   // (dy is read by scalar loads)
+    f.family = SG_WG_THIN;
+    f.S = 1;
+    return f;
+  }
+  uint32_t xb, yb;
+  wgrad_extents(dtype, d, xb, yb);
+  const bool a16 = ax == 16 && ay == 16;
+  const bool dma = a16 && xb != 0 && yb != 0 && !head32;   // what the wide pointwise and the patch kernel ask of their operands
+  const bool wide = !thin && (b16 || x6_mode() == 1) && wgrad_pw_wide_geom(dm, b16 ? 2 : 4);   // 1x1, stride 1, wide enough (conv_pw.h)
+  const bool patch = !thin && !wide && x6wp_geom(dm) && (b16 || x6_enabled()) && xl % (b16 ? 8 : 4) == 0 && yl % (b16 ? 8 : 4) == 0;
+  int S0;   // shares of the family's own kernel on dm
+  if (thin) {
+    S0 = 1;   // (unaligned x: one share of the slab kernels straight into dw, which needs no more workspace than the thin plan)
+  } else if (wide) {
+    const int kp = b16 ? WPB_KP : 16;
+    int k0;
+    wgrad_pw_wide_plan(num_cus, dm, S0, k0, kp);
+    if (dma) {
+      f.family = SG_WG_WIDE;
+      f.planes = (b16 || x6_mode() == 2) ? 1 : 3;
+      f.step_px = kp;
+      wgrad_pw_wide_plan(num_cus, d, f.S, f.steps, kp);   // its own k-steps: a last, smaller sub-batch has fewer
+      if (f.S > S0) {   // never more partial slabs than a full sub-batch
+        f.steps = (int)sg_cdiv(sg_cdiv(P, kp), S0);
+        f.S = (int)sg_cdiv(sg_cdiv(P, kp), f.steps);
+      }
+      return f;
+    }
+  } else if (patch) {
+    S0 = x6wp_grid(num_cus, dm);
+    if (dma) {
+      f.family = SG_WG_PATCH;
+      f.planes = (b16 || x6_mode() == 2) ? 1 : 3;
+      f.S = x6wp_grid(num_cus, d);   // (a last, smaller sub-batch may have fewer tiles than slots)
+      f.step_px = BK;
+      f.steps = (int)sg_cdiv(nslab, f.S);
+      return f;
+    }
+  } else {
+    S0 = wgrad_slab_split(num_cus, dm, b16);
+  }
+  // The slab kernels: the layer's own family, or the fallback of a thin / wide / patch layer whose operands miss that kernel's
+  // alignment or byte limit.  A fallback cuts ITS slabs into at most S0 shares (<= the aligned plan's partial slabs: no fallback
+  // needs more workspace than the aligned plan); the slab family proper keeps the shares of a full sub-batch for the last one too.
+  const int64_t ns = (thin || wide || patch) ? nslab : sg_cdiv((int64_t)dm->N * d->Ho * d->Wo, BK);
+  f.steps = (int)sg_cdiv(ns, S0);
+  f.S = (int)sg_cdiv(ns, f.steps);
+  f.step_px = BK;
+  f.bn = wgrad_bn(d->Cout);
+  const bool g4 = d->Cin % 4 == 0 && xl % 4 == 0 && d->Cout % 4 == 0 && yl % 4 == 0;
+  const bool g8 = d->Cin % 8 == 0 && xl % 8 == 0 && d->Cout % 8 == 0 && yl % 8 == 0;
+  if (head32) {   // x bf16, dy fp32 (not a thin 1x1 convolution)
+    f.family = SG_WG_HEAD32;
+    f.vec = (g4 && ax >= 8 && ay == 16) ? 4 : 0;
+    return f;
+  }
+  const bool vec = (b16 ? g8 : g4) && a16;
+  const int skip = (!sg_switch<SW_CONV_NOSKIP>() && d->dilation > 1 && taps > 1) ? 1 : 0;
+  if (wgrad_x6_ok(d, vec, b16, xb, yb)) {
+    f.family = SG_WG_SLAB_X6;
+    f.vec = b16 ? 8 : 4;
+    f.planes = (b16 || x6_mode() == 2) ? 1 : 3;   // 1 on fp32 storage: bf16 products in one pass
+    f.skip_slabs = skip;
+    f.tap_inner = ((conv_l2(true) & 4) && taps > 1 && d->Cin % BM == 0) ? 1 : 0;
+    f.stagger = b16 ? 0 : sg_switch<SW_X6_ABLATE>() & 7;  // the x6 wgrad kernel has no stagger; the field carries the ablation mask
+    return f;
+  }
+  f.family = SG_WG_SLAB_NATIVE;
+  if (b16) {   // widening loads, no buffer addressing
+    f.vec = (g4 && ax >= 8 && ay >= 8) ? 4 : 0;
+    return f;
+  }
+  f.vec = vec ? 4 : 0;
+  f.skip_slabs = skip;
+  f.tap_inner = ((conv_l2() & 4) && taps > 1 && d->Cin % BM == 0) ? 1 : 0;
+  f.stagger = 1;
+  if (vec && d->stride == 1 && d->Ho == d->H && d->Wo == d->W && xb != 0 && yb != 0) {   // FAST: see igemm_wgrad_kernel
+    const bool force1 = sg_switch<SW_WGRAD_FAST1>();  // A/B switch
+    f.fast = (!force1 && (d->Wo % BK == 0) && (taps == 1 || d->Cin % BM == 0) && ((int64_t)xb + 2 * 32 * (int64_t)xl * 4 < (1ll << 31))) ? 2 : 1;
+  }
+  return f;
+}
+
+// planes: the plan of sg_conv2d_wgrad_planes (fp32 layers, both operands as 16-byte aligned bf16 planes); family 0 = not covered
+WgradPlan plan_wgrad(int num_cus, int dtype, const sg_conv_desc* d, int ax, int ay, bool planes) {
+  WgradPlan pl = {};
+  const int64_t K = (int64_t)d->KH * d->KW * d->Cin, P = (int64_t)d->N * d->Ho * d->Wo;
+  if (planes) {
+    if (x6_mode() != 1) return pl;
+    if (d->stride != 1 || d->Ho != d->H || d->Wo != d->W || (d->Wo % 32) || (d->Cin % 8) || (d->Cout % 8) || d->Cout < 16) return pl;
+    if ((d->x_ld && d->x_ld != d->Cin) || (d->y_ld && d->y_ld != d->Cout)) return pl;   // planes are dense
+    const int64_t xp = (int64_t)d->N * d->H * d->W * d->Cin * 2, yp = P * d->Cout * 2;
+    const int64_t sh = ((int64_t)d->pad_t * d->W + d->pad_l + 64) * d->Cin * 4;
+    if (3 * xp + 2 * sh >= (1ll << 31) || 3 * yp >= (1ll << 31)) return pl;
+    dtype = SG_F32;   // the shares below are those of the layer's fp32-operand launch: the same sum in the same order
+    ax = ay = 16;
+  }
+  // Sub-batches of whole images keep every launch's operands inside a 2 GiB buffer descriptor.  images_per_2gib counts 4-byte
+  // elements for bf16 storage too: that fixes the chunking, and with it the order of the sum, for both storage types alike.
+  const int nb = images_per_2gib(d);
+  const bool chunked = nb >= 1 && nb < d->N && !thin_ok(d);
+  pl.nb = chunked ? nb : d->N;
+  pl.chunks = chunked ? (int)sg_cdiv(d->N, nb) : 1;
+  pl.tail_n = d->N - (pl.chunks - 1) * pl.nb;
+  sg_conv_desc dm = *d;
+  dm.N = pl.nb;
+  pl.main = plan_wgrad_launch(num_cus, dtype, &dm, pl.nb, ax, ay);
+  pl.tail = pl.tail_n == pl.nb ? pl.main : plan_wgrad_launch(num_cus, dtype, &dm, pl.tail_n, ax, ay);
+  if (planes) {
+    if (pl.main.family != SG_WG_SLAB_X6 || pl.chunks > 1) return WgradPlan{};   // a thin, wide pointwise or patch layer, or beyond 2 GiB
+    WgradLaunch& f = pl.main;
+    f.family = SG_WG_PLANES;
+    f.vec = 8;
+    f.stagger = sg_switch<SW_X6_ABLATE>() & 15;   // timing-only diagnostics
+    // SG_WGRAD_PIN_SMUL: more, shorter pixel shares than the fp32-operand plan (the planes are 1.5 x the bytes per pixel: the share
+    // of x that the workgroups of an XCD walk together should still fit its L2)
+    const int smul = sg_switch<SW_WGRAD_PIN_SMUL>();
+    if (smul > 1 && f.S > 1) {
+      const int64_t nslab = sg_cdiv(P, BK);
+      int64_t S = (int64_t)f.S * smul;
+      if (S > nslab / 4) S = nslab / 4 > 0 ? nslab / 4 : 1;
+      f.steps = (int)sg_cdiv(nslab, S);
+      f.S = (int)sg_cdiv(nslab, f.steps);
+    }
+    pl.tail = f;
+  }
+  pl.max_parts = (pl.chunks - 1) * pl.main.S + pl.tail.S;
+  if (pl.chunks > 1) pl.dw_part_bytes = (size_t)pl.chunks * pl.main.S * K * d->Cout * 4;   // every sub-batch writes partial slabs
+  else if (pl.main.family == SG_WG_THIN) pl.dw_part_bytes = thin_part_bytes(num_cus, d);
+  else pl.dw_part_bytes = pl.main.S > 1 ? (size_t)pl.main.S * K * d->Cout * 4 : 0;
+  pl.bias_part_bytes = planes ? 0 : colsum_ws_bytes(num_cus, P, d->Cout);   // (the planes-in call has no bias gradient)
+  pl.bias_off = (pl.dw_part_bytes + 255) & ~(size_t)255;   // 256-byte aligned, after the dw partials
+  pl.ws_bytes = pl.dw_part_bytes + pl.bias_part_bytes + 512;
+  // the fused operands: only the thin and the patch kernel apply a BatchNormalization to x (fp32 storage, dense pixels), only the
+  // patch kernel gathers from the source of an up-sampling
+  const bool f32 = dt_storage(dtype) == SG_F32 && !(dtype & SG_HEAD_F32);
+  const bool x_dense = !d->x_ld || d->x_ld == d->Cin;
+  // (a layer's forward and filter gradient take the BatchNormalization together or not at all: the forward's plan is asked too)
+  pl.bn_in = (pl.main.family == SG_WG_THIN || pl.main.family == SG_WG_PATCH) && f32 && !(dtype & SG_X_UP2) && x_dense &&
+             plan_conv(num_cus, dtype, d, false, 0).bn_in;
+  pl.up2 = pl.main.family == SG_WG_PATCH && !(dtype & SG_HEAD_F32) && x6p_up2_geom(d);
+  return pl;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1986,11 +2027,10 @@ static BnIn bn_in_of(const sg_bn_in* b) {
   return o;
 }
 // the launches that can apply a BatchNormalization to their input: the thin 1x1 kernels (Cout <= 4) and the patch kernels (3x3,
-// stride 1, SAME, 32 / 64 input channels: conv_x6p.h forward, conv_x6wp.h filter gradient), fp32 storage
+// stride 1, SAME, 32 / 64 input channels: conv_x6p.h forward, conv_x6wp.h filter gradient), fp32 storage.  Forward AND filter
+// gradient must both take the operand: the filter gradient's plan answers for the pair
 static bool bn_in_geom(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
-  const ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, false, 0);
-  // (patch: forward AND filter gradient must both take the patch kernels)
-  return pl.bn_in && (pl.family == CONV_THIN || plan_wgrad(ctx->num_cus, d, false).patch != 0);
+  return plan_wgrad(ctx->num_cus, dtype, d, 16, 16, false).bn_in != 0;
 }
 
 // sg_conv_opts: a NULL pointer is the plain launch
@@ -2386,209 +2426,206 @@ int sg_conv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d,
   return 0;
 }
 
+// alignment class of a pointer, as plan_wgrad takes it
+static int align_class(const void* p) { return aligned16(p) ? 16 : ((reinterpret_cast<uintptr_t>(p) & 7) == 0 ? 8 : 0); }
+
+// The checks that the two filter-gradient entry points and the plan query share, then the plan.  ax / ay: alignment class of x / dy.
+static int wgrad_plan_checked(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int ax, int ay, bool planes, const char* who, WgradPlan* pl) {
+  SG_CHECK_ARG(ctx != nullptr, "%s: null ctx", who);
+  SG_CHECK_ARG(dt_ok(dtype), "%s: dtype %d", who, dtype);
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0;
+  SG_CHECK_ARG(!head32 || (b16 && d->Cout <= 4), "%s: SG_HEAD_F32 needs Cout <= 4 (a softmax head) on bf16 storage", who);
+  SG_CHECK_ARG(!planes || (dtype == SG_F32 && ax == 16 && ay == 16), "%s: null / unaligned tensor", who);
+  *pl = plan_wgrad(ctx->num_cus, dtype, d, ax, ay, planes);
+  if (planes && !pl->main.family) {
+    sg_set_error("%s: geometry outside the planes-in kernel (stride 1 SAME, W %% 32 = 0, channels %% 8 = 0, dense "
+                 "planes below 2 GiB, not a wide pointwise / patch-form layer, x6 arithmetic)", who);
+    return SG_EUNSUPPORTED;
+  }
+  SG_CHECK_ARG(!(head32 && pl->chunks > 1), "%s: softmax head beyond 2 GiB", who);
+  return 0;
+}
+
+int sg_conv2d_wgrad_plan(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int aligned, int planes, sg_wgrad_plan* out) {
+  SG_CHECK_ARG(out != nullptr, "sg_conv2d_wgrad_plan: null out");
+  memset(out, 0, sizeof(*out));
+  SG_CHECK_ARG(aligned == 16 || aligned == 8 || aligned == 0, "sg_conv2d_wgrad_plan: aligned %d (16, 8 or 0)", aligned);
+  WgradPlan pl;
+  const int rc = wgrad_plan_checked(ctx, dtype, d, aligned, aligned, planes != 0, planes ? "sg_conv2d_wgrad_planes" : "sg_conv2d_wgrad", &pl);
+  if (!rc) *out = pl;
+  return rc;
+}
+
+// The storage-blind query: the larger of the fp32 and the bf16 plan at full alignment.  No plan of another alignment class needs
+// more: an unaligned thin layer writes dw directly (no partials), and the wide pointwise and patch fallbacks cut their slabs into
+// at most the aligned plan's share count (plan_wgrad_launch: S <= S0), so their partial slabs fit the aligned plan's.
 size_t sg_conv2d_wgrad_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d) {
   if (!ctx || !d) return 0;
-  // the query does not know the storage type: the larger of the fp32 and the bf16 plan
-  const WgradPlan pl = plan_wgrad(ctx->num_cus, d, false), pb = plan_wgrad(ctx->num_cus, d, true);
-  const size_t a = pl.dw_part_bytes + pl.bias_part_bytes, b = pb.dw_part_bytes + pb.bias_part_bytes;
-  return (a > b ? a : b) + 512;
+  const size_t a = plan_wgrad(ctx->num_cus, SG_F32, d, 16, 16, false).ws_bytes, b = plan_wgrad(ctx->num_cus, SG_BF16, d, 16, 16, false).ws_bytes;
+  return a > b ? a : b;
+}
+
+size_t sg_conv2d_wgrad_planes_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d) {
+  if (!ctx || !d || check_desc(d, "sg_conv2d_wgrad_planes_ws_bytes")) return 0;
+  const WgradPlan pl = plan_wgrad(ctx->num_cus, SG_F32, d, 16, 16, true);
+  return pl.main.family ? pl.ws_bytes : 0;
+}
+
+// WgradParams of one launch of the plan: `dd` = its images, `out` = where its first partial slab (or dw itself) goes
+static void fill_wgrad_params(WgradParams& p, int dtype, const sg_conv_desc& dd, const WgradLaunch& f, const void* xs, const void* dys,
+                              float* out, const sg_bn_in* bn) {
+  p.x = (const float*)xs;
+  p.dy = (const float*)dys;
+  p.out = out;
+  p.H = dd.H; p.W = dd.W; p.Cin = dd.Cin; p.x_ld = dd.x_ld ? dd.x_ld : dd.Cin;
+  p.OH = dd.Ho; p.OW = dd.Wo; p.Cout = dd.Cout; p.y_ld = dd.y_ld ? dd.y_ld : dd.Cout;
+  p.stride = dd.stride; p.dil = dd.dilation; p.pad_t = dd.pad_t; p.pad_l = dd.pad_l;
+  p.K = dd.KH * dd.KW * dd.Cin;
+  p.KH_KW = dd.KH * dd.KW;
+  p.P = dd.N * dd.Ho * dd.Wo;
+  p.slabs_per_split = f.steps;
+  p.skip_slabs = f.skip_slabs;
+  p.tap_inner = f.tap_inner;
+  p.stagger = f.stagger;
+  p.up = (dtype & SG_X_UP2) ? 1 : 0;
+  p.bn = bn_in_of(bn);
+  p.fd_ohow = make_fastdiv((uint32_t)(dd.Ho * dd.Wo));
+  p.fd_ow = make_fastdiv((uint32_t)dd.Wo);
+  p.fd_c = make_fastdiv((uint32_t)dd.Cin);
+  p.fd_kw = make_fastdiv((uint32_t)dd.KW);
+  p.fd_oh = make_fastdiv((uint32_t)dd.Ho);
+  if (f.family == SG_WG_PLANES) {   // x / dy = three dense bf16 planes each; the extents cover all three
+    p.x_plane_bytes = (uint32_t)((int64_t)dd.N * dd.H * dd.W * dd.Cin * 2);
+    p.dy_plane_bytes = (uint32_t)((int64_t)p.P * dd.Cout * 2);
+    p.x_bytes = 3 * p.x_plane_bytes;
+    p.dy_bytes = 3 * p.dy_plane_bytes;
+  } else {
+    p.x_plane_bytes = p.dy_plane_bytes = 0;
+    wgrad_extents(dtype, &dd, p.x_bytes, p.dy_bytes);
+  }
+}
+
+// the template instantiation the plan names, for the three tile widths
+#define WG_TILE(FN, ...)                                                             \
+  (f.bn == 128 ? FN<128, 2, 4, __VA_ARGS__>(p, f.S, st)                             \
+               : f.bn == 64 ? FN<64, 4, 2, __VA_ARGS__>(p, f.S, st) : FN<32, 4, 1, __VA_ARGS__>(p, f.S, st))
+
+static int launch_wgrad_plan(sg_ctx* ctx, hipStream_t st, int dtype, const sg_conv_desc& dd, const WgradLaunch& f, const WgradParams& p,
+                             void* ws, const sg_bn_in* bn) {
+  const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0;
+  const sg_conv_desc* d = &dd;
+  switch (f.family) {
+    case SG_WG_THIN:
+      if (!b16) {
+#define CALL(CO) thin_wgrad_t<CO, float, float>(ctx->num_cus, d, p.x, p.dy, p.out, (float*)ws, st, p.bn)
+        THIN_SWITCH(d->Cout, CALL)
+#undef CALL
+      } else if (head32) {
+#define CALL(CO) thin_wgrad_t<CO, bf16_t, float>(ctx->num_cus, d, (const bf16_t*)p.x, p.dy, p.out, (float*)ws, st)
+        THIN_SWITCH(d->Cout, CALL)
+#undef CALL
+      } else {
+#define CALL(CO) thin_wgrad_t<CO, bf16_t, bf16_t>(ctx->num_cus, d, (const bf16_t*)p.x, (const bf16_t*)p.dy, p.out, (float*)ws, st)
+        THIN_SWITCH(d->Cout, CALL)
+#undef CALL
+      }
+    case SG_WG_WIDE:
+      return b16 ? launch_wgrad_pw_wide_b16(p, f.S, st) : launch_wgrad_pw_wide(p, f.S, st);
+    case SG_WG_PATCH:
+      if (b16) return launch_x6wp<1, bf16_t>(p, f.S, st);
+      return f.planes == 1 ? launch_x6wp<1, float>(p, f.S, st) : launch_x6wp<3, float>(p, f.S, st);
+    case SG_WG_SLAB_X6:
+      if (b16) return WG_TILE(launch_wgrad_x6, 1, 1, bf16_t);
+      return f.planes == 1 ? WG_TILE(launch_wgrad_x6, 1, 1, float) : WG_TILE(launch_wgrad_x6, 1);
+    case SG_WG_PLANES:
+      // Single LDS buffer, two workgroups per CU, the fp32-operand kernel's structure.  Measured (scripts/wgrad_planes_bench.py, fourteen
+      // long-K shapes): 7301 us against 8485 for the fp32-operand kernel; a double-buffered woven form took 7577 and four waves of 64 x 64
+      // per tile changed nothing - the read + MFMA loop itself takes 640 of the 810 us of the ASPP launch either way.  Both are gone
+      // (retired).
+      return WG_TILE(launch_wgrad_x6, 1, 3, bf16_t, true);
+    case SG_WG_HEAD32:
+      return f.vec ? WG_TILE(launch_wgrad_f, 1, true, 0, bf16_t, float) : WG_TILE(launch_wgrad_f, 1, false, 0, bf16_t, float);
+    case SG_WG_SLAB_NATIVE:
+      if (b16) return f.vec ? WG_TILE(launch_wgrad_f, 1, true, 0, bf16_t) : WG_TILE(launch_wgrad_f, 1, false, 0, bf16_t);
+      if (!f.vec) return WG_TILE(launch_wgrad_f, 1, false, 0);
+      if (f.fast == 2) return WG_TILE(launch_wgrad_f, 2, true, 2);
+      return f.fast == 1 ? WG_TILE(launch_wgrad_f, 2, true, 1) : WG_TILE(launch_wgrad_f, 2, true, 0);
+  }
+  sg_set_error("filter gradient: plan without a family");
+  return SG_EINVAL;
+}
+#undef WG_TILE
+
+// Runs a checked plan: every sub-batch's launch, the fixed-order reduce of the partial slabs, the bias gradient.
+static int run_wgrad(sg_ctx* ctx, hipStream_t st, int dtype, const sg_conv_desc* d, const WgradPlan& pl, const void* x, const void* dy,
+                     void* dw, void* dbias, void* ws, const sg_bn_in* bn) {
+  const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0, up2 = (dtype & SG_X_UP2) != 0;
+  const int eb = dt_bytes(dtype);
+  const int64_t xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
+  const int64_t slab = (int64_t)d->KH * d->KW * d->Cin * d->Cout;
+  // sub-batches of whole images, each writing its partial slabs one after the other; one reduce over all of them.  (Where the plan
+  // names a vector form, the pixel strides are multiples of that vector, so every sub-batch's operands keep the call's alignment.)
+  int parts = 0;
+  for (int c = 0; c < pl.chunks; ++c) {
+    const WgradLaunch& f = c + 1 < pl.chunks ? pl.main : pl.tail;
+    sg_conv_desc sub = *d;
+    const int n0 = c * pl.nb;
+    sub.N = c + 1 < pl.chunks ? pl.nb : pl.tail_n;
+    WgradParams p;
+    fill_wgrad_params(p, dtype, sub, f, (const char*)x + (int64_t)n0 * (up2 ? (d->H / 2) * (d->W / 2) : d->H * d->W) * xl * eb,
+                      (const char*)dy + (int64_t)n0 * d->Ho * d->Wo * yl * eb,
+                      pl.max_parts > 1 ? (float*)ws + (int64_t)parts * slab : (float*)dw, bn);
+    const int rc = launch_wgrad_plan(ctx, st, dtype, sub, f, p, ws, bn);
+    if (rc) return rc;
+    parts += f.S;
+  }
+  if (parts > 1) {
+    const bool v4 = (slab % 4 == 0) && aligned16(ws) && aligned16(dw);
+    int64_t blocks = sg_cdiv(slab, v4 ? 1024 : 256);
+    if (blocks > 2048) blocks = 2048;
+    // (a four-lanes-per-quad kernel measured no gain - the reduce launches sit on the side stream behind their filter gradient
+    // and hide either way - and is gone: DESIGN.md, retired)
+    if (v4) hipLaunchKernelGGL(reduce_splits_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, (float*)dw, slab, parts);
+    else hipLaunchKernelGGL(reduce_splits_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, (float*)dw, slab, parts);
+    SG_LAUNCH_CHECK("reduce_splits_kernel");
+  }
+  if (!dbias) return 0;
+  const int64_t rows_y = (int64_t)d->N * d->Ho * d->Wo;
+  float* bias_part = (float*)((char*)ws + pl.bias_off);
+  if (!b16 || head32) return launch_colsum<float>(ctx->num_cus, (const float*)dy, rows_y, d->Cout, (int)yl, (float*)dbias, bias_part, st);
+  return launch_colsum<bf16_t>(ctx->num_cus, (const bf16_t*)dy, rows_y, d->Cout, (int)yl, (float*)dbias, bias_part, st);
 }
 
 int sg_conv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* dy,
                     void* dw, void* dbias, const sg_conv_opts* opts) {
   const sg_conv_opts& o = opts ? *opts : kNoOpts;
-  void* const ws = o.ws;
-  const size_t ws_bytes = o.ws_bytes;
   const sg_bn_in* const bn = o.bn_in;
   SG_CHECK_ARG(!o.stats && !o.tiles_out && !o.a_planes && !o.res && !o.bnb,
                "sg_conv2d_wgrad: stats / tiles_out / a_planes / res / bnb are operands of the forward and the input gradient");
-  if (bn) {
-    SG_CHECK_ARG(bn->mean && bn->invstd && bn->gamma && bn->beta, "sg_conv2d_wgrad: bn_in with null BatchNormalization parameters");
-    SG_CHECK_ARG(ctx && d, "sg_conv2d_wgrad: null argument");
-    if (check_desc(d, "sg_conv2d_wgrad") || !bn_in_geom(ctx, dtype, d)) {
-      sg_set_error("sg_conv2d_wgrad: bn_in, but this launch takes neither the thin 1x1 nor the patch filter-gradient kernel");
-      return SG_EUNSUPPORTED;
-    }
-  }
-  SG_CHECK_ARG(ctx != nullptr, "sg_conv2d_wgrad: null ctx");
-  SG_CHECK_ARG(dt_ok(dtype), "sg_conv2d_wgrad: dtype %d", dtype);
-  int rc = check_desc(d, "sg_conv2d_wgrad");
+  SG_CHECK_ARG(!bn || (bn->mean && bn->invstd && bn->gamma && bn->beta), "sg_conv2d_wgrad: bn_in with null BatchNormalization parameters");
+  WgradPlan pl;
+  // (dy of the softmax head is fp32: its 4-channel loads need 16 bytes, which the plan asks of that class itself)
+  int rc = wgrad_plan_checked(ctx, dtype, d, align_class(x), align_class(dy), false, "sg_conv2d_wgrad", &pl);
   if (rc) return rc;
   SG_CHECK_ARG(x && dy && dw, "sg_conv2d_wgrad: null tensor");
-  const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0, up2 = (dtype & SG_X_UP2) != 0;
-  const int eb = dt_bytes(dtype);
-  const WgradPlan pl = plan_wgrad(ctx->num_cus, d, b16);
-  if (up2 && !(pl.patch && !head32 && x6p_up2_geom(d) && aligned16(x) && aligned16(dy))) {
+  if (bn && !pl.bn_in) {
+    sg_set_error("sg_conv2d_wgrad: bn_in, but this launch takes neither the thin 1x1 nor the patch filter-gradient kernel (fp32 "
+                 "storage, 16-byte aligned operands below 2 GiB)");
+    return SG_EUNSUPPORTED;
+  }
+  if ((dtype & SG_X_UP2) && !pl.up2) {
     // x = the source of a 2x nearest up-sampling: only the patch kernel gathers that way (conv_x6wp.h)
     sg_set_error("sg_conv2d_wgrad: SG_X_UP2 on a launch the patch filter-gradient kernel does not cover");
     return SG_EUNSUPPORTED;
   }
-  const size_t need = pl.dw_part_bytes + pl.bias_part_bytes + 512;
-  if (!ws || ws_bytes < need) {
-    sg_set_error("sg_conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
+  if (!o.ws || o.ws_bytes < pl.ws_bytes) {
+    sg_set_error("sg_conv2d_wgrad: workspace %zu < %zu", o.ws_bytes, (size_t)pl.ws_bytes);
     return SG_EWORKSPACE;
   }
-  SG_CHECK_ARG(aligned16(ws), "sg_conv2d_wgrad: workspace must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const bool thin = thin_ok(d) && aligned16(x);
-  SG_CHECK_ARG(!head32 || (b16 && d->Cout <= 4), "sg_conv2d_wgrad: SG_HEAD_F32 needs Cout <= 4 (a softmax head) on bf16 storage");
-  const int64_t rows_y = (int64_t)d->N * d->Ho * d->Wo;
-  const int yl_ = d->y_ld ? d->y_ld : d->Cout;
-  float* bias_part = (float*)((char*)ws + ((pl.dw_part_bytes + 255) & ~(size_t)255));  // 256-byte aligned, after the dw partials
-  auto bias_grad = [&]() -> int {
-    if (!dbias) return 0;
-    if (!b16 || head32) return launch_colsum<float>(ctx->num_cus, (const float*)dy, rows_y, d->Cout, yl_, (float*)dbias, bias_part, st);
-    return launch_colsum<bf16_t>(ctx->num_cus, (const bf16_t*)dy, rows_y, d->Cout, yl_, (float*)dbias, bias_part, st);
-  };
-  if (thin) {
-    auto run = [&]() -> int {
-      if (!b16) {
-#define CALL(CO) thin_wgrad_t<CO, float, float>(ctx->num_cus, d, (const float*)x, (const float*)dy, (float*)dw, (float*)ws, st, bn_in_of(bn))
-        THIN_SWITCH(d->Cout, CALL)
-#undef CALL
-      } else if (head32) {
-#define CALL(CO) thin_wgrad_t<CO, bf16_t, float>(ctx->num_cus, d, (const bf16_t*)x, (const float*)dy, (float*)dw, (float*)ws, st)
-        THIN_SWITCH(d->Cout, CALL)
-#undef CALL
-      } else {
-#define CALL(CO) thin_wgrad_t<CO, bf16_t, bf16_t>(ctx->num_cus, d, (const bf16_t*)x, (const bf16_t*)dy, (float*)dw, (float*)ws, st)
-        THIN_SWITCH(d->Cout, CALL)
-#undef CALL
-      }
-    };
-    rc = run();
-    if (rc) return rc;
-    return bias_grad();
-  }
-  const int K_all = d->KH * d->KW * d->Cin;
-  // parts: in = the plan's S, out = the partial slabs actually written (a patch plan that has to fall back to the slab
-  // kernels - unaligned pointers - writes cdiv(slabs, slabs_per_split) <= S of them)
-  auto launch_part = [&](const sg_conv_desc& dd, const void* xs, const void* dys, float* out, int& parts, int sps) -> int {
-    int S = parts;
-    WgradParams p;
-    p.x = (const float*)xs;
-    p.dy = (const float*)dys;
-    p.out = out;
-    p.H = dd.H; p.W = dd.W; p.Cin = dd.Cin; p.x_ld = dd.x_ld ? dd.x_ld : dd.Cin;
-    p.OH = dd.Ho; p.OW = dd.Wo; p.Cout = dd.Cout; p.y_ld = dd.y_ld ? dd.y_ld : dd.Cout;
-    p.stride = dd.stride; p.dil = dd.dilation; p.pad_t = dd.pad_t; p.pad_l = dd.pad_l;
-    p.K = K_all;
-    p.P = dd.N * dd.Ho * dd.Wo;
-    p.slabs_per_split = sps;
-    p.up = up2 ? 1 : 0;
-    p.bn = bn_in_of(bn);
-    p.x_plane_bytes = p.dy_plane_bytes = 0;
-    p.fd_ohow = make_fastdiv((uint32_t)(dd.Ho * dd.Wo));
-    p.fd_ow = make_fastdiv((uint32_t)dd.Wo);
-    p.fd_c = make_fastdiv((uint32_t)dd.Cin);
-    p.fd_kw = make_fastdiv((uint32_t)dd.KW);
-    p.fd_oh = make_fastdiv((uint32_t)dd.Ho);
-    {
-      const int64_t xb = (((int64_t)dd.N * (dd.H >> p.up) * (dd.W >> p.up) - 1) * p.x_ld + dd.Cin) * eb;
-      const int64_t yb = (((int64_t)p.P - 1) * p.y_ld + dd.Cout) * eb;
-      p.x_bytes = xb < (1ll << 31) ? (uint32_t)xb : 0;
-      p.dy_bytes = yb < (1ll << 31) ? (uint32_t)yb : 0;
-    }
-    if (pl.wide) {
-      const bool al = aligned16(xs) && aligned16(dys) && p.x_bytes != 0 && p.dy_bytes != 0 && !head32;
-      if (al) {
-        int Sw, kps;   // re-planned for THIS part: a last, smaller sub-batch has fewer k-steps
-        const int kp = b16 ? WPB_KP : 16;
-        wgrad_pw_wide_plan(ctx->num_cus, &dd, Sw, kps, kp);
-        if (Sw > S) {  // never more partial slabs than the workspace was sized for
-          kps = (int)sg_cdiv(sg_cdiv((int64_t)p.P, kp), S);
-          Sw = (int)sg_cdiv(sg_cdiv((int64_t)p.P, kp), kps);
-        }
-        p.slabs_per_split = kps;
-        parts = Sw;
-        return b16 ? launch_wgrad_pw_wide_b16(p, Sw, st) : launch_wgrad_pw_wide(p, Sw, st);
-      }
-    }
-    if (pl.patch) {
-      const bool al = aligned16(xs) && aligned16(dys) && p.x_bytes != 0 && p.dy_bytes != 0 && !head32;
-      if ((up2 || p.bn.mean) && !al) {
-        sg_set_error("sg_conv2d_wgrad: SG_X_UP2 / a BatchNormalization on x need 16-byte aligned operands below 2 GiB (the patch kernel)");
-        return SG_EUNSUPPORTED;
-      }
-      if (al) {
-        const int grid = x6wp_grid(ctx->num_cus, &dd);  // a last, smaller sub-batch may have fewer tiles than slots
-        parts = grid;
-        p.out = out;
-        if (b16) return launch_x6wp<1, bf16_t>(p, grid, st);
-        return x6_mode() == 2 ? launch_x6wp<1, float>(p, grid, st) : launch_x6wp<3, float>(p, grid, st);
-      }
-      const int nslab = (int)sg_cdiv((int64_t)p.P, BK);
-      sps = (int)sg_cdiv(nslab, S);
-      p.slabs_per_split = sps;
-      S = (int)sg_cdiv(nslab, sps);
-      parts = S;
-    }
-    if (p.bn.mean) {   // (the patch branch above returned; nothing below applies a BatchNormalization to x)
-      sg_set_error("sg_conv2d_wgrad: bn_in, but the launch does not take the patch kernel after all");
-      return SG_EUNSUPPORTED;
-    }
-    if (pl.wide) {  // unaligned operands: the slab kernels, with the plan's share count
-      const int nslab = (int)sg_cdiv((int64_t)p.P, BK);
-      sps = (int)sg_cdiv(nslab, S);
-      p.slabs_per_split = sps;
-      S = (int)sg_cdiv(nslab, sps);
-      parts = S;
-    }
-    if (b16 && head32) {  // x bf16, dy fp32 (not a thin 1x1 convolution)
-      const int64_t yb32 = (((int64_t)p.P - 1) * p.y_ld + dd.Cout) * 4;
-      p.dy_bytes = yb32 < (1ll << 31) ? (uint32_t)yb32 : 0;
-      const bool vec4 = (dd.Cin % 4 == 0) && (p.x_ld % 4 == 0) && (dd.Cout % 4 == 0) && (p.y_ld % 4 == 0) &&
-                        (((uintptr_t)xs & 7) == 0) && aligned16(dys);
-      return dispatch_wgrad_head32(p, S, vec4, st);
-    }
-    if (b16) {
-      const bool vec8 = (dd.Cin % 8 == 0) && (p.x_ld % 8 == 0) && (dd.Cout % 8 == 0) && (p.y_ld % 8 == 0) && aligned16(xs) && aligned16(dys);
-      const bool vec4 = (dd.Cin % 4 == 0) && (p.x_ld % 4 == 0) && (dd.Cout % 4 == 0) && (p.y_ld % 4 == 0) &&
-                        (((uintptr_t)xs & 7) == 0) && (((uintptr_t)dys & 7) == 0);
-      return dispatch_wgrad_b16(p, S, vec8, vec4, st);
-    }
-    const bool vec = (dd.Cin % 4 == 0) && (p.x_ld % 4 == 0) && (dd.Cout % 4 == 0) && (p.y_ld % 4 == 0) &&
-                     aligned16(xs) && aligned16(dys);
-    return dispatch_wgrad(p, S, vec, st);
-  };
-  SG_CHECK_ARG(!(head32 && pl.chunks > 1), "sg_conv2d_wgrad: softmax head beyond 2 GiB");
-  int total_parts = pl.S;
-  if (pl.chunks > 1) {
-    // sub-batches of whole images, each writing its S partial slabs one after the other; one reduce over all of them
-    const int64_t xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-    const int64_t slab = (int64_t)K_all * d->Cout;
-    total_parts = 0;
-    for (int c = 0; c < pl.chunks; ++c) {
-      sg_conv_desc sub = *d;
-      const int n0 = c * pl.nb;
-      sub.N = (d->N - n0 < pl.nb) ? d->N - n0 : pl.nb;
-      int parts = pl.S;
-      rc = launch_part(sub, (const char*)x + (int64_t)n0 * (up2 ? (d->H / 2) * (d->W / 2) : d->H * d->W) * xl * eb,
-                       (const char*)dy + (int64_t)n0 * d->Ho * d->Wo * yl * eb,
-                       (float*)ws + (int64_t)total_parts * slab, parts, pl.slabs_per_split);
-      if (rc) return rc;
-      total_parts += parts;
-    }
-  } else {
-    int parts = pl.S;
-    rc = launch_part(*d, x, dy, pl.S > 1 ? (float*)ws : (float*)dw, parts, pl.slabs_per_split);
-    if (rc) return rc;
-    total_parts = parts;
-  }
-  if (total_parts > 1) {
-    const int64_t n = (int64_t)K_all * d->Cout;
-    const bool v4 = (n % 4 == 0) && aligned16(ws) && aligned16(dw);
-    int64_t blocks = sg_cdiv(n, v4 ? 1024 : 256);
-    if (blocks > 2048) blocks = 2048;
-    // (a four-lanes-per-quad kernel measured no gain - the reduce launches sit on the side stream behind their filter gradient
-    // and hide either way - and is gone: DESIGN.md, retired)
-    if (v4)
-      hipLaunchKernelGGL(reduce_splits_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, (float*)dw, n, total_parts);
-    else
-      hipLaunchKernelGGL(reduce_splits_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, (float*)dw, n, total_parts);
-    SG_LAUNCH_CHECK("reduce_splits_kernel");
-  }
-  return bias_grad();
+  SG_CHECK_ARG(aligned16(o.ws), "sg_conv2d_wgrad: workspace must be 16-byte aligned");
+  return run_wgrad(ctx, (hipStream_t)stream, dtype, d, pl, x, dy, dw, dbias, o.ws, bn);
 }
 
 // ---- planes-in filter gradient (round 5; conv_x6.h: wgrad_x6_kernel<.., PIN>) -------------------------------------------
@@ -2603,34 +2640,17 @@ int sg_split_planes(sg_ctx* ctx, void* stream, const void* x, int64_t rows, int 
   return 0;
 }
 
-static bool wgrad_planes_geom(const sg_ctx* ctx, const sg_conv_desc* d, WgradPlan* out) {
-  if (x6_mode() != 1) return false;
-  if (d->stride != 1 || d->Ho != d->H || d->Wo != d->W || (d->Wo % 32) || (d->Cin % 8) || (d->Cout % 8) || d->Cout < 16) return false;
-  if ((d->x_ld && d->x_ld != d->Cin) || (d->y_ld && d->y_ld != d->Cout)) return false;   // planes are dense
-  const int64_t xp = (int64_t)d->N * d->H * d->W * d->Cin * 2, yp = (int64_t)d->N * d->Ho * d->Wo * d->Cout * 2;
-  const int64_t sh = ((int64_t)d->pad_t * d->W + d->pad_l + 64) * d->Cin * 4;
-  if (3 * xp + 2 * sh >= (1ll << 31) || 3 * yp >= (1ll << 31)) return false;
-  WgradPlan pl = plan_wgrad(ctx->num_cus, d, false);
-  if (pl.wide || pl.patch || pl.chunks > 1 || thin_ok(d)) return false;
-  // SG_WGRAD_PIN_SMUL: more, shorter pixel shares than the fp32-operand plan (the planes are 1.5 x the bytes per pixel: the share
-  // of x that the workgroups of an XCD walk together should still fit its L2)
-  const int smul = sg_switch<SW_WGRAD_PIN_SMUL>();
-  if (smul > 1 && pl.S > 1) {
-    const int64_t nslab = sg_cdiv((int64_t)d->N * d->Ho * d->Wo, BK);
-    int64_t S = (int64_t)pl.S * smul;
-    if (S > nslab / 4) S = nslab / 4 > 0 ? nslab / 4 : 1;
-    pl.slabs_per_split = (int)sg_cdiv(nslab, S);
-    pl.S = (int)sg_cdiv(nslab, pl.slabs_per_split);
-    pl.dw_part_bytes = (size_t)pl.S * d->KH * d->KW * d->Cin * d->Cout * 4;
-  }
-  if (out) *out = pl;
-  return true;
-}
-
-size_t sg_conv2d_wgrad_planes_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d) {
+int sg_conv2d_wgrad_planes(sg_ctx* ctx, void* stream, const sg_conv_desc* d, const void* x_planes, const void* dy_planes, void* dw,
+                           void* ws, size_t ws_bytes) {
   WgradPlan pl;
-  if (!ctx || !d || check_desc(d, "sg_conv2d_wgrad_planes_ws_bytes") || !wgrad_planes_geom(ctx, d, &pl)) return 0;
-  return pl.dw_part_bytes + 512;
+  const int ok = x_planes && dy_planes && dw;   // (a null tensor answers like an unaligned one)
+  int rc = wgrad_plan_checked(ctx, SG_F32, d, ok ? align_class(x_planes) : 0, ok ? align_class(dy_planes) : 0, true, "sg_conv2d_wgrad_planes", &pl);
+  if (rc) return rc;
+  if (!ws || ws_bytes < pl.ws_bytes || !aligned16(ws)) {
+    sg_set_error("sg_conv2d_wgrad_planes: workspace %zu < %zu", ws_bytes, (size_t)pl.ws_bytes);
+    return SG_EWORKSPACE;
+  }
+  return run_wgrad(ctx, (hipStream_t)stream, SG_F32, d, pl, x_planes, dy_planes, dw, nullptr, ws, nullptr);
 }
 
 // what the launches of `d` can take: every answer from the plans they run by
@@ -2641,79 +2661,18 @@ int sg_conv2d_caps(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int dgra
   const ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, dgrad != 0, 0);
   out->thin = pl.family == CONV_THIN;
   out->planes_in = pl.planes_in;
-  out->wgrad_planes = dt_storage(dtype) == SG_F32 && wgrad_planes_geom(ctx, d, nullptr);   // (the filter gradient has no direction)
+  // (the filter gradient has no direction)
+  out->wgrad_planes = dt_storage(dtype) == SG_F32 && plan_wgrad(ctx->num_cus, SG_F32, d, 16, 16, true).main.family != 0;
   if (dgrad) {
     out->bnb = pl.bnb;
-  } else {
-    out->bn_in = bn_in_geom(ctx, dtype, d);
-    out->up2 = pl.up2;
+  } else if (pl.bn_in || pl.up2) {   // forward AND filter gradient must both take the fused operand
+    const WgradPlan wp = plan_wgrad(ctx->num_cus, dtype, d, 16, 16, false);
+    out->bn_in = wp.bn_in;
+    out->up2 = pl.up2 && wp.up2;
   }
   return 0;
 }
 
-int sg_conv2d_wgrad_planes(sg_ctx* ctx, void* stream, const sg_conv_desc* d, const void* x_planes, const void* dy_planes, void* dw,
-                           void* ws, size_t ws_bytes) {
-  SG_CHECK_ARG(ctx != nullptr, "sg_conv2d_wgrad_planes: null ctx");
-  int rc = check_desc(d, "sg_conv2d_wgrad_planes");
-  if (rc) return rc;
-  SG_CHECK_ARG(x_planes && dy_planes && dw && aligned16(x_planes) && aligned16(dy_planes), "sg_conv2d_wgrad_planes: null / unaligned tensor");
-  WgradPlan pl;
-  if (!wgrad_planes_geom(ctx, d, &pl)) {
-    sg_set_error("sg_conv2d_wgrad_planes: geometry outside the planes-in kernel (stride 1 SAME, W %% 32 = 0, channels %% 8 = 0, dense "
-                 "planes below 2 GiB, not a wide pointwise / patch-form layer, x6 arithmetic)");
-    return SG_EUNSUPPORTED;
-  }
-  const size_t need = pl.dw_part_bytes + 512;
-  if (!ws || ws_bytes < need || !aligned16(ws)) {
-    sg_set_error("sg_conv2d_wgrad_planes: workspace %zu < %zu", ws_bytes, need);
-    return SG_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int K_all = d->KH * d->KW * d->Cin;
-  WgradParams p;
-  memset(&p, 0, sizeof(p));
-  p.x = (const float*)x_planes;
-  p.dy = (const float*)dy_planes;
-  p.out = pl.S > 1 ? (float*)ws : (float*)dw;
-  p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.x_ld = d->Cin;
-  p.OH = d->Ho; p.OW = d->Wo; p.Cout = d->Cout; p.y_ld = d->Cout;
-  p.stride = 1; p.dil = d->dilation; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-  p.K = K_all;
-  p.P = d->N * d->Ho * d->Wo;
-  p.slabs_per_split = pl.slabs_per_split;
-  p.fd_ohow = make_fastdiv((uint32_t)(d->Ho * d->Wo));
-  p.fd_ow = make_fastdiv((uint32_t)d->Wo);
-  p.fd_c = make_fastdiv((uint32_t)d->Cin);
-  p.fd_kw = make_fastdiv((uint32_t)d->KW);
-  p.fd_oh = make_fastdiv((uint32_t)d->Ho);
-  p.x_plane_bytes = (uint32_t)((int64_t)d->N * d->H * d->W * d->Cin * 2);
-  p.dy_plane_bytes = (uint32_t)((int64_t)p.P * d->Cout * 2);
-  p.x_bytes = 3 * p.x_plane_bytes;
-  p.dy_bytes = 3 * p.dy_plane_bytes;
-  p.KH_KW = p.K / p.Cin;
-  p.skip_slabs = (!sg_switch<SW_CONV_NOSKIP>() && p.dil > 1 && p.KH_KW > 1) ? 1 : 0;
-  p.tap_inner = ((conv_l2(true) & 4) && p.KH_KW > 1 && p.Cin % BM == 0) ? 1 : 0;   // as dispatch_wgrad: the same tile order
-  p.stagger = sg_switch<SW_X6_ABLATE>() & 15;   // timing-only diagnostics
-  const int bn = wgrad_bn(p.Cout);
-  // Single LDS buffer, two workgroups per CU, the fp32-operand kernel's structure.  Measured (scripts/wgrad_planes_bench.py, fourteen
-  // long-K shapes): 7301 us against 8485 for the fp32-operand kernel; a double-buffered woven form took 7577 and four waves of 64 x 64
-  // per tile changed nothing - the read + MFMA loop itself takes 640 of the 810 us of the ASPP launch either way.  Both are gone
-  // (retired).
-  if (bn == 128) rc = launch_wgrad_x6<128, 2, 4, 1, 3, bf16_t, true>(p, pl.S, st);
-  else if (bn == 64) rc = launch_wgrad_x6<64, 4, 2, 1, 3, bf16_t, true>(p, pl.S, st);
-  else rc = launch_wgrad_x6<32, 4, 1, 1, 3, bf16_t, true>(p, pl.S, st);
-  if (rc) return rc;
-  if (pl.S > 1) {
-    const int64_t n = (int64_t)K_all * d->Cout;
-    const bool v4 = (n % 4 == 0) && aligned16(dw);
-    int64_t blocks = sg_cdiv(n, v4 ? 1024 : 256);
-    if (blocks > 2048) blocks = 2048;
-    if (v4) hipLaunchKernelGGL(reduce_splits_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, (float*)dw, n, pl.S);
-    else hipLaunchKernelGGL(reduce_splits_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, (float*)dw, n, pl.S);
-    SG_LAUNCH_CHECK("reduce_splits_kernel");
-  }
-  return 0;
-}
 
 size_t sg_bias_grad_ws_bytes(const sg_ctx* ctx, int64_t rows, int C) {
   if (!ctx) return 0;

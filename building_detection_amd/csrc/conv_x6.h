@@ -1224,13 +1224,18 @@ int launch_wgrad_x6(const WgradParams& p, int S, hipStream_t st) {
   return 0;
 }
 
-inline bool wgrad_x6_ok(const WgradParams& p, bool vec, bool force = false) {
+// the geometry wgrad_x6_kernel covers, from the descriptor alone (plan_wgrad's split model asks this much; wgrad_x6_ok the rest)
+inline bool wgrad_x6_geom(const sg_conv_desc* d) {
   // stride 1: "same" geometry; stride 2 (round 2: the Xception shortcuts, strided stems, Conv2DTranspose gradients): the
   // output is the input subsampled, OH = ceil(H / 2) - the slab addressing above covers both; dilation 1 only at stride 2
-  const bool geom = (p.stride == 1 && p.OH == p.H && p.OW == p.W) ||
-                    (p.stride == 2 && p.dil == 1 && p.OH == (p.H + 1) / 2 && p.OW == (p.W + 1) / 2);
-  const bool fast = geom && p.x_bytes != 0 && p.dy_bytes != 0;
-  const int64_t sh_bytes = ((int64_t)p.pad_t * p.W + p.pad_l + 64 * p.stride) * p.x_ld * 4;
-  return (force || x6_enabled()) && vec && fast && (p.OW % BK == 0) && p.Cout >= 16 &&
-         ((int64_t)p.x_bytes + 2 * sh_bytes < (1ll << 31));
+  const bool geom = (d->stride == 1 && d->Ho == d->H && d->Wo == d->W) ||
+                    (d->stride == 2 && d->dilation == 1 && d->Ho == (d->H + 1) / 2 && d->Wo == (d->W + 1) / 2);
+  return geom && (d->Wo % BK == 0) && d->Cout >= 16;
+}
+// ... and what a launch adds: 16-byte channel runs (vec), the arithmetic switch, operands inside one buffer descriptor
+// (x_bytes / dy_bytes: WgradParams' extents, 0 = beyond 2 GiB)
+inline bool wgrad_x6_ok(const sg_conv_desc* d, bool vec, bool force, uint32_t x_bytes, uint32_t dy_bytes) {
+  const int64_t sh_bytes = ((int64_t)d->pad_t * d->W + d->pad_l + 64 * d->stride) * (d->x_ld ? d->x_ld : d->Cin) * 4;
+  return (force || x6_enabled()) && vec && wgrad_x6_geom(d) && x_bytes != 0 && dy_bytes != 0 &&
+         ((int64_t)x_bytes + 2 * sh_bytes < (1ll << 31));
 }

@@ -360,6 +360,13 @@ class Engine:
         check(self.lib.sg_conv2d_caps(self.h, dt, C.byref(d), 1 if dgrad else 0, C.byref(caps)), "sg_conv2d_caps")
         return caps
 
+    def conv2d_wgrad_plan(self, d: ConvDesc, dt=SG_F32, aligned=16, planes=False) -> _lib.WgradPlan:
+        """The plan the filter gradient of convolution `d` runs by (sg_conv2d_wgrad_plan); aligned: 16, 8 or 0, the alignment of
+        x and dy in bytes; planes: the plan of conv2d_wgrad_planes."""
+        pl = _lib.WgradPlan()
+        check(self.lib.sg_conv2d_wgrad_plan(self.h, dt, C.byref(d), int(aligned), 1 if planes else 0, C.byref(pl)), "sg_conv2d_wgrad_plan")
+        return pl
+
     def conv2d_bn_in_ok(self, d: ConvDesc, dtype=torch.float32) -> bool:
         """Can the launches of convolution `d` apply a BatchNormalization(+ReLU) to their input themselves (bn_in of conv2d_fwd /
         conv2d_wgrad: the thin 1x1 and the patch kernels, fp32 storage)?"""

@@ -241,6 +241,54 @@ size_t sg_conv2d_wgrad_planes_ws_bytes(const sg_ctx* ctx, const sg_conv_desc* d)
 int sg_conv2d_wgrad_planes(sg_ctx* ctx, void* stream, const sg_conv_desc* d, const void* x_planes, const void* dy_planes, void* dw,
                            void* ws, size_t ws_bytes);
 
+/* The plan one filter-gradient call runs by (csrc/conv_igemm.hip, plan_wgrad - sg_conv2d_wgrad, sg_conv2d_wgrad_planes, both
+ * workspace queries and sg_conv2d_caps read the same one), for this storage type (SG_HEAD_F32 / SG_X_UP2 included), the current
+ * arithmetic switch and the experiment switches.  aligned: 16 - x and dy are 16-byte aligned; 8 - 8-byte aligned (the 4-channel
+ * loads of bf16 storage); 0 - neither.  planes: 1 asks about sg_conv2d_wgrad_planes (SG_F32, aligned 16).
+ * Tensors past the 2 GiB of a buffer descriptor are reduced as `chunks` sub-batches of `nb` whole images, the last one of
+ * `tail_n`; `main` is the launch of the whole batch or of a full sub-batch, `tail` that of the last one (= main when chunks == 1
+ * or the batch divides evenly).  Per launch:
+ *   family      SG_WG_THIN         thin 1x1 (Cout <= 4): ThinWgradOp on the segment reducer
+ *               SG_WG_WIDE         wide pointwise: wgrad_pw_wide_kernel / wgrad_pw_wide_b16_kernel, 128 x 384 tiles (conv_pw.h)
+ *               SG_WG_PATCH        patch form: wgrad_x6wp_kernel, one partial slab per workgroup (conv_x6wp.h)
+ *               SG_WG_SLAB_X6      wgrad_x6_kernel: bf16 products, `planes` planes per operand (conv_x6.h)
+ *               SG_WG_SLAB_NATIVE  igemm_wgrad_kernel on the fp32 MFMA: any shape, any alignment
+ *               SG_WG_HEAD32       igemm_wgrad_kernel on bf16 x and fp32 dy: a softmax head that is not thin
+ *               SG_WG_PLANES       wgrad_x6_kernel reading both operands as the caller's bf16 planes
+ *   bn          slab families: tile width 32 / 64 / 128 output channels (tiles are 128 rows of dw high); 0 otherwise
+ *   vec         slab families: channels per load, 8 / 4, or 0 for scalar loads
+ *   fast        SG_WG_SLAB_NATIVE: 0 gather, 1 linear buffer addressing, 2 wave-uniform aligned slabs
+ *   planes      bf16 planes multiplied per operand: 3 = the exact fp32 emulation, 1 = bf16 products; 0 = fp32 MFMA / no MFMA
+ *   skip_slabs, tap_inner, stagger   WgradParams' fields of the same names as the launch sets them
+ *   S           pixel shares = partial slabs this launch writes (1: straight into dw); SG_WG_PATCH: its workgroups
+ *   steps       reduction steps per share, of step_px pixels each: 16- or 32-pixel k-steps (SG_WG_WIDE), 32-pixel slabs (slab
+ *               families and SG_WG_PATCH, whose workgroups walk tiles instead); 0: SG_WG_THIN
+ * and for the call:
+ *   max_parts       upper bound of the partial slabs written: (chunks - 1) * main.S + tail.S
+ *   dw_part_bytes, bias_part_bytes, bias_off   the partial slabs at the workspace's start, the bias gradient's partials behind
+ *                   them at byte bias_off
+ *   ws_bytes        the workspace the entry point requires (sg_conv2d_wgrad_ws_bytes answers the larger of the SG_F32 and the
+ *                   SG_BF16 plan at aligned = 16; no other alignment needs more)
+ *   bn_in, up2      1 if the launch can take opts->bn_in / SG_X_UP2 (else the entry point answers SG_EUNSUPPORTED).  bn_in is
+ *                   sg_conv_caps.bn_in at aligned = 16: forward and filter gradient take a BatchNormalization together or not at all
+ * An input the entry point would refuse answers all-zero with the entry point's error code. */
+#define SG_WG_THIN 1
+#define SG_WG_WIDE 2
+#define SG_WG_PATCH 3
+#define SG_WG_SLAB_X6 4
+#define SG_WG_SLAB_NATIVE 5
+#define SG_WG_HEAD32 6
+#define SG_WG_PLANES 7
+typedef struct sg_wgrad_launch {
+  int family, bn, vec, fast, planes, skip_slabs, tap_inner, stagger, S, steps, step_px;
+} sg_wgrad_launch;
+typedef struct sg_wgrad_plan {
+  sg_wgrad_launch main, tail;
+  int chunks, nb, tail_n, max_parts, bn_in, up2;
+  size_t dw_part_bytes, bias_part_bytes, bias_off, ws_bytes;
+} sg_wgrad_plan;
+int sg_conv2d_wgrad_plan(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int aligned, int planes, sg_wgrad_plan* out);
+
 /* Bias gradient db[C] = column sums of dy[rows][C] (pixel stride ld, 0 = C); fixed-order two-stage reduce.
  * Used for the bias of Conv2DTranspose (v3plus.py:328,335; scse.py:71-89; res34.py:144), whose kernel
  * gradient comes from sg_conv2d_wgrad with the operand roles swapped. */

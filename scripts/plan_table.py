@@ -9,6 +9,9 @@ Folded so that the table can be read: one line per (direction, head, descriptor 
 workspace query (which knows neither storage nor mode); behind it one group per set of arithmetics with equal answers (x0 / x1 / x2:
 fp32 storage under sg_set_conv_x6 0 / 1 / 2, b16: bf16 storage); inside a group the batch sizes with equal answers share one
 entry, and a value that is the same at every batch is printed once.
+Behind those lines, the filter gradients: one line per (head, descriptor without N) with the batch sizes and, per arithmetic, the
+plan sg_conv2d_wgrad_plan answers at 16-byte alignment - what plan_wgrad() (csrc/conv_igemm.hip) decides -, the storage-blind
+sg_conv2d_wgrad_ws_bytes and the plan of sg_conv2d_wgrad_planes where it covers the layer.
 Use: python scripts/plan_table.py > profiles/plan_table.txt"""
 import collections
 import ctypes as C
@@ -43,6 +46,65 @@ def rows():
                                i.K, i.Kpad, i.N, i.Npad, i.Ck, i.Ckp, i.nblocks, i.bytes, i.ws, i.pin,
                                e.conv2d_caps(d, False, st).up2, e.conv2d_caps(d, False, st).bn_in, e.conv2d_caps(d, True, st).bnb))
     return len(uniq), out
+
+
+def wgrad_rows():
+    """(arith, head, desc fields, plan text) of every unique (descriptor, head, storage) under every arithmetic
+    mode its storage type runs in; a layer's forward, input gradient and Conv2DTranspose share the descriptor (needs the GPU)"""
+    import _plane_sites as PS
+    from building_detection_amd import _lib
+    from building_detection_amd.ops import get_engine
+    e = get_engine(0)
+    uniq, _ = PS.unique_sites(PS.enumerate_groups(geometries=tuple(g for g in PS.GEOMETRIES if g[2])))   # (training geometries)
+    sites = collections.OrderedDict(((s.desc, s.head, s.policy), s) for s in uniq.values())
+    out = []
+    for mode in (0, 1, 2, None):
+        with PS.mode_set(e, mode):
+            for s in sites.values():
+                if mode not in PS.modes_of(s.policy):
+                    continue
+                d = PS.make_desc(s)
+                pl = e.conv2d_wgrad_plan(d, PS.abi_dtype(s))
+                m, t = pl.main, pl.tail
+                txt = (f"{_lib.WG_FAMILY_NAMES[m.family]} bn{m.bn} v{m.vec} f{m.fast} pl{m.planes} skip{m.skip_slabs} tap{m.tap_inner} "
+                       f"stag{m.stagger} S{m.S}x{m.steps}/{m.step_px}px")
+                if pl.chunks > 1:
+                    txt += f" chunks{pl.chunks}x{pl.nb}+{pl.tail_n} tailS{t.S}x{t.steps}"
+                pin = "-"
+                if s.policy == "float32" and e.conv2d_caps(d).wgrad_planes:
+                    pp = e.conv2d_wgrad_plan(d, _lib.SG_F32, planes=True)
+                    pin = f"S{pp.main.S}x{pp.main.steps} ws{pp.ws_bytes}"
+                txt += (f" parts{pl.max_parts} ws{pl.ws_bytes} q{int(e.lib.sg_conv2d_wgrad_ws_bytes(e.h, C.byref(d)))} "
+                        f"sup{pl.up2}{pl.bn_in} pin {pin}")
+                out.append(("b16" if mode is None else f"x{mode}", s.head, dict(zip(PS.desc_fields(), s.desc)), txt))
+    return out
+
+
+def fold_wgrad(rs):
+    table = collections.OrderedDict()   # line -> arithmetic -> batch -> plan text
+    for arith, head, f, txt in rs:
+        key = (f"wgrad{' head' if head else ''} {f['H']}x{f['W']}x{f['Cin']}>{f['Cout']} k{f['KH']}s{f['stride']}d{f['dilation']} "
+               f"o{f['Ho']}x{f['Wo']}")
+        table.setdefault(key, collections.OrderedDict()).setdefault(arith, {})[f["N"]] = txt
+    lines = [f"# filter gradients: {len(rs)} (descriptor, storage, mode) plans on {len(table)} lines",
+             "# wgrad [head] HxWxCin>Cout k<K>s<stride>d<dilation> o<Ho>x<Wo> b<batch sizes>",
+             "#   | <arithmetics with equal plans>: [b<batches>:] family bn<tile width> v<channels per load> f<FAST> pl<bf16 planes> "
+             "skip<skip_slabs> tap<tap_inner> stag<stagger> S<shares>x<steps per share>/<pixels per step> [chunks<n>x<images>+<last> "
+             "tailS..] parts<max_parts> ws<plan.ws_bytes> q<sg_conv2d_wgrad_ws_bytes, which knows no storage type> sup<up2, bn_in> pin <planes-in plan or -> ; ..."]
+    for key, ariths in table.items():
+        batches = sorted({b for per in ariths.values() for b in per})
+        line = f"{key} b{','.join(map(str, batches))}"
+        texts = collections.OrderedDict()
+        for arith, per in ariths.items():
+            by = collections.OrderedDict()
+            for b in sorted(per):
+                by.setdefault(per[b], []).append(b)
+            parts = [(f"b{','.join(map(str, bs))}: " if (len(by) > 1 or sorted(per) != batches) else "") + t for t, bs in by.items()]
+            texts.setdefault("; ".join(parts), []).append(arith)
+        for txt, names in texts.items():
+            line += f" | {','.join(names)}: {txt}"
+        lines.append(line)
+    return lines
 
 
 def once(vals):
@@ -85,4 +147,4 @@ def fold(n_unique, rs):
 
 
 if __name__ == "__main__":
-    print("\n".join(fold(*rows())))
+    print("\n".join(fold(*rows()) + fold_wgrad(wgrad_rows())))

@@ -1176,6 +1176,9 @@ for tag, dt in (("f32", torch.float32), ("bf16", torch.bfloat16)):
     dw, db = e.conv2d_wgrad(x, dy, d)
     for k, v in (("y", y), ("dx", dx), ("dw", dw), ("db", db)):
         out[f"{tag}{shp}_{k}"] = v.float().cpu().numpy()
+    pl = e.conv2d_wgrad_plan(d, 0 if dt == torch.float32 else 1)
+    out[f"{tag}{shp}_plan"] = np.array([pl.chunks, pl.nb, pl.tail_n, pl.main.S, pl.tail.S, pl.max_parts, pl.dw_part_bytes, pl.ws_bytes,
+                                        e.lib.sg_conv2d_wgrad_ws_bytes(e.h, d)], dtype=np.int64)
 # the fp32 softmax head of a bf16 model that is not a 1x1 convolution (Res34-UNet: 3x3, 64 -> 2): bf16 in, fp32 out
 x = torch.randn(5, 32, 32, 64, generator=g).cuda().to(torch.bfloat16)
 w = (torch.randn(3, 3, 64, 2, generator=g) * 0.05).cuda()
@@ -1207,6 +1210,16 @@ np.savez(sys.argv[2], **out)
         for k in ("dw", "db"):
             a, b = res["whole"][f"{tag}_{k}"], res["chunked"][f"{tag}_{k}"]
             assert np.abs(a - b).max() <= 2e-5 * np.abs(a).max(), (tag, k)
+        # the filter gradient's plan (sg_conv2d_wgrad_plan): sub-batches of as many images as fit the limit with the larger of x
+        # and dy counted at 4 bytes per element for either storage type (32 channels out: 2 + 2 + 1 images; 96: one by one), and its
+        # bound of the partial slabs covers what the run writes - every full sub-batch its S slabs, the last one its own - inside
+        # the workspace
+        assert res["whole"][f"{tag}_plan"][0] == 1
+        chunks, nb, tail_n, S, tail_S, max_parts, dw_part, ws, query = (int(v) for v in res["chunked"][f"{tag}_plan"])
+        fit = (2 * 32 * 32 * 64 * 4 + 1000) // (32 * 32 * max(64, 96 if tag.endswith("a") else 32) * 4)
+        assert chunks > 1 and (chunks, nb, tail_n) == (-(-5 // fit), fit, 5 - (-(-5 // fit) - 1) * fit), (tag, chunks, nb, tail_n)
+        slab = res["chunked"][f"{tag}_dw"].size * 4
+        assert max_parts >= (chunks - 1) * S + tail_S and 1 <= tail_S <= S and max_parts * slab <= dw_part <= ws <= query, tag
 
 
 def test_fused_second_stage_of_the_reductions_is_bit_identical(engine):

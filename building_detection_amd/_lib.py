@@ -184,6 +184,8 @@ _SIGNATURES = {
     "sg_bn_train_fwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _sz]),
     "sg_bn_train_bwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz]),
     "sg_bn_train_bwd_apply": (_i, [_vp, _vp, _i, _i64, _i] + [_vp] * 9 + [_i]),
+    "sg_bn_train_bwd_thin_ok": (_i, [_vp, _i, _i64, _i, _i, _i]),
+    "sg_bn_train_bwd_thin": (_i, [_vp, _vp, _i, _i64, _i, _i, _i] + [_vp] * 10 + [_i, _vp, _sz]),
     "sg_bn_infer": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i]),
     "sg_add2_bn": (_i, [_vp, _vp, _i, _i64, _i] + [_vp] * 11 + [_i, _i, _f, _i, _i]),
     "sg_bn_plan": (_i, [_vp, _i, _i64, _i, _i, _i, C.POINTER(BnPlan)]),
@@ -204,6 +206,8 @@ _SIGNATURES = {
     "sg_scse_fwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     "sg_scse_bwd_ws_bytes": (_sz, [_vp, _i, _i64, _i]),
     "sg_scse_bwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "sg_scse_bwd_sums": (_i, [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "sg_scse_bwd_final": (_i, [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "sg_bam_fwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     "sg_bam_bwd_ws_bytes": (_sz, [_vp, _i, _i64, _i]),
     "sg_bam_bwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),

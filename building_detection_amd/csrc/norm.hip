@@ -117,6 +117,83 @@ struct BnBwdOp {
   }
 };
 
+// ---- dy that is the input gradient of a thin 1x1 convolution (Cout = CO <= 4: the softmax head, the sSE gate), never written out ----
+// dy[r][c] = sum_o g[r][o] * w[c][o] is evaluated where the backward consumes it, with thin_dgrad_kernel's own expression
+// (csrc/conv_igemm.hip), so the sums and dx have the bits of thin dgrad + sg_bn_train_bwd without the C-wide tensor.  fp32 storage.
+// The value is the result of explicit fmaf calls, which the compiler does not contract into their uses: it reaches them as the rounded
+// fp32 the other path stores.  (No asm fence: inline asm is convergent, and the reducer's row loop is then not unrolled.)
+template <int V, int CO>
+__device__ __forceinline__ void thin_w(const float* __restrict__ w, int c, float (&wv)[V][CO]) {
+#pragma unroll
+  for (int k = 0; k < V; ++k)
+#pragma unroll
+    for (int o = 0; o < CO; ++o) wv[k][o] = w[(c + k) * CO + o];
+}
+template <int V, int CO>
+__device__ __forceinline__ void thin_dy(const float* __restrict__ g, const float (&wv)[V][CO], float (&dy)[V]) {
+  float gv[CO];
+#pragma unroll
+  for (int o = 0; o < CO; ++o) gv[o] = g[o];
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    float a = 0.f;
+#pragma unroll
+    for (int o = 0; o < CO; ++o) a = fmaf(gv[o], wv[k][o], a);
+    dy[k] = a;
+  }
+}
+
+template <int V, int CO>
+struct BnThinCtx {
+  BnCtx<V> k;
+  float wv[V][CO];
+};
+
+// BnBwdOp on that source (MODE 0 or 2: the mask is recomputed from x)
+template <int MODE, int CO>
+struct BnBwdThinOp {
+  static constexpr int NOUT = 2;
+  const float* __restrict__ x;
+  const float* __restrict__ g;   // [rows][y_ld], CO live columns
+  const float* __restrict__ w;   // [C][CO]
+  const float* __restrict__ mean;
+  const float* __restrict__ invstd;
+  const float* __restrict__ gamma;
+  const float* __restrict__ beta;
+  float* dgamma;
+  float* dbeta;
+  int C, y_ld;
+
+  template <int V>
+  __device__ __forceinline__ BnThinCtx<V, CO> begin(int, int c) const {
+    BnThinCtx<V, CO> q;
+    ldv<V>(mean + c, q.k.mv);
+    ldv<V>(invstd + c, q.k.iv);
+    if constexpr (MODE == 2) {
+      ldv<V>(gamma + c, q.k.gm);
+      ldv<V>(beta + c, q.k.bt);
+    }
+    thin_w<V, CO>(w, c, q.wv);
+    return q;
+  }
+  template <int V>
+  __device__ __forceinline__ void accum(int, int64_t r, int c, float (&acc)[2][V], const BnThinCtx<V, CO>& q) const {
+    float xv[V], gv[V], yv[V];
+    ldv<V>(x + r * C + c, xv);
+    thin_dy<V, CO>(g + r * y_ld, q.wv, gv);
+    bn_mask<MODE>(gv, xv, yv, q.k.mv, q.k.iv, q.k.gm, q.k.bt);
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      acc[0][i] += gv[i];
+      acc[1][i] = fmaf(gv[i], (xv[i] - q.k.mv[i]) * q.k.iv[i], acc[1][i]);
+    }
+  }
+  __device__ __forceinline__ void finalize(int, int c, const double (&s)[2]) const {
+    dbeta[c] = (float)s[0];
+    dgamma[c] = (float)s[1];
+  }
+};
+
 template <int V, typename T>
 __global__ void bn_apply_kernel(const T* __restrict__ x, const float* __restrict__ mean,
                                 const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -295,6 +372,83 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cols_kernel(const T* __restr
   }
 }
 constexpr int BN_BWD_PERIODS = 1;   // ONE: this kernel's two rows lie a whole grid apart, so a group owns a single period per trip
+
+// bn_bwd_apply_kernel / bn_bwd_apply_cols_kernel with dy from the thin source (BnBwdThinOp): same index space, same expressions
+template <int V, int MODE, int CO>
+__global__ void bn_bwd_apply_thin_kernel(const BnBwdThinOp<MODE, CO> q, float* __restrict__ dx, int64_t rows, FastDiv fd_cv) {
+  const int C = q.C;
+  const uint32_t cv = C / V;
+  const uint32_t total = (uint32_t)(rows * cv);
+  const uint32_t stride = gridDim.x * blockDim.x;
+  const float inv_n = 1.0f / (float)rows;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t r = fd_div(i, fd_cv);
+    const int c = (int)(i - (uint32_t)r * cv) * V;
+    float xv[V], gv[V], mv[V], iv[V], gam[V], dg[V], db[V], o[V], wv[V][CO];
+    ldv<V>(q.x + r * C + c, xv);
+    thin_w<V, CO>(q.w, c, wv);
+    thin_dy<V, CO>(q.g + r * q.y_ld, wv, gv);
+    ldv<V>(q.mean + c, mv);
+    ldv<V>(q.invstd + c, iv);
+    ldv<V>(q.gamma + c, gam);
+    ldv<V>(q.dgamma + c, dg);
+    ldv<V>(q.dbeta + c, db);
+    if constexpr (MODE == 2) {
+      float bt[V];
+      ldv<V>(q.beta + c, bt);
+#pragma unroll
+      for (int k = 0; k < V; ++k) gv[k] = bn_affine(xv[k], mv[k], iv[k], gam[k], bt[k]) > 0.f ? gv[k] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const float xh = (xv[k] - mv[k]) * iv[k];
+      o[k] = gam[k] * iv[k] * (gv[k] - db[k] * inv_n - xh * dg[k] * inv_n);
+    }
+    stv<V>(dx + r * C + c, o);
+  }
+}
+
+template <int V, int MODE, int CO>
+__global__ __launch_bounds__(256) void bn_bwd_apply_cols_thin_kernel(const BnBwdThinOp<MODE, CO> q, float* __restrict__ dx,
+                                                                     int64_t rows, int prow, FastDiv fd_cv) {
+  const int C = q.C;
+  const uint32_t i0 = blockIdx.x * 256u + threadIdx.x, cv = (uint32_t)(C / V);
+  const uint32_t r0 = fd_div(i0, fd_cv);
+  const int c = (int)(i0 - r0 * cv) * V;
+  float mv[V], iv[V], gam[V], dg[V], db[V], bt[V], wv[V][CO];
+  ldv<V>(q.mean + c, mv);
+  ldv<V>(q.invstd + c, iv);
+  ldv<V>(q.gamma + c, gam);
+  ldv<V>(q.dgamma + c, dg);
+  ldv<V>(q.dbeta + c, db);
+  if constexpr (MODE == 2) ldv<V>(q.beta + c, bt);
+  thin_w<V, CO>(q.w, c, wv);
+  const float inv_n = 1.0f / (float)rows;
+  auto one = [&](const float (&xv)[V], float (&gv)[V], int64_t r) {
+    float o[V];
+    bn_mask<MODE>(gv, xv, xv, mv, iv, gam, bt);   // (MODE 0 / 2 never read the y operand)
+#pragma unroll
+    for (int k = 0; k < V; ++k) o[k] = bn_dx(xv[k], gv[k], mv[k], iv[k], gam[k], dg[k], db[k], inv_n);
+    stv<V>(dx + r * C + c, o);
+  };
+  const int64_t stride = (int64_t)gridDim.y * prow, gstep = 2 * stride;
+  for (int64_t r = (int64_t)blockIdx.y * prow + r0; r < rows; r += gstep) {
+    if (r + stride < rows) {
+      float x0[V], x1[V], g0[V], g1[V];
+      ldv<V>(q.x + r * C + c, x0);
+      ldv<V>(q.x + (r + stride) * C + c, x1);
+      thin_dy<V, CO>(q.g + r * q.y_ld, wv, g0);
+      thin_dy<V, CO>(q.g + (r + stride) * q.y_ld, wv, g1);
+      one(x0, g0, r);
+      one(x1, g1, r + stride);
+    } else {
+      float x0[V], g0[V];
+      ldv<V>(q.x + r * C + c, x0);
+      thin_dy<V, CO>(q.g + r * q.y_ld, wv, g0);
+      one(x0, g0, r);
+    }
+  }
+}
 
 // y = [relu]( f_a(a) + f_b(b) ), f = BatchNormalization's apply (training: saved mean / invstd; inference: moving mean /
 // variance) for an operand whose parameter pointers are given, the identity otherwise: the residual add of an Xception block
@@ -482,6 +636,22 @@ int launch_bn_bwd_apply(hipStream_t st, const BnPlan& pl, const BnBwdOp<T, MODE>
   return 0;
 }
 
+template <int MODE, int CO>
+int launch_bn_bwd_apply_thin(hipStream_t st, const BnPlan& pl, const BnBwdThinOp<MODE, CO>& q, float* dx, int64_t rows) {
+  const FastDiv fd = make_fastdiv((uint32_t)(q.C / pl.V));
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+  bn_with_form(pl, [&](auto v, auto cols) {
+    constexpr int V = decltype(v)::value;
+    if constexpr (V == 8) return;   // (bf16 storage only: refused before any launch)
+    else if constexpr (decltype(cols)::value)
+      hipLaunchKernelGGL((bn_bwd_apply_cols_thin_kernel<V, MODE, CO>), grid, dim3(256), 0, st, q, dx, rows, pl.prow, fd);
+    else
+      hipLaunchKernelGGL((bn_bwd_apply_thin_kernel<V, MODE, CO>), grid, dim3(256), 0, st, q, dx, rows, fd);
+  });
+  SG_LAUNCH_CHECK(pl.cols ? "bn_bwd_apply_cols_thin_kernel" : "bn_bwd_apply_thin_kernel");
+  return 0;
+}
+
 // rows per launch of sg_add2_bn: its kernel indexes with 32 bits, so a tensor of 2^31 elements or more (the BatchNormalization
 // in front of this add has already handed its RAW input on: there is no unfused form to fall back to) is walked in row chunks
 // below that, each an even number of rows so that a chunk starts 16-byte aligned with bf16 storage too.  Element-wise: same bits.
@@ -577,6 +747,43 @@ int sg_bn_train_bwd_apply(sg_ctx* ctx, void* stream, int dtype, int64_t rows, in
     });
   });
   return 0;
+}
+
+// fp32 storage only: under bf16 the thin dgrad rounds dy through the storage type, which these kernels do not
+int sg_bn_train_bwd_thin_ok(const sg_ctx* ctx, int dtype, int64_t rows, int C, int CO, int y_ld) {
+  return ctx && dtype == SG_F32 && rows > 0 && C > 0 && rows * C < (1ll << 31) && CO >= 1 && CO <= 4 && y_ld >= CO &&
+         rows * y_ld < (1ll << 31);
+}
+
+int sg_bn_train_bwd_thin(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, int CO, int y_ld, const void* x, const void* g,
+                         const void* w, const void* gamma, const void* beta, const void* save_mean, const void* save_invstd, void* dx,
+                         void* dgamma, void* dbeta, int relu, void* ws, size_t ws_bytes) {
+  if (int e = bn_check(ctx, dtype, rows, C, false, "sg_bn_train_bwd_thin")) return e;
+  SG_CHECK_ARG(x && g && w && gamma && save_mean && save_invstd && dx && dgamma && dbeta, "sg_bn_train_bwd_thin: bad argument");
+  SG_CHECK_ARG(!relu || beta, "sg_bn_train_bwd_thin: relu needs beta (the mask is recomputed from x)");
+  if (!sg_bn_train_bwd_thin_ok(ctx, dtype, rows, C, CO, y_ld)) {
+    sg_set_error("sg_bn_train_bwd_thin: needs fp32 storage and 1 <= CO <= 4, CO <= y_ld; run the thin dgrad and sg_bn_train_bwd instead");
+    return SG_EUNSUPPORTED;
+  }
+  // the plan of the materialised call (dy there is a dense tensor of x's shape, aligned like dx): same grids, same order of sums
+  const BnPlan pl = plan_bn(ctx->num_cus, dtype, rows, C, SG_BN_BWD, sg_all_aligned16({x, dx}));
+  if (int e = bn_refuse(pl, "sg_bn_train_bwd_thin", ws, ws_bytes)) return e;
+  auto run = [&](auto m, auto co) -> int {
+    const BnBwdThinOp<decltype(m)::value, decltype(co)::value> op = {
+        (const float*)x, (const float*)g, (const float*)w, (const float*)save_mean, (const float*)save_invstd, (const float*)gamma,
+        (const float*)beta, (float*)dgamma, (float*)dbeta, C, y_ld};
+    if (int e = seg_reduce_launch(op, pl.seg, 1, rows, C, (float*)ws, (hipStream_t)stream, "bn_bwd_thin_reduce")) return e;
+    return launch_bn_bwd_apply_thin((hipStream_t)stream, pl, op, (float*)dx, rows);
+  };
+  auto with_co = [&](auto m) -> int {
+    switch (CO) {
+      case 1: return run(m, std::integral_constant<int, 1>{});
+      case 2: return run(m, std::integral_constant<int, 2>{});
+      case 3: return run(m, std::integral_constant<int, 3>{});
+      default: return run(m, std::integral_constant<int, 4>{});
+    }
+  };
+  return relu ? with_co(std::integral_constant<int, 2>{}) : with_co(std::integral_constant<int, 0>{});
 }
 
 int sg_bn_apply(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* gamma,

@@ -367,6 +367,77 @@ struct ScseBwdRow {  // dx = dy*(sig s + sig c) ; ds[row] = sig'(s) * sum_c dy*x
   }
 };
 
+// The block's backward without the passes that only add rank-one terms (sg_scse_bwd_sums + sg_scse_bwd_final).  Today's sweep writes
+// dx0 = dy (sig s + sig c) here, then the GAP's backward adds dg[n,c] / HW over the whole tensor (avgpool_bwd_kernel, accumulate) and
+// the sSE convolution's dgrad adds w[c] ds'[p] over it again (thin_dgrad_kernel<1>, res): nine passes.  ScseBwdRowDs is ScseBwdRow
+// without the dx store (same terms, same order: same ds), and ScseBwdFinal forms the complete dx in one pass over dy.
+template <typename T>
+struct ScseBwdRowDs {  // ds[row] = sig'(s) * sum_c dy*x
+  const T* __restrict__ x;
+  const T* __restrict__ s;
+  const T* __restrict__ dy;
+  T* __restrict__ ds;
+  int C;
+  __device__ __forceinline__ float row_ctx(int64_t, int) const { return 0.f; }
+  template <int V>
+  __device__ __forceinline__ float term(int64_t row, int, int c, float) const {
+    float xv[V], d[V];
+    ldv<V>(x + row * C + c, xv);
+    ldv<V>(dy + row * C + c, d);
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc = fmaf(xv[k], d[k], acc);
+    return acc;
+  }
+  __device__ __forceinline__ void store(int64_t row, float acc) const {
+    const float ss = sigmoidf_(ld1<T>(s + row));
+    st1<T>(ds + row, acc * ss * (1.f - ss));
+  }
+};
+
+// dx = the three terms summed in the order the unfused sweep sums them (gap_first: the GAP's backward ran before the sSE
+// convolution's; else after it), every sum on the rounded fp32 values the unfused kernels store: t as ScseBwdRow writes it, the GAP
+// term as avgpool_bwd_kernel's `o = dg * sc; o += t`, the sSE term as thin_dgrad_kernel<1>'s `r = fmaf(g, w, 0); r += t`.  The
+// additions are kept from contracting with the products in front of them.  fp32 storage.
+struct ScseBwdFinal {
+  const float* __restrict__ dy;
+  const float* __restrict__ s;    // [N*HW] logits
+  const float* __restrict__ cl;   // [N,C] logits
+  const float* __restrict__ dsp;  // [N*HW] gradient of the sSE convolution's output
+  const float* __restrict__ w;    // [C] the sSE convolution's kernel
+  const float* __restrict__ dg;   // [N,C] gradient of the GAP's output
+  float* __restrict__ dx;
+  int C, gap_first;
+  float sc;                       // 1 / HW
+  template <int V>
+  __device__ __forceinline__ void apply(int64_t r, int n, int c) const {
+    float d[V], cv[V], gq[V], wv[V], t[V], o[V];
+    ldv<V>(dy + r * C + c, d);
+    ldv<V>(cl + (int64_t)n * C + c, cv);
+    ldv<V>(dg + (int64_t)n * C + c, gq);
+    ldv<V>(w + c, wv);
+    const float ss = sigmoidf_(s[r]), g1 = dsp[r];
+#pragma unroll
+    for (int k = 0; k < V; ++k) t[k] = d[k] * (ss + sigmoidf_(cv[k]));
+    {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        const float a = fmaf(g1, wv[k], 0.f);
+        float p = gq[k] * sc;
+        if (gap_first) {
+          p = p + t[k];
+          o[k] = a + p;
+        } else {
+          const float q = a + t[k];
+          o[k] = p + q;
+        }
+      }
+    }
+    stv<V>(dx + r * C + c, o);
+  }
+};
+
 // -------------------------------------------------------------------------------------------------- BAM
 template <typename T>
 struct BamFwd {  // y = x + x * sigmoid(mc[n,c] + ms[row])
@@ -678,6 +749,47 @@ int sg_scse_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int64_t HW, int C, 
     return seg_reduce_launch(op, pl, N, HW, C, (float*)ws, st, "scse_bwd_dc");
   });
   return 0;
+}
+
+// sg_scse_bwd without dx: the same two reductions (the same launches for the same N, HW, C and alignment: same ds and dc)
+int sg_scse_bwd_sums(sg_ctx* ctx, void* stream, int dtype, int N, int64_t HW, int C, const void* x, const void* s, const void* c,
+                     const void* dy, void* ds, void* dc, void* ws, size_t ws_bytes) {
+  SG_GATE_ARGS_CHECK("sg_scse_bwd_sums");
+  SG_CHECK_ARG(x && s && c && dy && ds && dc, "sg_scse_bwd_sums: null tensor");
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = vec_ok(C, {x, c, dy});
+  SG_DTYPE_SWITCH(dtype, "sg_scse_bwd_sums", {
+    const SegPlan pl = seg_plan<1>(ctx->num_cus, N, HW, C, vec);
+    if (!ws || ws_bytes < pl.part_bytes) {
+      sg_set_error("sg_scse_bwd_sums: workspace %zu < %zu", ws_bytes, pl.part_bytes);
+      return SG_EWORKSPACE;
+    }
+    ScseBwdRowDs<T> r;
+    r.x = (const T*)x; r.s = (const T*)s; r.dy = (const T*)dy; r.ds = (T*)ds; r.C = C;
+    int rc = launch_row_reduce(r, (int64_t)N * HW, HW, C, vec, st, "scse_bwd_row_ds");
+    if (rc) return rc;
+    ChanDotOp<T> op;
+    op.x = (const T*)x; op.dy = (const T*)dy; op.logit = (const T*)c; op.out = (T*)dc; op.HW = HW; op.C = C;
+    op.kind = 1;
+    return seg_reduce_launch(op, pl, N, HW, C, (float*)ws, st, "scse_bwd_dc");
+  });
+  return 0;
+}
+
+int sg_scse_bwd_final(sg_ctx* ctx, void* stream, int dtype, int N, int64_t HW, int C, const void* dy, const void* s, const void* c,
+                      const void* dsp, const void* w, const void* dg, void* dx, int gap_first) {
+  SG_GATE_ARGS_CHECK("sg_scse_bwd_final");
+  SG_CHECK_ARG(dy && s && c && dsp && w && dg && dx, "sg_scse_bwd_final: null tensor");
+  if (dtype != SG_F32) {
+    sg_set_error("sg_scse_bwd_final: fp32 storage only (bf16 rounds every partial sum through its storage type); use sg_scse_bwd, "
+                 "sg_avgpool_bwd and sg_conv2d_dgrad instead");
+    return SG_EUNSUPPORTED;
+  }
+  ScseBwdFinal f;
+  f.dy = (const float*)dy; f.s = (const float*)s; f.cl = (const float*)c; f.dsp = (const float*)dsp; f.w = (const float*)w;
+  f.dg = (const float*)dg; f.dx = (float*)dx; f.C = C; f.gap_first = gap_first ? 1 : 0;
+  f.sc = 1.0f / (float)(int)HW;
+  return launch_rowcol(f, (int64_t)N * HW, HW, C, vec_ok(C, {dy, c, w, dg, dx}), (hipStream_t)stream, "scse_bwd_final");
 }
 
 int sg_bam_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int64_t HW, int C, const void* x, const void* mc,

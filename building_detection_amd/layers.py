@@ -16,6 +16,7 @@ import numpy as np
 from .graph import KTensor, Node
 from .ops import conv_out_geometry, same_pad
 from . import _lib
+from . import switches
 
 
 def _pair(v):
@@ -81,6 +82,10 @@ class _ConvNode(Node):
     # BatchNormalization(+ReLU) -> this convolution, the normalisation applied in this layer's loaders (Model._fuse sets bn_src /
     # _BNNode.defer_conv; the BatchNormalization node then hands its RAW input through - saved state "deferred")
     bn_src = None
+    # BatchNormalization(+ReLU) -> this thin 1x1 convolution, the layer's only consumer (Model._fuse sets thin_bn): the input gradient
+    # is a rank-Cout function of dz, so this node hands on (dz, kernel) - a ThinGradDeferred - and the BatchNormalization's backward
+    # kernels evaluate it where they read it; the Cin-wide gradient is never written
+    thin_bn = None
 
     def _bn_in(self, rt, training):
         """(gamma, beta, mean, invstd | moving variance, relu, infer, eps) when this call's input is the raw input of bn_src"""
@@ -185,9 +190,17 @@ class _ConvNode(Node):
                     root = self.inputs[0]
                     while isinstance(root.node, _ActNode) and root.node.fused_away and len(root.consumers) == 1:
                         root = root.node.inputs[0]
-                    res = rt.take_pending(root)
-                dx = e.conv2d_dgrad(dz, rt.param(self.w), d, out_dtype=x.dtype, planes=rt.planes(self, "d"), res=res, down2=up2,
-                                    dy_planes=dzp if res is None else None)
+                    if (caps.thin and self.thin_bn is not None and switches.get("SG_THIN_GRAD_BN")
+                            and (rt._pending is None or id(root) not in rt._pending)
+                            and e.bn_train_bwd_thin_ok(rt.values[id(self.thin_bn.inputs[0])], dz, rt.param(self.w))):
+                        dx = ThinGradDeferred(dz, rt.param(self.w), d, x.dtype)
+                    else:
+                        res = rt.take_pending(root)
+                        if isinstance(res, ScseGradDeferred):   # the sSE gate of a marked scSE block: rank one, added by the final kernel
+                            dx, res = res.add(e, "sse", dz, rt.param(self.w), d), None
+                if dx is None:
+                    dx = e.conv2d_dgrad(dz, rt.param(self.w), d, out_dtype=x.dtype, planes=rt.planes(self, "d"), res=res, down2=up2,
+                                        dy_planes=dzp if res is None else None)
             gw, gb = rt.grad(self.w), (rt.grad(self.b) if want_b else None)
             bn_in = rt.saved(self).get("bn_in") if id(self) in rt._saved else None
             if bn_in is not None:   # x is the raw input of the BatchNormalization in front: the filter gradient normalises it as the forward did
@@ -464,6 +477,50 @@ class BnBackwardDeferred:
         return (self.dy, self.gamma, self.beta, self.mean, self.invstd, self.dgamma, self.dbeta)
 
 
+class ThinGradDeferred:
+    """What a thin 1x1 convolution (Cout <= 4) hands the BatchNormalization in front of it instead of dx: the gradient g of its own
+    output and its kernel w.  dx[p, c] = sum_o g[p, o] w[c, o] is evaluated inside that layer's backward kernels
+    (Engine.bn_train_bwd_thin).  Any other receiver gets the tensor: materialise() is the thin dgrad itself (the sweep calls it)."""
+
+    def __init__(self, g, w, desc, dtype):
+        self.g, self.w, self.desc, self.dtype = g, w, desc, dtype
+        self.shape = (desc.N, desc.H, desc.W, desc.Cin)
+
+    def materialise(self, eng):
+        return eng.conv2d_dgrad(self.g, self.w, self.desc, out_dtype=self.dtype)
+
+
+class ScseGradDeferred:
+    """The gradient of an scSE block's input while its three consumers report (Model._fuse: _ScseCombineNode.lowrank): the combine
+    node leaves dy and the gate logits, the GlobalAveragePooling and the sSE convolution add their small operands - dg [N, C] and
+    (ds', w) - instead of launching a pass over the tensor each, and the last of them runs the one kernel that writes dx
+    (Engine.scse_bwd_final), summing in the order the three arrived.  materialise() is the unfused sequence on what has arrived."""
+
+    def __init__(self, x, s, cl, dy):
+        self.x, self.s, self.cl, self.dy = x, s, cl, dy
+        self.dtype, self.shape = dy.dtype, dy.shape
+        self.parts = []   # ("gap", dg) / ("sse", ds', w, desc) in arrival order
+
+    def add(self, eng, *part):
+        """-> the finished dx once both operands are here, else this object again"""
+        self.parts.append(part)
+        if len(self.parts) < 2:
+            return self
+        gap = next(p for p in self.parts if p[0] == "gap")
+        sse = next(p for p in self.parts if p[0] == "sse")
+        return eng.scse_bwd_final(self.dy, self.s, self.cl, sse[1], sse[2], gap[1], gap_first=self.parts[0][0] == "gap")
+
+    def materialise(self, eng):
+        dx, _, _ = eng.scse_bwd(self.x, self.s, self.cl, self.dy)
+        n, h, w, c = self.shape
+        for p in self.parts:
+            if p[0] == "gap":
+                dx = eng.avgpool_bwd(p[1], (n, h, w, c), h, w, out=dx, accumulate=True)
+            else:
+                dx = eng.conv2d_dgrad(p[1], p[2], p[3], out_dtype=self.dtype, res=dx)
+        return dx
+
+
 class _BNNode(Node):
     op = "batch_normalization"
 
@@ -516,6 +573,12 @@ class _BNNode(Node):
     def backward(self, rt, xs, y, dy):
         (x,) = xs
         s = rt.saved(self)
+        if isinstance(dy, ThinGradDeferred):   # from the thin 1x1 convolution behind this layer: its input gradient, unexpanded
+            if not s.get("sums_done") and rt.eng.bn_train_bwd_thin_ok(x, dy.g, dy.w):
+                dx, _, _ = rt.eng.bn_train_bwd_thin(x, dy.g, dy.w, rt.param(self.gamma), s["mean"], s["invstd"], relu=self.relu,
+                                                    dgamma=rt.grad(self.gamma), dbeta=rt.grad(self.beta), beta=rt.param(self.beta))
+                return [dx]
+            dy = dy.materialise(rt.eng)
         if s.get("sums_done") and self.bnb_to is not None and rt.bnb_on(self, x):
             # ... and that pass rides in the A path of the producer's pointwise dgrad: hand the pieces over
             return [BnBackwardDeferred(dy, rt.param(self.gamma), rt.param(self.beta), s["mean"], s["invstd"], rt.grad(self.gamma),
@@ -688,6 +751,10 @@ class _AvgPoolNode(Node):
         # a gradient buffer the sweep already owns for this input (scSE's combine node, the other ASPP branches): the spread-out
         # dy / (kh kw) is added into it in place instead of being written out and summed by a separate add
         acc = rt.take_pending(self.inputs[0], owned_only=True)
+        if isinstance(acc, ScseGradDeferred):   # the squeeze of a marked scSE block: dy / (H W) is added by the block's final kernel
+            if self.global_pool and acc.dtype == dy.dtype:
+                return [acc.add(rt.eng, "gap", dy)]
+            acc = acc.materialise(rt.eng)
         if acc is not None and acc.dtype == dy.dtype:
             return [rt.eng.avgpool_bwd(dy, tuple(x.shape), kh, kw, out=acc, accumulate=True)]
         if acc is not None:
@@ -922,8 +989,19 @@ class _ScseCombineNode(Node):
         x, s, c = xs
         return rt.eng.scse_fwd(x, s, c)
 
+    # (sSE convolution, GlobalAveragePooling) when they and this node are the only consumers of x (Model._fuse): their input gradients
+    # are rank-one terms the block's final kernel adds (ScseGradDeferred) - six passes over the tensor instead of nine
+    lowrank = None
+
     def backward(self, rt, xs, y, dy):
         x, s, c = xs
+        torch = rt.torch
+        if (self.lowrank is not None and switches.get("SG_SCSE_LOWRANK") and switches.get("SG_GRAD_ACC") and rt._pending is not None
+                and id(self.inputs[0]) not in rt._pending and rt.needs_grad(self.inputs[0])
+                and all(t.dtype == torch.float32 and t.is_contiguous() for t in (x, s, c, dy))
+                and rt.eng.conv2d_caps(self.lowrank[0].desc(rt, x), dgrad=True).thin):
+            ds, dc = rt.eng.scse_bwd_sums(x, s, c, dy)
+            return [ScseGradDeferred(x, s, c, dy), ds, dc]
         dx, ds, dc = rt.eng.scse_bwd(x, s, c, dy)
         return [dx, ds, dc]
 

@@ -636,6 +636,28 @@ class Engine:
               "sg_bn_train_bwd")
         return dx, dgamma, dbeta
 
+    def bn_train_bwd_thin_ok(self, x, g, w) -> bool:
+        """Can bn_train_bwd_thin take the gradient g of a thin 1x1 convolution (kernel w) for the BatchNormalization input x?"""
+        c = x.shape[-1]
+        return (x.dtype == torch.float32 and g.dtype == torch.float32 and x.is_contiguous() and g.is_contiguous()
+                and bool(self.lib.sg_bn_train_bwd_thin_ok(self.h, SG_F32, x.numel() // c, c, int(w.shape[-1]), int(g.shape[-1]))))
+
+    def bn_train_bwd_thin(self, x, g, w, gamma, mean, invstd, relu=False, out=None, dgamma=None, dbeta=None, beta=None):
+        """bn_train_bwd whose dy is conv2d_dgrad(g, w) of a thin 1x1 convolution, evaluated inside the kernels instead of written
+        out (sg_bn_train_bwd_thin): the same bits without the C-wide tensor.  g: [..., CO] fp32, w: [1, 1, C, CO]."""
+        _chk32(x, "x"); _chk32(g, "g"); _chk32(w, "w")
+        c, co = x.shape[-1], w.shape[-1]
+        rows = x.numel() // c
+        assert w.shape[-2] == c and g.numel() // g.shape[-1] == rows and g.shape[-1] >= co
+        dx = out if out is not None else torch.empty_like(x)
+        dgamma = dgamma if dgamma is not None else self.empty(c)
+        dbeta = dbeta if dbeta is not None else self.empty(c)
+        wsp, wsn = self.ws(self.lib.sg_bn_ws_bytes(self.h, rows, c))
+        check(self.lib.sg_bn_train_bwd_thin(self.h, self.stream, SG_F32, rows, c, int(co), int(g.shape[-1]), _ptr(x), _ptr(g), _ptr(w),
+                                            _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(dx), _ptr(dgamma), _ptr(dbeta),
+                                            int(relu), wsp, wsn), "sg_bn_train_bwd_thin")
+        return dx, dgamma, dbeta
+
     def bn_infer(self, x, gamma, beta, mm, mv, relu=False, eps=1e-3, out=None):
         _chk(x, "x")
         c = x.shape[-1]
@@ -769,6 +791,27 @@ class Engine:
         check(self.lib.sg_scse_bwd(self.h, self.stream, _dt(x), n, h * w, c, _ptr(x), _ptr(s), _ptr(cl), _ptr(dy), _ptr(dx),
                                    _ptr(ds), _ptr(dc), wsp, wsn), "sg_scse_bwd")
         return dx, ds, dc
+
+    def scse_bwd_sums(self, x, s, cl, dy):
+        """ds, dc of scse_bwd without dx (sg_scse_bwd_sums: the same reductions, the same bits)."""
+        n, h, w, c = x.shape
+        ds, dc = torch.empty_like(s), torch.empty_like(cl)
+        wsp, wsn = self.ws(self.lib.sg_scse_bwd_ws_bytes(self.h, n, h * w, c))
+        check(self.lib.sg_scse_bwd_sums(self.h, self.stream, _dt(x), n, h * w, c, _ptr(x), _ptr(s), _ptr(cl), _ptr(dy), _ptr(ds),
+                                        _ptr(dc), wsp, wsn), "sg_scse_bwd_sums")
+        return ds, dc
+
+    def scse_bwd_final(self, dy, s, cl, dsp, w, dg, gap_first=True):
+        """The complete gradient of an scSE block's input in one pass over dy (sg_scse_bwd_final, fp32): dy (sig s + sig c), the GAP's
+        dg [N, C] / HW and the sSE convolution's w [C] * dsp [N, H, W, 1], added in the unfused sweep's order (gap_first)."""
+        for t, name in ((dy, "dy"), (s, "s"), (cl, "c"), (dsp, "dsp"), (w, "w"), (dg, "dg")):
+            _chk32(t, name)
+        n, h, w_, c = dy.shape
+        assert s.numel() == dsp.numel() == n * h * w_ and cl.numel() == dg.numel() == n * c and w.numel() == c
+        dx = torch.empty_like(dy)
+        check(self.lib.sg_scse_bwd_final(self.h, self.stream, SG_F32, n, h * w_, c, _ptr(dy), _ptr(s), _ptr(cl), _ptr(dsp), _ptr(w),
+                                         _ptr(dg), _ptr(dx), int(bool(gap_first))), "sg_scse_bwd_final")
+        return dx
 
     def bam_fwd(self, x, mc, ms, out=None):
         n, h, w, c = x.shape

@@ -251,6 +251,37 @@ class Model:
                 if sc.stride == 1 and not sc.pre_relu and sc.bn_src is None and w % 4 == 0 and c % 4 == 0:
                     n.defer_to, sc.bn_src = sc, n
         self._fuse_bn_conv(outs)
+        # BatchNormalization (+ fused ReLU) -> thin 1x1 Conv2D (Cout <= 4: the softmax head), the layer's only consumer: the
+        # convolution's input gradient stays unexpanded and the BatchNormalization's backward evaluates it (layers.ThinGradDeferred;
+        # decided again at run time: storage type, SG_THIN_GRAD_BN)
+        for n in self.nodes:
+            if not isinstance(n, L._BNNode) or len(n.output.shape) != 4 or id(n.output) in outs:
+                continue
+            t = n.output
+            while (len(t.consumers) == 1 and isinstance(t.consumers[0], L._ActNode) and t.consumers[0].fused_away
+                   and id(t.consumers[0].output) not in outs):
+                t = t.consumers[0].output
+            if len(t.consumers) != 1 or id(t) in outs:
+                continue
+            c = t.consumers[0]
+            cin = t.shape[-1]
+            if (isinstance(c, L._ConvNode) and c.k == 1 and c.stride == 1 and c.filters <= 4 and c.up_src is None
+                    and cin % 4 == 0 and cin >= 16):
+                c.thin_bn = n
+        # scSE block: x feeds the sSE convolution (1x1, one output channel, on the thin kernel's geometry), the GlobalAveragePooling of
+        # the cSE path and the combine node, and nothing else.  The two gates' input gradients are rank-one terms; the combine node's
+        # backward leaves the block's dx to one final kernel that adds them (layers.ScseGradDeferred; SG_SCSE_LOWRANK at run time).
+        for n in self.nodes:
+            if not isinstance(n, L._ScseCombineNode):
+                continue
+            x, s = n.inputs[0], n.inputs[1]
+            sse, cons = s.node, x.consumers
+            gaps = [q for q in cons if isinstance(q, L._AvgPoolNode) and q.global_pool]
+            if (isinstance(sse, L._ConvNode) and len(cons) == 3 and len(gaps) == 1 and sse in cons and n in cons and id(x) not in outs
+                    and x.node is not None and sse.inputs[0] is x and sse.k == 1 and sse.stride == 1 and sse.filters == 1
+                    and sse.activation is None and sse.bn_src is None and sse.up_src is None and len(s.consumers) == 1
+                    and x.shape[-1] % 4 == 0 and x.shape[-1] >= 16):
+                n.lowrank = (sse, gaps[0])
         # SeparableConv2D -> BatchNormalization whose backward column sums come from elsewhere (sums_from): the backward APPLY can
         # ride in the A path of the pointwise dgrad (csrc/conv_pw.h, BNB form; _Runtime.bnb_on decides per runtime and batch)
         for n in self.nodes:
@@ -1291,6 +1322,10 @@ class _Runtime:
                     hook(n.index)
                 continue
             dy = slot[0]
+            if isinstance(dy, L.ThinGradDeferred) and not (isinstance(n, L._BNNode) or (isinstance(n, L._ActNode) and n.fused_away)):
+                dy = dy.materialise(e)   # only a BatchNormalization (through an absorbed ReLU) evaluates it unexpanded
+            elif isinstance(dy, L.ScseGradDeferred):
+                dy = dy.materialise(e)   # (a consumer of the block's input did not report: never with the graphs Model._fuse marks)
             xs = [self.values[id(t)] for t in n.inputs]
             y = self.values[id(n.output)]
             self._pending = grads
@@ -1305,6 +1340,11 @@ class _Runtime:
                 elif g is dy:
                     fresh = False
                 cur = grads.get(id(sym))
+                if cur is not None:   # a sum: of tensors (never reached by the graphs Model._fuse marks)
+                    if isinstance(g, (L.ThinGradDeferred, L.ScseGradDeferred)):
+                        g, fresh = g.materialise(e), True
+                    if isinstance(cur[0], (L.ThinGradDeferred, L.ScseGradDeferred)):
+                        cur[0], cur[1] = cur[0].materialise(e), True
                 if cur is None:
                     grads[id(sym)] = [g, fresh]
 

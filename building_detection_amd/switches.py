@@ -19,6 +19,8 @@ SWITCHES = {
     "SG_BN_DEFER": ("eq1", "1", "BatchNormalization(+ReLU) in front of a SeparableConv2D is applied in the depthwise gather"),
     "SG_BN_PW": ("eq1", "0", "the BatchNormalization backward apply rides in the A path of the pointwise dgrad (bit-identical, a loss in the step)"),
     "SG_BN_CONV": ("ne0", "1", "BatchNormalization layers in front of thin 1x1 / patch-kernel convolutions ride in their loader; 0: own launch"),
+    "SG_THIN_GRAD_BN": ("ne0", "1", "a thin 1x1 convolution's input gradient is evaluated inside the BatchNormalization backward in front of it; 0: written out"),
+    "SG_SCSE_LOWRANK": ("ne0", "1", "an scSE block's input gradient is written once, by a final kernel that adds the two gates' rank-one terms; 0: three passes"),
     "SG_ACT_PLANES": ("ne0", "1", "activation planes made once per tensor and step, kept for the planes-in filter gradient; 0: split in every launch"),
     "SG_UP2_FUSE": ("ne0", "1", "UpSampling2D(2) -> Conv2D 3x3 as one sub-pixel launch; 0: a pair of launches"),
     "SG_GRAD_ACC": ("eq1", "1", "the gradient of a two-consumer block input is summed in the dgrad epilogue; off: by a separate add"),

@@ -434,6 +434,15 @@ int sg_bn_train_bwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, c
 int sg_bn_train_bwd_apply(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x, const void* dy,
                           const void* gamma, const void* beta, const void* save_mean, const void* save_invstd,
                           const void* dgamma, const void* dbeta, void* dx, int relu);
+/* sg_bn_train_bwd whose dy is the input gradient of a thin 1x1 convolution (Cout = CO <= 4, kernel w [C][CO]: the softmax head, the
+ * sSE gate) and is never written out: the kernels evaluate dy[r][c] = sum_o g[r][o] * w[c][o] (g: [rows][y_ld], CO live columns,
+ * fp32) where they consume it, with the thin dgrad's own expression, on the plan sg_bn_plan gives sg_bn_train_bwd for the same rows,
+ * C and storage type - dx, dgamma and dbeta have the bits of sg_conv2d_dgrad + sg_bn_train_bwd.  relu: the mask is recomputed from x
+ * (beta required).  fp32 storage only: sg_bn_train_bwd_thin_ok answers 0 for anything the entry point refuses (SG_EUNSUPPORTED). */
+int sg_bn_train_bwd_thin_ok(const sg_ctx* ctx, int dtype, int64_t rows, int C, int CO, int y_ld);
+int sg_bn_train_bwd_thin(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, int CO, int y_ld, const void* x,
+                         const void* g, const void* w, const void* gamma, const void* beta, const void* save_mean,
+                         const void* save_invstd, void* dx, void* dgamma, void* dbeta, int relu, void* ws, size_t ws_bytes);
 int sg_bn_infer(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const void* x,
                 const void* gamma, const void* beta, const void* moving_mean, const void* moving_var,
                 void* y, float eps, int relu);
@@ -530,6 +539,16 @@ size_t sg_scse_bwd_ws_bytes(const sg_ctx* ctx, int N, int64_t HW, int C);
 int sg_scse_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int64_t HW, int C, const void* x,
                 const void* s, const void* c, const void* dy, void* dx, void* ds, void* dc, void* ws,
                 size_t ws_bytes);
+/* The block's backward without the passes that only add rank-one terms.  sg_scse_bwd_sums: ds and dc of sg_scse_bwd (the same
+ * launches: the same bits) without dx; workspace as sg_scse_bwd_ws_bytes.  sg_scse_bwd_final: the complete gradient of the block's
+ * input in one pass, dx = dy (sig s + sig c) + dg[n,c] / HW + w[c] dsp[p], where dsp [N*HW] is the gradient of the sSE convolution's
+ * output (kernel w [C]) and dg [N,C] that of the GlobalAveragePooling's; the terms are added in the order of the unfused sweep -
+ * sg_scse_bwd, then sg_avgpool_bwd(accumulate) and sg_conv2d_dgrad(res) (gap_first != 0), or the last two the other way round - on
+ * the same rounded values: the same bits.  fp32 storage only (SG_EUNSUPPORTED otherwise). */
+int sg_scse_bwd_sums(sg_ctx* ctx, void* stream, int dtype, int N, int64_t HW, int C, const void* x, const void* s,
+                     const void* c, const void* dy, void* ds, void* dc, void* ws, size_t ws_bytes);
+int sg_scse_bwd_final(sg_ctx* ctx, void* stream, int dtype, int N, int64_t HW, int C, const void* dy, const void* s,
+                      const void* c, const void* dsp, const void* w, const void* dg, void* dx, int gap_first);
 /* BAM combine  y = x + x * sigmoid(mc[n,c] + ms[n,hw])  (BAM_attention, bam.py:57-71); backward. */
 int sg_bam_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int64_t HW, int C, const void* x,
                const void* mc, const void* ms, void* y);

@@ -133,6 +133,73 @@ SG_WG_THIN, SG_WG_WIDE, SG_WG_PATCH, SG_WG_SLAB_X6, SG_WG_SLAB_NATIVE, SG_WG_HEA
 WG_FAMILY_NAMES = {0: "none", 1: "thin", 2: "wide", 3: "patch", 4: "slab-x6", 5: "slab-native", 6: "head32", 7: "planes-in"}
 
 
+class ConvLaunch(C.Structure):
+    """Mirror of `sg_conv_launch` (include/segengine.h): the kernel form of one forward / input-gradient launch."""
+
+    _fields_ = [(n, C.c_int) for n in ("kernel", "bn", "vec", "ut", "var", "mf16", "ks", "pd", "skip_taps", "group_m", "cb", "pc",
+                                       "pmulti")]
+
+
+class ConvPlan(C.Structure):
+    """Mirror of `sg_conv_plan` (include/segengine.h): the plan one forward / input-gradient call runs by (sg_conv2d_plan)."""
+
+    _fields_ = ([("main", ConvLaunch), ("tail", ConvLaunch), ("with_res", ConvLaunch)] +
+                [(n, C.c_int) for n in ("family", "fast", "nb", "nsub", "tail_n", "vec", "perm2", "npl", "kd", "Ck", "Ckp", "wbn",
+                                        "x6w_S", "b16w_S", "deep", "res", "bn_in", "up2", "bnb", "planes_in")] +
+                [("ws_bytes", C.c_size_t)])
+
+
+SG_CF_NATIVE, SG_CF_THIN, SG_CF_HEAD, SG_CF_SLAB, SG_CF_PATCH, SG_CF_WIDE = range(6)
+CONV_FAMILY_NAMES = {0: "native", 1: "thin", 2: "head", 3: "slab", 4: "patch", 5: "wide"}
+SG_CK_NATIVE, SG_CK_THIN, SG_CK_X6, SG_CK_B16, SG_CK_X6W, SG_CK_B16W, SG_CK_PATCH, SG_CK_WIDE = range(1, 9)
+CONV_KERNEL_NAMES = {0: "none", 1: "native", 2: "thin", 3: "slab.x6", 4: "slab.b16", 5: "slab.x6w", 6: "slab.b16w", 7: "patch",
+                     8: "wide"}
+
+
+def conv_form_name(pl: ConvPlan, la: ConvLaunch, dgrad: bool, dt: int, operands=()) -> str:
+    """The name of one launch `la` of plan `pl` (DESIGN.md, appendix "convolution form names"):
+        fwd|dgrad.native.BN<w>.<scalar|vec|ut>[.b16|.b16>f32|.f32>b16]      fwd|dgrad.thin.CO<n>.<f32|b16|b16>f32>
+        fwd|dgrad.slab.x6.BN<w>.v<0|1>[.mf16][.npl1]                        fwd|dgrad.slab.b16.BN<w>.KS<2|4>.PD<1|2>
+        fwd|dgrad.slab.x6w.S<1|2>        fwd|dgrad.slab.b16w.S<1-4>         fwd|dgrad.patch.C<32|64|64m>.BN<w>
+        fwd|dgrad.wide.<x6|b16>.W<384|256>
+    then the operands the call brings (`operands`, e.g. "bn", "res", "pin", "up2", "down2", "bnb"), then the modifiers
+    .skip .perm2 .gm<n> .cb<n> .vpad .sub<nb>+<tail>."""
+    b16, head = (dt & 0xff) == SG_BF16, bool(dt & SG_HEAD_F32)
+    n = ("dgrad." if dgrad else "fwd.") + CONV_KERNEL_NAMES[la.kernel]
+    k = la.kernel
+    if k == SG_CK_NATIVE:
+        n += f".BN{la.bn}." + ("ut" if la.ut else ("vec" if la.vec else "scalar"))
+        n += (".f32>b16" if dgrad else ".b16>f32") if head else (".b16" if b16 else "")
+    elif k == SG_CK_THIN:
+        n += f".CO{la.bn}." + ("b16>f32" if head else ("b16" if b16 else "f32"))
+    elif k == SG_CK_X6:
+        n += f".BN{la.bn}.v{la.var}" + (".mf16" if la.mf16 else "") + (".npl1" if pl.npl == 1 else "")
+    elif k == SG_CK_B16:
+        n += f".BN{la.bn}.KS{la.ks}.PD{la.pd}"
+    elif k == SG_CK_X6W:
+        n += f".S{pl.x6w_S}"
+    elif k == SG_CK_B16W:
+        n += f".S{pl.b16w_S}"
+    elif k == SG_CK_PATCH:
+        n += f".C{la.pc}" + ("m" if la.pmulti else "") + f".BN{la.bn}"
+    elif k == SG_CK_WIDE:
+        n += (".b16" if b16 else ".x6") + f".W{la.bn}"
+    n += "".join("." + o for o in operands)
+    if la.skip_taps:
+        n += ".skip"
+    if pl.perm2 and k in (SG_CK_X6, SG_CK_B16):
+        n += ".perm2"
+    if la.group_m > 1:
+        n += f".gm{la.group_m}"
+    if la.cb:
+        n += f".cb{la.cb}"
+    if pl.Ckp != pl.Ck and pl.family == SG_CF_SLAB and pl.fast:
+        n += ".vpad"
+    if pl.nsub > 1:
+        n += f".sub{pl.nb}+{pl.tail_n}"
+    return n
+
+
 class SegPlan(C.Structure):
     """Mirror of `sg_seg_plan_t` (include/segengine.h): the segment reducer's plan (sg_seg_plan)."""
 
@@ -167,6 +234,7 @@ _SIGNATURES = {
     "sg_conv2d_wgrad_ws_bytes": (_sz, [_vp, _dp]),
     "sg_conv2d_wgrad": (_i, [_vp, _vp, _i, _dp, _vp, _vp, _vp, _vp, _op]),
     "sg_conv2d_caps": (_i, [_vp, _i, _dp, _i, C.POINTER(ConvCaps)]),
+    "sg_conv2d_plan": (_i, [_vp, _i, _dp, _i, _i, _i, C.POINTER(ConvPlan)]),
     "sg_split_planes": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "sg_conv2d_wgrad_planes_ws_bytes": (_sz, [_vp, _dp]),
     "sg_conv2d_wgrad_planes": (_i, [_vp, _vp, _dp, _vp, _vp, _vp, _vp, _sz]),

@@ -440,10 +440,14 @@ int launch_b16_pd(const IgemmParams& p, hipStream_t st) {
 // SG_B16_PD = 1 / 2: one / two register sets of prefetched slabs for every launch (A/B switch); default 0 = by shape: two
 // sets for the long-K multi-tap FORWARD launches (the ASPP convolutions, K = 18432: 308 -> 280 us, 225 -> 195 us), one
 // everywhere else (the same convolutions' dgrad loses 10 - 18 % with two, the short-K layers 8 %: profiles/r02_b16_prefetch_ab.txt)
+// (launch_b16 and the plan query, sg_conv2d_plan, both ask b16_pd_of)
+inline int b16_pd_of(const IgemmParams& p) {
+  const int pd = sg_switch<SW_B16_PD>();
+  return (pd == 2 || (pd == 0 && p.k_mul > 0 && p.K != p.C && p.K >= 8192 && p.div == 1)) ? 2 : 1;
+}
 template <int BN, int WGM, int WGN, int KS>
 int launch_b16(const IgemmParams& p, hipStream_t st) {
-  const int pd = sg_switch<SW_B16_PD>();
-  const bool two = pd == 2 || (pd == 0 && p.k_mul > 0 && p.K != p.C && p.K >= 8192 && p.div == 1);
+  const bool two = b16_pd_of(p) == 2;
   return two ? launch_b16_pd<BN, WGM, WGN, KS, 2>(p, st) : launch_b16_pd<BN, WGM, WGN, KS, 1>(p, st);
 }
 
@@ -460,8 +464,7 @@ inline int b16_ks(int c, bool one_tap) {
 
 inline int dispatch_b16(const IgemmParams& p_in, int num_cus, hipStream_t st) {
   IgemmParams p = p_in;
-  const int bn = pick_bn(p.M, p.Nout, num_cus);
-  plan_common(p, true, bn, true, 2);
+  const int bn = slab_common(p, SLAB_B16, 2, num_cus);
   p.stagger = 0;
   p.ablate = 0;
 #ifdef SG_B16_ABL

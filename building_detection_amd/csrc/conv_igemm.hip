@@ -1067,11 +1067,14 @@ int launch_igemm_ut(const IgemmParams& p, hipStream_t st) {
   return 0;
 }
 
+// The vector form's wave-uniform tap (UT): a slab never straddles a tap, and both operands fit a 2 GiB buffer descriptor
+// (launch_igemm and the plan query, sg_conv2d_plan, both ask here)
+inline bool igemm_ut_of(const IgemmParams& p) { return ((p.C % BK == 0) || (p.K == p.C)) && p.x_bytes != 0 && p.w_bytes != 0; }
+
 template <int BN, int WGM, int WGN, int PF, bool VEC>
 int launch_igemm(const IgemmParams& p, hipStream_t st) {
   if constexpr (VEC) {
-    // slab never straddles a tap, and both operands fit a 2 GiB buffer descriptor
-    const bool ut = ((p.C % BK == 0) || (p.K == p.C)) && p.x_bytes != 0 && p.w_bytes != 0;
+    const bool ut = igemm_ut_of(p);
     if (ut) return launch_igemm_ut<BN, WGM, WGN, PF, true, true>(p, st);
   }
   return launch_igemm_ut<BN, WGM, WGN, PF, VEC, false>(p, st);
@@ -1118,6 +1121,33 @@ void plan_common(IgemmParams& p, bool vec, int bn, bool x6 = false, int eb = 4) 
   p.cb = ((conv_l2(x6) & 2) && ut && ntaps > 1 && spt > cbv && spt % cbv == 0 && img_bytes > (2ll << 20)) ? cbv : 0;
 }
 
+// The kernels of the slab family (plan_conv: CONV_SLAB) and what every one of their launches sets before it starts: the tile width
+// (the two 256-wide forms plan with 128-wide column tiles, the others by wave quantisation) and plan_common's fields.  The
+// dispatchers, run_x6 and the plan query (sg_conv2d_plan) all come through here; slab_kernel_of (behind ConvPlan) picks the kernel.
+enum SlabKernel { SLAB_X6, SLAB_B16, SLAB_X6W, SLAB_B16W };
+inline int slab_common(IgemmParams& p, SlabKernel sk, int eb, int num_cus) {
+  const int bn = (sk == SLAB_X6W || sk == SLAB_B16W) ? 128 : pick_bn(p.M, p.Nout, num_cus);
+  plan_common(p, true, bn, true, eb);
+  return bn;
+}
+// the mixed-storage forms of the native kernel (bf16 storage, the softmax head): scalar-gather planning whatever the loads, no tap
+// elimination, no K order, never the wave-uniform-tap form.  dispatch_igemm_mixed and the plan query both come through here.
+inline int mixed_common(IgemmParams& p, int num_cus) {
+  const int bn = pick_bn(p.M, p.Nout, num_cus);
+  plan_common(p, false, bn);
+  p.stagger = 0;
+  p.ablate = 0;
+  p.skip_taps = 0;
+  p.cb = 0;
+  return bn;
+}
+// the fp32 native kernel: planning by its channel runs; the UT form is launch_igemm's (igemm_ut_of)
+inline int native_common(IgemmParams& p, bool vec, int num_cus) {
+  const int bn = pick_bn(p.M, p.Nout, num_cus);
+  plan_common(p, vec, bn);
+  return bn;
+}
+
 #include "conv_x6.h"
 #include "conv_x6p.h"
 #include "conv_b16.h"
@@ -1126,11 +1156,19 @@ void plan_common(IgemmParams& p, bool vec, int bn, bool x6 = false, int eb = 4) 
 #include "conv_b16w.h"
 #include "conv_x6w.h"
 
+// conv_x6_kernel's structure for a launch of `tiles` tiles (1: double-buffered, one workgroup per CU; 0: single-buffered, two per
+// CU; the measurements: in dispatch_x6) and its product shape (16x16x32 for the multi-tap convolutions of the six-pass arithmetic).
+// dispatch_x6 and the plan query (sg_conv2d_plan) both ask here.
+inline int x6_var_of(int64_t tiles, int num_cus) {
+  const int var = x6_variant();
+  return var < 0 ? ((tiles <= 3 * (int64_t)num_cus) ? 1 : 0) : var;
+}
+inline bool x6_mf16_of(const IgemmParams& p) { return sg_switch<SW_X6_MF16>() && p.K != p.C; }
+
 template <int NPL, typename TA>
 int dispatch_x6(const IgemmParams& p_in, int num_cus, hipStream_t st) {
   IgemmParams p = p_in;
-  const int bn = pick_bn(p.M, p.Nout, num_cus);
-  plan_common(p, true, bn, true, EL<TA>::BYTES);
+  const int bn = slab_common(p, SLAB_X6, EL<TA>::BYTES, num_cus);
   p.stagger = sg_switch<SW_X6_INTERLEAVE>() ? 2 : 0;  // 0: staggered halves instead of the hand-interleaved step (A/B switch)
   p.ablate = sg_switch<SW_X6_ABLATE>() & 15;
   // Structure by tile count (measured, profiles/r01_ab_x6.txt, r01_ab_x6_interleave.txt, r01_ab_tiles1024.txt): up to
@@ -1140,8 +1178,7 @@ int dispatch_x6(const IgemmParams& p_in, int num_cus, hipStream_t st) {
   // 1024->1024 pointwise 233 vs 252 us; ASPP dgrad 0.83 vs 0.94 ms, decoder 128->64 dgrad 0.92 vs 1.03 ms).
   // SG_X6_VARIANT overrides.  (4-wave workgroups, 64x64 per wave, lost to both 8-wave structures and are gone: DESIGN.md, retired.)
   const int64_t tiles = sg_cdiv(p.M, BM) * sg_cdiv(p.Nout, bn);
-  int var = x6_variant();
-  if (var < 0) var = (tiles <= 3 * (int64_t)num_cus) ? 1 : 0;
+  const int var = x6_var_of(tiles, num_cus);
   if constexpr (NPL == 1) {  // the one-plane (bf16 product) kernels come in the two 8-wave structures only
     if (bn == 128) return (var & 1) ? launch_x6<128, 2, 4, 2, 1, TA>(p, st) : launch_x6<128, 2, 4, 1, 1, TA>(p, st);
     if (bn == 64) return (var & 1) ? launch_x6<64, 4, 2, 2, 1, TA>(p, st) : launch_x6<64, 4, 2, 1, 1, TA>(p, st);
@@ -1149,7 +1186,7 @@ int dispatch_x6(const IgemmParams& p_in, int num_cus, hipStream_t st) {
   } else {
   // 16x16x32 products for the multi-tap convolutions (conv_x6_kernel, MF): a property of the layer, never of the batch.
   // SG_X6_MF16=0 keeps every launch on 32x32x16 (A/B runs).
-  const bool mf = sg_switch<SW_X6_MF16>() && p.K != p.C;
+  const bool mf = x6_mf16_of(p);
   if (bn == 128) {
     if (mf) return var ? launch_x6<128, 2, 4, 2, 3, float, 1>(p, st) : launch_x6<128, 2, 4, 1, 3, float, 1>(p, st);
     return var ? launch_x6<128, 2, 4, 2>(p, st) : launch_x6<128, 2, 4, 1>(p, st);
@@ -1212,6 +1249,26 @@ struct ConvPlan {
   }
 };
 
+// Which kernel a launch of the slab family takes: the planes-in kernel / the 256-wide bf16 kernel where the plan names K shares and
+// the launch adds no collected gradient (they have no such epilogue), conv_b16_kernel for deep bf16 slabs, else conv_x6_kernel.
+inline SlabKernel slab_kernel_of(const ConvPlan& pl, bool b16, bool with_res) {
+  if (pl.npl == 3 && !b16 && pl.x6w_S > 0 && !with_res) return SLAB_X6W;
+  if (b16 && pl.deep) return (pl.b16w_S > 0 && !with_res) ? SLAB_B16W : SLAB_B16;
+  return SLAB_X6;
+}
+// A slab launch's parameters from the plan: virtual channel padding, the planes' geometry and bytes
+inline void slab_fill(IgemmParams& p, const ConvPlan& pl) {
+  if (pl.Ckp != p.C) {   // virtual channel padding
+    p.K = pl.K;
+    p.C = pl.Ckp;
+    p.fd_c = make_fastdiv((uint32_t)pl.Ckp);
+  }
+  p.kd = pl.kd;
+  p.Kpad = pl.Kpad;
+  p.Npad = pl.Npad;
+  p.w_bytes = (uint32_t)pl.w_bytes;
+}
+
 // Run a launch of the plan's family (>= CONV_SLAB) on its weight planes in `ws`; the scratch of a wide slab form lies behind them.
 // prepared: `ws` already holds the planes (sg_prepare_planes, once per optimiser step), no split here.
 // NPL = 3: the exact fp32 emulation; NPL = 1: bf16 products (TA = float: fp32 storage rounded on the way into LDS,
@@ -1247,16 +1304,8 @@ int run_x6(const ConvPlan& pl, IgemmParams& p, const float* w, bool dgrad, int C
       break;
     case CONV_SLAB: {
       const int Ck = p.C;
-      if (pl.Ckp != Ck) {   // virtual channel padding
-        p.K = pl.K;
-        p.C = pl.Ckp;
-        p.fd_c = make_fastdiv((uint32_t)pl.Ckp);
-      }
-      p.kd = pl.kd;
-      p.Kpad = pl.Kpad;
-      p.Npad = pl.Npad;
+      slab_fill(p, pl);
       p.wq = (const unsigned short*)ws;
-      p.w_bytes = (uint32_t)pl.w_bytes;
       if (!prepared) {
         dim3 grid((unsigned)(p.Kpad / 32), (unsigned)(p.Npad / 32));
         hipLaunchKernelGGL(split3_weights_kernel, grid, dim3(256), 0, st, w, (unsigned short*)ws, pl.K, N, p.Kpad, p.Npad, Ck,
@@ -1264,24 +1313,24 @@ int run_x6(const ConvPlan& pl, IgemmParams& p, const float* w, bool dgrad, int C
         SG_LAUNCH_CHECK("split3_weights_kernel");
       }
       char* scratch = (char*)ws + ((pl.w_bytes + 255) & ~(size_t)255);
+      const SlabKernel sk = slab_kernel_of(pl, B16, p.res != nullptr);
       if constexpr (NPL == 3 && !B16) {
-        if (pl.x6w_S > 0 && !p.res) {   // scratch: the planes of A, then split-K partial slabs
+        if (sk == SLAB_X6W) {   // scratch: the planes of A, then split-K partial slabs
           IgemmParams q = p;
-          plan_common(q, true, 128, true, 4);
+          slab_common(q, sk, 4, num_cus);
           q.ablate = sg_switch<SW_X6W_ABLATE>();
           return launch_x6w(q, pl.x6w_S, scratch, st);
         }
       }
       if constexpr (NPL == 1 && B16) {
-        if (pl.deep) {
-          if (pl.b16w_S > 0 && !p.res) {
-            IgemmParams q = p;
-            plan_common(q, true, 128, true, 2);
-            return launch_b16w(q, pl.b16w_S, pl.b16w_S > 1 ? reinterpret_cast<float*>(scratch) : nullptr, st);
-          }
-          return dispatch_b16(p, num_cus, st);
+        if (sk == SLAB_B16W) {
+          IgemmParams q = p;
+          slab_common(q, sk, 2, num_cus);
+          return launch_b16w(q, pl.b16w_S, pl.b16w_S > 1 ? reinterpret_cast<float*>(scratch) : nullptr, st);
         }
+        if (sk == SLAB_B16) return dispatch_b16(p, num_cus, st);
       }
+      if (sk != SLAB_X6) break;   // (a plan of another arithmetic than this instantiation's)
       return dispatch_x6<NPL, TA>(p, num_cus, st);
     }
     default:
@@ -1304,8 +1353,7 @@ inline size_t x6_ws_bytes(int taps, int C, int N) {
 
 int dispatch_igemm(const IgemmParams& p_in, bool vec, int num_cus, hipStream_t st) {
   IgemmParams p = p_in;
-  const int bn = pick_bn(p.M, p.Nout, num_cus);
-  plan_common(p, vec, bn);
+  const int bn = native_common(p, vec, num_cus);
   // the structure that won every A/B: 8-wave workgroups, two-slab prefetch, staggered wave halves (the 4-wave and one-slab
   // forms are gone: DESIGN.md, retired)
   p.stagger = 1;
@@ -1656,12 +1704,7 @@ void fill_dgrad_params(IgemmParams& p, const sg_conv_desc* d, const void* dy, co
 template <typename TA, typename TY>
 int dispatch_igemm_mixed(const IgemmParams& p_in, bool vec, int num_cus, hipStream_t st) {
   IgemmParams p = p_in;
-  const int bn = pick_bn(p.M, p.Nout, num_cus);
-  plan_common(p, false, bn);
-  p.stagger = 0;
-  p.ablate = 0;
-  p.skip_taps = 0;
-  p.cb = 0;
+  const int bn = mixed_common(p, num_cus);
   if (vec) {
     if (bn == 128) return launch_igemm_ut<128, 2, 4, 1, true, false, TA, TY>(p, st);
     if (bn == 64) return launch_igemm_ut<64, 4, 2, 1, true, false, TA, TY>(p, st);
@@ -2036,6 +2079,29 @@ static bool bn_in_geom(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
 // sg_conv_opts: a NULL pointer is the plain launch
 static const sg_conv_opts kNoOpts = {};
 
+// alignment class of a pointer, as plan_wgrad and sg_conv2d_plan take it
+static int align_class(const void* p) { return aligned16(p) ? 16 : ((reinterpret_cast<uintptr_t>(p) & 7) == 0 ? 8 : 0); }
+
+// Channel runs of a launch of the native kernel (16 bytes of fp32, 8 of bf16): from the descriptor, the alignment class of the
+// activation operand it reads (x; dgrad: dy) and, where the kernel reads w itself (the fp32 forward), that of w.  The launches and
+// sg_conv2d_plan both ask here.
+static bool native_vec_of(int dtype, const sg_conv_desc* d, bool dgrad, int a_class, bool w16) {
+  const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0;
+  const int ca = dgrad ? d->Cout : d->Cin, cn = dgrad ? d->Cin : d->Cout;
+  const int ld = dgrad ? (d->y_ld ? d->y_ld : d->Cout) : (d->x_ld ? d->x_ld : d->Cin);
+  if ((ca % 4) || (ld % 4)) return false;
+  if (head32 && dgrad) return a_class == 16;   // (fp32 dy)
+  if (b16) return a_class >= 8;                // the 4-channel loads of bf16 storage
+  return cn % 4 == 0 && a_class == 16 && (dgrad || w16);
+}
+
+// A thin launch's operands against its kernels' alignment: the tensor with Cin channels (x; dgrad: dx) 16-byte aligned, in every
+// sub-batch.  Where this fails the plan is taken again with PLAN_NOT_THIN.
+static bool thin_operands_ok(const ConvPlan& pl, const sg_conv_desc* d, bool a16, int ebx) {
+  const int xl = d->x_ld ? d->x_ld : d->Cin;
+  return a16 && (pl.nb >= d->N || pl.nb < 1 || ((int64_t)d->H * d->W * xl * ebx) % 16 == 0);
+}
+
 // one launch of the plan: the whole batch or one sub-batch of it (`d`: its images).  The caller has checked the operands against
 // the plan: `fast` = they allow the plan's plane kernel (else: the native kernel)
 static int conv2d_fwd_launch(sg_ctx* ctx, hipStream_t st, int dtype, const sg_conv_desc* d, const ConvPlan& pl, bool fast,
@@ -2060,8 +2126,7 @@ static int conv2d_fwd_launch(sg_ctx* ctx, hipStream_t st, int dtype, const sg_co
   IgemmParams p;
   fill_fwd_params(p, d, x, w, bias, y, flags, dt_bytes(dtype));
   if (pl.family == CONV_HEAD) {   // a head that is not a 1x1 convolution: the any-shape kernel, fp32 out
-    const bool vec4 = (d->Cin % 4 == 0) && (p.x_ld % 4 == 0) && (((uintptr_t)x & 7) == 0);
-    return dispatch_igemm_mixed<bf16_t, float>(p, vec4, ctx->num_cus, st);
+    return dispatch_igemm_mixed<bf16_t, float>(p, native_vec_of(dtype, d, false, align_class(x), true), ctx->num_cus, st);
   }
   if (fast) {
     if (!b16 && p.x_ld == d->Cin) p.a_planes = (const unsigned short*)x_planes;
@@ -2074,11 +2139,9 @@ static int conv2d_fwd_launch(sg_ctx* ctx, hipStream_t st, int dtype, const sg_co
     if (pl.npl == 1) return run_x6<1, float>(pl, p, (const float*)w, false, d->Cin, d->Cout, ws, ctx->num_cus, st, prepared);
     return run_x6<3, float>(pl, p, (const float*)w, false, d->Cin, d->Cout, ws, ctx->num_cus, st, prepared);
   }
-  if (b16) {
-    const bool vec4 = (d->Cin % 4 == 0) && (p.x_ld % 4 == 0) && (((uintptr_t)x & 7) == 0);
-    return dispatch_igemm_b16(p, vec4, ctx->num_cus, st);
-  }
-  return dispatch_igemm(p, (d->Cin % 4 == 0) && (p.x_ld % 4 == 0) && (d->Cout % 4 == 0) && aligned16(x) && aligned16(w), ctx->num_cus, st);
+  const bool vec4 = native_vec_of(dtype, d, false, align_class(x), aligned16(w));
+  if (b16) return dispatch_igemm_b16(p, vec4, ctx->num_cus, st);
+  return dispatch_igemm(p, vec4, ctx->num_cus, st);
 }
 
 int sg_conv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* x, const void* w,
@@ -2145,7 +2208,7 @@ int sg_conv2d_fwd(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, c
   // ---- the operands against the plan, once and before anything is written
   const bool prepared = ws_bytes == SG_WS_PREPARED;
   const int ebx = head32 ? 2 : eb, eby = head32 ? 4 : eb;
-  if (pl.family == CONV_THIN && !(aligned16(x) && (pl.nb >= d->N || pl.nb < 1 || ((int64_t)d->H * d->W * xl * ebx) % 16 == 0)))
+  if (pl.family == CONV_THIN && !thin_operands_ok(pl, d, aligned16(x), ebx))
     pl = plan_conv(ctx->num_cus, dtype, d, false, flags | PLAN_NOT_THIN);   // (every sub-batch's x must meet the thin kernels' alignment)
   if (pl.family == CONV_HEAD) SG_CHECK_ARG(pl.nb >= 1, "sg_conv2d_fwd: one image of the softmax head beyond 2 GiB");
   // The fast kernels address their operands through 2 GiB buffer descriptors.  A larger batch is run as sub-batches of whole
@@ -2309,15 +2372,10 @@ static int conv2d_dgrad_launch(sg_ctx* ctx, hipStream_t st, int dtype, const sg_
     hipLaunchKernelGGL(transpose_taps_kernel, grid, dim3(256), 0, st, (const float*)w, wt, d->Cin, d->Cout);
     SG_LAUNCH_CHECK("transpose_taps_kernel");
   }
-  if (pl.family == CONV_HEAD) {   // fp32 dy in, bf16 dx out, any shape
-    const bool vec4 = (d->Cout % 4 == 0) && (p.x_ld % 4 == 0) && aligned16(dy);
-    return dispatch_igemm_mixed<float, bf16_t>(p, vec4, ctx->num_cus, st);
-  }
-  if (b16) {
-    const bool vec4 = (d->Cout % 4 == 0) && (p.x_ld % 4 == 0) && (((uintptr_t)dy & 7) == 0);
-    return dispatch_igemm_b16(p, vec4, ctx->num_cus, st);
-  }
-  return dispatch_igemm(p, (d->Cout % 4 == 0) && (p.x_ld % 4 == 0) && (d->Cin % 4 == 0) && aligned16(dy), ctx->num_cus, st);
+  const bool vec4 = native_vec_of(dtype, d, true, align_class(dy), true);
+  if (pl.family == CONV_HEAD) return dispatch_igemm_mixed<float, bf16_t>(p, vec4, ctx->num_cus, st);   // fp32 dy in, bf16 dx out, any shape
+  if (b16) return dispatch_igemm_b16(p, vec4, ctx->num_cus, st);
+  return dispatch_igemm(p, vec4, ctx->num_cus, st);
 }
 
 int sg_conv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d, const void* dy, const void* w,
@@ -2374,7 +2432,7 @@ int sg_conv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d,
   const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
   const int ebx = head32 ? 2 : eb, eby = head32 ? 4 : eb;   // dx (the forward's x) / dy
   ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, true, flags);
-  if (pl.family == CONV_THIN && !(aligned16(dx) && (pl.nb >= d->N || pl.nb < 1 || ((int64_t)d->H * d->W * xl * ebx) % 16 == 0)))
+  if (pl.family == CONV_THIN && !thin_operands_ok(pl, d, aligned16(dx), ebx))
     pl = plan_conv(ctx->num_cus, dtype, d, true, flags | PLAN_NOT_THIN);   // (every sub-batch's dx must meet the thin kernels' alignment)
   if (pl.family == CONV_HEAD) SG_CHECK_ARG(pl.nb >= 1, "sg_conv2d_dgrad: one image of the softmax head beyond 2 GiB");
   const int nb = (pl.nb >= 1 && pl.nb < d->N) ? pl.nb : d->N;   // sub-batches of whole images: see sg_conv2d_fwd
@@ -2426,8 +2484,113 @@ int sg_conv2d_dgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d,
   return 0;
 }
 
-// alignment class of a pointer, as plan_wgrad takes it
-static int align_class(const void* p) { return aligned16(p) ? 16 : ((reinterpret_cast<uintptr_t>(p) & 7) == 0 ? 8 : 0); }
+// The form of ONE launch of the plan (`d`: its images), for sg_conv2d_plan: the parameter fills of conv2d_fwd_launch /
+// conv2d_dgrad_launch and run_x6, then the very rules the launchers ask (pick_bn, plan_common, igemm_ut_of, x6_var_of, x6_mf16_of,
+// b16_ks, b16_pd_of, x6p_bn_of, native_vec_of).  a_class: the alignment class of the activation operand the kernel reads.
+static sg_conv_launch conv_launch_form(int num_cus, int dtype, const sg_conv_desc* d, const ConvPlan& pl, bool fast, bool dgrad,
+                                       int a_class, bool with_res) {
+  sg_conv_launch f;
+  memset(&f, 0, sizeof(f));
+  const bool b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0;
+  if (pl.family == CONV_THIN) {
+    f.kernel = SG_CK_THIN;
+    f.bn = d->Cout;
+    f.vec = 1;
+    return f;
+  }
+  IgemmParams p;
+  if (!dgrad) fill_fwd_params(p, d, nullptr, nullptr, nullptr, nullptr, 0, dt_bytes(dtype));
+  else fill_dgrad_params(p, d, nullptr, nullptr, nullptr, nullptr, 0, head32 ? 4 : dt_bytes(dtype));
+  if (pl.family == CONV_HEAD || !fast) {
+    const bool vec = native_vec_of(dtype, d, dgrad, a_class, true);
+    f.kernel = SG_CK_NATIVE;
+    f.vec = vec;
+    if (b16) {
+      f.bn = mixed_common(p, num_cus);
+    } else {
+      f.bn = native_common(p, vec, num_cus);
+      f.ut = vec && igemm_ut_of(p);
+    }
+    f.skip_taps = p.skip_taps; f.group_m = p.group_m; f.cb = p.cb;
+    return f;
+  }
+  if (dgrad && pl.perm2) p.perm2 = 1;
+  if (pl.family == CONV_PATCH) {
+    f.kernel = SG_CK_PATCH;
+    f.bn = x6p_bn_of(p.Nout);
+    f.pc = x6p_c_of(p.C);
+    f.pmulti = x6p_multi_of(p.C);
+    return f;
+  }
+  if (pl.family == CONV_WIDE) {
+    f.kernel = SG_CK_WIDE;
+    f.bn = pl.wbn;
+    return f;
+  }
+  slab_fill(p, pl);
+  const SlabKernel sk = slab_kernel_of(pl, b16, with_res);
+  f.bn = slab_common(p, sk, b16 ? 2 : 4, num_cus);
+  switch (sk) {
+    case SLAB_X6W: f.kernel = SG_CK_X6W; f.bn = XW_N; break;
+    case SLAB_B16W: f.kernel = SG_CK_B16W; f.bn = BW_N; break;
+    case SLAB_B16:
+      f.kernel = SG_CK_B16;
+      f.ks = b16_ks(p.C, p.K == p.C);
+      f.pd = b16_pd_of(p);
+      break;
+    default:
+      f.kernel = SG_CK_X6;
+      f.var = x6_var_of(sg_cdiv(p.M, BM) * sg_cdiv(p.Nout, f.bn), num_cus);
+      f.mf16 = pl.npl == 3 && x6_mf16_of(p);
+  }
+  f.vec = 1;
+  f.skip_taps = p.skip_taps; f.group_m = p.group_m; f.cb = p.cb;
+  return f;
+}
+
+int sg_conv2d_plan(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int dgrad, int flags, int aligned, sg_conv_plan* out) {
+  const char* who = dgrad ? "sg_conv2d_dgrad" : "sg_conv2d_fwd";
+  SG_CHECK_ARG(out != nullptr, "sg_conv2d_plan: null out");
+  memset(out, 0, sizeof(*out));
+  SG_CHECK_ARG(aligned == 16 || aligned == 8 || aligned == 0, "sg_conv2d_plan: aligned %d (16, 8 or 0)", aligned);
+  SG_CHECK_ARG((flags & ~(SG_EPI_BIAS | SG_EPI_RELU)) == 0, "sg_conv2d_plan: flags %d (SG_EPI_BIAS, SG_EPI_RELU; the fused up-sampling forms: `up2`)", flags);
+  SG_CHECK_ARG(ctx != nullptr, "%s: null ctx", who);
+  SG_CHECK_ARG(dt_ok(dtype) && !(dtype & SG_X_UP2), "%s: dtype %d", who, dtype);
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  const bool dg = dgrad != 0, b16 = dt_storage(dtype) == SG_BF16, head32 = (dtype & SG_HEAD_F32) != 0;
+  SG_CHECK_ARG(!head32 || (b16 && d->Cout <= 4), "%s: SG_HEAD_F32 needs Cout <= 4 (a softmax head) on bf16 storage", who);
+  if (dg && d->stride != 1 && d->stride != 2) {
+    sg_set_error("sg_conv2d_dgrad: stride %d unsupported (the path uses strides 1 and 2 only)", d->stride);
+    return SG_EUNSUPPORTED;
+  }
+  const int ebx = head32 ? 2 : dt_bytes(dtype);
+  ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, dg, flags);
+  if (pl.family == CONV_THIN && !thin_operands_ok(pl, d, aligned == 16, ebx)) pl = plan_conv(ctx->num_cus, dtype, d, dg, flags | PLAN_NOT_THIN);
+  if (pl.family == CONV_HEAD) SG_CHECK_ARG(pl.nb >= 1, "%s: one image of the softmax head beyond 2 GiB", who);
+  const int nb = (pl.nb >= 1 && pl.nb < d->N) ? pl.nb : d->N;
+  const bool fast = pl.family >= CONV_SLAB && pl.vec && aligned == 16;
+  sg_conv_plan o;
+  memset(&o, 0, sizeof(o));
+  o.family = (int)pl.family;
+  o.fast = fast;
+  o.nb = nb;
+  o.nsub = (int)sg_cdiv(d->N, nb);
+  o.tail_n = d->N - (o.nsub - 1) * nb;
+  o.vec = pl.vec; o.perm2 = pl.perm2; o.npl = pl.npl; o.kd = pl.kd; o.Ck = pl.Ck; o.Ckp = pl.Ckp; o.wbn = pl.wbn;
+  o.x6w_S = pl.x6w_S; o.b16w_S = pl.b16w_S; o.deep = pl.deep;
+  o.res = pl.res; o.bn_in = pl.bn_in; o.up2 = pl.up2; o.bnb = pl.bnb; o.planes_in = pl.planes_in;
+  o.ws_bytes = pl.ws_bytes(nb);
+  sg_conv_desc sub = *d;
+  sub.N = nb;
+  o.main = conv_launch_form(ctx->num_cus, dtype, &sub, pl, fast, dg, aligned, false);
+  // (the entry point's own rule for opts->res: the thin kernels that are not the fp32 head, and fast launches of the slab family)
+  if (dg && pl.res && !head32 && (pl.family == CONV_THIN || fast)) o.with_res = conv_launch_form(ctx->num_cus, dtype, &sub, pl, fast, dg, aligned, true);
+  sub.N = o.tail_n;
+  o.tail = conv_launch_form(ctx->num_cus, dtype, &sub, pl, fast, dg, aligned, false);
+  *out = o;
+  return 0;
+}
 
 // The checks that the two filter-gradient entry points and the plan query share, then the plan.  ax / ay: alignment class of x / dy.
 static int wgrad_plan_checked(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int ax, int ay, bool planes, const char* who, WgradPlan* pl) {
@@ -2658,7 +2821,10 @@ int sg_conv2d_caps(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int dgra
   SG_CHECK_ARG(ctx && d && out && dt_ok(dtype), "sg_conv2d_caps: bad argument");
   memset(out, 0, sizeof(*out));
   if (check_desc(d, "sg_conv2d_caps")) return 0;   // a descriptor no launch takes: no option either (the launch says why)
-  const ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, dgrad != 0, 0);
+  ConvPlan pl = plan_conv(ctx->num_cus, dtype, d, dgrad != 0, 0);
+  // (aligned pointers assumed; a thin launch in sub-batches whose images are no multiple of 16 bytes leaves the family for any pointer)
+  if (pl.family == CONV_THIN && !thin_operands_ok(pl, d, true, (dtype & SG_HEAD_F32) ? 2 : dt_bytes(dtype)))
+    pl = plan_conv(ctx->num_cus, dtype, d, dgrad != 0, PLAN_NOT_THIN);
   out->thin = pl.family == CONV_THIN;
   out->planes_in = pl.planes_in;
   // (the filter gradient has no direction)

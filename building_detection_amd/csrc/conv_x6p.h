@@ -641,6 +641,12 @@ int launch_x6p(const IgemmParams& p, int num_cus, hipStream_t st) {
   return 0;
 }
 
+// the patch kernel's tile width for N output columns (run_x6p and the plan query, sg_conv2d_plan); its <C, MULTI> follow from the
+// tap depth alone: 32 -> <32>, 64 -> <64>, more -> <64, MULTI> (chunks of 64)
+inline int x6p_bn_of(int N) { return N >= 128 ? 128 : N; }
+inline int x6p_c_of(int C) { return C == 32 ? 32 : 64; }
+inline bool x6p_multi_of(int C) { return C > 64; }
+
 // split the weights fragment-major (in `ws`, x6_planes_bytes() is enough) and run the patch kernel
 int run_x6p(IgemmParams& p, const float* w, bool dgrad, int Cin, int Cout, void* ws, int num_cus, hipStream_t st,
             bool prepared = false) {
@@ -656,13 +662,13 @@ int run_x6p(IgemmParams& p, const float* w, bool dgrad, int Cin, int Cout, void*
       hipLaunchKernelGGL(split3_weights_frag_kernel, grid, dim3(256), 0, st, w, (unsigned short*)ws, K, N, Cout, Cin * Cout, 1, Cout);
     SG_LAUNCH_CHECK("split3_weights_frag_kernel");
   }
-  const int bn = N >= 128 ? 128 : N;
-  if (p.C == 32) {
+  const int bn = x6p_bn_of(N);
+  if (x6p_c_of(p.C) == 32) {
     if (bn == 32) return launch_x6p<32, 32>(p, num_cus, st);
     if (bn == 64) return launch_x6p<32, 64>(p, num_cus, st);
     return launch_x6p<32, 128>(p, num_cus, st);
   }
-  if (p.C > 64) {   // 128 / 256 / ... reduction channels per tap: chunks of 64
+  if (x6p_multi_of(p.C)) {   // 128 / 256 / ... reduction channels per tap: chunks of 64
     if (bn == 32) return launch_x6p<64, 32, false, true>(p, num_cus, st);
     if (bn == 64) return launch_x6p<64, 64, false, true>(p, num_cus, st);
     return launch_x6p<64, 128, false, true>(p, num_cus, st);

@@ -367,6 +367,14 @@ class Engine:
         check(self.lib.sg_conv2d_wgrad_plan(self.h, dt, C.byref(d), int(aligned), 1 if planes else 0, C.byref(pl)), "sg_conv2d_wgrad_plan")
         return pl
 
+    def conv2d_plan(self, d: ConvDesc, dt=SG_F32, dgrad=False, flags=0, aligned=16) -> _lib.ConvPlan:
+        """The plan the forward (dgrad: the input gradient) of convolution `d` runs by and the kernel form of each of its launches
+        (sg_conv2d_plan; read-only).  flags: SG_EPI_BIAS | SG_EPI_RELU; aligned: 16, 8 or 0, the alignment of the activation
+        operands in bytes.  _lib.conv_form_name() spells a launch."""
+        pl = _lib.ConvPlan()
+        check(self.lib.sg_conv2d_plan(self.h, dt, C.byref(d), 1 if dgrad else 0, int(flags), int(aligned), C.byref(pl)), "sg_conv2d_plan")
+        return pl
+
     def conv2d_bn_in_ok(self, d: ConvDesc, dtype=torch.float32) -> bool:
         """Can the launches of convolution `d` apply a BatchNormalization(+ReLU) to their input themselves (bn_in of conv2d_fwd /
         conv2d_wgrad: the thin 1x1 and the patch kernels, fp32 storage)?"""

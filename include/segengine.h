@@ -180,6 +180,56 @@ int sg_conv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* d,
 typedef struct sg_conv_caps { int thin, bn_in, up2, bnb, planes_in, wgrad_planes; } sg_conv_caps;
 int sg_conv2d_caps(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int dgrad, sg_conv_caps* out);
 
+/* The plan one forward (dgrad = 0) or input-gradient (dgrad = 1) call runs by, and the kernel form each of its launches takes
+ * (csrc/conv_igemm.hip: plan_conv, which the launches, the workspace queries, sg_conv2d_caps and sg_conv2d_planes_job read too, and
+ * the small rules the launchers ask at launch time - the query asks the same functions).  For this storage type (SG_HEAD_F32
+ * included), these `flags` (SG_EPI_*), the current arithmetic switch and the experiment switches.  Read-only: nothing is launched.
+ * aligned: 16 - every operand is 16-byte aligned and the call brings the workspace of sg_conv2d_*_ws_bytes; 8 / 0 - the activation
+ * operands (x; dgrad: dy and dx) are 8-byte aligned / neither, everything else as for 16.
+ *   family      SG_CF_* : plan_conv's family (what sg_conv2d_planes_job's kind and sg_conv2d_caps.thin are read from)
+ *   fast        1: the operands allow the family's plane kernel; 0 with family >= SG_CF_SLAB: the launches take the native kernel
+ *   nb, nsub, tail_n   images per launch, launches, images of the last one (nsub = 1: the whole batch in one launch)
+ *   vec, perm2, npl, kd, Ck, Ckp, wbn, x6w_S, b16w_S, deep, res, bn_in, up2, bnb, planes_in   ConvPlan's fields of these names
+ *   ws_bytes    weight planes + scratch of one launch of nb images (what a fast launch checks opts->ws_bytes against)
+ * Per launch (main: the whole batch or a full sub-batch; tail: the last sub-batch; with_res: main when opts->res is given - all-zero
+ * where the call refuses res):
+ *   kernel      SG_CK_NATIVE  igemm_conv_kernel            SG_CK_THIN  thin_fwd_kernel / thin_dgrad_kernel
+ *               SG_CK_X6      conv_x6_kernel               SG_CK_B16   conv_b16_kernel
+ *               SG_CK_X6W     conv_x6w_kernel              SG_CK_B16W  conv_b16w_kernel
+ *               SG_CK_PATCH   conv_x6p_kernel              SG_CK_WIDE  pw_wide_kernel
+ *   bn          tile width: 32 / 64 / 128 (native, x6, b16, patch), 256 (x6w, b16w), wbn (wide); thin: Cout
+ *   vec, ut     native: 16-byte (bf16: 8-byte) channel runs; the wave-uniform-tap form of the vector kernel
+ *   var, mf16   x6: structure (1 = double-buffered, one workgroup per CU; 0 = two single-buffered per CU), 16x16x32 products
+ *   ks, pd      b16: k-steps per slab (2 / 4), prefetched register sets (1 / 2)
+ *   skip_taps, group_m, cb   IgemmParams' fields of these names as the launch sets them
+ *   pc, pmulti  patch: the kernel's <C> (32 / 64) and its MULTI form (chunks of 64 channels)
+ * An input the entry point would refuse answers all-zero with the entry point's error code. */
+#define SG_CF_NATIVE 0
+#define SG_CF_THIN 1
+#define SG_CF_HEAD 2
+#define SG_CF_SLAB 3
+#define SG_CF_PATCH 4
+#define SG_CF_WIDE 5
+#define SG_CK_NATIVE 1
+#define SG_CK_THIN 2
+#define SG_CK_X6 3
+#define SG_CK_B16 4
+#define SG_CK_X6W 5
+#define SG_CK_B16W 6
+#define SG_CK_PATCH 7
+#define SG_CK_WIDE 8
+typedef struct sg_conv_launch {
+  int kernel, bn, vec, ut, var, mf16, ks, pd, skip_taps, group_m, cb, pc, pmulti;
+} sg_conv_launch;
+typedef struct sg_conv_plan {
+  sg_conv_launch main, tail, with_res;
+  int family, fast, nb, nsub, tail_n;
+  int vec, perm2, npl, kd, Ck, Ckp, wbn, x6w_S, b16w_S, deep;
+  int res, bn_in, up2, bnb, planes_in;
+  size_t ws_bytes;
+} sg_conv_plan;
+int sg_conv2d_plan(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, int dgrad, int flags, int aligned, sg_conv_plan* out);
+
 /* opts->bn_in: a training- or inference-mode BatchNormalization (+ReLU) applied to the convolution's INPUT while the kernel loads
  * it (round 5): the normalised tensor between `BatchNormalization -> [ReLU] -> Conv2D` (conv_bn_relu chains,
  * train_model/DeepLabv3plus.py:424-429, 476-480: the 512 x 512 x 32 tensors in front of the decoder's last 3x3 convolution and of

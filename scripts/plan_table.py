@@ -12,6 +12,9 @@ entry, and a value that is the same at every batch is printed once.
 Behind those lines, the filter gradients: one line per (head, descriptor without N) with the batch sizes and, per arithmetic, the
 plan sg_conv2d_wgrad_plan answers at 16-byte alignment - what plan_wgrad() (csrc/conv_igemm.hip) decides -, the storage-blind
 sg_conv2d_wgrad_ws_bytes and the plan of sg_conv2d_wgrad_planes where it covers the layer.
+Behind those, the kernel forms: one line per (direction, head, descriptor without N) and, per arithmetic, the name of the form the
+launch takes at 16-byte alignment (sg_conv2d_plan, _lib.conv_form_name: kernel, tile width, structure and the launch-time choices of
+the dispatchers), `res>` the form of the same launch with a collected gradient where that is another one, and the plan's workspace.
 Use: python scripts/plan_table.py > profiles/plan_table.txt"""
 import collections
 import ctypes as C
@@ -78,6 +81,60 @@ def wgrad_rows():
                         f"sup{pl.up2}{pl.bn_in} pin {pin}")
                 out.append(("b16" if mode is None else f"x{mode}", s.head, dict(zip(PS.desc_fields(), s.desc)), txt))
     return out
+
+
+def form_rows():
+    """(arith, dgrad, head, desc fields, form text) of every unique site under every arithmetic mode (needs the GPU)"""
+    import _plane_sites as PS
+    from building_detection_amd import _lib
+    from building_detection_amd.ops import get_engine
+    e = get_engine(0)
+    uniq, _ = PS.unique_sites(PS.enumerate_groups())
+    out = []
+    for mode in (0, 1, 2, None):
+        with PS.mode_set(e, mode):
+            for s in uniq.values():
+                if mode not in PS.modes_of(s.policy):
+                    continue
+                d = PS.make_desc(s)
+                dt = PS.abi_dtype(s)
+                pl = e.conv2d_plan(d, dt, dgrad=bool(s.dgrad))
+                txt = _lib.conv_form_name(pl, pl.main, bool(s.dgrad), dt)
+                if pl.nsub > 1 and pl.tail_n != pl.nb:
+                    tail = _lib.conv_form_name(pl, pl.tail, bool(s.dgrad), dt)
+                    txt += f" tail>{tail}" if tail != txt else ""
+                if pl.with_res.kernel:
+                    r = _lib.conv_form_name(pl, pl.with_res, bool(s.dgrad), dt)
+                    txt += f" res>{r}" if r != txt else ""
+                txt += f" ws{pl.ws_bytes}"
+                out.append(("b16" if mode is None else f"x{mode}", s.dgrad, s.head, dict(zip(PS.desc_fields(), s.desc)), txt))
+    return out
+
+
+def fold_forms(rs):
+    table = collections.OrderedDict()   # line -> arithmetic -> batch -> form text
+    for arith, dgrad, head, f, txt in rs:
+        key = (f"form {'dgrad' if dgrad else 'fwd'}{' head' if head else ''} {f['H']}x{f['W']}x{f['Cin']}>{f['Cout']} "
+               f"k{f['KH']}s{f['stride']}d{f['dilation']} o{f['Ho']}x{f['Wo']}")
+        table.setdefault(key, collections.OrderedDict()).setdefault(arith, {})[f["N"]] = txt
+    lines = [f"# kernel forms: {len(rs)} (site, storage, mode, direction) plans on {len(table)} lines",
+             "# form <direction> [head] HxWxCin>Cout k<K>s<stride>d<dilation> o<Ho>x<Wo> b<batch sizes>",
+             "#   | <arithmetics with equal forms>: [b<batches>:] <form name of the main launch> [tail><last sub-batch's>] "
+             "[res><with a collected gradient>] ws<plan.ws_bytes> ; ..."]
+    for key, ariths in table.items():
+        batches = sorted({b for per in ariths.values() for b in per})
+        line = f"{key} b{','.join(map(str, batches))}"
+        texts = collections.OrderedDict()
+        for arith, per in ariths.items():
+            by = collections.OrderedDict()
+            for b in sorted(per):
+                by.setdefault(per[b], []).append(b)
+            parts = [(f"b{','.join(map(str, bs))}: " if (len(by) > 1 or sorted(per) != batches) else "") + t for t, bs in by.items()]
+            texts.setdefault("; ".join(parts), []).append(arith)
+        for txt, names in texts.items():
+            line += f" | {','.join(names)}: {txt}"
+        lines.append(line)
+    return lines
 
 
 def fold_wgrad(rs):
@@ -147,4 +204,4 @@ def fold(n_unique, rs):
 
 
 if __name__ == "__main__":
-    print("\n".join(fold(*rows()) + fold_wgrad(wgrad_rows())))
+    print("\n".join(fold(*rows()) + fold_wgrad(wgrad_rows()) + fold_forms(form_rows())))

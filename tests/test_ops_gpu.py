@@ -91,6 +91,54 @@ CONV_CASES = [
     (1, 64, 64, 3, 64, 7, 2, 1, "stem7_s2_w32"),
     (2, 32, 32, 3, 64, 3, 1, 1, "stem_s1_w32"),
 ]
+# Which kernel form each tag takes (fp32 storage, default arithmetic, 256 CUs: forward / input gradient), as the mirror of the dispatch
+# rules in tests/_conv_cases.py names it (DESIGN.md, appendix "convolution form names").  A comment: nothing here asserts it, and the
+# list reaches no v0 structure, no BN128 tile, no gm8 and no native vec / ut form; tests/test_conv_forms_gpu.py runs every form by name.
+#   aspp_d6: fwd.slab.x6w.S2.skip.cb4 / dgrad.slab.x6w.S1.skip.gm16
+#   aspp_d12: fwd.slab.x6w.S2.skip.cb4 / dgrad.slab.x6w.S1.skip.gm16
+#   aspp_d18: fwd.slab.x6w.S2.skip.cb4 / dgrad.slab.x6w.S1.skip.gm16
+#   sk_d6: fwd.slab.x6.BN64.v1.mf16.skip.gm16 / dgrad.slab.x6.BN64.v1.mf16.skip.gm16
+#   pw_728: fwd.slab.x6.BN64.v1.gm16 / dgrad.slab.x6.BN64.v1.gm16
+#   stem_s2: fwd.native.BN32.scalar / dgrad.native.BN32.scalar
+#   odd_s2: fwd.slab.x6.BN64.v1.mf16 / dgrad.slab.x6.BN64.v1.mf16
+#   short_1x1_s2: fwd.slab.x6.BN64.v1 / dgrad.slab.x6.BN64.v1.skip.perm2.gm16
+#   bam_d4_c45: fwd.native.BN64.scalar.skip / dgrad.native.BN64.scalar.skip
+#   sse_cout1: fwd.thin.CO1.f32 / dgrad.thin.CO1.f32
+#   head_cout2: fwd.thin.CO2.f32 / dgrad.thin.CO2.f32
+#   res34_head: fwd.native.BN32.scalar / dgrad.native.BN64.scalar
+#   cout96: fwd.slab.x6.BN64.v1.mf16 / dgrad.slab.x6.BN64.v1.mf16.gm16
+#   gap_1x1: fwd.slab.x6.BN32.v1 / dgrad.slab.x6.BN64.v1.gm16
+#   thin_sse_ragged: fwd.thin.CO1.f32 / dgrad.thin.CO1.f32
+#   thin_c48_cout2: fwd.thin.CO2.f32 / dgrad.thin.CO2.f32
+#   thin_c256_cout3: fwd.thin.CO3.f32 / dgrad.thin.CO3.f32
+#   thin_c728_cout4: fwd.thin.CO4.f32 / dgrad.thin.CO4.f32
+#   wgrad_aligned_pw_ragged: fwd.slab.x6.BN64.v1 / dgrad.slab.x6.BN64.v1.gm16
+#   wgrad_aligned_3x3_d2: fwd.slab.x6.BN64.v1.mf16.skip / dgrad.slab.x6.BN64.v1.mf16.skip
+#   x6_wgrad_c32: fwd.patch.C32.BN32 / dgrad.patch.C32.BN32
+#   x6_wgrad_c64_cout48: fwd.slab.x6.BN64.v1.mf16 / dgrad.slab.x6.BN64.v1.mf16.vpad
+#   x6_wgrad_c48_d3: fwd.slab.x6.BN64.v1.mf16.skip.vpad / dgrad.slab.x6.BN64.v1.mf16.skip.vpad
+#   patch_chunks_128_to_64: fwd.patch.C64m.BN64 / dgrad.patch.C64.BN128
+#   patch_chunks_256_to_128: fwd.patch.C64m.BN128 / dgrad.patch.C64m.BN128
+#   patch_chunks_dgrad_128: fwd.patch.C64.BN128 / dgrad.patch.C64m.BN64
+#   patch_chunks_128_to_32: fwd.patch.C64m.BN32 / dgrad.patch.C32.BN128
+#   patch_chunks_256_to_32: fwd.patch.C64m.BN32 / dgrad.patch.C32.BN128
+#   patch_chunks_512_to_64: fwd.patch.C64m.BN64 / dgrad.patch.C64.BN128
+#   patch_c32_n32: fwd.patch.C32.BN32 / dgrad.patch.C32.BN32
+#   patch_c64_n64: fwd.patch.C64.BN64 / dgrad.patch.C64.BN64
+#   patch_c64_n32: fwd.patch.C64.BN32 / dgrad.patch.C32.BN64
+#   patch_c32_n64_one_tile: fwd.patch.C32.BN64 / dgrad.patch.C64.BN32
+#   patch_c64_n128: fwd.patch.C64.BN128 / dgrad.patch.C64m.BN64
+#   patch_c32_n256: fwd.patch.C32.BN128 / dgrad.patch.C64m.BN32
+#   wpatch_c64_n32_576_tiles: fwd.patch.C64.BN32 / dgrad.patch.C32.BN64
+#   wpatch_c32_n32_h20: fwd.slab.x6.BN32.v1.mf16 / dgrad.slab.x6.BN32.v1.mf16
+#   wpatch_c32_n64: fwd.slab.x6.BN64.v1.mf16 / dgrad.slab.x6.BN32.v1.mf16
+#   wpatch_c64_n64: fwd.slab.x6.BN64.v1.mf16 / dgrad.slab.x6.BN64.v1.mf16
+#   x6_wgrad_s2_3x3: fwd.slab.x6.BN64.v1.mf16 / dgrad.slab.x6.BN64.v1.mf16.skip.perm2
+#   x6_wgrad_s2_1x1: fwd.slab.x6.BN64.v1.gm16 / dgrad.slab.x6.BN64.v1.skip.perm2
+#   x6_wgrad_s2_odd_h: fwd.slab.x6.BN64.v1.mf16 / dgrad.slab.x6.BN32.v1.mf16.vpad
+#   stem_s2_w32: fwd.native.BN32.scalar / dgrad.native.BN32.scalar
+#   stem7_s2_w32: fwd.native.BN64.scalar / dgrad.native.BN32.scalar
+#   stem_s1_w32: fwd.native.BN64.scalar / dgrad.native.BN32.scalar
 
 
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[-1] for c in CONV_CASES])

@@ -320,6 +320,9 @@ _SIGNATURES = {
     "sg_objects_label": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _i, _vp]),
     "sg_objects_overlap_ws_bytes": (_sz, [_i64]),
     "sg_objects_overlap": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp, _vp]),
+    "sg_object_distances_ws_bytes": (_sz, [_i, _i, _i]),
+    "sg_object_distances": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
+    "sg_separation_weights": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _f, _vp]),
     "sg_u8_to_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _f, _f]),
     "sg_cast": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp]),
     "sg_fill_f32": (_i, [_vp, _vp, _vp, _i64, _f]),

@@ -128,7 +128,8 @@ def _augment_sources(engine, rgb_u8, gray_u8, entries, slot):
     return engine.augment_u8(rgb_u8, xi, IMAGE_FILL), engine.augment_u8(gray_u8, li, LABEL_FILL)
 
 
-def device_augment_gen(img_path, lab_path, BATCH_SIZE, engine, seed=0, redraw=False, depth: int = 2, workers: int = 4):
+def device_augment_gen(img_path, lab_path, BATCH_SIZE, engine, seed=0, redraw=False, depth: int = 2, workers: int = 4,
+                       separation=None):
     """device_data_gen over the reference's augmented folder, without writing it: the (image, label) pairs sorted and zipped
     as train_data_gen pairs them, the virtual stream of `plan` cycled.  Per batch every distinct source is decoded once
     (`workers` threads, `depth` batches ahead), crosses PCIe as pinned uint8 and is expanded on the device (sg_augment_u8,
@@ -136,8 +137,12 @@ def device_augment_gen(img_path, lab_path, BATCH_SIZE, engine, seed=0, redraw=Fa
     (sg_edge_labels).  Yields device tensors x float32 [N,512,512,3], y float32 [N,512,512,4], bit-identical to
     train_data_gen over the folder Data_Enhance would write with the same seed.
     redraw=False repeats that one folder (the reference); redraw=True draws a fresh plan for every cycle, continuing the
-    same random.Random(seed) sequence (online augmentation)."""
+    same random.Random(seed) sequence (online augmentation).
+    separation=(w0, sigma): Engine.edge_labels adds the separation weight of narrow gaps to f_edge, as in device_data_gen."""
     import torch
+    if separation is not None:
+        from .data import check_separation
+        separation = check_separation(separation)
     from concurrent.futures import ThreadPoolExecutor
     images, label = img_path, lab_path
     images.sort()  # in place, as train_data_gen does
@@ -174,7 +179,7 @@ def device_augment_gen(img_path, lab_path, BATCH_SIZE, engine, seed=0, redraw=Fa
             ld = lb.to(engine.device, non_blocking=True)
             xa, la = _augment_sources(engine, xd, ld, batch, slot)
             x = engine.u8_to_f32(xa, 127.5, 1.0)
-            y = engine.edge_labels(engine.u8_to_f32(la, 255.0, 0.0))
+            y = engine.edge_labels(engine.u8_to_f32(la, 255.0, 0.0), separation=separation)
             yield x, y
     finally:
         feed.close()

@@ -27,6 +27,44 @@ def edge_weight_channels(mask: np.ndarray):
     return f_edge, p_edge
 
 
+def check_separation(separation):
+    """`separation=(w0, sigma)` of the generators and Engine.edge_labels -> (float w0, float sigma); w0 >= 0, sigma > 0, finite."""
+    try:
+        w0, sigma = (float(v) for v in separation)
+    except (TypeError, ValueError):
+        raise ValueError(f"separation = {separation!r}: expected (w0, sigma)") from None
+    if not (np.isfinite(w0) and np.isfinite(sigma) and w0 >= 0.0 and sigma > 0.0):
+        raise ValueError(f"separation = ({w0}, {sigma}): w0 >= 0 and sigma > 0, both finite")
+    return w0, sigma
+
+
+def separation_term(mask: np.ndarray, w0: float = 10.0, sigma: float = 5.0) -> np.ndarray:
+    """The U-Net border weight (Ronneberger et al. 2015) of a binary building mask [H,W] (non-zero = building), float64:
+    w0 * exp(-(d1 + d2)^2 / (2 sigma^2)) on background pixels, d1 / d2 the Euclidean distances in pixels to the nearest and the
+    second-nearest distinct building (8-connected, as findContours and the clean-up count buildings); 0 on buildings and
+    where the tile holds fewer than two.  The term is large only in narrow gaps between two buildings.  It is ADDED to
+    f_edge (channel 2 of y), which edge_focal_loss multiplies into its background term.  One distance_transform_edt per
+    building: the host definition of sg_object_distances + sg_separation_weights (Engine.edge_labels(separation=...))."""
+    from scipy import ndimage
+    w0, sigma = check_separation((w0, sigma))
+    m = np.asarray(mask) != 0
+    if m.ndim != 2:
+        raise ValueError(f"separation_term: a mask is [H, W], got {m.shape}")
+    lab, n = ndimage.label(m, structure=np.ones((3, 3), np.int8))
+    out = np.zeros(m.shape, np.float64)
+    if n < 2:
+        return out
+    d1 = np.full(m.shape, np.inf)
+    d2 = np.full(m.shape, np.inf)
+    for k in range(1, n + 1):
+        d = ndimage.distance_transform_edt(lab != k)
+        d2 = np.minimum(d2, np.maximum(d1, d))
+        d1 = np.minimum(d1, d)
+    bg = ~m
+    out[bg] = w0 * np.exp(-((d1[bg] + d2[bg]) ** 2) / (2.0 * sigma * sigma))
+    return out
+
+
 def class_edge_weights(class_map: np.ndarray, num_classes: int) -> np.ndarray:
     """[H,W] integer class map -> [H,W,C] edge weights: w_c = 2 where the pixel is of class c and its 11 x 11 in-image window
     (five 3 x 3 iterations) holds a pixel of another class, else 1.  At C = 2 this is (f_edge, p_edge) of

@@ -25,7 +25,7 @@ import threading
 
 import numpy as np
 
-from .data import edge_weight_channels
+from .data import check_separation, edge_weight_channels, separation_term
 
 SIZE = 512  # the reference resizes every tile and label to 512 x 512 (`:35`, `:45`)
 
@@ -101,7 +101,7 @@ def to_categorical(label: np.ndarray, num_classes: int = 2) -> np.ndarray:
     return out
 
 
-def _sample(img, seg, label_smooth, loss, engine):
+def _sample(img, seg, label_smooth, loss, engine, separation=None):
     image = decode_img(img)
     label = decode_lbel(seg)
     one_hot = to_categorical(label, num_classes=2)
@@ -112,14 +112,26 @@ def _sample(img, seg, label_smooth, loss, engine):
         lab2 = np.squeeze(label)
         if engine is not None:  # the same four channels from the GPU kernel (one-hot of label == 1, f_edge, p_edge)
             import torch
-            y = engine.edge_labels(torch.from_numpy(np.ascontiguousarray(lab2[None])).to(engine.device))
+            y = engine.edge_labels(torch.from_numpy(np.ascontiguousarray(lab2[None])).to(engine.device), separation=separation)
             return image, y[0].cpu().numpy().astype(np.float64)
         f_edge, p_edge = edge_weight_channels(lab2)
+        if separation is not None:  # buildings = the pixels of class 1 (label == 1.0), as on the device
+            f_edge = f_edge + separation_term(lab2 == 1.0, *separation)
         one_hot = np.concatenate((one_hot, f_edge[..., np.newaxis], p_edge[..., np.newaxis]), axis=-1)  # float64, as there
     return image, one_hot
 
 
-def _gen(img_path, lab_path, BATCH_SIZE, label_smooth, loss, engine):
+def _gen_separation(separation, loss):
+    """The generators' `separation` keyword, checked when the generator is made (not at its first next())."""
+    if separation is None:
+        return None
+    separation = check_separation(separation)
+    if loss != "edge_focal_loss":
+        raise ValueError(f"separation = {separation}: the term is added to f_edge, which only loss='edge_focal_loss' yields")
+    return separation
+
+
+def _gen(img_path, lab_path, BATCH_SIZE, label_smooth, loss, engine, separation=None):
     images, label = img_path, lab_path
     images.sort()  # in place, as the reference does to its caller's lists
     label.sort()
@@ -128,22 +140,24 @@ def _gen(img_path, lab_path, BATCH_SIZE, label_smooth, loss, engine):
         x_train, y_train = [], []
         for _ in range(BATCH_SIZE):
             img, seg = next(zipped)
-            x, y = _sample(img, seg, label_smooth, loss, engine)
+            x, y = _sample(img, seg, label_smooth, loss, engine, separation)
             x_train.append(x)
             y_train.append(y)
         yield np.array(x_train), np.array(y_train)
 
 
-def train_data_gen(img_path, lab_path, BATCH_SIZE, label_smooth=False, loss="edge_focal_loss", engine=None):
+def train_data_gen(img_path, lab_path, BATCH_SIZE, label_smooth=False, loss="edge_focal_loss", engine=None, separation=None):
     """`DeepLabv3plus.py:53-107`: endless generator of (x float32 [N,512,512,3], y [N,512,512,4] float64 with
     loss="edge_focal_loss", else [N,512,512,2] float32) over the sorted, cycled (image, label) pairs.
-    `engine` (an `ops.Engine`, not in the reference): build the label channels with the GPU kernel."""
-    return _gen(img_path, lab_path, BATCH_SIZE, label_smooth, loss, engine)
+    `engine` (an `ops.Engine`, not in the reference): build the label channels with the GPU kernel.
+    `separation=(w0, sigma)` (not in the reference): add the U-Net border weight of narrow gaps between two buildings to
+    f_edge (data.separation_term; with `engine` on the GPU).  Bad parameters raise ValueError here, not at the first next()."""
+    return _gen(img_path, lab_path, BATCH_SIZE, label_smooth, loss, engine, _gen_separation(separation, loss))
 
 
-def val_data_gen(img_path, lab_path, BATCH_SIZE, label_smooth=False, loss="edge_focal_loss", engine=None):
+def val_data_gen(img_path, lab_path, BATCH_SIZE, label_smooth=False, loss="edge_focal_loss", engine=None, separation=None):
     """`DeepLabv3plus.py:110-153`: the same generator over the validation lists."""
-    return _gen(img_path, lab_path, BATCH_SIZE, label_smooth, loss, engine)
+    return _gen(img_path, lab_path, BATCH_SIZE, label_smooth, loss, engine, _gen_separation(separation, loss))
 
 
 # ---- not in the reference: a non-blocking feed for the GPU -------------------------------------------------------------------
@@ -230,7 +244,7 @@ def _decode_u8(img, seg, resize=True):
     return rgb, gray
 
 
-def device_data_gen(img_path, lab_path, BATCH_SIZE, engine, depth: int = 2, workers: int = 4):
+def device_data_gen(img_path, lab_path, BATCH_SIZE, engine, depth: int = 2, workers: int = 4, separation=None):
     """train_data_gen for the GPU (loss="edge_focal_loss"): the same sorted, cycled (image, label) pairs, but
       * files are decoded by `workers` threads, `depth` batches ahead of the consumer (Prefetcher),
       * the batch crosses PCIe as uint8 pixels (a quarter of the fp32 bytes), from pinned memory,
@@ -239,8 +253,11 @@ def device_data_gen(img_path, lab_path, BATCH_SIZE, engine, depth: int = 2, work
       * normalisation (`/ 127.5 - 1`, `/ 255`: sg_u8_to_f32) and the four label channels (sg_edge_labels) run on the device.
     Yields DEVICE tensors (x float32 [N,512,512,3], y float32 [N,512,512,4]) that `fit_generator` / `train_on_batch` take as
     they are; values are bit-identical to train_data_gen's (tests/test_pipeline_gpu.py).  y is float32 where the reference
-    yields float64: Keras casts y_true to y_pred's float32 before the loss anyway."""
+    yields float64: Keras casts y_true to y_pred's float32 before the loss anyway.
+    separation=(w0, sigma): Engine.edge_labels adds the separation weight of narrow gaps to f_edge (train_data_gen's keyword)."""
     import torch
+    if separation is not None:
+        separation = check_separation(separation)
     from concurrent.futures import ThreadPoolExecutor
     images, label = img_path, lab_path
     images.sort()
@@ -269,7 +286,7 @@ def device_data_gen(img_path, lab_path, BATCH_SIZE, engine, depth: int = 2, work
                 xd = engine.resize_linear_u8(xd, SIZE, SIZE)
                 ld = engine.resize_linear_u8(ld, SIZE, SIZE)
             x = engine.u8_to_f32(xd, 127.5, 1.0)
-            y = engine.edge_labels(engine.u8_to_f32(ld, 255.0, 0.0))
+            y = engine.edge_labels(engine.u8_to_f32(ld, 255.0, 0.0), separation=separation)
             yield x, y
     finally:
         feed.close()

@@ -1,6 +1,7 @@
 """Per-building evaluation of a scene: how many true buildings were found, how many predicted ones are real, by size.
 
     label(map, connectivity=8)         -> (labels i32 device tensor, object table numpy [n, 8])      sg_objects_label
+    distances(map, connectivity=8)     -> (d1sq, d2sq) i32 device tensors: squared distance to the two nearest objects  sg_object_distances
     overlaps(labels_a, labels_b)       -> numpy [n_pairs, 3] = (a, b, intersection px), sorted         sg_objects_overlap
     match(pairs, table_pred, table_truth, iou=0.5, ...)   greedy IoU matching, exact integers (host)
     ObjectScores(iou=0.5, bins=...)    accumulator over scenes: .update(pred, truth), .result()
@@ -73,6 +74,30 @@ def label(map, connectivity: int = 8, engine=None, max_objs: int = 1 << 14):
                 break
             max_objs = _pow2_at_least(n)
         return labels, table[:n].cpu().numpy()
+
+
+def distances(map, connectivity: int = 8, second: bool = True, engine=None):
+    """label(map, connectivity), then the exact squared Euclidean distance of every pixel to the nearest object (d1sq, 0 on an
+    object) and to the nearest object other than that one (d2sq): int32 device tensors [H, W], 0x7fffffff where there is no
+    such object.  second=False -> (d1sq, None): the plain exact distance transform of the map's background.  On a class map
+    the objects are the regions of equal value, as for label."""
+    import torch
+    from .ops import get_engine
+    if connectivity not in (4, 8):
+        raise ValueError(f"objects.distances: connectivity {connectivity} (4 or 8)")
+    eng = engine or get_engine(0)
+    m = _dev_map(map, eng)
+    h, w = m.shape
+    lib = eng.lib
+    with eng.lock:
+        ws = torch.empty(lib.sg_objects_label_ws_bytes(h, w), dtype=torch.uint8, device=eng.device)
+        labels = torch.empty(h, w, dtype=torch.int32, device=eng.device)
+        row = torch.empty(1, 8, dtype=torch.int32, device=eng.device)   # labels are written whatever max_objs is: the table
+        count = torch.empty(1, dtype=torch.int32, device=eng.device)    # and the count are never read
+        _lib.check(lib.sg_objects_label(eng.h, eng.stream, h, w, C.c_void_p(m.data_ptr()), 1 if connectivity == 8 else 0,
+                                        C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(labels.data_ptr()),
+                                        C.c_void_p(row.data_ptr()), 1, C.c_void_p(count.data_ptr())), "sg_objects_label")
+        return eng.object_distances(labels, second=second)
 
 
 def overlaps(labels_a, labels_b, engine=None, slots: int = 1 << 12):

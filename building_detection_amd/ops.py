@@ -1031,13 +1031,64 @@ class Engine:
         check(self.lib.sg_adam_step(self.h, self.stream, w.numel(), _ptr(w), _ptr(m), _ptr(v), _ptr(g), float(lr_t), beta1,
                                     beta2, eps, float(grad_scale)), "sg_adam_step")
 
-    def edge_labels(self, label, iterations=5):
-        """label [N,H,W] float (gray/255) -> y_true [N,H,W,4] as train_data_gen builds it (DeepLabv3plus.py:70-100)."""
+    def edge_labels(self, label, iterations=5, separation=None):
+        """label [N,H,W] float (gray/255) -> y_true [N,H,W,4] as train_data_gen builds it (DeepLabv3plus.py:70-100).
+        separation=(w0, sigma) (not in the reference) adds the U-Net border weight w0 * exp(-(d1 + d2)^2 / (2 sigma^2)) to
+        f_edge (channel 2) on background pixels: the buildings of every image (label == 1.0, the pixels with fg = 1) are
+        labelled 8-connected (sg_objects_label), d1 / d2 are the distances to the two nearest distinct ones
+        (sg_object_distances, sg_separation_weights; data.separation_term is the host definition).  No host read in between."""
         _chk(label, "label")
         n, h, w = label.shape
+        if separation is not None:
+            from .data import check_separation
+            separation = check_separation(separation)
         y = self.empty(n, h, w, 4)
         check(self.lib.sg_edge_labels(self.h, self.stream, n, h, w, int(iterations), _ptr(label), _ptr(y)), "sg_edge_labels")
+        if separation is None:
+            return y
+        _chk32(y, "y_true")
+        fg = y[..., 1].to(torch.uint8).contiguous()   # 0 / 1: one value, so an object is a connected building
+        labels = torch.empty((n, h, w), dtype=torch.int32, device=self.device)
+        ws = torch.empty(self.lib.sg_objects_label_ws_bytes(h, w), dtype=torch.uint8, device=self.device)
+        row = torch.empty((1, 8), dtype=torch.int32, device=self.device)   # labels are written whatever max_objs is
+        count = torch.empty(1, dtype=torch.int32, device=self.device)
+        for i in range(n):
+            check(self.lib.sg_objects_label(self.h, self.stream, h, w, _ptr(fg[i]), 1, _ptr(ws), ws.numel(), _ptr(labels[i]),
+                                            _ptr(row), 1, _ptr(count)), "sg_objects_label")
+        d1, d2 = self.object_distances(labels)
+        self.separation_weights(d1, d2, separation[0], separation[1], y)
         return y
+
+    def object_distances(self, labels, second=True):
+        """sg_object_distances: int32 device labels [N,H,W] or [H,W] (object number >= 0 or -1, as sg_objects_label writes them
+        per image) -> (d1sq, d2sq) int32 of the same shape: the exact squared distance to the nearest object and to the
+        nearest object other than that one, 0x7fffffff where there is none.  second=False: (d1sq, None), a plain exact
+        Euclidean distance transform."""
+        self._chk_dev(labels, torch.int32, "labels")
+        if labels.dim() not in (2, 3) or labels.numel() == 0:
+            raise _lib.SgError(f"labels: expected [N,H,W] or [H,W] and not empty, got {tuple(labels.shape)}")
+        h, w = labels.shape[-2:]
+        n = labels.shape[0] if labels.dim() == 3 else 1
+        ws = torch.empty(max(1, self.lib.sg_object_distances_ws_bytes(n, h, w)), dtype=torch.uint8, device=self.device)
+        d1 = torch.empty_like(labels)
+        d2 = torch.empty_like(labels) if second else None
+        check(self.lib.sg_object_distances(self.h, self.stream, n, h, w, _ptr(labels), _ptr(ws), ws.numel(), _ptr(d1), _ptr(d2)),
+              "sg_object_distances")
+        return d1, d2
+
+    def separation_weights(self, d1sq, d2sq, w0, sigma, y_true):
+        """sg_separation_weights: y_true[N,H,W,4] channel 2 += w0 * exp(-(sqrt(d1sq) + sqrt(d2sq))^2 / (2 sigma^2)) where
+        d1sq > 0 and a second object exists; in place."""
+        self._chk_dev(d1sq, torch.int32, "d1sq")
+        self._chk_dev(d2sq, torch.int32, "d2sq")
+        _chk32(y_true, "y_true")
+        if y_true.dim() != 4 or y_true.shape[3] != 4 or d1sq.shape != d2sq.shape or d1sq.numel() * 4 != y_true.numel():
+            raise _lib.SgError(f"y_true {tuple(y_true.shape)} / d1sq {tuple(d1sq.shape)} / d2sq {tuple(d2sq.shape)}: expected "
+                               "[N,H,W,4] and two [N,H,W]")
+        n, h, w = y_true.shape[:3]
+        check(self.lib.sg_separation_weights(self.h, self.stream, n, h, w, _ptr(d1sq), _ptr(d2sq), float(w0), float(sigma),
+                                             _ptr(y_true)), "sg_separation_weights")
+        return y_true
 
     # -------------------------------------------------------------------------------------- inference tail
     def argmax_accumulate(self, p, canvas, y0, x0):

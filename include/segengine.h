@@ -876,6 +876,31 @@ int sg_objects_label(sg_ctx* ctx, void* stream, int H, int W, const void* map_u8
 size_t sg_objects_overlap_ws_bytes(int64_t slots);
 int sg_objects_overlap(sg_ctx* ctx, void* stream, int H, int W, const void* labels_a_i32, const void* labels_b_i32, int64_t slots,
                        void* ws, size_t ws_bytes, void* pairs_i32, void* stat_i32);
+/* Separation weights for buildings that nearly touch (no counterpart in the reference, whose only per-pixel weights are the
+ * 11 x 11 rims of sg_edge_labels): the exact distances to the two nearest distinct objects of a label map, and the U-Net border
+ * weight (Ronneberger et al. 2015) built on them (csrc/separation.hip).
+ *   sg_object_distances    labels_i32[N][H][W] (what sg_objects_label writes per image: object number >= 0, or -1; numbers only
+ *                          have to be distinct per object within one image) -> d1sq_i32[N][H][W], d2sq_i32[N][H][W].  d1sq =
+ *                          the exact squared Euclidean distance in pixels to the nearest labelled pixel of the same image (0 on
+ *                          an object); d2sq = the same to the nearest pixel of any object other than the one that realises d1sq
+ *                          (on a building pixel: the nearest other building; two objects equally near: d2sq = d1sq).  Both are
+ *                          0x7fffffff where the image holds no such object.  Distances never cross from one image of the batch
+ *                          into the next.  d2sq_i32 == NULL: a plain exact distance transform, without any of the second-object
+ *                          work.  1 <= H, W <= 16384 and N*H*W < 2^31, else SG_EINVAL.  ws: sg_object_distances_ws_bytes(N, H,
+ *                          W) = one dword per pixel (two signed 16-bit column offsets: the two nearest distinct objects along
+ *                          the pixel's row), rounded up to 256 bytes; 0 for a shape the call refuses.  Integers throughout: the
+ *                          same bits in every run.
+ *   sg_separation_weights  where d1sq > 0 and d2sq != 0x7fffffff: y_true4[n,h,w,2] += w0 * expf(-s*s / (2*sigma*sigma)), s =
+ *                          sqrtf(d1sq) + sqrtf(d2sq), in float32 (a term that rounds to 0 is not added).  Every other float of
+ *                          y_true4[N][H][W][4] keeps its bits: channels 0, 1, 3, and channel 2 on objects and in images with
+ *                          fewer than two objects.  w0 >= 0, sigma > 0, both finite, and the shape limits above, else
+ *                          SG_EINVAL.  edge_focal_loss multiplies its background term by this channel as it stands.
+ * Neither call allocates or synchronises; a bad argument or a short workspace launches and writes nothing. */
+size_t sg_object_distances_ws_bytes(int N, int H, int W);
+int sg_object_distances(sg_ctx* ctx, void* stream, int N, int H, int W, const void* labels_i32, void* ws, size_t ws_bytes,
+                        void* d1sq_i32, void* d2sq_i32);
+int sg_separation_weights(sg_ctx* ctx, void* stream, int N, int H, int W, const void* d1sq_i32, const void* d2sq_i32, float w0,
+                          float sigma, void* y_true4);
 /* dst[i] = (float)src[i] / div - sub: decode_img's `np.array(img, np.float32) / 127.5 - 1` and decode_lbel's `/ 255`
  * (train_model/DeepLabv3plus.py:36-37, 48) on the GPU, so the input pipeline ships uint8 pixels over PCIe (a quarter of
  * the fp32 bytes) and converts on the device; bit-identical to the numpy float32 arithmetic. */

@@ -16,6 +16,7 @@ import numpy as np
 from .graph import KTensor, Node
 from .ops import conv_out_geometry, same_pad
 from . import _lib
+from . import fusion
 from . import switches
 
 
@@ -62,6 +63,20 @@ class _ConvNode(Node):
         super().__init__(name)
         self.filters, self.k, self.stride, self.dilation, self.padding = filters, k, stride, dilation, padding
         self.activation, self.use_bias, self.kinit = activation, use_bias, kinit
+        # marks of the fusion pass (fusion.py), each with the rule that sets it
+        self.bias_grad_zero = False  # bias_and_stats: a training-mode BatchNormalization follows, the bias gradient is 0
+        self.emit_bn_stats = False   # bias_and_stats: this convolution's epilogue hands that layer its statistics
+        # UpSampling2D(2) -> this 3x3 convolution, fused (runtime._Runtime.up2_on decides per runtime): the up-sampling node hands
+        # its SOURCE through, this node's kernels read / write it directly (csrc/conv_x6p.h: sub-pixel forward, dgrad with the
+        # 2 x 2 sum in its epilogue, filter gradient gathering h >> 1, w >> 1)
+        self.up_src = None           # up2_conv: that UpSampling2D
+        # BatchNormalization(+ReLU) -> this convolution, the normalisation applied in this layer's loaders (_BNNode.defer_conv;
+        # the BatchNormalization node then hands its RAW input through - saved state "deferred")
+        self.bn_src = None           # bn_conv: that BatchNormalization
+        # BatchNormalization(+ReLU) -> this thin 1x1 convolution, the layer's only consumer: the input gradient is a rank-Cout
+        # function of dz, so this node hands on (dz, kernel) - a ThinGradDeferred - and the BatchNormalization's backward kernels
+        # evaluate it where they read it; the Cin-wide gradient is never written
+        self.thin_bn = None          # thin_grad: that BatchNormalization
 
     def build(self, x: KTensor) -> KTensor:
         _, h, w, cin = x.shape
@@ -74,18 +89,6 @@ class _ConvNode(Node):
 
     def desc(self, rt, x):
         return rt.eng.conv_desc(tuple(x.shape), self.filters, self.k, self.k, self.stride, self.dilation, self.padding)
-
-    # UpSampling2D(2) -> this 3x3 convolution, fused (Model._fuse sets up_src; runtime._Runtime.up2_on decides per runtime):
-    # the up-sampling node hands its SOURCE through, this node's kernels read / write it directly (csrc/conv_x6p.h:
-    # sub-pixel forward, dgrad with the 2 x 2 sum in its epilogue, filter gradient gathering h >> 1, w >> 1)
-    up_src = None
-    # BatchNormalization(+ReLU) -> this convolution, the normalisation applied in this layer's loaders (Model._fuse sets bn_src /
-    # _BNNode.defer_conv; the BatchNormalization node then hands its RAW input through - saved state "deferred")
-    bn_src = None
-    # BatchNormalization(+ReLU) -> this thin 1x1 convolution, the layer's only consumer (Model._fuse sets thin_bn): the input gradient
-    # is a rank-Cout function of dz, so this node hands on (dz, kernel) - a ThinGradDeferred - and the BatchNormalization's backward
-    # kernels evaluate it where they read it; the Cin-wide gradient is never written
-    thin_bn = None
 
     def _bn_in(self, rt, training):
         """(gamma, beta, mean, invstd | moving variance, relu, infer, eps) when this call's input is the raw input of bn_src"""
@@ -136,7 +139,7 @@ class _ConvNode(Node):
             bn_in = self._bn_in(rt, training)
             if training:
                 rt.save(self, bn_in=bn_in)
-            if training and getattr(self, "emit_bn_stats", False):
+            if training and self.emit_bn_stats:
                 # the following BatchNormalization takes its statistics from this conv's epilogue
                 y, st = rt.eng.conv2d_fwd(x, rt.param(self.w), b, desc=d, want_stats=True,
                                           planes=None if up2 else rt.planes(self, "f"), up2=up2, x_planes=xp, bn_in=bn_in)
@@ -167,7 +170,7 @@ class _ConvNode(Node):
         up2 = self._up2(rt)
         d = self._up_desc(rt, x) if up2 else self.desc(rt, x)
         with e.timed(self._tag):
-            want_b = self.b is not None and not getattr(self, "bias_grad_zero", False)
+            want_b = self.b is not None and not self.bias_grad_zero
             # planes of the forward's activation (kept by rt.act_planes) and of dz: the planes-in filter gradient takes both as
             # they are, the planes-in dgrad shares dz's (one split of dz instead of one per launch)
             xp = None if up2 else rt.act_planes(self, x, d, make=False)
@@ -187,9 +190,7 @@ class _ConvNode(Node):
                 # or the thin 1x1 kernel (scSE's spatial squeeze, Cout = 1)
                 if (self._tag is None and dz.dtype == x.dtype and not up2
                         and (caps.thin or (rt.plane_kind(self, "d") == 1 and rt.planes(self, "d") is not None))):
-                    root = self.inputs[0]
-                    while isinstance(root.node, _ActNode) and root.node.fused_away and len(root.consumers) == 1:
-                        root = root.node.inputs[0]
+                    root = fusion.root_of(self.inputs[0])
                     if (caps.thin and self.thin_bn is not None and switches.get("SG_THIN_GRAD_BN")
                             and (rt._pending is None or id(root) not in rt._pending)
                             and e.bn_train_bwd_thin_ok(rt.values[id(self.thin_bn.inputs[0])], dz, rt.param(self.w))):
@@ -239,9 +240,12 @@ class _SepConvNode(Node):
     def __init__(self, name, filters, stride, activation):
         super().__init__(name)
         self.filters, self.stride, self.activation = filters, stride, activation
-        self.pre_relu = False  # set by the fusion pass when the producer is a single-consumer ReLU
-        self.bn_src = None     # set by the fusion pass: the training-mode BatchNormalization(+ReLU) applied in the gather
-        self.bnsum_src = None  # set by the fusion pass: the BatchNormalization whose backward sums this layer's dgrad produces
+        # marks of the fusion pass (fusion.py), each with the rule that sets it
+        self.bias_grad_zero = False  # bias_and_stats: a training-mode BatchNormalization follows, the bias gradient is 0
+        self.emit_bn_stats = False   # bias_and_stats: the pointwise convolution's epilogue hands that layer its statistics
+        self.pre_relu = False        # absorb_relu: the producer is a single-consumer ReLU, applied in the gather
+        self.bn_src = None           # bn_gather: the training-mode BatchNormalization(+ReLU) applied in the gather
+        self.bnsum_src = None        # bn_sums, bn_sums_via_add: the BatchNormalization whose backward sums this layer's dgrad produces
 
     def build(self, x):
         _, h, w, c = x.shape
@@ -268,7 +272,7 @@ class _SepConvNode(Node):
         t = e.dwconv_fwd(x, rt.param(self.dw), self.stride, self.pre_relu, bn=bn)
         if training:
             rt.save(self, t=t, bn=bn)
-            if getattr(self, "emit_bn_stats", False):
+            if self.emit_bn_stats:
                 y, st = e.conv2d_fwd(t, rt.param(self.pw), rt.param(self.b), want_stats=True, planes=rt.planes(self, "f"))
                 if st is not None:
                     rt.bn_stats[id(y)] = st
@@ -280,7 +284,7 @@ class _SepConvNode(Node):
         e = rt.eng
         t = rt.saved(self)["t"]
         dpw = e.conv_desc(tuple(t.shape), self.filters, 1, 1)
-        want_b = not getattr(self, "bias_grad_zero", False)
+        want_b = not self.bias_grad_zero
         keep = ()
         if isinstance(dy, BnBackwardDeferred):
             # the BatchNormalization behind this layer left its backward apply to this dgrad (y = its raw input): one launch gives
@@ -298,9 +302,7 @@ class _SepConvNode(Node):
         if rt.needs_grad(self.inputs[0]):
             # a gradient already collected for this layer's input (the residual add of the block it opens) is added by the kernel
             # (looked up through ReLU nodes that were absorbed into this layer's gather: they pass their gradient on unchanged)
-            root = self.inputs[0]
-            while isinstance(root.node, _ActNode) and root.node.fused_away and len(root.consumers) == 1:
-                root = root.node.inputs[0]
+            root = fusion.root_of(self.inputs[0])
             res = rt.take_pending(root) if e.dwconv_dgrad_acc_ok(ddw) else None
             # this layer's input is the output of a training-mode BatchNormalization with no other consumer: dx IS that layer's
             # output gradient, and the kernel sums what its backward needs (dgamma, dbeta) while it writes dx - the
@@ -463,21 +465,41 @@ class Dense(Layer):
 
 
 # ======================================================================================== normalisation
-class BnBackwardDeferred:
-    """What a BatchNormalization hands its producer instead of dx when that producer - a pointwise convolution on the wide
-    kernel - evaluates the backward apply in its own dgrad (csrc/conv_pw.h, BNB form; Engine.conv2d_dgrad_bnb): the gradient of
-    the layer's output and everything the apply needs.  The column sums dgamma / dbeta are finished (sums_done)."""
+class DeferredGrad:
+    """A gradient a node's backward hands on unexpanded, for a node further up the sweep to evaluate inside a kernel of its own.
+    runtime._Runtime.backward expands one (materialise) before a node that does not take it as it is (taken_by), and before it
+    sums one with another gradient."""
 
-    def __init__(self, dy, gamma, beta, mean, invstd, dgamma, dbeta, relu):
-        self.dy, self.gamma, self.beta, self.mean, self.invstd = dy, gamma, beta, mean, invstd
+    def materialise(self, eng):
+        """-> the gradient as a tensor, by the unfused launches"""
+        raise NotImplementedError
+
+    def taken_by(self, node) -> bool:
+        """Does `node`'s backward evaluate this object as its output gradient, unexpanded?"""
+        return False
+
+
+class BnBackwardDeferred(DeferredGrad):
+    """What a BatchNormalization hands its producer instead of dx when that producer - a pointwise convolution on the wide
+    kernel - evaluates the backward apply in its own dgrad (csrc/conv_pw.h, BNB form; Engine.conv2d_dgrad_bnb): the layer's raw
+    input, the gradient of its output and everything the apply needs.  The column sums dgamma / dbeta are finished (sums_done).
+    materialise() is the unfused apply pass; no graph Model._fuse marks reaches it (bnb_to: the SeparableConv2D is the only
+    receiver)."""
+
+    def __init__(self, x, dy, gamma, beta, mean, invstd, dgamma, dbeta, relu):
+        self.x, self.dy, self.gamma, self.beta, self.mean, self.invstd = x, dy, gamma, beta, mean, invstd
         self.dgamma, self.dbeta, self.relu = dgamma, dbeta, relu
         self.dtype, self.shape = dy.dtype, dy.shape
 
-    def tensors(self):
-        return (self.dy, self.gamma, self.beta, self.mean, self.invstd, self.dgamma, self.dbeta)
+    def materialise(self, eng):
+        return eng.bn_train_bwd_apply(self.x, self.dy, self.gamma, self.beta, self.mean, self.invstd, self.dgamma, self.dbeta,
+                                      relu=self.relu)
+
+    def taken_by(self, node):
+        return isinstance(node, _SepConvNode)
 
 
-class ThinGradDeferred:
+class ThinGradDeferred(DeferredGrad):
     """What a thin 1x1 convolution (Cout <= 4) hands the BatchNormalization in front of it instead of dx: the gradient g of its own
     output and its kernel w.  dx[p, c] = sum_o g[p, o] w[c, o] is evaluated inside that layer's backward kernels
     (Engine.bn_train_bwd_thin).  Any other receiver gets the tensor: materialise() is the thin dgrad itself (the sweep calls it)."""
@@ -489,12 +511,16 @@ class ThinGradDeferred:
     def materialise(self, eng):
         return eng.conv2d_dgrad(self.g, self.w, self.desc, out_dtype=self.dtype)
 
+    def taken_by(self, node):   # only a BatchNormalization (through an absorbed ReLU) evaluates it unexpanded
+        return isinstance(node, _BNNode) or (isinstance(node, _ActNode) and node.fused_away)
 
-class ScseGradDeferred:
+
+class ScseGradDeferred(DeferredGrad):
     """The gradient of an scSE block's input while its three consumers report (Model._fuse: _ScseCombineNode.lowrank): the combine
     node leaves dy and the gate logits, the GlobalAveragePooling and the sSE convolution add their small operands - dg [N, C] and
     (ds', w) - instead of launching a pass over the tensor each, and the last of them runs the one kernel that writes dx
-    (Engine.scse_bwd_final), summing in the order the three arrived.  materialise() is the unfused sequence on what has arrived."""
+    (Engine.scse_bwd_final), summing in the order the three arrived.  materialise() is the unfused sequence on what has arrived
+    (no node takes it as its output gradient: the two gates find it in the sweep's table, take_pending)."""
 
     def __init__(self, x, s, cl, dy):
         self.x, self.s, self.cl, self.dy = x, s, cl, dy
@@ -527,12 +553,13 @@ class _BNNode(Node):
     def __init__(self, name, momentum, epsilon):
         super().__init__(name)
         self.momentum, self.epsilon = momentum, epsilon
-        self.relu = False  # fused by the optimisation pass when followed by a single-consumer ReLU
-        self.defer_to = None  # fused by the optimisation pass: the SeparableConv2D that applies this layer in its gather
-        self.defer_add = None  # fused by the optimisation pass: the two-operand Add that applies this layer while it sums
-        self.sums_from = None  # fused by the optimisation pass: the SeparableConv2D whose depthwise dgrad sums this layer's dgamma / dbeta
-        self.defer_conv = None  # fused by the optimisation pass: the Conv2D whose loaders apply this layer (thin 1x1 / patch kernels)
-        self.bnb_to = None  # fused by the optimisation pass: the SeparableConv2D / 1x1 Conv2D whose dgrad evaluates this layer's backward apply
+        # marks of the fusion pass (fusion.py), each with the rule that sets it
+        self.relu = False       # absorb_relu: followed by a single-consumer ReLU, applied here
+        self.defer_to = None    # bn_gather: the SeparableConv2D that applies this layer in its gather
+        self.defer_add = None   # bn_add: the two-operand Add that applies this layer while it sums
+        self.sums_from = None   # bn_sums, bn_sums_via_add: the SeparableConv2D whose depthwise dgrad sums this layer's dgamma / dbeta
+        self.defer_conv = None  # bn_conv: the Conv2D whose loaders apply this layer (thin 1x1 / patch kernels)
+        self.bnb_to = None      # bn_backward_in_pw: the SeparableConv2D whose pointwise dgrad evaluates this layer's backward apply
 
     def build(self, x):
         c = x.shape[-1]
@@ -581,7 +608,7 @@ class _BNNode(Node):
             dy = dy.materialise(rt.eng)
         if s.get("sums_done") and self.bnb_to is not None and rt.bnb_on(self, x):
             # ... and that pass rides in the A path of the producer's pointwise dgrad: hand the pieces over
-            return [BnBackwardDeferred(dy, rt.param(self.gamma), rt.param(self.beta), s["mean"], s["invstd"], rt.grad(self.gamma),
+            return [BnBackwardDeferred(x, dy, rt.param(self.gamma), rt.param(self.beta), s["mean"], s["invstd"], rt.grad(self.gamma),
                                        rt.grad(self.beta), self.relu)]
         if s.get("sums_done"):   # dgamma / dbeta came out of the consumer's depthwise dgrad (sums_from): only the apply pass is left
             return [rt.eng.bn_train_bwd_apply(x, dy, rt.param(self.gamma), rt.param(self.beta), s["mean"], s["invstd"],
@@ -610,7 +637,7 @@ class _ActNode(Node):
     def __init__(self, name, act, axis=-1):
         super().__init__(name)
         self.act, self.axis = act, axis
-        self.fused_away = False  # True => identity (absorbed into producer / consumer)
+        self.fused_away = False  # mark of the fusion pass (fusion.py), absorb_relu: identity, absorbed into producer / consumer
 
     def build(self, x):
         if self.act == "softmax":
@@ -789,12 +816,13 @@ class _UpNode(Node):
         super().__init__(name)
         self.size = size
         self.interpolation = interpolation   # "nearest" | "bilinear" (tf.image.resize, half-pixel centres)
+        # mark of the fusion pass (fusion.py), up2_conv: the 3x3 convolution that reads this node's SOURCE directly
+        # (_ConvNode.up_src); nearest only
+        self.fused_into = None
 
     def build(self, x):
         _, h, w, c = x.shape
         return self.connect([x], (None, h * self.size, w * self.size, c))
-
-    fused_into = None   # the 3x3 convolution that reads this node's SOURCE directly (Model._fuse; _ConvNode.up_src); nearest only
 
     def forward(self, rt, xs, training):
         if self.interpolation == "bilinear":
@@ -904,8 +932,9 @@ class _AddNode(Node):
 
     def __init__(self, name=None):
         super().__init__(name)
-        self.relu = False
-        self.bn_src = [None, None]   # fused by the optimisation pass: the BatchNormalization layers this Add applies to its operands
+        # marks of the fusion pass (fusion.py), each with the rule that sets it
+        self.relu = False            # absorb_relu: followed by a single-consumer ReLU, applied here
+        self.bn_src = [None, None]   # bn_add: the BatchNormalization layers this Add applies to its operands
 
     def build(self, xs):
         for t in xs:
@@ -981,6 +1010,13 @@ class _ScseCombineNode(Node):
     """y = x * (sigmoid(s) + sigmoid(c)):  sSE_block + cSE + tf.add of predict_model/v3plus.py:141-167."""
     op = "scse_combine"
 
+    def __init__(self, name=None):
+        super().__init__(name)
+        # mark of the fusion pass (fusion.py), scse_lowrank: (sSE convolution, GlobalAveragePooling) when they and this node are
+        # the only consumers of x: their input gradients are rank-one terms the block's final kernel adds (ScseGradDeferred) -
+        # six passes over the tensor instead of nine
+        self.lowrank = None
+
     def build(self, x, s, c):
         assert s.shape[-1] == 1 and c.shape[-1] == x.shape[-1]
         return self.connect([x, s, c], x.shape)
@@ -988,10 +1024,6 @@ class _ScseCombineNode(Node):
     def forward(self, rt, xs, training):
         x, s, c = xs
         return rt.eng.scse_fwd(x, s, c)
-
-    # (sSE convolution, GlobalAveragePooling) when they and this node are the only consumers of x (Model._fuse): their input gradients
-    # are rank-one terms the block's final kernel adds (ScseGradDeferred) - six passes over the tensor instead of nine
-    lowrank = None
 
     def backward(self, rt, xs, y, dy):
         x, s, c = xs

@@ -23,6 +23,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
+from . import fusion
 from . import switches
 from .graph import KTensor, Node, ParamSpec, collect_nodes, init_array
 from . import layers as L
@@ -118,205 +119,8 @@ class Model:
 
     # ------------------------------------------------------------------------------------- graph passes
     def _fuse(self):
-        """Peephole fusions that remove full-tensor passes (each is exact, not an approximation):
-        BN -> ReLU   => BN kernel applies ReLU (and masks in backward);
-        ReLU -> SeparableConv2D => depthwise gather applies ReLU (pre_relu);
-        Add -> ReLU  => add_n applies ReLU.
-        A ReLU is absorbed only if its output has exactly one consumer (or, for producers, it is the only
-        consumer of the producer's output and is not a model output)."""
-        outs = {id(t) for t in self.outputs}
-        # A bias added right before a training-mode BatchNormalization has an identically zero gradient (BN's input
-        # gradient sums to zero over the batch by construction): the column-sum launch is dropped and the slot in the
-        # gradient arena stays at its initial 0 (what the sum would return up to fp32 noise of ~1e-10).
-        for n in self.nodes:
-            if isinstance(n, (L._ConvNode, L._SepConvNode)) and getattr(n, "activation", None) in (None, "linear") \
-                    and id(n.output) not in outs:
-                cons = n.output.consumers
-                if len(cons) == 1 and isinstance(cons[0], L._BNNode) and len(n.output.shape) == 4:
-                    n.bias_grad_zero = True
-                    n.emit_bn_stats = True  # the conv epilogue hands BN its statistics (stats of sg_conv2d_fwd)
-        # UpSampling2D(2) -> Conv2D 3x3 'same' (the decoder's last stage, train_model/DeepLabv3plus.py:476-477): the convolution's
-        # kernels read the up-sampling's source directly (sub-pixel forward with 4/9 of the products; csrc/conv_x6p.h) and the
-        # 4x tensor and its gradient are never built.  Marked here for every such pair; whether a runtime takes the fused
-        # kernels (fp32 storage, geometry, SG_UP2_FUSE != 0) is _Runtime.up2_on.
-        for n in self.nodes:
-            if (isinstance(n, L._UpNode) and n.size == 2 and n.interpolation == "nearest" and id(n.output) not in outs
-                    and len(n.output.consumers) == 1):
-                c = n.output.consumers[0]
-                if (isinstance(c, L._ConvNode) and c.k == 3 and c.stride == 1 and c.dilation == 1 and c.padding == "same"
-                        and c.activation in (None, "linear", "relu")):
-                    n.fused_into, c.up_src = c, n
-        for n in self.nodes:
-            if not isinstance(n, L._ActNode) or n.act != "relu" or n.fused_away:
-                continue
-            src = n.inputs[0]
-            prod = src.node
-            if prod is not None and len(src.consumers) == 1 and id(src) not in outs:
-                if isinstance(prod, L._BNNode) and not prod.relu:
-                    prod.relu, n.fused_away = True, True
-                    continue
-                if isinstance(prod, L._AddNode) and not prod.relu:
-                    prod.relu, n.fused_away = True, True
-                    continue
-            cons = n.output.consumers
-            if len(cons) == 1 and isinstance(cons[0], L._SepConvNode) and id(n.output) not in outs and not cons[0].pre_relu:
-                cons[0].pre_relu, n.fused_away = True, True
-        # BatchNormalization (+ fused ReLU) -> SeparableConv2D, training mode: the depthwise gather applies the normalisation
-        # to the raw tensor (bn of sg_dwconv2d_fwd / _wgrad), so the normalised tensor is never written or read - two of the
-        # layer's seven tensor passes.  Needs the statistics from the producing convolution's epilogue (decided at run
-        # time: _BNNode.forward falls back to the materialising form) and the stride-1 run kernels' geometry.
-        # Default ON since round 4 (SG_BN_DEFER=0 restores the materialising form; tests/test_models_gpu.py keeps one leg on it).
-        # Round 2 measured "no net gain" (the 39 dropped bn_apply launches saved 1.05 ms and the depthwise kernels of that
-        # round gave 0.8 ms of it back); re-measured on the round-3 run kernels: 76.59 -> 75.71 and 76.96 -> 75.93 ms per fp32
-        # step, bit-identical, peak memory -2.7 GiB (LAB_NOTEBOOK.md 11.2).
-        # BatchNormalization (no ReLU) -> two-operand Add: the residual adds of the Xception blocks sum a normalised branch and
-        # the shortcut (itself a normalised 1x1 convolution in the entry / exit flow).  The Add applies the normalisation while
-        # it sums (sg_add2_bn), the normalised tensor is never written or read: one of the layer's two forward passes
-        # (SG_BN_ADD=0 keeps them apart).  The backward is untouched: dy of the Add IS dy of the BatchNormalization, whose
-        # backward reads its raw input.
-        if switches.get("SG_BN_ADD"):
-            for n in self.nodes:
-                if not isinstance(n, L._AddNode) or len(n.inputs) != 2 or len(n.output.shape) != 4:
-                    continue
-                epss = set()
-                for i, t in enumerate(n.inputs):
-                    p_ = t.node
-                    through_relu = False   # BN -> ReLU (absorbed into the BN) -> Add: the Add applies both (res34.py's blocks)
-                    if (isinstance(p_, L._ActNode) and p_.fused_away and len(t.consumers) == 1 and id(t) not in outs
-                            and isinstance(p_.inputs[0].node, L._BNNode) and p_.inputs[0].node.relu
-                            and len(p_.inputs[0].consumers) == 1):
-                        t, p_, through_relu = p_.inputs[0], p_.inputs[0].node, True
-                    if (isinstance(p_, L._BNNode) and p_.relu == through_relu and p_.defer_to is None and p_.defer_add is None
-                            and len(t.consumers) == 1 and id(t) not in outs and t.shape[-1] % 4 == 0
-                            and n.inputs[0] is not n.inputs[1]):
-                        n.bn_src[i], p_.defer_add = p_, n
-                        epss.add(p_.epsilon)
-                if len(epss) > 1:   # (one eps per launch: two different ones never occur on this path)
-                    for i, p_ in enumerate(n.bn_src):
-                        if p_ is not None:
-                            p_.defer_add, n.bn_src[i] = None, None
-        # BatchNormalization (+ fused ReLU) -> SeparableConv2D (stride 1), the layer's only consumer: the input gradient that the
-        # depthwise convolution's dgrad writes IS the BatchNormalization's output gradient.  That kernel also sums, per channel,
-        # dbeta = sum g and dgamma = sum g * xhat in its epilogue (sums of sg_dwconv2d_dgrad: one more read of the layer's raw
-        # input), so the reduction pass of the BatchNormalization's backward - two tensor reads of its five passes - is not run
-        # (round 4; conv_bn_relu / the Xception blocks, train_model/DeepLabv3plus.py:323-416,424-429; SG_BN_SUMS=0 switches it
-        # off).  Decided again at run time (geometry, training mode: _SepConvNode.backward).
-        if switches.get("SG_BN_SUMS"):
-            for n in self.nodes:
-                if not isinstance(n, L._BNNode) or len(n.output.shape) != 4 or id(n.output) in outs or n.defer_add is not None:
-                    continue
-                t = n.output
-                while (len(t.consumers) == 1 and isinstance(t.consumers[0], L._ActNode) and t.consumers[0].fused_away
-                       and id(t.consumers[0].output) not in outs):
-                    t = t.consumers[0].output
-                if len(t.consumers) != 1 or not isinstance(t.consumers[0], L._SepConvNode) or id(t) in outs:
-                    continue
-                sc = t.consumers[0]
-                _, h, w, c = t.shape
-                if sc.stride == 1 and sc.bnsum_src is None and w % 4 == 0 and c % 4 == 0:
-                    n.sums_from, sc.bnsum_src = sc, n
-            # The same through a residual Add that applies the layer (defer_add): the Add hands its output gradient on unchanged,
-            # so a BatchNormalization in front of it receives the gradient of the Add's OUTPUT - and where that output opens the
-            # next Xception block, its complete gradient leaves the depthwise dgrad of the block's first SeparableConv2D (which
-            # adds the gradient collected from the block's own residual add: take_pending).  Condition: that SeparableConv2D
-            # (with the ReLU absorbed into its gather) is the LAST consumer of the tensor in the backward sweep, i.e. the first
-            # in node order.
-            for sc in self.nodes:
-                if not isinstance(sc, L._SepConvNode) or sc.bnsum_src is not None or sc.stride != 1:
-                    continue
-                root, first = sc.inputs[0], sc
-                while isinstance(root.node, L._ActNode) and root.node.fused_away and len(root.consumers) == 1:
-                    root, first = root.node.inputs[0], root.node
-                a = root.node
-                if not isinstance(a, L._AddNode) or a.relu or id(root) in outs or len(root.shape) != 4:
-                    continue
-                if any(cn is not first and cn.index < sc.index for cn in root.consumers):
-                    continue
-                cands = [b for b in a.bn_src if b is not None and b.sums_from is None and b.defer_add is a]
-                _, h, w, c = root.shape
-                if cands and w % 4 == 0 and c % 4 == 0:
-                    cands[0].sums_from, sc.bnsum_src = sc, cands[0]
-        if switches.get("SG_BN_DEFER"):
-            for n in self.nodes:
-                if not isinstance(n, L._BNNode) or len(n.output.shape) != 4 or id(n.output) in outs:
-                    continue
-                t = n.output
-                while (len(t.consumers) == 1 and isinstance(t.consumers[0], L._ActNode) and t.consumers[0].fused_away
-                       and id(t.consumers[0].output) not in outs):
-                    t = t.consumers[0].output
-                if len(t.consumers) != 1 or not isinstance(t.consumers[0], L._SepConvNode) or id(t) in outs:
-                    continue
-                sc = t.consumers[0]
-                _, h, w, c = t.shape
-                if sc.stride == 1 and not sc.pre_relu and sc.bn_src is None and w % 4 == 0 and c % 4 == 0:
-                    n.defer_to, sc.bn_src = sc, n
-        self._fuse_bn_conv(outs)
-        # BatchNormalization (+ fused ReLU) -> thin 1x1 Conv2D (Cout <= 4: the softmax head), the layer's only consumer: the
-        # convolution's input gradient stays unexpanded and the BatchNormalization's backward evaluates it (layers.ThinGradDeferred;
-        # decided again at run time: storage type, SG_THIN_GRAD_BN)
-        for n in self.nodes:
-            if not isinstance(n, L._BNNode) or len(n.output.shape) != 4 or id(n.output) in outs:
-                continue
-            t = n.output
-            while (len(t.consumers) == 1 and isinstance(t.consumers[0], L._ActNode) and t.consumers[0].fused_away
-                   and id(t.consumers[0].output) not in outs):
-                t = t.consumers[0].output
-            if len(t.consumers) != 1 or id(t) in outs:
-                continue
-            c = t.consumers[0]
-            cin = t.shape[-1]
-            if (isinstance(c, L._ConvNode) and c.k == 1 and c.stride == 1 and c.filters <= 4 and c.up_src is None
-                    and cin % 4 == 0 and cin >= 16):
-                c.thin_bn = n
-        # scSE block: x feeds the sSE convolution (1x1, one output channel, on the thin kernel's geometry), the GlobalAveragePooling of
-        # the cSE path and the combine node, and nothing else.  The two gates' input gradients are rank-one terms; the combine node's
-        # backward leaves the block's dx to one final kernel that adds them (layers.ScseGradDeferred; SG_SCSE_LOWRANK at run time).
-        for n in self.nodes:
-            if not isinstance(n, L._ScseCombineNode):
-                continue
-            x, s = n.inputs[0], n.inputs[1]
-            sse, cons = s.node, x.consumers
-            gaps = [q for q in cons if isinstance(q, L._AvgPoolNode) and q.global_pool]
-            if (isinstance(sse, L._ConvNode) and len(cons) == 3 and len(gaps) == 1 and sse in cons and n in cons and id(x) not in outs
-                    and x.node is not None and sse.inputs[0] is x and sse.k == 1 and sse.stride == 1 and sse.filters == 1
-                    and sse.activation is None and sse.bn_src is None and sse.up_src is None and len(s.consumers) == 1
-                    and x.shape[-1] % 4 == 0 and x.shape[-1] >= 16):
-                n.lowrank = (sse, gaps[0])
-        # SeparableConv2D -> BatchNormalization whose backward column sums come from elsewhere (sums_from): the backward APPLY can
-        # ride in the A path of the pointwise dgrad (csrc/conv_pw.h, BNB form; _Runtime.bnb_on decides per runtime and batch)
-        for n in self.nodes:
-            if isinstance(n, L._BNNode) and n.sums_from is not None and len(n.output.shape) == 4:
-                prod = n.inputs[0].node
-                if (isinstance(prod, L._SepConvNode) and prod.activation in (None, "linear") and len(n.inputs[0].consumers) == 1
-                        and id(n.inputs[0]) not in outs):
-                    n.bnb_to = prod
-
-    # (continued in _fuse_bn_conv, called at the end of _fuse)
-    def _fuse_bn_conv(self, outs):
-        """BatchNormalization(+ReLU) -> Conv2D whose kernels can normalise while they load (round 5): a thin 1x1 convolution (the
-        softmax head, the sSE gate) or a 3x3 stride-1 convolution on 32 / 64 channels (the patch kernels).  The decoder's last stage
-        `conv_bn_relu(32) -> conv_bn_relu(32) -> Conv2D(2, softmax)` (train_model/DeepLabv3plus.py:477-480) has two such pairs on
-        512 x 512 x 32 tensors.  The normalised tensor is then never written or read (forward: one write + one read of the
-        tensor; the filter gradient re-normalises in its loader; backward of the BatchNormalization is unchanged - it already
-        recomputes the ReLU mask from its raw input)."""
-        for n in self.nodes:
-            if (not isinstance(n, L._BNNode) or len(n.output.shape) != 4 or id(n.output) in outs
-                    or n.defer_to is not None or n.defer_add is not None):
-                continue
-            t = n.output
-            while (len(t.consumers) == 1 and isinstance(t.consumers[0], L._ActNode) and t.consumers[0].fused_away
-                   and id(t.consumers[0].output) not in outs):
-                t = t.consumers[0].output
-            if len(t.consumers) != 1 or id(t) in outs:
-                continue
-            c = t.consumers[0]
-            if not isinstance(c, L._ConvNode) or c.bn_src is not None or c.up_src is not None or c.stride != 1 or c.dilation != 1:
-                continue
-            cin = t.shape[-1]
-            thin = c.k == 1 and c.filters <= 4 and cin % 4 == 0 and cin >= 16
-            patch = c.k == 3 and c.padding == "same" and cin in (32, 64)
-            if thin or patch:
-                n.defer_conv, c.bn_src = c, n
+        """Mark the fusions this graph takes (fusion.py: the rules, their order and what each reads of the others)."""
+        fusion.run(self.nodes, self.outputs)
 
     def _layout_params(self):
         self.params: List[ParamSpec] = [p for n in self.nodes for p in n.params]
@@ -1013,6 +817,11 @@ def run_segments(segments, arena, transport, lanes=None):
         transport.join()
 
 
+# mark -> (its run-time switch, the Engine query that says whether the library takes the launch): _Runtime._gate
+_GATES = {"bnb_to": ("SG_BN_PW", "conv2d_dgrad_bnb_ok"), "defer_conv": ("SG_BN_CONV", "conv2d_bn_in_ok"),
+          "fused_into": ("SG_UP2_FUSE", "conv2d_up2_ok")}
+
+
 class _Runtime:
     """Device state of one model: arenas, saved activations, gradient bookkeeping."""
 
@@ -1024,9 +833,8 @@ class _Runtime:
         dev = int(os.environ.get("LOCAL_RANK", "0")) if torch.cuda.is_available() and torch.cuda.device_count() > 1 else 0
         self.eng = get_engine(dev)  # makes `dev` torch's current device (Engine.__init__)
         e = self.eng
-        self._up2: Dict[tuple, bool] = {}   # up_sampling2d node -> fused with its convolution on this runtime (up2_on)
-        self._bn_conv: Dict[tuple, bool] = {}        # (batch_normalization node, arithmetic) -> applied by its consumer convolution
-        self._bnb: Dict[tuple, bool] = {}            # (batch_normalization node, batch, arithmetic) -> backward apply in the producer's dgrad
+        self._gates: Dict[tuple, bool] = {}          # (mark, node, batch, arithmetic) -> the marked fusion is on here (_gate)
+        self._x6 = e.lib.sg_get_conv_x6              # the arithmetic mode now: part of that key, asked per node and step
         self._act_planes: Dict[int, tuple] = {}      # id(symbolic tensor) -> (fp32 activation, its bf16 planes) of this step
         self._act_planes_use: Dict[int, bool] = {}   # id(conv node) -> its forward reads planes (geometry)
         self.w_train = e.zeros(max(model._n_train, ALIGN))
@@ -1099,6 +907,28 @@ class _Runtime:
                                                       C.c_void_p(arena.data_ptr()), C.c_void_p(jobs.data_ptr()), launch[0],
                                                       launch[1]), "sg_prepare_planes")
 
+    def _gate(self, node, mark, x=None) -> bool:
+        """Is the fusion that Model._fuse marked on `node` (attribute `mark`: the partner node) on in THIS runtime?  The mark is
+        set, the fusion's switch is on, fp32 storage, and the library takes the launch: the partner convolution's own at batch 1,
+        or - given `x`, the BatchNormalization's input - the pointwise convolution that produced x, at its batch.  Decided once
+        per (node, batch, arithmetic mode: the arithmetic switch may change between steps, tests do)."""
+        key = (mark, id(node), 0 if x is None else x.shape[0], self._x6())
+        got = self._gates.get(key)
+        if got is None:
+            c, (switch, ask) = getattr(node, mark), _GATES[mark]
+            got = False
+            if (c is not None and switches.get(switch) and self.model.compute_dtype == "float32"
+                    and (x is None or x.dtype == self.torch.float32)):
+                if x is None:
+                    _, h, w, cin = c.inputs[0].shape
+                    d = self.eng.conv_desc((1, h, w, cin), c.filters, c.k, c.k, c.stride, c.dilation, c.padding)
+                else:
+                    n, h, w, cout = x.shape
+                    d = self.eng.conv_desc((n, h, w, c.inputs[0].shape[-1]), cout, 1, 1, 1, 1, "same")
+                got = bool(getattr(self.eng, ask)(d))
+            self._gates[key] = got
+        return got
+
     def bnb_on(self, bn_node, x) -> bool:
         """Does THIS runtime leave BatchNormalization `bn_node`'s backward apply to the dgrad of the pointwise convolution that
         produced its input (Model._fuse: bnb_to)?  fp32 storage, a launch the wide pointwise kernel takes at this batch (asked of
@@ -1106,32 +936,12 @@ class _Runtime:
         bn_bwd_apply launches it removes (47 us each in the profile) ran beside the side stream's filter gradients for free,
         while the 25 us it adds to every dgrad sit on the matrix pipe, which is what bounds the step (71.13 / 71.43 ms without,
         71.58 / 71.69 with, alternating runs on one box: gpurun_out/r5x; stand-alone 123 us against 22.5 + 96.8)."""
-        key = (id(bn_node), int(x.shape[0]), int(self.eng.lib.sg_get_conv_x6()))
-        got = self._bnb.get(key)
-        if got is None:
-            p = bn_node.bnb_to
-            got = False
-            if p is not None and switches.get("SG_BN_PW") and self.model.compute_dtype == "float32" and x.dtype == self.torch.float32:
-                n, h, w, c = x.shape
-                cin = p.inputs[0].shape[-1]
-                got = bool(self.eng.conv2d_dgrad_bnb_ok(self.eng.conv_desc((n, h, w, cin), c, 1, 1, 1, 1, "same")))
-            self._bnb[key] = got
-        return got
+        return self._gate(bn_node, "bnb_to", x)
 
     def bn_conv_on(self, bn_node) -> bool:
         """Does THIS runtime apply BatchNormalization `bn_node` in the loaders of its consumer convolution (Model._fuse: defer_conv /
         bn_src)?  fp32 storage, a launch geometry the thin 1x1 / patch kernels cover (asked of the library), SG_BN_CONV != 0."""
-        key = (id(bn_node), int(self.eng.lib.sg_get_conv_x6()))
-        got = self._bn_conv.get(key)
-        if got is None:
-            c = bn_node.defer_conv
-            got = False
-            if c is not None and switches.get("SG_BN_CONV") and self.model.compute_dtype == "float32":
-                _, h, w, cin = c.inputs[0].shape
-                d = self.eng.conv_desc((1, h, w, cin), c.filters, c.k, c.k, c.stride, c.dilation, c.padding)
-                got = bool(self.eng.conv2d_bn_in_ok(d))
-            self._bn_conv[key] = got
-        return got
+        return self._gate(bn_node, "defer_conv")
 
     def planes_in_on(self) -> bool:
         """fp32 storage with the six-pass arithmetic, SG_ACT_PLANES != 0: activation planes are made once per tensor and step."""
@@ -1164,17 +974,7 @@ class _Runtime:
         """Does THIS runtime run the pair `up_node` -> 3x3 convolution (Model._fuse: fused_into / up_src) on the fused kernels?
         fp32 storage, the geometry csrc/conv_x6p.h covers (asked of the library), SG_UP2_FUSE != 0.  Decided once per pair:
         the up-sampling node (identity then) and the convolution must agree."""
-        key = (id(up_node), int(self.eng.lib.sg_get_conv_x6()))   # (the arithmetic switch may change between steps: tests do)
-        got = self._up2.get(key)
-        if got is None:
-            c = up_node.fused_into
-            got = False
-            if c is not None and switches.get("SG_UP2_FUSE") and self.model.compute_dtype == "float32":
-                _, h, w, cin = c.inputs[0].shape
-                d = self.eng.conv_desc((1, h, w, cin), c.filters, c.k, c.k, c.stride, c.dilation, c.padding)
-                got = bool(self.eng.conv2d_up2_ok(d))
-            self._up2[key] = got
-        return got
+        return self._gate(up_node, "fused_into")
 
     def plane_kind(self, node, tag) -> int:
         """Which kernel family `node`'s launch `tag` takes (sg_conv2d_planes_job's kind; 0: none of the prepared-plane kernels)."""
@@ -1322,10 +1122,8 @@ class _Runtime:
                     hook(n.index)
                 continue
             dy = slot[0]
-            if isinstance(dy, L.ThinGradDeferred) and not (isinstance(n, L._BNNode) or (isinstance(n, L._ActNode) and n.fused_away)):
-                dy = dy.materialise(e)   # only a BatchNormalization (through an absorbed ReLU) evaluates it unexpanded
-            elif isinstance(dy, L.ScseGradDeferred):
-                dy = dy.materialise(e)   # (a consumer of the block's input did not report: never with the graphs Model._fuse marks)
+            if isinstance(dy, L.DeferredGrad) and not dy.taken_by(n):
+                dy = dy.materialise(e)   # (this node does not evaluate it unexpanded: never with the graphs Model._fuse marks)
             xs = [self.values[id(t)] for t in n.inputs]
             y = self.values[id(n.output)]
             self._pending = grads
@@ -1341,9 +1139,9 @@ class _Runtime:
                     fresh = False
                 cur = grads.get(id(sym))
                 if cur is not None:   # a sum: of tensors (never reached by the graphs Model._fuse marks)
-                    if isinstance(g, (L.ThinGradDeferred, L.ScseGradDeferred)):
+                    if isinstance(g, L.DeferredGrad):
                         g, fresh = g.materialise(e), True
-                    if isinstance(cur[0], (L.ThinGradDeferred, L.ScseGradDeferred)):
+                    if isinstance(cur[0], L.DeferredGrad):
                         cur[0], cur[1] = cur[0].materialise(e), True
                 if cur is None:
                     grads[id(sym)] = [g, fresh]

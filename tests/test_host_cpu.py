@@ -60,6 +60,61 @@ def test_fusion_pass_counts():
         zoo.ResNetFamily().run_model("res18")
 
 
+FUSION_MARKS = {  # node class -> the marks fusion.py's rules may set on it
+    "_ConvNode": ("bias_grad_zero", "emit_bn_stats", "up_src", "bn_src", "thin_bn"),
+    "_SepConvNode": ("bias_grad_zero", "emit_bn_stats", "pre_relu", "bn_src", "bnsum_src"),
+    "_BNNode": ("relu", "defer_to", "defer_add", "sums_from", "defer_conv", "bnb_to"),
+    "_ActNode": ("fused_away",), "_UpNode": ("fused_into",), "_AddNode": ("relu", "bn_src"), "_ScseCombineNode": ("lowrank",)}
+# nodes that carry each mark, per model at (512, 512, 3) under the default switches: counted at the commit before the pass moved
+# into fusion.py (its rules then sat inline in Model._fuse), not by the code under test
+FUSION_MARK_COUNTS = {
+    "v3plus": {"_ActNode.fused_away": 87, "_AddNode.bn_src": 20, "_BNNode.bnb_to": 56, "_BNNode.defer_add": 23, "_BNNode.defer_conv": 4,
+               "_BNNode.defer_to": 39, "_BNNode.relu": 68, "_BNNode.sums_from": 56, "_ConvNode.bias_grad_zero": 29,
+               "_ConvNode.bn_src": 4, "_ConvNode.emit_bn_stats": 29, "_ConvNode.thin_bn": 1, "_ConvNode.up_src": 1,
+               "_ScseCombineNode.lowrank": 4, "_SepConvNode.bias_grad_zero": 62, "_SepConvNode.bn_src": 39,
+               "_SepConvNode.bnsum_src": 56, "_SepConvNode.emit_bn_stats": 62, "_SepConvNode.pre_relu": 19, "_UpNode.fused_into": 1},
+    "bam": {"_ActNode.fused_away": 103, "_AddNode.bn_src": 20, "_BNNode.bnb_to": 56, "_BNNode.defer_add": 23, "_BNNode.defer_conv": 3,
+            "_BNNode.defer_to": 39, "_BNNode.relu": 84, "_BNNode.sums_from": 56, "_ConvNode.bias_grad_zero": 37, "_ConvNode.bn_src": 3,
+            "_ConvNode.emit_bn_stats": 37, "_ConvNode.thin_bn": 1, "_ScseCombineNode.lowrank": 3, "_SepConvNode.bias_grad_zero": 62,
+            "_SepConvNode.bn_src": 39, "_SepConvNode.bnsum_src": 56, "_SepConvNode.emit_bn_stats": 62, "_SepConvNode.pre_relu": 19},
+    "scse": {"_ScseCombineNode.lowrank": 4},
+    "res34": {"_ActNode.fused_away": 68, "_AddNode.bn_src": 20, "_AddNode.relu": 20, "_BNNode.defer_add": 20, "_BNNode.defer_conv": 6,
+              "_BNNode.relu": 48, "_ConvNode.bias_grad_zero": 43, "_ConvNode.bn_src": 6, "_ConvNode.emit_bn_stats": 43},
+    "hrnet": {"_ActNode.fused_away": 96, "_AddNode.bn_src": 41, "_AddNode.relu": 40, "_BNNode.defer_add": 42, "_BNNode.defer_conv": 29,
+              "_BNNode.relu": 56, "_ConvNode.bias_grad_zero": 108, "_ConvNode.bn_src": 29, "_ConvNode.emit_bn_stats": 108,
+              "_ConvNode.thin_bn": 1, "_ConvNode.up_src": 1, "_UpNode.fused_into": 1}}
+
+
+def test_fusion_marks_per_model_declarations_and_rule_order(monkeypatch):
+    """fusion.py: (a) every mark is an instance attribute at its default on a node no pass has seen; (b) the number of nodes of each
+    class that carry each mark, per model, is what the pass gave before it was split into rules (an _AddNode counts under bn_src when
+    either operand's entry is set); (c) RULES is in the order the module's docstring documents."""
+    from building_detection_amd import fusion, zoo, layers as L
+    fresh = [L._ConvNode(None, 8, 3, 1, 1, "same", None, True, "glorot_uniform"), L._SepConvNode(None, 8, 1, None),
+             L._BNNode(None, 0.99, 1e-3), L._ActNode(None, "relu"), L._UpNode(None, 2), L._AddNode(), L._ScseCombineNode()]
+    assert {type(n).__name__ for n in fresh} == set(FUSION_MARKS)
+    for n in fresh:
+        for mark in FUSION_MARKS[type(n).__name__]:
+            assert mark in vars(n), f"{type(n).__name__}.{mark} is not declared in __init__"
+            assert vars(n)[mark] in (None, False, [None, None]), (type(n).__name__, mark, vars(n)[mark])
+    for k in ("SG_BN_ADD", "SG_BN_SUMS", "SG_BN_DEFER"):
+        monkeypatch.delenv(k, raising=False)
+    for name, want in FUSION_MARK_COUNTS.items():
+        got = {}
+        for n in zoo.BUILDERS[name]((512, 512, 3)).nodes:
+            cls = type(n).__name__
+            for mark in FUSION_MARKS.get(cls, ()):
+                v = getattr(n, mark)
+                if not (v is None or v is False or v == [None, None]):
+                    got[f"{cls}.{mark}"] = got.get(f"{cls}.{mark}", 0) + 1
+        assert got == want, name
+    names = [r.__name__ for r in fusion.RULES]
+    assert names == ["bias_and_stats", "up2_conv", "absorb_relu", "bn_add", "bn_sums", "bn_sums_via_add", "bn_gather", "bn_conv",
+                     "thin_grad", "scse_lowrank", "bn_backward_in_pw"]
+    documented = re.findall(r"^ +(\d+) (\w+) ", fusion.__doc__, re.M)
+    assert documented == [(str(i + 1), r) for i, r in enumerate(names)]
+
+
 def test_reference_layer_names_res34():
     from building_detection_amd import zoo
     names = {n.name for n in zoo.ResNetFamily((64, 64, 3)).run_model("res34").nodes}

@@ -738,7 +738,7 @@ def test_batchnorm_applied_in_the_depthwise_gather(engine, policy, monkeypatch):
 
 @pytest.mark.parametrize("name", ["v3plus", "hrnet", "res34"])
 def test_batchnorm_applied_by_the_consuming_convolution_gives_the_same_bits(engine, name, monkeypatch):
-    """Round 5 (Model._fuse_bn_conv, _Runtime.bn_conv_on): BatchNormalization(+ReLU) -> Conv2D pairs whose convolution runs on the
+    """Round 5 (fusion.bn_conv, _Runtime.bn_conv_on): BatchNormalization(+ReLU) -> Conv2D pairs whose convolution runs on the
     thin 1x1 or the patch kernels hand the RAW tensor through and the convolution's loaders normalise (training statistics in
     fit, moving statistics in predict).  Same expression on the same numbers: predict(), the loss, every gradient and the weights
     after two Adam steps equal the materialising graph's (SG_BN_CONV=0) to the bit; the fused graphs really contain such pairs

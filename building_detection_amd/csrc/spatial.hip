@@ -1,6 +1,6 @@
-// HBM-bound spatial kernels of the hot path (NHWC, channels innermost so every access is a coalesced run of
-// 16-byte channel chunks): depthwise 3x3 (SeparableConv2D's first half) forward / dgrad / wgrad, max / average
-// pooling, nearest and bilinear up-sampling.
+// The depthwise convolution (SeparableConv2D's first half), HBM-bound (NHWC, channels innermost so every access is a
+// coalesced run of 16-byte channel chunks): forward / dgrad / wgrad and plan_dw(), which chooses their kernels.  Pooling
+// and up-sampling are in resample.hip.
 #include <algorithm>
 #include <initializer_list>
 #include "sg_reduce.h"
@@ -961,529 +961,6 @@ int launch_dw_stencil(const DwPlan& pl, DwForm form, const sg_conv_desc* d, DwRu
   return 0;
 }
 
-// ---------------------------------------------------------------------------------------------- pooling
-template <typename T>
-struct PoolParams {
-  const T* __restrict__ x;
-  const T* __restrict__ y;
-  const T* __restrict__ dy;
-  T* __restrict__ out;
-  int N, H, W, C, Ho, Wo, k, stride, pad_t, pad_l;
-  FastDiv fd_cv, fd_w, fd_h;
-};
-
-template <int V, typename T>
-__global__ void maxpool_fwd_kernel(const PoolParams<T> p) {
-  const uint32_t cv = p.C / V;
-  const uint32_t total = (uint32_t)((int64_t)p.N * p.Ho * p.Wo * cv), stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    uint32_t pix, cc, row, ow, n, oh;
-    fd_divmod(i, p.fd_cv, pix, cc);
-    fd_divmod(pix, p.fd_w, row, ow);
-    fd_divmod(row, p.fd_h, n, oh);
-    const int c = (int)cc * V;
-    float m[V];
-#pragma unroll
-    for (int k = 0; k < V; ++k) m[k] = -INFINITY;
-    for (int a = 0; a < p.k; ++a) {
-      const int ih = (int)oh * p.stride - p.pad_t + a;
-      if ((unsigned)ih >= (unsigned)p.H) continue;
-      for (int b = 0; b < p.k; ++b) {
-        const int iw = (int)ow * p.stride - p.pad_l + b;
-        if ((unsigned)iw >= (unsigned)p.W) continue;
-        float xv[V];
-        ldv<V>(p.x + ((int64_t)(n * p.H + ih) * p.W + iw) * p.C + c, xv);
-#pragma unroll
-        for (int k = 0; k < V; ++k) m[k] = fmaxf(m[k], xv[k]);
-      }
-    }
-    stv<V>(p.out + (int64_t)pix * p.C + c, m);
-  }
-}
-
-// Gather form (deterministic, no atomics): input element (ih,iw) receives dy of every window in which it is the
-// FIRST maximum in window scan order (row-major), which is where TF / Eigen route the gradient.
-template <int V, typename T>
-__global__ void maxpool_bwd_kernel(const PoolParams<T> p) {
-  const uint32_t cv = p.C / V;
-  const uint32_t total = (uint32_t)((int64_t)p.N * p.H * p.W * cv), stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    uint32_t pix, cc, row, iw, n, ih;
-    fd_divmod(i, p.fd_cv, pix, cc);
-    fd_divmod(pix, p.fd_w, row, iw);
-    fd_divmod(row, p.fd_h, n, ih);
-    const int c = (int)cc * V;
-    float xv[V], acc[V];
-    ldv<V>(p.x + (int64_t)pix * p.C + c, xv);
-#pragma unroll
-    for (int k = 0; k < V; ++k) acc[k] = 0.f;
-    // windows (oh, ow) that contain (ih, iw): oh*s - pt <= ih < oh*s - pt + k
-    const int th = (int)ih + p.pad_t, tw = (int)iw + p.pad_l;
-    int oh_hi = th / p.stride, ow_hi = tw / p.stride;
-    int oh_lo = (th - p.k + p.stride) / p.stride, ow_lo = (tw - p.k + p.stride) / p.stride;  // ceil((t-k+1)/s)
-    if (th - p.k + 1 <= 0) oh_lo = 0;
-    if (tw - p.k + 1 <= 0) ow_lo = 0;
-    if (oh_hi >= p.Ho) oh_hi = p.Ho - 1;
-    if (ow_hi >= p.Wo) ow_hi = p.Wo - 1;
-    for (int oh = oh_lo; oh <= oh_hi; ++oh) {
-      for (int ow = ow_lo; ow <= ow_hi; ++ow) {
-        const int64_t opix = ((int64_t)n * p.Ho + oh) * p.Wo + ow;
-        float yv[V], gv[V];
-        ldv<V>(p.y + opix * p.C + c, yv);
-        ldv<V>(p.dy + opix * p.C + c, gv);
-        bool first[V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) first[k] = (xv[k] == yv[k]);
-        // any earlier element of this window (scan order) equal to the max takes precedence
-        const int a0 = (int)ih - (oh * p.stride - p.pad_t), b0 = (int)iw - (ow * p.stride - p.pad_l);
-        for (int a = 0; a <= a0; ++a) {
-          const int jh = oh * p.stride - p.pad_t + a;
-          if ((unsigned)jh >= (unsigned)p.H) continue;
-          const int bend = (a == a0) ? b0 : p.k;
-          for (int b = 0; b < bend; ++b) {
-            const int jw = ow * p.stride - p.pad_l + b;
-            if ((unsigned)jw >= (unsigned)p.W) continue;
-            float ev[V];
-            ldv<V>(p.x + ((int64_t)(n * p.H + jh) * p.W + jw) * p.C + c, ev);
-#pragma unroll
-            for (int k = 0; k < V; ++k) first[k] = first[k] && !(ev[k] == yv[k]);
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < V; ++k) acc[k] += first[k] ? gv[k] : 0.f;
-      }
-    }
-    stv<V>(p.out + (int64_t)pix * p.C + c, acc);
-  }
-}
-
-// Training form (round 3): the forward also writes WHICH cell of the window held the (first) maximum, one byte per output
-// element (cell = a * k + b in scan order), and the backward reads that byte and dy instead of x, y and up to eight more x
-// values per window: 0.7 GB instead of 1.3 GB of traffic for the 256x256x128 pool of the Xception entry flow and a fraction
-// of the loads (maxpool_bwd_kernel: 711 us for a 280 us floor).  Same routing as maxpool_bwd_kernel: strict '>' keeps the
-// first maximum in scan order; a window of -inf only (or NaN only) routes to its first valid cell.
-template <int V, typename T>
-__global__ void maxpool_fwd_idx_kernel(const PoolParams<T> p, unsigned char* __restrict__ idx) {
-  const uint32_t cv = p.C / V;
-  const uint32_t total = (uint32_t)((int64_t)p.N * p.Ho * p.Wo * cv), stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    uint32_t pix, cc, row, ow, n, oh;
-    fd_divmod(i, p.fd_cv, pix, cc);
-    fd_divmod(pix, p.fd_w, row, ow);
-    fd_divmod(row, p.fd_h, n, oh);
-    const int c = (int)cc * V;
-    float m[V];
-    unsigned id[V];
-#pragma unroll
-    for (int k = 0; k < V; ++k) { m[k] = -INFINITY; id[k] = 255u; }
-    for (int a = 0; a < p.k; ++a) {
-      const int ih = (int)oh * p.stride - p.pad_t + a;
-      if ((unsigned)ih >= (unsigned)p.H) continue;
-      for (int b = 0; b < p.k; ++b) {
-        const int iw = (int)ow * p.stride - p.pad_l + b;
-        if ((unsigned)iw >= (unsigned)p.W) continue;
-        float xv[V];
-        ldv<V>(p.x + ((int64_t)(n * p.H + ih) * p.W + iw) * p.C + c, xv);
-        const unsigned cell = (unsigned)(a * p.k + b);
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-          const bool take = xv[k] > m[k] || id[k] == 255u;
-          m[k] = take ? xv[k] : m[k];
-          id[k] = take ? cell : id[k];
-        }
-      }
-    }
-    stv<V>(p.out + (int64_t)pix * p.C + c, m);
-    if constexpr (V == 4) {
-      *reinterpret_cast<unsigned*>(idx + (int64_t)pix * p.C + c) = id[0] | (id[1] << 8) | (id[2] << 16) | (id[3] << 24);
-    } else {
-#pragma unroll
-      for (int k = 0; k < V; ++k) idx[(int64_t)pix * p.C + c + k] = (unsigned char)id[k];
-    }
-  }
-}
-
-// gather, deterministic: input element (ih, iw) adds dy of every window whose recorded cell is (ih, iw)
-template <int V, typename T>
-__global__ void maxpool_bwd_idx_kernel(const PoolParams<T> p, const unsigned char* __restrict__ idx) {
-  const uint32_t cv = p.C / V;
-  const uint32_t total = (uint32_t)((int64_t)p.N * p.H * p.W * cv), stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    uint32_t pix, cc, row, iw, n, ih;
-    fd_divmod(i, p.fd_cv, pix, cc);
-    fd_divmod(pix, p.fd_w, row, iw);
-    fd_divmod(row, p.fd_h, n, ih);
-    const int c = (int)cc * V;
-    float acc[V];
-#pragma unroll
-    for (int k = 0; k < V; ++k) acc[k] = 0.f;
-    const int th = (int)ih + p.pad_t, tw = (int)iw + p.pad_l;
-    int oh_hi = th / p.stride, ow_hi = tw / p.stride;
-    int oh_lo = (th - p.k + p.stride) / p.stride, ow_lo = (tw - p.k + p.stride) / p.stride;  // ceil((t-k+1)/s)
-    if (th - p.k + 1 <= 0) oh_lo = 0;
-    if (tw - p.k + 1 <= 0) ow_lo = 0;
-    if (oh_hi >= p.Ho) oh_hi = p.Ho - 1;
-    if (ow_hi >= p.Wo) ow_hi = p.Wo - 1;
-    for (int oh = oh_lo; oh <= oh_hi; ++oh) {
-      const unsigned ca = (unsigned)(th - oh * p.stride) * (unsigned)p.k;
-      for (int ow = ow_lo; ow <= ow_hi; ++ow) {
-        const unsigned cell = ca + (unsigned)(tw - ow * p.stride);
-        const int64_t o = (((int64_t)n * p.Ho + oh) * p.Wo + ow) * p.C + c;
-        float gv[V];
-        ldv<V>(p.dy + o, gv);
-        if constexpr (V == 4) {
-          const unsigned w = *reinterpret_cast<const unsigned*>(idx + o);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) acc[k] += ((w >> (8 * k)) & 255u) == cell ? gv[k] : 0.f;
-        } else {
-#pragma unroll
-          for (int k = 0; k < V; ++k) acc[k] += (unsigned)idx[o + k] == cell ? gv[k] : 0.f;
-        }
-      }
-    }
-    stv<V>(p.out + (int64_t)pix * p.C + c, acc);
-  }
-}
-
-// AveragePooling2D(k) / GlobalAveragePooling2D as a segmented reduction: segment = output pixel (n,oh,ow),
-// rows = kh*kw window cells.
-template <typename T>
-struct AvgPoolOp {
-  static constexpr int NOUT = 1;
-  const T* __restrict__ x;
-  T* y;
-  int H, W, C, Ho, Wo, kh, kw;
-  FastDiv fd_howo, fd_wo, fd_kw;
-  template <int V>
-  __device__ __forceinline__ void accum(int seg, int64_t r, int c, float (&acc)[1][V]) const {
-    uint32_t n, rem, oh, ow, a, b;
-    fd_divmod((uint32_t)seg, fd_howo, n, rem);
-    fd_divmod(rem, fd_wo, oh, ow);
-    fd_divmod((uint32_t)r, fd_kw, a, b);
-    float xv[V];
-    ldv<V>(x + ((int64_t)(n * H + oh * kh + a) * W + ow * kw + b) * C + c, xv);
-#pragma unroll
-    for (int k = 0; k < V; ++k) acc[0][k] += xv[k];
-  }
-  __device__ __forceinline__ void finalize(int seg, int c, const double (&s)[1]) const {
-    st1<T>(y + (int64_t)seg * C + c, (float)(s[0] / (double)(kh * kw)));
-  }
-};
-
-template <int V, typename T>
-__global__ void avgpool_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx, int N, int H, int W, int C,
-                                   int kh, int kw, int accumulate, FastDiv fd_cv, FastDiv fd_w, FastDiv fd_h) {
-  const uint32_t cv = C / V;
-  const uint32_t total = (uint32_t)((int64_t)N * H * W * cv), stride = gridDim.x * blockDim.x;
-  const int Ho = H / kh, Wo = W / kw;
-  const float sc = 1.0f / (float)(kh * kw);
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    uint32_t pix, cc, row, iw, n, ih;
-    fd_divmod(i, fd_cv, pix, cc);
-    fd_divmod(pix, fd_w, row, iw);
-    fd_divmod(row, fd_h, n, ih);
-    const int c = (int)cc * V;
-    const int oh = (int)ih / kh, ow = (int)iw / kw;
-    float o[V];
-    if (oh < Ho && ow < Wo) {
-      ldv<V>(dy + (((int64_t)n * Ho + oh) * Wo + ow) * C + c, o);
-#pragma unroll
-      for (int k = 0; k < V; ++k) o[k] *= sc;
-    } else {
-#pragma unroll
-      for (int k = 0; k < V; ++k) o[k] = 0.f;
-    }
-    if (accumulate) {
-      float t[V];
-      ldv<V>(dx + (int64_t)pix * C + c, t);
-#pragma unroll
-      for (int k = 0; k < V; ++k) o[k] += t[k];
-    }
-    stv<V>(dx + (int64_t)pix * C + c, o);
-  }
-}
-
-template <int V, typename T>
-__global__ void upsample_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W, int C,
-                                    int sh, int sw, int y_ld, FastDiv fd_cv, FastDiv fd_w, FastDiv fd_h) {
-  const uint32_t cv = C / V;
-  const int OH = H * sh, OW = W * sw;
-  const uint32_t total = (uint32_t)((int64_t)N * OH * OW * cv), stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    uint32_t pix, cc, row, ow, n, oh;
-    fd_divmod(i, fd_cv, pix, cc);
-    fd_divmod(pix, fd_w, row, ow);
-    fd_divmod(row, fd_h, n, oh);
-    const int c = (int)cc * V;
-    float v[V];
-    ldv<V>(x + (((int64_t)n * H + oh / sh) * W + ow / sw) * C + c, v);
-    stv<V>(y + (int64_t)pix * y_ld + c, v);
-  }
-}
-
-template <int V, typename T>
-__global__ void upsample_bwd_kernel(const T* __restrict__ dy, int dy_ld, T* __restrict__ dx, int N, int H,
-                                    int W, int C, int sh, int sw, int accumulate, FastDiv fd_cv, FastDiv fd_w,
-                                    FastDiv fd_h) {
-  const uint32_t cv = C / V;
-  const uint32_t total = (uint32_t)((int64_t)N * H * W * cv), stride = gridDim.x * blockDim.x;
-  const int OW = W * sw, OH = H * sh;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    uint32_t pix, cc, row, iw, n, ih;
-    fd_divmod(i, fd_cv, pix, cc);
-    fd_divmod(pix, fd_w, row, iw);
-    fd_divmod(row, fd_h, n, ih);
-    const int c = (int)cc * V;
-    float acc[V];
-#pragma unroll
-    for (int k = 0; k < V; ++k) acc[k] = 0.f;
-    for (int a = 0; a < sh; ++a)
-      for (int b = 0; b < sw; ++b) {
-        float g[V];
-        ldv<V>(dy + (((int64_t)n * OH + ih * sh + a) * OW + iw * sw + b) * dy_ld + c, g);
-#pragma unroll
-        for (int k = 0; k < V; ++k) acc[k] += g[k];
-      }
-    if (accumulate) {
-      float t[V];
-      ldv<V>(dx + (int64_t)pix * C + c, t);
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] += t[k];
-    }
-    stv<V>(dx + (int64_t)pix * C + c, acc);
-  }
-}
-
-// Large windows (the ASPP image-pooling branch: 1x1 -> 32x32, 1024 cells per output element): the kernel above would give
-// each of N*C/4 = 1024 lanes a serial sum of 1024 loads (285 us for 17 MB).  Here a workgroup owns one output pixel and 8
-// channel chunks, 32 lanes share the window cells, the 32 partial sums are added in fixed order through LDS.
-template <typename T>
-__global__ __launch_bounds__(256) void upsample_bwd_window_kernel(const T* __restrict__ dy, int dy_ld, T* __restrict__ dx, int H,
-                                                                  int W, int C, int sh, int sw, int accumulate, FastDiv fd_w,
-                                                                  FastDiv fd_h, FastDiv fd_sw) {
-  constexpr int TX = 8, TY = 32;
-  __shared__ float red[TY][TX][4];
-  const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> 3;
-  const int c = (blockIdx.x * TX + tx) * 4;
-  uint32_t row, iw, n, ih;
-  fd_divmod(blockIdx.y, fd_w, row, iw);
-  fd_divmod(row, fd_h, n, ih);
-  const int OW = W * sw, OH = H * sh;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (c < C) {
-    const T* base = dy + (((int64_t)n * OH + ih * sh) * OW + iw * sw) * dy_ld + c;
-#pragma unroll 4
-    for (int r = ty; r < sh * sw; r += TY) {
-      uint32_t a, b;
-      fd_divmod((uint32_t)r, fd_sw, a, b);
-      const f32x4 g = ld4<T>(base + ((int64_t)a * OW + b) * dy_ld);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] += g[e];
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[ty][tx][e] = acc[e];
-  __syncthreads();
-  if (ty == 0 && c < C) {
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int y = 0; y < TY; ++y)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] += red[y][tx][e];
-    T* o = dx + (int64_t)blockIdx.y * C + c;
-    if (accumulate) {
-      const f32x4 t = ld4<T>(o);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] += t[e];
-    }
-    st4<T>(o, s);
-  }
-}
-
-// ---------------------------------------------------------------------------------------- bilinear up-sampling
-// tf.image.resize(method='bilinear'), half-pixel centres, integer factor s per axis.  Output o = i * s + p (phase p) sits at
-// in = i + t, t = (2p + 1 - s) / (2s) in [-1/2, 1/2):
-//   t < 0: lo = max(i - 1, 0), hi = i,                 f = t + 1
-//   t > 0: lo = i,             hi = min(i + 1, n - 1), f = t
-//   t = 0: lo = hi = i,                                f = 0      (odd s only; s = 1 is a copy)
-// so the weights depend on the phase alone and come from a per-axis table built in LDS by every workgroup (one correctly
-// rounded division of two small integers per entry; no division per element).
-__device__ __forceinline__ float bilinear_phase(int p, int s) {
-  const int t2 = 2 * p + 1 - s;
-  return (float)(t2 < 0 ? t2 + 2 * s : t2) / (float)(2 * s);
-}
-
-__device__ __forceinline__ void bilinear_taps(int i, int p, int s, int n, int& lo, int& hi) {
-  const int t2 = 2 * p + 1 - s;
-  lo = t2 < 0 ? max(i - 1, 0) : i;
-  hi = t2 > 0 ? min(i + 1, n - 1) : i;
-}
-
-// One work item = one output pixel x V channels: four loads (the 2 x 2 neighbours, three of them cache hits), columns
-// first, then rows (tf's order), one store.
-template <int V, typename T>
-__global__ void upsample_bilinear_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W, int C, int sh,
-                                             int sw, int y_ld, FastDiv fd_cv, FastDiv fd_w, FastDiv fd_h, FastDiv fd_sh,
-                                             FastDiv fd_sw) {
-  extern __shared__ float bilinear_tab[];   // [sh] row phases, then [sw] column phases
-  for (int p = threadIdx.x; p < sh + sw; p += blockDim.x) bilinear_tab[p] = p < sh ? bilinear_phase(p, sh) : bilinear_phase(p - sh, sw);
-  __syncthreads();
-  const float* fh = bilinear_tab;
-  const float* fw = bilinear_tab + sh;
-  const uint32_t cv = C / V;
-  const int OH = H * sh, OW = W * sw;
-  const uint32_t total = (uint32_t)((int64_t)N * OH * OW * cv), stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    uint32_t pix, cc, row, ow, n, oh, ih, ph, iw, pw;
-    fd_divmod(i, fd_cv, pix, cc);
-    fd_divmod(pix, fd_w, row, ow);
-    fd_divmod(row, fd_h, n, oh);
-    fd_divmod(oh, fd_sh, ih, ph);
-    fd_divmod(ow, fd_sw, iw, pw);
-    const int c = (int)cc * V;
-    int h0, h1, w0, w1;
-    bilinear_taps((int)ih, (int)ph, sh, H, h0, h1);
-    bilinear_taps((int)iw, (int)pw, sw, W, w0, w1);
-    const float fy = fh[ph], fx = fw[pw];
-    const T* r0 = x + ((int64_t)n * H + h0) * W * C + c;
-    const T* r1 = x + ((int64_t)n * H + h1) * W * C + c;
-    float tl[V], tr[V], bl[V], br[V], o[V];
-    ldv<V>(r0 + (int64_t)w0 * C, tl);
-    ldv<V>(r0 + (int64_t)w1 * C, tr);
-    ldv<V>(r1 + (int64_t)w0 * C, bl);
-    ldv<V>(r1 + (int64_t)w1 * C, br);
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      const float top = fmaf(tr[k] - tl[k], fx, tl[k]), bot = fmaf(br[k] - bl[k], fx, bl[k]);
-      o[k] = fmaf(bot - top, fy, top);
-    }
-    stv<V>(y + (int64_t)pix * y_ld + c, o);
-  }
-}
-
-// The transpose, as a gather so that no atomics are needed and the order of every sum is fixed (run-to-run bit-identity
-// and batch-slice invariance rest on that).  Per axis, dx[i] hears from the outputs o0 + d, o0 = (i - 1) * s + (s + 1) / 2,
-// d in [0, 2s - (s & 1)): the upper phases of block i - 1, block i, the lower phases of block i + 1.  Their weight is the
-// tent 1 - |in(o) - i| = wt[d], independent of i, except at the borders: outputs clamped onto row 0 / row n - 1 count in
-// full.  The table holds the numerators over 2s, each one correctly rounded division.
-__device__ __forceinline__ float bilinear_tent(int d, int s) {
-  const int orel = d + (s + 1) / 2, blk = orel / s, t2 = 2 * (orel - blk * s) + 1 - s;
-  const int num = blk == 0 ? t2 : blk == 1 ? (t2 < 0 ? t2 + 2 * s : 2 * s - t2) : (t2 < 0 ? -t2 : 0);
-  return (float)num / (float)(2 * s);
-}
-
-__device__ __forceinline__ void bilinear_tent_tables(float* tab, int sh, int sw) {   // [2 sh] rows, then [2 sw] columns
-  for (int p = threadIdx.x; p < 2 * (sh + sw); p += blockDim.x) tab[p] = p < 2 * sh ? bilinear_tent(p, sh) : bilinear_tent(p - 2 * sh, sw);
-  __syncthreads();
-}
-
-__device__ __forceinline__ float bilinear_weight(const float* wt, int d, int o, int i, int n, int s) {
-  return ((i == 0 && o < s / 2) || (i == n - 1 && o >= (n - 1) * s + (s + 1) / 2)) ? 1.f : wt[d];
-}
-
-// first and one-past-last d of axis position i whose output o0 + d exists
-__device__ __forceinline__ void bilinear_span(int i, int n, int s, int& o0, int& d0, int& d1) {
-  o0 = (i - 1) * s + (s + 1) / 2;
-  d0 = max(0, -o0);
-  d1 = min(2 * s - (s & 1), n * s - o0);
-}
-
-// One work item = one dx pixel x V channels; it walks its at most 2 sh x 2 sw outputs rows outer, columns inner.
-template <int V, typename T>
-__global__ void upsample_bilinear_bwd_kernel(const T* __restrict__ dy, int dy_ld, T* __restrict__ dx, int N, int H, int W,
-                                             int C, int sh, int sw, int accumulate, FastDiv fd_cv, FastDiv fd_w, FastDiv fd_h) {
-  extern __shared__ float bilinear_tab[];
-  bilinear_tent_tables(bilinear_tab, sh, sw);
-  const float* wth = bilinear_tab;
-  const float* wtw = bilinear_tab + 2 * sh;
-  const uint32_t cv = C / V;
-  const uint32_t total = (uint32_t)((int64_t)N * H * W * cv), stride = gridDim.x * blockDim.x;
-  const int OW = W * sw, OH = H * sh;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    uint32_t pix, cc, row, iw, n, ih;
-    fd_divmod(i, fd_cv, pix, cc);
-    fd_divmod(pix, fd_w, row, iw);
-    fd_divmod(row, fd_h, n, ih);
-    const int c = (int)cc * V;
-    int oh0, a0, a1, ow0, b0, b1;
-    bilinear_span((int)ih, H, sh, oh0, a0, a1);
-    bilinear_span((int)iw, W, sw, ow0, b0, b1);
-    float acc[V];
-#pragma unroll
-    for (int k = 0; k < V; ++k) acc[k] = 0.f;
-    for (int a = a0; a < a1; ++a) {
-      const float wy = bilinear_weight(wth, a, oh0 + a, (int)ih, H, sh);
-      const T* rowp = dy + (((int64_t)n * OH + oh0 + a) * OW + ow0) * dy_ld + c;
-      for (int b = b0; b < b1; ++b) {
-        const float wgt = wy * bilinear_weight(wtw, b, ow0 + b, (int)iw, W, sw);
-        float g[V];
-        ldv<V>(rowp + (int64_t)b * dy_ld, g);
-#pragma unroll
-        for (int k = 0; k < V; ++k) acc[k] = fmaf(g[k], wgt, acc[k]);
-      }
-    }
-    if (accumulate) {
-      float t[V];
-      ldv<V>(dx + (int64_t)pix * C + c, t);
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] += t[k];
-    }
-    stv<V>(dx + (int64_t)pix * C + c, acc);
-  }
-}
-
-// Large factors (the ASPP image-pooling branch again: 1x1 -> 32x32), the shape of upsample_bwd_window_kernel: a workgroup
-// owns one dx pixel and 8 channel chunks, 32 lanes share the pixel's cells (cell r = row-major index in its span, lane ty
-// takes r = ty, ty + 32, ...), the 32 partial sums are added in fixed order through LDS.
-template <typename T>
-__global__ __launch_bounds__(256) void upsample_bilinear_bwd_window_kernel(const T* __restrict__ dy, int dy_ld, T* __restrict__ dx,
-                                                                           int H, int W, int C, int sh, int sw, int accumulate,
-                                                                           FastDiv fd_w, FastDiv fd_h) {
-  constexpr int TX = 8, TY = 32;
-  __shared__ float red[TY][TX][4];
-  extern __shared__ float bilinear_tab[];
-  bilinear_tent_tables(bilinear_tab, sh, sw);
-  const float* wth = bilinear_tab;
-  const float* wtw = bilinear_tab + 2 * sh;
-  const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> 3;
-  const int c = (blockIdx.x * TX + tx) * 4;
-  uint32_t row, iw, n, ih;
-  fd_divmod(blockIdx.y, fd_w, row, iw);
-  fd_divmod(row, fd_h, n, ih);
-  const int OW = W * sw, OH = H * sh;
-  int oh0, a0, a1, ow0, b0, b1;
-  bilinear_span((int)ih, H, sh, oh0, a0, a1);
-  bilinear_span((int)iw, W, sw, ow0, b0, b1);
-  const int nw = b1 - b0, cells = (a1 - a0) * nw;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (c < C) {
-    const T* base = dy + (((int64_t)n * OH + oh0) * OW + ow0) * dy_ld + c;
-    int a = a0 + ty / nw, b = b0 + ty % nw;
-    for (int r = ty; r < cells; r += TY) {
-      const float wgt = bilinear_weight(wth, a, oh0 + a, (int)ih, H, sh) * bilinear_weight(wtw, b, ow0 + b, (int)iw, W, sw);
-      const f32x4 g = ld4<T>(base + ((int64_t)a * OW + b) * dy_ld);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = fmaf(g[e], wgt, acc[e]);
-      for (b += TY; b >= b1; b -= nw) ++a;
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[ty][tx][e] = acc[e];
-  __syncthreads();
-  if (ty == 0 && c < C) {
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int y = 0; y < TY; ++y)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] += red[y][tx][e];
-    T* o = dx + (int64_t)blockIdx.y * C + c;
-    if (accumulate) {
-      const f32x4 t = ld4<T>(o);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] += t[e];
-    }
-    st4<T>(o, s);
-  }
-}
-
 int dw_check(const sg_ctx* ctx, int dtype, const sg_conv_desc* d, const char* who) {
   SG_CHECK_ARG(ctx && (dtype == SG_F32 || dtype == SG_BF16) && d, "%s: bad ctx/dtype/desc", who);
   SG_CHECK_ARG(d->Cin == d->Cout, "%s: depthwise needs Cin == Cout (depth_multiplier 1)", who);
@@ -1708,250 +1185,6 @@ int sg_dwconv2d_wgrad(sg_ctx* ctx, void* stream, int dtype, const sg_conv_desc* 
     op.fd_w = make_fastdiv((uint32_t)d->Wo); op.fd_h = make_fastdiv((uint32_t)d->Ho);
     return seg_reduce_launch(op, pl.seg, 1, (int64_t)d->N * d->Ho * d->Wo, d->Cin, (float*)ws, (hipStream_t)stream, "dw_wgrad");
   });
-  return 0;
-}
-
-int sg_maxpool_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int k, int stride, int pad_t,
-                   int pad_l, int Ho, int Wo, const void* x, void* y) {
-  SG_CHECK_ARG(ctx && x && y, "sg_maxpool_fwd: bad argument");
-  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && Ho > 0 && Wo > 0 && pad_t >= 0 && pad_l >= 0,
-               "sg_maxpool_fwd: bad geometry");
-  SG_CHECK_ARG((int64_t)N * H * W * C < (1ll << 31), "sg_maxpool_fwd: tensor exceeds 2^31 elements");
-  SG_DTYPE_SWITCH(dtype, "sg_maxpool_fwd", {
-    PoolParams<T> p;
-    p.x = (const T*)x; p.y = nullptr; p.dy = nullptr; p.out = (T*)y;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.k = k; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-    const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
-    const int V = vec ? 4 : 1;
-    p.fd_cv = make_fastdiv((uint32_t)(C / V)); p.fd_w = make_fastdiv((uint32_t)Wo); p.fd_h = make_fastdiv((uint32_t)Ho);
-    const unsigned blocks = ew_blocks((int64_t)N * Ho * Wo * (C / V), EW_CAP);
-    if (vec) hipLaunchKernelGGL((maxpool_fwd_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((maxpool_fwd_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-  });
-  SG_LAUNCH_CHECK("maxpool_fwd_kernel");
-  return 0;
-}
-
-int sg_maxpool_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int k, int stride, int pad_t,
-                   int pad_l, int Ho, int Wo, const void* x, const void* y, const void* dy, void* dx) {
-  SG_CHECK_ARG(ctx && x && y && dy && dx, "sg_maxpool_bwd: bad argument");
-  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && Ho > 0 && Wo > 0 && pad_t >= 0 && pad_l >= 0,
-               "sg_maxpool_bwd: bad geometry");
-  SG_CHECK_ARG((int64_t)N * H * W * C < (1ll << 31), "sg_maxpool_bwd: tensor exceeds 2^31 elements");
-  SG_DTYPE_SWITCH(dtype, "sg_maxpool_bwd", {
-    PoolParams<T> p;
-    p.x = (const T*)x; p.y = (const T*)y; p.dy = (const T*)dy; p.out = (T*)dx;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.k = k; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-    const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(y) && sg_aligned16(dy) && sg_aligned16(dx);
-    const int V = vec ? 4 : 1;
-    p.fd_cv = make_fastdiv((uint32_t)(C / V)); p.fd_w = make_fastdiv((uint32_t)W); p.fd_h = make_fastdiv((uint32_t)H);
-    const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V), EW_CAP);
-    if (vec) hipLaunchKernelGGL((maxpool_bwd_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((maxpool_bwd_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-  });
-  SG_LAUNCH_CHECK("maxpool_bwd_kernel");
-  return 0;
-}
-
-int sg_maxpool_fwd_idx(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int k, int stride, int pad_t,
-                       int pad_l, int Ho, int Wo, const void* x, void* y, void* idx) {
-  SG_CHECK_ARG(ctx && x && y && idx, "sg_maxpool_fwd_idx: bad argument");
-  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && k <= 15 && stride > 0 && Ho > 0 && Wo > 0 && pad_t >= 0 && pad_l >= 0,
-               "sg_maxpool_fwd_idx: bad geometry (windows up to 15 x 15: the cell index is one byte)");
-  SG_CHECK_ARG((int64_t)N * H * W * C < (1ll << 31), "sg_maxpool_fwd_idx: tensor exceeds 2^31 elements");
-  SG_DTYPE_SWITCH(dtype, "sg_maxpool_fwd_idx", {
-    PoolParams<T> p;
-    p.x = (const T*)x; p.y = nullptr; p.dy = nullptr; p.out = (T*)y;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.k = k; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-    const bool vec = (C % 4 == 0) && sg_aligned16(x) && sg_aligned16(y) && sg_aligned16(idx);
-    const int V = vec ? 4 : 1;
-    p.fd_cv = make_fastdiv((uint32_t)(C / V)); p.fd_w = make_fastdiv((uint32_t)Wo); p.fd_h = make_fastdiv((uint32_t)Ho);
-    const unsigned blocks = ew_blocks((int64_t)N * Ho * Wo * (C / V), EW_CAP);
-    if (vec) hipLaunchKernelGGL((maxpool_fwd_idx_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, (unsigned char*)idx);
-    else hipLaunchKernelGGL((maxpool_fwd_idx_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, (unsigned char*)idx);
-  });
-  SG_LAUNCH_CHECK("maxpool_fwd_idx_kernel");
-  return 0;
-}
-
-int sg_maxpool_bwd_idx(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int k, int stride, int pad_t,
-                       int pad_l, int Ho, int Wo, const void* dy, const void* idx, void* dx) {
-  SG_CHECK_ARG(ctx && dy && idx && dx, "sg_maxpool_bwd_idx: bad argument");
-  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && k <= 15 && stride > 0 && Ho > 0 && Wo > 0 && pad_t >= 0 && pad_l >= 0,
-               "sg_maxpool_bwd_idx: bad geometry");
-  SG_CHECK_ARG((int64_t)N * H * W * C < (1ll << 31), "sg_maxpool_bwd_idx: tensor exceeds 2^31 elements");
-  SG_DTYPE_SWITCH(dtype, "sg_maxpool_bwd_idx", {
-    PoolParams<T> p;
-    p.x = nullptr; p.y = nullptr; p.dy = (const T*)dy; p.out = (T*)dx;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.k = k; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-    const bool vec = (C % 4 == 0) && sg_aligned16(dy) && sg_aligned16(dx) && sg_aligned16(idx);
-    const int V = vec ? 4 : 1;
-    p.fd_cv = make_fastdiv((uint32_t)(C / V)); p.fd_w = make_fastdiv((uint32_t)W); p.fd_h = make_fastdiv((uint32_t)H);
-    const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V), EW_CAP);
-    if (vec) hipLaunchKernelGGL((maxpool_bwd_idx_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, (const unsigned char*)idx);
-    else hipLaunchKernelGGL((maxpool_bwd_idx_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, (const unsigned char*)idx);
-  });
-  SG_LAUNCH_CHECK("maxpool_bwd_idx_kernel");
-  return 0;
-}
-
-size_t sg_avgpool_ws_bytes(const sg_ctx* ctx, int N, int H, int W, int C, int kh, int kw) {
-  if (!ctx || kh <= 0 || kw <= 0) return 0;
-  const int nseg = N * (H / kh) * (W / kw);
-  const SegPlan a = seg_plan<1>(ctx->num_cus, nseg, (int64_t)kh * kw, C, true),
-                b = seg_plan<1>(ctx->num_cus, nseg, (int64_t)kh * kw, C, false);
-  return (a.part_bytes > b.part_bytes ? a.part_bytes : b.part_bytes) + 256;
-}
-
-int sg_avgpool_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int kh, int kw, const void* x,
-                   void* y, void* ws, size_t ws_bytes) {
-  SG_CHECK_ARG(ctx && x && y, "sg_avgpool_fwd: bad argument");
-  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && kh > 0 && kw > 0 && H >= kh && W >= kw, "sg_avgpool_fwd: bad geometry");
-  SG_CHECK_ARG((int64_t)N * H * W * C < (1ll << 31), "sg_avgpool_fwd: tensor exceeds 2^31 elements");
-  SG_DTYPE_SWITCH(dtype, "sg_avgpool_fwd", {
-  AvgPoolOp<T> op;
-  op.x = (const T*)x; op.y = (T*)y; op.H = H; op.W = W; op.C = C; op.Ho = H / kh; op.Wo = W / kw; op.kh = kh; op.kw = kw;
-  op.fd_howo = make_fastdiv((uint32_t)(op.Ho * op.Wo)); op.fd_wo = make_fastdiv((uint32_t)op.Wo); op.fd_kw = make_fastdiv((uint32_t)kw);
-  const int nseg = N * op.Ho * op.Wo;
-  const bool vec = (C % 4 == 0) && sg_aligned16(x);
-  const SegPlan pl = seg_plan<1>(ctx->num_cus, nseg, (int64_t)kh * kw, C, vec);
-  if (!ws || ws_bytes < pl.part_bytes) {
-    sg_set_error("sg_avgpool_fwd: workspace %zu < %zu", ws_bytes, pl.part_bytes);
-    return SG_EWORKSPACE;
-  }
-  return seg_reduce_launch(op, pl, nseg, (int64_t)kh * kw, C, (float*)ws, (hipStream_t)stream, "avgpool_fwd");
-  });
-  return 0;
-}
-
-int sg_avgpool_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int kh, int kw, const void* dy,
-                   void* dx, int accumulate) {
-  SG_CHECK_ARG(ctx && dy && dx, "sg_avgpool_bwd: bad argument");
-  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && kh > 0 && kw > 0 && H >= kh && W >= kw, "sg_avgpool_bwd: bad geometry");
-  SG_CHECK_ARG((int64_t)N * H * W * C < (1ll << 31), "sg_avgpool_bwd: tensor exceeds 2^31 elements");
-  const bool vec = (C % 4 == 0) && sg_aligned16(dy) && sg_aligned16(dx);
-  const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V), EW_CAP);
-  const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)W), c = make_fastdiv((uint32_t)H);
-  SG_DTYPE_SWITCH(dtype, "sg_avgpool_bwd", {
-    if (vec)
-      hipLaunchKernelGGL((avgpool_bwd_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (T*)dx, N, H,
-                         W, C, kh, kw, accumulate, a, b, c);
-    else
-      hipLaunchKernelGGL((avgpool_bwd_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (T*)dx, N, H,
-                         W, C, kh, kw, accumulate, a, b, c);
-  });
-  SG_LAUNCH_CHECK("avgpool_bwd_kernel");
-  return 0;
-}
-
-int sg_upsample_nearest_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int sh, int sw,
-                            const void* x, void* y, int y_ld) {
-  SG_CHECK_ARG(ctx && x && y, "sg_upsample_nearest_fwd: bad argument");
-  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && sh > 0 && sw > 0, "sg_upsample_nearest_fwd: bad geometry");
-  if (y_ld == 0) y_ld = C;
-  SG_CHECK_ARG(y_ld >= C, "sg_upsample_nearest_fwd: y_ld < C");
-  SG_CHECK_ARG((int64_t)N * H * sh * W * sw * y_ld < (1ll << 31), "sg_upsample_nearest_fwd: tensor exceeds 2^31 elements");
-  const bool vec = (C % 4 == 0) && (y_ld % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
-  const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks((int64_t)N * H * sh * W * sw * (C / V), EW_CAP);
-  const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)(W * sw)), c = make_fastdiv((uint32_t)(H * sh));
-  SG_DTYPE_SWITCH(dtype, "sg_upsample_nearest_fwd", {
-    if (vec)
-      hipLaunchKernelGGL((upsample_fwd_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, N, H, W,
-                         C, sh, sw, y_ld, a, b, c);
-    else
-      hipLaunchKernelGGL((upsample_fwd_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, N, H, W,
-                         C, sh, sw, y_ld, a, b, c);
-  });
-  SG_LAUNCH_CHECK("upsample_fwd_kernel");
-  return 0;
-}
-
-int sg_upsample_nearest_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int sh, int sw,
-                            const void* dy, int dy_ld, void* dx, int accumulate) {
-  SG_CHECK_ARG(ctx && dy && dx, "sg_upsample_nearest_bwd: bad argument");
-  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && sh > 0 && sw > 0, "sg_upsample_nearest_bwd: bad geometry");
-  if (dy_ld == 0) dy_ld = C;
-  SG_CHECK_ARG(dy_ld >= C, "sg_upsample_nearest_bwd: dy_ld < C");
-  SG_CHECK_ARG((int64_t)N * H * sh * W * sw * dy_ld < (1ll << 31), "sg_upsample_nearest_bwd: tensor exceeds 2^31 elements");
-  const bool vec = (C % 4 == 0) && (dy_ld % 4 == 0) && sg_aligned16(dy) && sg_aligned16(dx);
-  const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V), EW_CAP);
-  const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)W), c = make_fastdiv((uint32_t)H);
-  SG_DTYPE_SWITCH(dtype, "sg_upsample_nearest_bwd", {
-    if (vec && sh * sw >= 64 && (int64_t)N * H * W < 65536) {
-      hipLaunchKernelGGL((upsample_bwd_window_kernel<T>), dim3((unsigned)sg_cdiv(C / 4, 8), (unsigned)(N * H * W)), dim3(256), 0,
-                         (hipStream_t)stream, (const T*)dy, dy_ld, (T*)dx, H, W, C, sh, sw, accumulate, b, c,
-                         make_fastdiv((uint32_t)sw));
-    } else if (vec)
-      hipLaunchKernelGGL((upsample_bwd_kernel<4, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)dy, dy_ld, (T*)dx,
-                         N, H, W, C, sh, sw, accumulate, a, b, c);
-    else
-      hipLaunchKernelGGL((upsample_bwd_kernel<1, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)dy, dy_ld, (T*)dx,
-                         N, H, W, C, sh, sw, accumulate, a, b, c);
-  });
-  SG_LAUNCH_CHECK("upsample_bwd_kernel");
-  return 0;
-}
-
-// The phase tables live in LDS, so a factor is capped (far above any use: the ASPP branch's 32 is the largest known).
-#define SG_BILINEAR_MAX_FACTOR 1024
-
-int sg_upsample_bilinear_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int sh, int sw,
-                             const void* x, void* y, int y_ld) {
-  SG_CHECK_ARG(ctx && x && y, "sg_upsample_bilinear_fwd: bad argument");
-  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && sh > 0 && sw > 0 && sh <= SG_BILINEAR_MAX_FACTOR && sw <= SG_BILINEAR_MAX_FACTOR,
-               "sg_upsample_bilinear_fwd: bad geometry");
-  if (y_ld == 0) y_ld = C;
-  SG_CHECK_ARG(y_ld >= C, "sg_upsample_bilinear_fwd: y_ld < C");
-  SG_CHECK_ARG((int64_t)N * H * sh * W * sw * y_ld < (1ll << 31), "sg_upsample_bilinear_fwd: tensor exceeds 2^31 elements");
-  // the vector form under sg_upsample_nearest_fwd's conditions
-  const bool vec = (C % 4 == 0) && (y_ld % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
-  const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks((int64_t)N * H * sh * W * sw * (C / V), EW_CAP);
-  const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)(W * sw)), c = make_fastdiv((uint32_t)(H * sh));
-  const FastDiv dh = make_fastdiv((uint32_t)sh), dw = make_fastdiv((uint32_t)sw);
-  const size_t lds = (size_t)(sh + sw) * sizeof(float);
-  SG_DTYPE_SWITCH(dtype, "sg_upsample_bilinear_fwd", {
-    if (vec)
-      hipLaunchKernelGGL((upsample_bilinear_fwd_kernel<4, T>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const T*)x, (T*)y,
-                         N, H, W, C, sh, sw, y_ld, a, b, c, dh, dw);
-    else
-      hipLaunchKernelGGL((upsample_bilinear_fwd_kernel<1, T>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const T*)x, (T*)y,
-                         N, H, W, C, sh, sw, y_ld, a, b, c, dh, dw);
-  });
-  SG_LAUNCH_CHECK("upsample_bilinear_fwd_kernel");
-  return 0;
-}
-
-int sg_upsample_bilinear_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int sh, int sw,
-                             const void* dy, int dy_ld, void* dx, int accumulate) {
-  SG_CHECK_ARG(ctx && dy && dx, "sg_upsample_bilinear_bwd: bad argument");
-  SG_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && sh > 0 && sw > 0 && sh <= SG_BILINEAR_MAX_FACTOR && sw <= SG_BILINEAR_MAX_FACTOR,
-               "sg_upsample_bilinear_bwd: bad geometry");
-  if (dy_ld == 0) dy_ld = C;
-  SG_CHECK_ARG(dy_ld >= C, "sg_upsample_bilinear_bwd: dy_ld < C");
-  SG_CHECK_ARG((int64_t)N * H * sh * W * sw * dy_ld < (1ll << 31), "sg_upsample_bilinear_bwd: tensor exceeds 2^31 elements");
-  const bool vec = (C % 4 == 0) && (dy_ld % 4 == 0) && sg_aligned16(dy) && sg_aligned16(dx);
-  const int V = vec ? 4 : 1;
-  const unsigned blocks = ew_blocks((int64_t)N * H * W * (C / V), EW_CAP);
-  const FastDiv a = make_fastdiv((uint32_t)(C / V)), b = make_fastdiv((uint32_t)W), c = make_fastdiv((uint32_t)H);
-  const size_t lds = (size_t)2 * (sh + sw) * sizeof(float);
-  SG_DTYPE_SWITCH(dtype, "sg_upsample_bilinear_bwd", {
-    // The window kernel under sg_upsample_nearest_bwd's predicate: 16-byte channel chunks, at least 64 cells per block of
-    // the factor (a dx pixel then has up to 4 sh sw >= 256 taps), and few enough dx pixels for grid.y.
-    if (vec && sh * sw >= 64 && (int64_t)N * H * W < 65536) {
-      hipLaunchKernelGGL((upsample_bilinear_bwd_window_kernel<T>), dim3((unsigned)sg_cdiv(C / 4, 8), (unsigned)(N * H * W)), dim3(256),
-                         lds, (hipStream_t)stream, (const T*)dy, dy_ld, (T*)dx, H, W, C, sh, sw, accumulate, b, c);
-    } else if (vec)
-      hipLaunchKernelGGL((upsample_bilinear_bwd_kernel<4, T>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const T*)dy, dy_ld,
-                         (T*)dx, N, H, W, C, sh, sw, accumulate, a, b, c);
-    else
-      hipLaunchKernelGGL((upsample_bilinear_bwd_kernel<1, T>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const T*)dy, dy_ld,
-                         (T*)dx, N, H, W, C, sh, sw, accumulate, a, b, c);
-  });
-  SG_LAUNCH_CHECK("upsample_bilinear_bwd_kernel");
   return 0;
 }
 

@@ -1,4 +1,4 @@
-"""Every variant of the HBM-bound kernels (csrc/pointwise.hip, the pooling / up-sampling part of csrc/spatial.hip, the loss,
+"""Every variant of the HBM-bound kernels (csrc/pointwise.hip, the pooling / up-sampling kernels of csrc/resample.hip, the loss,
 Adam, metrics and tail kernels of csrc/train.hip) against plain float64 torch on the CPU, through the C ABI itself.
 
 Each entry point picks one of several kernels at launch time; every case below names the dispatch predicate it satisfies.
@@ -29,7 +29,7 @@ F32, BF16 = torch.float32, torch.bfloat16
 DTYPES = [pytest.param(F32, id="f32"), pytest.param(BF16, id="bf16")]
 OFFS = [pytest.param(False, id="aligned"), pytest.param(True, id="offset")]
 EW_CAP = 8192 * 256      # work items after which pointwise.hip's / train.hip's grid-stride loops take a second trip
-SP_CAP = 16384 * 256     # the same for spatial.hip's ew_blocks
+SP_CAP = 16384 * 256     # the same for resample.hip's ew_blocks
 
 
 def sgdt(dtype):
@@ -545,7 +545,7 @@ def test_maxpool(engine, dtype, off, cfg, Cc):
 
 @gpu
 def test_maxpool_wrapped(engine):
-    # scalar kernels (C = 5), spatial.hip's ew_blocks caps at 16384 blocks: the backward kernels walk N H W C = 917 * 917 * 5 =
+    # scalar kernels (C = 5), resample.hip's ew_blocks caps at 16384 blocks: the backward kernels walk N H W C = 917 * 917 * 5 =
     # 4 204 445 > 16384 * 256 input elements (17 MB in fp32)
     _maxpool_case(engine, F32, False, (2, 2, False), 1, 917, 917, 5, ref_dtype=torch.float32)
     # ... and the forward kernels N Ho Wo C = 917 * 917 * 5 output elements: H = W = 1835 (odd), bf16 (34 MB)
@@ -562,6 +562,21 @@ AVGPOOLS = [
     (2, 64, 64, 64, 64, 64, "many"),   # global pool of 4096 rows: S = 64 >= 32 (16-lane finalize)
     (2, 64, 64, 45, 64, 64, "many"),   # the same, scalar
 ]
+
+
+def _avgpool_bwd_case(engine, dtype, off, N, H, W, Cc, kh, kw, dy, prior, what):
+    dt, Ho, Wo = sgdt(dtype), H // kh, W // kw
+    dref = avgpool_bwd_ref(dy.double(), H, W, kh, kw)
+    for acc in (0, 1):
+        DY, DX = G(dy, off), out_or_prior(prior, acc, off)
+        done(engine, call(engine, "sg_avgpool_bwd", dt, N, H, W, Cc, kh, kw, DY.ptr(), DX.ptr(), acc), what + f" bwd acc={acc}", DY, DX)
+        dx = DX.read()
+        assert_written(dx, what)
+        close(dx, dref + prior.double() if acc else dref, tol(dtype), what + f" bwd acc={acc}")
+        rem, want_rem = dx.clone(), (prior if acc else torch.zeros_like(prior)).clone()
+        rem[:, :Ho * kh, :Wo * kw] = 0
+        want_rem[:, :Ho * kh, :Wo * kw] = 0
+        assert torch.equal(rem, want_rem), what + ": the remainder rows / columns receive zero (stay untouched under accumulate)"
 
 
 @gpu
@@ -584,17 +599,16 @@ def test_avgpool(engine, dtype, off, case):
     done(engine, call(engine, "sg_avgpool_fwd", dt, N, H, W, Cc, kh, kw, X.ptr(), Y.ptr(), Wk.ptr(), nws), what, X, Y, Wk)
     assert_written(Y.read(), what)
     close(Y.read(), avgpool_ref(x.double(), kh, kw), tol(dtype, True), what + " fwd")     # the remainder contributes nothing
-    dref = avgpool_bwd_ref(dy.double(), H, W, kh, kw)
-    for acc in (0, 1):
-        DY, DX = G(dy, off), out_or_prior(prior, acc, off)
-        done(engine, call(engine, "sg_avgpool_bwd", dt, N, H, W, Cc, kh, kw, DY.ptr(), DX.ptr(), acc), what + f" bwd acc={acc}", DY, DX)
-        dx = DX.read()
-        assert_written(dx, what)
-        close(dx, dref + prior.double() if acc else dref, tol(dtype), what + f" bwd acc={acc}")
-        rem, want_rem = dx.clone(), (prior if acc else torch.zeros_like(prior)).clone()
-        rem[:, :Ho * kh, :Wo * kw] = 0
-        want_rem[:, :Ho * kh, :Wo * kw] = 0
-        assert torch.equal(rem, want_rem), what + ": the remainder rows / columns receive zero (stay untouched under accumulate)"
+    _avgpool_bwd_case(engine, dtype, off, N, H, W, Cc, kh, kw, dy, prior, what)
+
+
+@gpu
+def test_avgpool_wrapped(engine):
+    # scalar backward kernel (C = 5): N H W C = 917 * 917 * 5 = 4 204 445 > 16384 * 256 input elements; H % kh = W % kw = 1
+    N, H, W, Cc, kh, kw = 1, 917, 917, 5, 2, 2
+    g = gen("avgpool wrapped")
+    dy, prior = rnd(g, N, H // kh, W // kw, Cc, dtype=F32), rnd(g, N, H, W, Cc, dtype=F32)
+    _avgpool_bwd_case(engine, F32, False, N, H, W, Cc, kh, kw, dy, prior, "avgpool wrapped")
 
 
 # ------------------------------------------------------------------------------------------------ up-sampling
@@ -653,6 +667,13 @@ def test_upsample_wrapped(engine):
     _up_bwd_case(engine, F32, False, 1, 917, 917, 5, 1, 2, 5)
     # scalar forward kernel: N (H sh) (W sw) C = 917 * 2 * 459 * 5 = 4 209 030 > 16384 * 256
     _up_fwd_case(engine, F32, False, 1, 917, 459, 5, 1, 2, 5, 0)
+
+
+@gpu
+def test_upsample_wrapped_vector(engine):
+    # the V = 4 form's second trip, through the cheapest op with an exact reference (a copy: sh = sw = 1): N H W C / 4 =
+    # 1025 * 1025 * 4 = 4 202 500 > 16384 * 256 = 4 194 304 chunks (67 MB in fp32, aligned, dense)
+    _up_fwd_case(engine, F32, False, 1, 1025, 1025, 16, 1, 1, 16, 0)
 
 
 # ================================================================================================ loss / metrics

@@ -1,4 +1,4 @@
-"""sg_upsample_bilinear_fwd / _bwd (csrc/spatial.hip) through the C ABI, in tests/_guarded.py arenas, against float64 on the CPU.
+"""sg_upsample_bilinear_fwd / _bwd (csrc/resample.hip) through the C ABI, in tests/_guarded.py arenas, against float64 on the CPU.
 
 Semantics: tf.image.resize(method='bilinear'), half-pixel centres, no antialiasing, integer factor s per axis:
     in = (o + 0.5) / s - 0.5,  lo = max(floor(in), 0),  hi = min(ceil(in), n - 1),  f = in - floor(in),  y = x[lo] + (x[hi] - x[lo]) f
@@ -21,7 +21,7 @@ DEV = "cuda"
 F32, BF16, F64 = torch.float32, torch.bfloat16, torch.float64
 DTYPES = [pytest.param(F32, id="f32"), pytest.param(BF16, id="bf16")]
 OFFS = [pytest.param(False, id="aligned"), pytest.param(True, id="offset")]
-SP_CAP = 16384 * 256     # work items after which spatial.hip's grid-stride loops take a second trip
+SP_CAP = 16384 * 256     # work items after which resample.hip's grid-stride loops take a second trip
 REF_AGREE = 1e-12
 
 

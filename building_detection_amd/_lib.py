@@ -25,6 +25,10 @@ SG_AUGMENT_MAX_ITEMS = 64
 SG_AUG_FLIP_UD, SG_AUG_FLIP_LR, SG_AUG_SWAP_RB, SG_AUG_THRESHOLD = 1, 2, 4, 8
 SG_SCENE_MAX_ITEMS = 64
 SG_SYM_FLIP_UD, SG_SYM_FLIP_LR, SG_SYM_TRANSPOSE = 1, 2, 4
+SG_OPT_ADAM, SG_OPT_SGD = 0, 1
+SG_OPT_AMSGRAD, SG_OPT_NESTEROV, SG_OPT_EMA = 1, 2, 4
+SG_OPT_CLIP_NONE, SG_OPT_CLIP_VALUE, SG_OPT_CLIP_NORM, SG_OPT_CLIP_GLOBAL = 0, 1, 2, 3
+SG_OPT_SEG_DECAY = 1
 
 
 class SgError(RuntimeError):
@@ -56,6 +60,28 @@ class RegionDesc(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("C", "y_cols", "images", "point_kind")] + [("rows_per_image", C.c_int64)] +
                 [(n, C.c_float) for n in ("a", "b", "smooth", "gamma", "point_weight", "region_weight")] +
                 [("class_w", C.c_float * SG_MAX_CLASSES), ("point_alpha", C.c_float * SG_MAX_CLASSES)])
+
+
+class OptimChunk(C.Structure):
+    """Mirror of `sg_optim_chunk` (include/segengine.h): a 16-byte aligned run of one parameter's elements."""
+    _fields_ = [("start", C.c_int64), ("length", C.c_int32), ("segment", C.c_int32)]
+
+
+class OptimSeg(C.Structure):
+    """Mirror of `sg_optim_seg` (include/segengine.h): one trainable parameter's chunks and flags."""
+    _fields_ = [(n, C.c_int32) for n in ("chunk_begin", "chunk_end", "flags", "reserved")]
+
+
+class OptimTable(C.Structure):
+    """Mirror of `sg_optim_table` (include/segengine.h): the chunk table in host and in device memory."""
+    _fields_ = [("chunks", C.c_void_p), ("segs", C.c_void_p), ("chunks_dev", C.c_void_p), ("segs_dev", C.c_void_p),
+                ("nchunks", C.c_int32), ("nseg", C.c_int32), ("n", C.c_int64)]
+
+
+class OptimDesc(C.Structure):
+    """Mirror of `sg_optim_desc` (include/segengine.h): the update rule of sg_optim_step."""
+    _fields_ = ([(n, C.c_int32) for n in ("kind", "flags", "clip")] + [(n, C.c_float) for n in (
+        "beta1", "beta2", "eps", "momentum", "weight_decay", "clip_c", "ema_momentum", "grad_scale")])
 
 
 class ConvDesc(C.Structure):
@@ -303,6 +329,9 @@ _SIGNATURES = {
     "sg_loss_region_bwd": (_i, [_vp, _vp, C.POINTER(RegionDesc), _vp, _vp, _vp, _vp, _f]),
     "sg_adam_step": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f]),
     "sg_adam_step_lr": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f]),
+    "sg_optim_norms_ws_bytes": (_sz, [_i]),
+    "sg_optim_grad_norms": (_i, [_vp, _vp, C.POINTER(OptimTable), _vp, _f, _vp, _vp, _sz]),
+    "sg_optim_step": (_i, [_vp, _vp, C.POINTER(OptimDesc), C.POINTER(OptimTable), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp]),
     "sg_edge_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sg_resize_linear_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "sg_augment_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),

@@ -115,6 +115,23 @@ class _Timed:
         return False
 
 
+class OptimTable:
+    """A model's chunk table on one device (Engine.optim_table): `c` is the sg_optim_table both optimizer calls take."""
+
+    def __init__(self, eng, chunks, segs, n):
+        import numpy as np
+        self.chunks = np.ascontiguousarray(chunks)   # kept alive: `c` points into them
+        self.segs = np.ascontiguousarray(segs)
+        assert self.chunks.dtype.itemsize == C.sizeof(_lib.OptimChunk) and self.segs.dtype.itemsize == C.sizeof(_lib.OptimSeg)
+        self.nchunks, self.nseg, self.n = len(self.chunks), len(self.segs), int(n)
+        dev = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(eng.device)
+        self.chunks_dev, self.segs_dev = dev(self.chunks), dev(self.segs)
+        self.ws = torch.zeros(max(self.nchunks, 2), dtype=torch.float64, device=eng.device)
+        self.norms = torch.zeros(1 + self.nseg, dtype=torch.float64, device=eng.device)
+        self.c = _lib.OptimTable(self.chunks.ctypes.data, self.segs.ctypes.data, self.chunks_dev.data_ptr(),
+                                 self.segs_dev.data_ptr(), self.nchunks, self.nseg, self.n)
+
+
 class Engine:
     """Per-device launcher state: the `sg_ctx`, one reusable scratch buffer and the stream to launch on."""
 
@@ -1030,6 +1047,24 @@ class Engine:
             return
         check(self.lib.sg_adam_step(self.h, self.stream, w.numel(), _ptr(w), _ptr(m), _ptr(v), _ptr(g), float(lr_t), beta1,
                                     beta2, eps, float(grad_scale)), "sg_adam_step")
+
+    def optim_table(self, chunks, segs, n):
+        """The chunk table of optimizers.chunk_table (numpy structured arrays) as sg_optim_grad_norms / sg_optim_step take it:
+        the host arrays, their copies in device memory, the partial-sum workspace and the norm buffer (1 + nseg doubles)."""
+        return OptimTable(self, chunks, segs, n)
+
+    def optim_grad_norms(self, table, g, grad_scale=1.0):
+        """table.norms[0] = sum (grad_scale * g)^2 over every parameter element, table.norms[1 + s] over parameter s (fp64)."""
+        _chk32(g, "g")
+        check(self.lib.sg_optim_grad_norms(self.h, self.stream, C.byref(table.c), _ptr(g), float(grad_scale), _ptr(table.norms),
+                                           _ptr(table.ws), table.ws.numel() * 8), "sg_optim_grad_norms")
+        return table.norms
+
+    def optim_step(self, desc, table, w, g, m=None, v=None, vhat=None, ema=None, lr_t=0.0, lr=0.0, lr_dev=None):
+        """One sg_optim_step: desc an _lib.OptimDesc; lr_dev a device tensor {lr_t, lr, ..} (a captured step) or None."""
+        check(self.lib.sg_optim_step(self.h, self.stream, C.byref(desc), C.byref(table.c), _ptr(w), _ptr(g), _ptr(m), _ptr(v),
+                                     _ptr(vhat), _ptr(ema), _ptr(table.norms), float(lr_t), float(lr), _ptr(lr_dev)),
+              "sg_optim_step")
 
     def edge_labels(self, label, iterations=5, separation=None):
         """label [N,H,W] float (gray/255) -> y_true [N,H,W,4] as train_data_gen builds it (DeepLabv3plus.py:70-100).

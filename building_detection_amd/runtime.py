@@ -76,6 +76,26 @@ class Optimizer:
 
     learning_rate = lr
 
+    def step_scalars(self):
+        """(lr_t, lr) of the step just counted (iterations already incremented): Adam's bias-corrected rate and the plain one."""
+        t = self.iterations
+        lr = float(self.lr)
+        return lr * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t), lr
+
+    def _plain(self):
+        """The reference's Adam: the update is the one sg_adam_step call (optimizers.py overrides this when an option is set)."""
+        return True
+
+    def prepare(self, rt):
+        """State beyond the runtime's own m / v arenas (optimizers.py): plain Adam has none."""
+
+    def apply(self, rt, eng, grad_scale=1.0, lr_dev=None):
+        """The update of one step on rt's arenas - the one place the eager step, the captured step and its segmented form
+        launch it.  lr_dev: a device tensor {lr_t, lr, ..} the kernel reads instead of arguments (GraphedTrainStep.lr)."""
+        lr_t = 0.0 if lr_dev is not None else self.step_scalars()[0]
+        eng.adam_step(rt.w_train, rt.adam_m, rt.adam_v, rt.g_train, lr_t, self.beta_1, self.beta_2, self.epsilon, grad_scale,
+                      lr_dev=lr_dev)
+
 
 class History:
     def __init__(self):
@@ -223,10 +243,9 @@ class Model:
         losses.compound(pointwise, region); logs["loss"] is then L = pointwise_weight * L_point + region_weight * L_region.
         Under data parallelism (model.dist) every rank computes the region term on its own batch; the gradients are averaged
         as ever and the logged loss is the mean over the ranks."""
-        if isinstance(optimizer, str):
-            if optimizer.lower() != "adam":
-                raise ValueError("the reference compiles with optimizer='adam' (DeepLabv3plus.py:835)")
-            optimizer = Optimizer()
+        if isinstance(optimizer, str):   # 'adam' (the reference's, DeepLabv3plus.py:835) | 'adamw' | 'sgd'; else a ValueError
+            from . import optimizers
+            optimizer = optimizers.get(optimizer)
         self.optimizer = optimizer
         self.loss_kind = LS.resolve_loss(loss)
         # per-class weights of the focal losses (loss.with_alpha(...)); None: the 2-class kernels' built-in ones.  A wrong
@@ -241,6 +260,12 @@ class Model:
         self.jit_compile = bool(jit_compile)
         self._train_graphs = {}
         self._train_graph_seen = {}
+
+    def ema_weights(self):
+        """Context manager: inside it the trainable weights are the optimizer's moving average (use_ema=True), for predict /
+        test_on_batch / save_weights; on exit the training weights are back to the bit (optimizers.ema_weights)."""
+        from . import optimizers
+        return optimizers.ema_weights(self)
 
     @property
     def num_classes(self) -> int:
@@ -353,10 +378,7 @@ class Model:
                 loss, counts = self.dist.reduce_step_scalars(loss, counts)  # logs describe the GLOBAL batch
             opt = self.optimizer
             opt.iterations += 1
-            t = opt.iterations
-            lr_t = float(opt.lr) * math.sqrt(1.0 - opt.beta_2 ** t) / (1.0 - opt.beta_1 ** t)
-            rt.eng.adam_step(rt.w_train, rt.adam_m, rt.adam_v, rt.g_train, lr_t, opt.beta_1, opt.beta_2, opt.epsilon,
-                             grad_scale)
+            opt.apply(rt, rt.eng, grad_scale)
             rt.weights_changed()
             rt.release()
         if return_device_scalars:
@@ -533,8 +555,9 @@ class _Lane:
 class GraphedTrainStep:
     """One optimisation step of a compiled model - forward, loss, confusion counts, backward, Adam - captured into
     hipGraphs for one (x, y) shape (Model.compile(jit_compile=True)).  The step's inputs are two static device buffers, its
-    outputs (loss, counts) two more; Adam's bias-corrected learning rate, the only number that changes from replay to
-    replay, is read by the kernel from a one-float device buffer written before each replay (sg_adam_step_lr).  The weight
+    outputs (loss, counts) two more; the learning rates (Adam's bias-corrected one and the plain one), the only numbers that
+    change from replay to replay, are read by the kernel from a small device buffer written before each replay
+    (sg_adam_step_lr; sg_optim_step for an optimizer with options, whose norm pass is recorded in front of it).  The weight
     planes are rebuilt inside the graph (the capture starts with them marked stale), BatchNorm's moving statistics and the
     optimiser moments are updated in place as in the eager step.
 
@@ -561,7 +584,9 @@ class GraphedTrainStep:
         opt = model.optimizer
         dist = model.dist
         self.x, self.y = torch.empty_like(xd), torch.empty_like(yd)
-        self.lr = eng.zeros(4)
+        self.lr = eng.zeros(4)     # {lr_t, lr, -, -}: the step's scalars, written before every replay
+        self._lr1 = self.lr[1:2]
+        opt.prepare(rt)            # tables and arenas of an optimizer with options: allocated here, outside the capture
         lanes = switches.get("SG_JIT_LANES") and eng._side_on
         lane_blocks = max(1, switches.get("SG_JIT_LANE_BLOCKS"))
         # (the eager sizing steps ran the filter gradients on the side stream with its own scratch; without lanes they run
@@ -641,9 +666,8 @@ class GraphedTrainStep:
                 self.counts = model._counts(eng, p, self.y)   # zeroed inside the graph, four counts or C x C
                 dp = model._loss_bwd(eng, p, self.y)
                 rt.backward(dp)
-                if not segmented:  # Adam rides in the same graph
-                    eng.adam_step(rt.w_train, rt.adam_m, rt.adam_v, rt.g_train, 0.0, opt.beta_1, opt.beta_2, opt.epsilon, 1.0,
-                                  lr_dev=self.lr)
+                if not segmented:  # the optimizer rides in the same graph
+                    opt.apply(rt, eng, 1.0, lr_dev=self.lr)
                     end([])
                 else:
                     if state["ctx"] is not None:
@@ -651,8 +675,7 @@ class GraphedTrainStep:
                     assert cuts is None or cuts.done(), "a gradient bucket was never handed over"
                     eng.lane = None
                     begin()  # its own graph: it runs after the LAST all-reduce / side graph has joined the compute stream
-                    eng.adam_step(rt.w_train, rt.adam_m, rt.adam_v, rt.g_train, 0.0, opt.beta_1, opt.beta_2, opt.epsilon,
-                                  1.0 / (dist.world if dist is not None else 1), lr_dev=self.lr)
+                    opt.apply(rt, eng, 1.0 / (dist.world if dist is not None else 1), lr_dev=self.lr)
                     end([])
             finally:
                 eng.lane = None
@@ -681,9 +704,10 @@ class GraphedTrainStep:
         self.x.copy_(xd, non_blocking=True)
         self.y.copy_(yd, non_blocking=True)
         opt.iterations += 1
-        t = opt.iterations
-        lr_t = float(opt.lr) * math.sqrt(1.0 - opt.beta_2 ** t) / (1.0 - opt.beta_1 ** t)
+        lr_t, lr = opt.step_scalars()
         self.lr.fill_(lr_t)
+        if not opt._plain():   # sg_optim_step reads the plain rate too (decay, SGD); the reference's Adam keeps its one launch
+            self._lr1.fill_(lr)
         if not self.segmented:
             self.graph.replay()
             self.rt.weights_changed()

@@ -21,6 +21,7 @@ from typing import List, Sequence
 import numpy as np
 
 from . import layers as L
+from . import optimizers as _optimizers
 from .callbacks import Callback as _Callback, backend as _backend
 from .graph import KTensor
 from .runtime import Model as _Model
@@ -312,8 +313,10 @@ backend = _module(__name__ + ".keras.backend", epsilon=_backend.epsilon, get_val
 callbacks = _module(__name__ + ".keras.callbacks", Callback=_Callback)
 models = _module(__name__ + ".keras.models", Model=_ModelFactory())
 utils = _module(__name__ + ".keras.utils", to_categorical=to_categorical)
+optimizers = _module(__name__ + ".keras.optimizers", Adam=_optimizers.Adam, AdamW=_optimizers.AdamW, SGD=_optimizers.SGD,
+                     get=_optimizers.get)
 keras = _module(__name__ + ".keras", layers=layers, backend=backend, callbacks=callbacks, models=models, utils=utils,
-                Model=_ModelFactory())
+                optimizers=optimizers, Model=_ModelFactory())
 image = _module(__name__ + ".image", resize=_image_resize)
 config = _module(__name__ + ".config", experimental=_module(
     __name__ + ".config.experimental", list_physical_devices=lambda kind=None: [], set_memory_growth=lambda *a: None))
@@ -326,7 +329,8 @@ def install(as_name: str = "tensorflow"):
     me = sys.modules[__name__]
     table = {as_name: me, as_name + ".keras": keras, as_name + ".keras.layers": layers,
              as_name + ".keras.backend": backend, as_name + ".keras.callbacks": callbacks,
-             as_name + ".keras.models": models, as_name + ".keras.utils": utils, as_name + ".config": config, as_name + ".image": image}
+             as_name + ".keras.models": models, as_name + ".keras.utils": utils, as_name + ".keras.optimizers": optimizers,
+             as_name + ".config": config, as_name + ".image": image}
     for k, v in table.items():
         sys.modules[k] = v
     return list(table)

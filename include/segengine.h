@@ -744,6 +744,63 @@ int sg_adam_step(sg_ctx* ctx, void* stream, int64_t n, void* w, void* m, void* v
 int sg_adam_step_lr(sg_ctx* ctx, void* stream, int64_t n, void* w, void* m, void* v, const void* g, const void* lr_t_dev,
                     float beta1, float beta2, float eps, float grad_scale);
 
+/* ---- optimizers beyond plain Adam: decoupled weight decay, AMSGrad, SGD momentum, clipping, weight average (csrc/optim.hip) ----
+ * The trainable arena is a sequence of parameters, each starting on a 16-byte boundary with up to 3 elements of padding behind
+ * it.  Both calls below walk a CHUNK TABLE instead of the flat arena, so the padding is never read or written and what differs
+ * from parameter to parameter is uniform in a workgroup:
+ *   chunk    `length` elements from element `start` of the arena, all of parameter `segment`; start % 4 == 0, chunks ascending
+ *            and disjoint, length in [1, 2^20] (the host builds them at most 4 Ki long);
+ *   segment  one trainable parameter: its chunks [chunk_begin, chunk_end) of the table - the segments tile the table in order -
+ *            and flags (SG_OPT_SEG_DECAY: the decoupled weight decay applies to it).
+ * `chunks` / `segs` are the table in HOST memory (checked at every call: a malformed table is SG_EINVAL and nothing is launched),
+ * `chunks_dev` / `segs_dev` the same bytes in device memory (what the kernels read); n = the arena's elements. */
+typedef struct sg_optim_chunk { int64_t start; int32_t length, segment; } sg_optim_chunk;
+typedef struct sg_optim_seg { int32_t chunk_begin, chunk_end, flags, reserved; } sg_optim_seg;
+#define SG_OPT_SEG_DECAY 1
+typedef struct sg_optim_table {
+  const sg_optim_chunk* chunks;
+  const sg_optim_seg* segs;
+  const void* chunks_dev;
+  const void* segs_dev;
+  int32_t nchunks, nseg;
+  int64_t n;
+} sg_optim_table;
+#define SG_OPT_ADAM 0
+#define SG_OPT_SGD 1
+#define SG_OPT_AMSGRAD 1  /* flags */
+#define SG_OPT_NESTEROV 2
+#define SG_OPT_EMA 4
+#define SG_OPT_CLIP_NONE 0
+#define SG_OPT_CLIP_VALUE 1  /* g = clamp(g, -c, c) */
+#define SG_OPT_CLIP_NORM 2   /* per parameter: g *= c / max(||g_p||, c) */
+#define SG_OPT_CLIP_GLOBAL 3 /* the same with the norm over all parameters */
+typedef struct sg_optim_desc {
+  int32_t kind, flags, clip;
+  float beta1, beta2, eps; /* Adam */
+  float momentum;          /* SGD; 0: no moment arena */
+  float weight_decay, clip_c, ema_momentum, grad_scale;
+} sg_optim_desc;
+/* norms (device, 1 + nseg doubles, 16-byte aligned): norms[0] = sum over every table element of (grad_scale * g)^2,
+ * norms[1 + s] = the same over segment s.  Accumulated in fp64 in a fixed order without atomics: two calls give the same bits,
+ * and the value is the exact sum to within an fp32 rounding whatever the table's shape.  ws: the first function's bytes. */
+size_t sg_optim_norms_ws_bytes(int32_t nchunks);
+int sg_optim_grad_norms(sg_ctx* ctx, void* stream, const sg_optim_table* table, const void* g, float grad_scale, void* norms,
+                        void* ws, size_t ws_bytes);
+/* One update of every table element, in this order (g, w, m, v, vhat, ema: fp32 arenas of n elements, 16-byte aligned; an
+ * arena the configuration does not use may be NULL):
+ *   g   = grad_scale * g, then clipped (clip modes 2 and 3 read `norms` as sg_optim_grad_norms left it; a non-finite norm gets
+ *         no special case: an infinite one scales g by 0, and max(NaN, c) = c leaves g unscaled);
+ *   w  -= lr * weight_decay * w                                           on segments with SG_OPT_SEG_DECAY;
+ *   SG_OPT_ADAM  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  [vhat = max(vhat, v)]  w -= lr_t m / (sqrt(vhat | v) + eps),
+ *                lr_t = lr sqrt(1-b2^t) / (1-b1^t) from the host as for sg_adam_step;
+ *   SG_OPT_SGD   momentum == 0: w -= lr g;  else m = momentum m - lr g and w += m, or (SG_OPT_NESTEROV) w += momentum m - lr g;
+ *   SG_OPT_EMA   ema = ema_momentum ema + (1 - ema_momentum) w, with the updated w.
+ * lr_dev NULL: lr_t and lr are the two arguments; else they are read from device memory, lr_dev[0] = lr_t, lr_dev[1] = lr
+ * (a captured step; same arithmetic, same bits).  Unaligned arenas, a malformed table, an unknown kind / flag / clip mode, a
+ * negative or non-finite hyperparameter or a missing arena: SG_EINVAL, nothing launched or written. */
+int sg_optim_step(sg_ctx* ctx, void* stream, const sg_optim_desc* desc, const sg_optim_table* table, void* w, const void* g,
+                  void* m, void* v, void* vhat, void* ema, const void* norms, float lr_t, float lr, const void* lr_dev);
+
 /* Label channels of train_data_gen (DeepLabv3plus.py:70-100) from label[N,H,W] (gray/255, float): y[N,H,W,4] =
  * (1-fg, fg, f_edge, p_edge); fg = 1 iff label == 1.0 (to_categorical truncation); `iterations` (5 in the
  * reference) erosions / dilations with a 3x3 kernel = (2*iterations+1)^2 min / max box ignoring out-of-image

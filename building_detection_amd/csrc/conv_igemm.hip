@@ -24,124 +24,21 @@
 //   read element 0 and are zeroed by a select) so a slab is a single basic block for the scheduler.
 //   Block ids are remapped so each XCD owns a contiguous run of M-tiles (shared halo / weights hit one L2).
 //   Tile width and the wgrad split are chosen per launch to fill whole "waves" of 2 workgroups per CU.
+//
+// The shared types live in conv_common.h (namespace sgconv).  The patch family is a translation unit of its own (conv_x6p.hip
+// behind conv_x6p.h / conv_x6wp.h); the other families' kernels are still included below, inside this file's anonymous namespace.
+#include "conv_common.h"
+#include "conv_x6p.h"
+#include "conv_x6wp.h"
 #include "sg_reduce.h"
-#include <stdlib.h>
-#include <string.h>
-#include <type_traits>
+
+using namespace sgconv;
 
 namespace {
 
-constexpr int BM = 128;
-constexpr int BK = 32;
-constexpr int LDA = BK + 4;  // floats; 144-byte rows
-
-template <int V>
-using IC = std::integral_constant<int, V>;
-
-// A BatchNormalization (+ReLU) applied to the convolution's INPUT while it is loaded (round 5: sg_conv_opts.bn_in of
-// sg_conv2d_fwd / _wgrad; the patch kernels and the thin 1x1 kernels): y = [relu](fmaf((x - mean) * invstd, gamma, beta)), bn_apply's own
-// expression, on every pixel inside the image (the zero padding stays zero).  mean == nullptr: none.
-struct BnIn {
-  const float* mean;
-  const float* invstd;   // infer: the moving variance, invstd = rsqrtf(var + eps)
-  const float* gamma;
-  const float* beta;
-  int relu, infer;
-  float eps;
-};
-__device__ __forceinline__ f32x4 bn_in_inv(const BnIn& b, int c) {
-  f32x4 is = *reinterpret_cast<const f32x4*>(b.invstd + c);
-  if (b.infer) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) is[k] = rsqrtf(is[k] + b.eps);
-  }
-  return is;
-}
-__device__ __forceinline__ float bn_in_one(float x, float m, float is, float g, float bt, int relu) {
-  const float t = fmaf((x - m) * is, g, bt);
-  return relu ? fmaxf(t, 0.f) : t;
-}
-
-// pw_wide_kernel<3, float, BN, true> (conv_pw.h): the BatchNormalization backward apply evaluated in the dgrad's A path
-struct BnBwdIn {
-  const float* x;        // the BatchNormalization's raw input (= the pointwise convolution's forward output), same layout as dy
-  const float* mean;
-  const float* invstd;
-  const float* gamma;
-  const float* beta;     // null: no fused ReLU
-  const float* dgamma;   // finished column sums
-  const float* dbeta;
-  float* dz;             // out: the applied gradient (for the filter gradient)
-  int relu;
-  float inv_n;
-};
-
-struct IgemmParams {
-  const float* __restrict__ x;
-  const float* __restrict__ w;
-  const float* __restrict__ bias;
-  float* __restrict__ y;
-  int H, W, C, x_ld;
-  int OH, OW;
-  int Nout, y_ld;
-  int a_mul, k_mul, off_h, off_w, div;
-  int K, M;
-  int flags;
-  int stagger;  // waves in the upper half of the workgroup issue their gathers AFTER their MFMAs
-  int ablate;   // timing-only diagnostics (results wrong): 1 = no global loads in the loop, 2 = no LDS store/barrier
-  uint32_t x_bytes, w_bytes;  // extents for the buffer descriptors of the UT path (both < 2^31)
-  int skip_taps;              // drop taps that are pure padding for the whole tile (dilated convs)
-  int group_m;                // > 1: tiles are walked in groups of group_m row tiles, row tile fastest (L2 reuse of B)
-  int cb;                     // > 0: K order = (channel block of cb slabs) x tap x slab, so the 9 taps of a
-                              //      channel block re-read x from L2 instead of the fabric; 0: tap-major
-  FastDiv fd_ohow, fd_ow, fd_c, fd_kw;
-  // x6 path (conv_x6.h): the weights as three bf16 planes [3][Npad][Kpad]; w_bytes then is their extent
-  const unsigned short* __restrict__ wq;
-  int Kpad, Npad;
-  int kd;  // k-block depth of the plane layout [npl][Kpad / kd][Npad][kd] (= the kernel's slab depth); 0: rows [npl][Npad][Kpad]
-  float* __restrict__ stats;  // SG_EPI_BN_STATS: [tiles_m][2][Nout] per-tile (sum, centred sum of squares), else null
-  // Stride-2 dgrad (and Conv2DTranspose forward) with rows in PARITY-CLASS order (conv_x6_kernel / conv_b16_kernel only):
-  // GEMM row m = ((cls * N + n) * OH/2 + i) * OW/2 + j is output pixel (n, 2i + (cls >> 1), 2j + (cls & 1)).  Of the KH x KW
-  // taps only those of matching parity reach a pixel of class cls; in raster order a 128-row tile mixes the column
-  // parities, so every tap had a valid row and the tile multiplied all of them (3/4 of the products masked to zero).
-  // Class-pure tiles let the existing padding-tap elimination drop the taps of the other parities: a 3x3 kernel runs 1 / 2 /
-  // 2 / 4 taps instead of 9 four times, a 1x1 kernel one tap for a quarter of the tiles and none for the rest.
-  int perm2;
-  FastDiv fd_mc, fd_hcwc, fd_wc;
-  // dgrad: a gradient already collected for the same tensor (y's layout, may be y itself), added in the epilogue
-  // (sg_conv_opts.res; conv_x6_kernel / conv_b16_kernel only)
-  const float* res;
-  // the A operand already split into three bf16 planes [3][pixels][C] (sg_split_planes; sg_conv_opts.a_planes): the
-  // planes-in kernel (conv_x6w.h) reads them instead of splitting x itself; ignored by every other kernel; null: none
-  const unsigned short* a_planes;
-  BnIn bn;   // conv_x6p_kernel only: the BatchNormalization applied in the patch loader (mean == nullptr: none)
-  BnBwdIn bnb;   // pw_wide_kernel<.., BNB> only (x == nullptr: none)
-};
-
-__device__ __forceinline__ int spt_of(const IgemmParams& p) { return p.C / BK; }  // slabs per tap (UT)
-
-// GEMM row -> output pixel coordinates (image, row, column); see IgemmParams::perm2
-__device__ __forceinline__ void row_to_pixel(const IgemmParams& p, uint32_t m, uint32_t& n, uint32_t& oh, uint32_t& ow) {
-  if (p.perm2) {
-    uint32_t cls, r, rem, i, j;
-    fd_divmod(m, p.fd_mc, cls, r);
-    fd_divmod(r, p.fd_hcwc, n, rem);
-    fd_divmod(rem, p.fd_wc, i, j);
-    oh = 2 * i + (cls >> 1);
-    ow = 2 * j + (cls & 1);
-  } else {
-    uint32_t rem;
-    fd_divmod(m, p.fd_ohow, n, rem);
-    fd_divmod(rem, p.fd_ow, oh, ow);
-  }
-}
-// element offset of GEMM row `row` in y
-__device__ __forceinline__ int64_t row_to_yoff(const IgemmParams& p, int row) {
-  if (!p.perm2) return (int64_t)row * p.y_ld;
-  uint32_t n, oh, ow;
-  row_to_pixel(p, (uint32_t)row, n, oh, ow);
-  return ((int64_t)(n * p.OH + oh) * p.OW + ow) * p.y_ld;
-}
+// Convolution arithmetic on fp32 storage (conv_x6.h: x6_mode()), the one piece of state that can be set at run time
+// (sg_set_conv_x6): -1 = not yet read from the environment
+int g_x6_mode = -1;
 
 // UT ("uniform tap"): Cin % 32 == 0 or a 1x1 kernel, so every 32-deep slab lies inside ONE filter tap.  The
 // per-row source offsets and bounds flags then change only when the slab stream crosses a tap boundary (every
@@ -559,28 +456,6 @@ __global__ void transpose_taps_kernel(const float* __restrict__ w, float* __rest
 }
 
 // ---- wgrad --------------------------------------------------------------------------------------------
-struct WgradParams {
-  const float* __restrict__ x;
-  const float* __restrict__ dy;
-  float* __restrict__ out;  // [S][K][Cout] partials (or dw itself when S == 1)
-  int H, W, Cin, x_ld;
-  int OH, OW, Cout, y_ld;
-  int stride, dil, pad_t, pad_l;
-  int K, P;
-  int slabs_per_split;
-  int stagger;
-  uint32_t x_bytes, dy_bytes;  // extents for the buffer descriptors of the FAST path (both < 2^31)
-  int skip_slabs;              // drop 32-pixel slabs that are pure padding for every tap of the tile (dilated convs)
-  int KH_KW;
-  int tap_inner;               // tile order (channel block, tap, column tile) instead of (tap, channel block, column tile)
-  uint32_t x_plane_bytes, dy_plane_bytes;   // planes-in filter gradient (wgrad_x6_kernel<.., PIN>): bytes from one bf16 plane of
-                               //    x / dy to the next; x_bytes / dy_bytes then cover all three
-  BnIn bn;                     // wgrad_x6wp_kernel only: the BatchNormalization applied to x in the patch loader (mean == nullptr: none)
-  int up;                      // 1: x is the source of a nearest 2x up-sampling (SG_X_UP2; wgrad_x6wp_kernel only): pixel (h, w)
-                               //    of the H x W tensor is x[n, h >> 1, w >> 1, :] of the (H / 2) x (W / 2) source
-  FastDiv fd_ohow, fd_ow, fd_c, fd_kw, fd_oh;
-};
-
 // FAST: stride-1 "same" convolution (H == Ho, W == Wo) with 16-byte-aligned channel runs: the source pixel of
 // output pixel p under tap (dh,dw) is p + dh*W + dw, i.e. LINEAR in p, so the gather offset advances by a constant
 // per slab; only the tap's bounds flags depend on (oh, ow), which are carried incrementally (no div/mod), and
@@ -1022,31 +897,6 @@ int launch_colsum(int num_cus, const T* dy, int64_t rows, int C, int ld, float* 
   return seg_reduce_launch(op, pl, 1, rows, C, part, st, "colsum");
 }
 
-template <typename KernelT>
-int set_dyn_lds(KernelT k, size_t bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) {
-    sg_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
-// x6 == true: the switches as the x6 kernels use them.  Re-measured with those kernels (profiles/r01_ab_l2_orders.txt,
-// second part): the grouped order takes the ASPP dgrad fetch from 1998 to 485 MiB and the tap-inner wgrad order from
-// 795 to 279 MiB at 0-3 % of kernel time (the fp32 kernels paid 6-13 %), so both are on there: default 7.
-int conv_l2(bool x6 = false) {
-  if (sg_switch_set<SW_CONV_L2>()) return sg_switch<SW_CONV_L2>() & 7;
-  if (x6) return 7;
-  // the fp32 kernels, default 2: measured on the ASPP convs (scripts/ab_l2.sh, 30 iterations, two interleaved rounds):
-  //   bit 1 (channel-block K order): forward fetch 1039 -> 451 MiB per launch, time unchanged      -> on
-  //   bit 0 (grouped tile order):    dgrad fetch 1808 -> 461 MiB, but 6-13 % SLOWER               -> off
-  //   bit 2 (wgrad tap-inner order): wgrad fetch 1018 -> 314 MiB, but 2-8 % SLOWER                 -> off
-  // The re-reads are served by the 256 MiB Infinity Cache (operands total < 150 MiB), not by HBM, and the
-  // orders that remove them make many CUs hit the same L2 lines at the same time.
-  return 2;
-}
-
 template <int BN, int WGM, int WGN, int PF, bool VEC, bool UT, typename TA = float, typename TY = TA>
 int launch_igemm_ut(const IgemmParams& p, hipStream_t st) {
   // + tapinfo[64] + row_lin[NA][NT] (NA * NT = BM * BK / 4 ints)
@@ -1080,78 +930,8 @@ int launch_igemm(const IgemmParams& p, hipStream_t st) {
   return launch_igemm_ut<BN, WGM, WGN, PF, VEC, false>(p, st);
 }
 
-// Tile width by wave quantisation: two workgroups fit a CU (LDS), so one "wave" of the grid is 2*CUs tiles; pick
-// the BN in {128, 64} whose tile count wastes the least of its last wave and of its last column tile (e.g.
-// M = 16384, N = 728: 128-wide = 768 tiles = 1.5 waves (75 %), 64-wide = 1536 tiles = 3.0 waves (100 %)).
-int pick_bn(int64_t M, int N, int num_cus) {
-  if (N <= 32) return 32;
-  if (N <= 64) return 64;
-  // quantum = one workgroup per CU: an 8-wave workgroup keeps a CU's matrix pipes fed on its own, and tiles
-  // beyond the resident ones are dispatched as CUs free up, so the makespan is ceil(tiles / CUs) tile-times
-  const int64_t slots = (int64_t)num_cus;
-  double best = -1.0;
-  int best_bn = 128;
-  for (int bn : {128, 64}) {
-    const int64_t tiles = sg_cdiv(M, BM) * sg_cdiv(N, bn);
-    const double eff = (double)tiles / (double)(sg_cdiv(tiles, slots) * slots) * (double)N / (double)(sg_cdiv(N, bn) * bn) *
-                       (bn == 128 ? 1.0 : 0.93);  // the wider tile re-reads A half as often
-    if (eff > best) { best = eff; best_bn = bn; }
-  }
-  return best_bn;
-}
-
-// fields shared by the fp32 and the x6 kernel: padding-tap elimination, tile order, K order
-void plan_common(IgemmParams& p, bool vec, int bn, bool x6 = false, int eb = 4) {
-  const int noskip = sg_switch<SW_CONV_NOSKIP>();  // A/B switch for the padding-tap elimination
-  const int ntaps = p.K / p.C, spt = p.C / BK;
-  p.skip_taps = (!noskip && (p.k_mul > 1 || p.k_mul < -1) && ntaps > 1 && ntaps <= 64) ? 1 : 0;
-  if (p.perm2) p.skip_taps = 1;  // parity-pure tiles: taps of the other parities have no valid row (also a lone 1x1 tap)
-  // L2 locality (A/B switch SG_CONV_L2: bit 0 grouped tile order, bit 1 channel-block K order, bit 2 wgrad order).
-  // An XCD owns 1/8 of the tiles and with them about 1/8 of the A operand's pixels.
-  const int64_t ntn = sg_cdiv(p.Nout, bn);
-  const int64_t a_per_xcd = p.x_bytes ? (int64_t)p.x_bytes / 8 : (1ll << 40);
-  p.group_m = ((conv_l2(x6) & 1) && ntn >= 4) ? (a_per_xcd <= (2ll << 20) ? 16 : 8) : 1;
-  const int gm_force = sg_switch<SW_CONV_GM>();   // experiment: row tiles per group
-  if (gm_force > 0 && ntn >= 2) p.group_m = gm_force;
-  const bool ut = vec && (p.C % BK == 0) && p.x_bytes != 0 && p.w_bytes != 0;
-  // decided from ONE image's footprint, never from the batch: the K order fixes the rounding order, and
-  // inference must not depend on how many tiles travel together (tests/test_fullsize_gpu.py)
-  const int64_t img_bytes = (int64_t)p.H * p.W * p.x_ld * eb;
-  const int cbv = sg_switch<SW_CONV_CB>();  // experiment switch: slabs per channel block of the K order (default 4)
-  p.cb = ((conv_l2(x6) & 2) && ut && ntaps > 1 && spt > cbv && spt % cbv == 0 && img_bytes > (2ll << 20)) ? cbv : 0;
-}
-
-// The kernels of the slab family (plan_conv: CONV_SLAB) and what every one of their launches sets before it starts: the tile width
-// (the two 256-wide forms plan with 128-wide column tiles, the others by wave quantisation) and plan_common's fields.  The
-// dispatchers, run_x6 and the plan query (sg_conv2d_plan) all come through here; slab_kernel_of (behind ConvPlan) picks the kernel.
-enum SlabKernel { SLAB_X6, SLAB_B16, SLAB_X6W, SLAB_B16W };
-inline int slab_common(IgemmParams& p, SlabKernel sk, int eb, int num_cus) {
-  const int bn = (sk == SLAB_X6W || sk == SLAB_B16W) ? 128 : pick_bn(p.M, p.Nout, num_cus);
-  plan_common(p, true, bn, true, eb);
-  return bn;
-}
-// the mixed-storage forms of the native kernel (bf16 storage, the softmax head): scalar-gather planning whatever the loads, no tap
-// elimination, no K order, never the wave-uniform-tap form.  dispatch_igemm_mixed and the plan query both come through here.
-inline int mixed_common(IgemmParams& p, int num_cus) {
-  const int bn = pick_bn(p.M, p.Nout, num_cus);
-  plan_common(p, false, bn);
-  p.stagger = 0;
-  p.ablate = 0;
-  p.skip_taps = 0;
-  p.cb = 0;
-  return bn;
-}
-// the fp32 native kernel: planning by its channel runs; the UT form is launch_igemm's (igemm_ut_of)
-inline int native_common(IgemmParams& p, bool vec, int num_cus) {
-  const int bn = pick_bn(p.M, p.Nout, num_cus);
-  plan_common(p, vec, bn);
-  return bn;
-}
-
 #include "conv_x6.h"
-#include "conv_x6p.h"
 #include "conv_b16.h"
-#include "conv_x6wp.h"
 #include "conv_pw.h"
 #include "conv_b16w.h"
 #include "conv_x6w.h"
@@ -1206,69 +986,6 @@ int dispatch_x6(const IgemmParams& p_in, int num_cus, hipStream_t st) {
 // from nothing else: no pointers, no `res`.  The workspace queries, sg_conv2d_caps, sg_conv2d_planes_job and the launch
 // all read this one plan (the filter gradient's counterpart is plan_wgrad), so they cannot disagree.  What the descriptor does
 // not say - the alignment of the operands, the workspace a launch was handed - is checked once, at the launch, against the plan.
-enum ConvFamily {   // (from CONV_SLAB on: the kernels that read prepared weight planes, sg_planes_job.kind 1 / 2 / 3)
-  CONV_NATIVE,   // the fp32-MFMA kernels: any shape, any alignment
-  CONV_THIN,     // 1x1 with at most 4 output channels: the streaming kernels
-  CONV_HEAD,     // the softmax head of a bf16 model that is not thin: the native kernel on mixed storage types
-  CONV_SLAB,     // conv_x6 / conv_b16 and, on the same planes, their wide forms conv_x6w (planes-in) / conv_b16w
-  CONV_PATCH,    // conv_x6p
-  CONV_WIDE      // conv_pw
-};
-constexpr int PLAN_NOT_THIN = 1 << 30;   // plan_conv `flags` (no SG_EPI_* / SG_PRO_* bit): the operands of a thin launch missed its alignment
-
-struct ConvPlan {
-  ConvFamily family = CONV_NATIVE;
-  int nb = 0;         // images per launch: >= N the whole batch; fewer: sub-batches of whole images (2 GiB buffer descriptors),
-                      // none of which takes the wide pointwise kernel; 0: one image alone passes the limit (native, whole batch)
-  bool vec = false;   // 16-byte channel runs as far as the descriptor says (the launch adds the pointers' alignment)
-  int perm2 = 0;      // stride-2 dgrad: rows in parity-class order (IgemmParams::perm2; the slab kernels)
-  // the weight planes (family >= CONV_SLAB): sg_planes_job's fields; Ckp = the tap depth after virtual channel padding
-  int npl = 0, Ck = 0, Ckp = 0, K = 0, kd = 0, Kpad = 0, Npad = 0, nblocks = 0;
-  int wbn = 0;        // CONV_WIDE: tile width, 384 or 256
-  size_t w_bytes = 0;
-  // CONV_SLAB: K shares of the planes-in kernel / of the 256-wide bf16 kernel (0: conv_x6_kernel / conv_b16_kernel); deep bf16 slabs
-  int x6w_S = 0, b16w_S = 0;
-  bool deep = false;
-  size_t a_img_bytes = 0, part_img_bytes = 0;   // scratch behind the planes per image: activation planes, split-K partial slabs
-  // what the family can do
-  bool res = false;        // add a collected gradient (sg_conv_opts.res).  Of the plane kernels only the slab family: a launch
-                           // with `res` whose plan names a wide slab form takes conv_x6_kernel / conv_b16_kernel on the same planes
-  bool bn_in = false;      // apply a BatchNormalization in its loader (thin; patch with 32 / 64 reduction channels per tap)
-  bool up2 = false;        // the fused up-sampling forms exist for this layer (SG_PRO_UP2; with CONV_PATCH: SG_EPI_DOWN2)
-  bool bnb = false;        // evaluate the BatchNormalization backward in its A path (wide pointwise dgrad)
-  bool planes_in = false;  // read the activation as bf16 planes the caller made (sg_split_planes)
-
-  // scratch behind the weight planes of a launch of `images` images
-  size_t scratch_bytes(int images) const {
-    return (((size_t)images * a_img_bytes + 255) & ~(size_t)255) + (size_t)images * part_img_bytes;
-  }
-  // the weight planes and that scratch
-  size_t ws_bytes(int images) const {
-    const size_t sc = scratch_bytes(images);
-    return sc ? ((w_bytes + 255) & ~(size_t)255) + sc : w_bytes;
-  }
-};
-
-// Which kernel a launch of the slab family takes: the planes-in kernel / the 256-wide bf16 kernel where the plan names K shares and
-// the launch adds no collected gradient (they have no such epilogue), conv_b16_kernel for deep bf16 slabs, else conv_x6_kernel.
-inline SlabKernel slab_kernel_of(const ConvPlan& pl, bool b16, bool with_res) {
-  if (pl.npl == 3 && !b16 && pl.x6w_S > 0 && !with_res) return SLAB_X6W;
-  if (b16 && pl.deep) return (pl.b16w_S > 0 && !with_res) ? SLAB_B16W : SLAB_B16;
-  return SLAB_X6;
-}
-// A slab launch's parameters from the plan: virtual channel padding, the planes' geometry and bytes
-inline void slab_fill(IgemmParams& p, const ConvPlan& pl) {
-  if (pl.Ckp != p.C) {   // virtual channel padding
-    p.K = pl.K;
-    p.C = pl.Ckp;
-    p.fd_c = make_fastdiv((uint32_t)pl.Ckp);
-  }
-  p.kd = pl.kd;
-  p.Kpad = pl.Kpad;
-  p.Npad = pl.Npad;
-  p.w_bytes = (uint32_t)pl.w_bytes;
-}
-
 // Run a launch of the plan's family (>= CONV_SLAB) on its weight planes in `ws`; the scratch of a wide slab form lies behind them.
 // prepared: `ws` already holds the planes (sg_prepare_planes, once per optimiser step), no split here.
 // NPL = 3: the exact fp32 emulation; NPL = 1: bf16 products (TA = float: fp32 storage rounded on the way into LDS,
@@ -1380,26 +1097,6 @@ int launch_wgrad_f(const WgradParams& p, int S, hipStream_t st) {
   const int64_t tiles = sg_cdiv(p.K, BM) * sg_cdiv(p.Cout, BN);
   hipLaunchKernelGGL((igemm_wgrad_kernel<BN, WGM, WGN, PF, VEC, FAST, TA, TD>), dim3((unsigned)tiles, 1, (unsigned)S), dim3(64 * WGM * WGN), lds, st, p);
   SG_LAUNCH_CHECK("igemm_wgrad_kernel");
-  return 0;
-}
-
-inline int wgrad_bn(int cout) { return cout > 64 ? 128 : (cout > 32 ? 64 : 32); }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-int check_desc(const sg_conv_desc* d, const char* who) {
-  SG_CHECK_ARG(d != nullptr, "%s: null desc", who);
-  SG_CHECK_ARG(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "%s: non-positive dims", who);
-  SG_CHECK_ARG(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->dilation > 0, "%s: bad kernel geometry", who);
-  SG_CHECK_ARG(d->Ho > 0 && d->Wo > 0, "%s: bad output dims", who);
-  SG_CHECK_ARG(d->pad_t >= 0 && d->pad_l >= 0, "%s: negative pad", who);
-  // the gather packs a row's scaled (oh, ow) into signed 16-bit halves
-  SG_CHECK_ARG(d->H < 8192 && d->W < 8192 && (int64_t)d->Ho * d->stride < 16384 && (int64_t)d->Wo * d->stride < 16384 &&
-                   (int64_t)d->KH * d->dilation < 8192 && (int64_t)d->KW * d->dilation < 8192,
-               "%s: map or kernel extent beyond the 16-bit coordinate range", who);
-  const int xl = d->x_ld ? d->x_ld : d->Cin, yl = d->y_ld ? d->y_ld : d->Cout;
-  SG_CHECK_ARG(xl >= d->Cin && yl >= d->Cout, "%s: pixel stride smaller than channel count", who);
-  SG_CHECK_ARG((int64_t)d->N * d->H * d->W * xl < (1ll << 31) && (int64_t)d->N * d->Ho * d->Wo * yl < (1ll << 31),
-               "%s: tensor exceeds 2^31 elements", who);
   return 0;
 }
 
@@ -1550,14 +1247,6 @@ size_t thin_part_bytes(int num_cus, const sg_conv_desc* d) {
   }
 }
 
-inline BnIn bn_in_none() {
-  BnIn b;
-  b.mean = b.invstd = b.gamma = b.beta = nullptr;
-  b.relu = b.infer = 0;
-  b.eps = 0.f;
-  return b;
-}
-
 template <int CO, typename TA, typename TY>
 int thin_fwd_t(const sg_conv_desc* d, const TA* x, const float* w, const float* bias, TY* y, int flags, hipStream_t st,
                const BnIn bn = bn_in_none()) {
@@ -1630,17 +1319,6 @@ inline int images_per_2gib_mixed(const sg_conv_desc* d, int ebx, int eby) {
   const int64_t nb = lim / per;
   return (int)(nb < 1 ? 0 : nb);
 }
-
-// ---- storage-type plumbing of the entry points ---------------------------------------------------------------------
-// dtype = SG_F32 or SG_BF16 (activation storage), optionally | SG_HEAD_F32: the few-channel side of a thin 1x1
-// convolution (y of the forward, dy of dgrad / wgrad) is fp32 although the activations are bf16 - the softmax head,
-// whose logits, probabilities and loss stay in fp32.
-inline int dt_storage(int dtype) { return dtype & 0xff; }
-inline bool dt_ok(int dtype) {
-  const int st = dt_storage(dtype);
-  return (st == SG_F32 || st == SG_BF16) && (dtype & ~(0xff | SG_HEAD_F32 | SG_X_UP2)) == 0;
-}
-inline int dt_bytes(int dtype) { return dt_storage(dtype) == SG_BF16 ? 2 : 4; }
 
 void fill_fwd_params(IgemmParams& p, const sg_conv_desc* d, const void* x, const void* w, const void* bias, void* y,
                      int flags, int eb) {
@@ -1824,9 +1502,6 @@ ConvPlan plan_conv(int num_cus, int dtype, const sg_conv_desc* d, bool dgrad, in
 // SG_X_UP2 included), the descriptor, the alignment CLASS of x and of dy (16, 8 or 0 bytes; never the pointers) and whether the
 // operands are bf16 planes.  sg_conv2d_wgrad, sg_conv2d_wgrad_planes, both workspace queries, sg_conv2d_caps and
 // sg_conv2d_wgrad_plan read this one plan; run_wgrad() launches what it names and decides nothing.
-typedef sg_wgrad_launch WgradLaunch;
-typedef sg_wgrad_plan WgradPlan;
-
 // WgradParams' x_bytes / dy_bytes for a launch of `d`: the operands' extents, 0 = beyond the 2 GiB of a buffer descriptor
 inline void wgrad_extents(int dtype, const sg_conv_desc* d, uint32_t& x_bytes, uint32_t& dy_bytes) {
   const int up = (dtype & SG_X_UP2) ? 1 : 0, eb = dt_bytes(dtype), eby = (dtype & SG_HEAD_F32) ? 4 : eb;
@@ -2036,7 +1711,7 @@ extern "C" {
 
 int sg_set_conv_x6(int on) {
   const int prev = x6_mode();
-  g_x6_enabled = (on < 0 || on > 2) ? 1 : on;
+  g_x6_mode = (on < 0 || on > 2) ? 1 : on;
   return prev;
 }
 
@@ -2061,15 +1736,6 @@ size_t sg_conv2d_fwd_stats_bytes(const sg_conv_desc* d) {
   return (size_t)sg_cdiv((int64_t)d->N * d->Ho * d->Wo, BM) * 2 * d->Cout * sizeof(float);
 }
 
-static BnIn bn_in_of(const sg_bn_in* b) {
-  BnIn o = bn_in_none();
-  if (b && b->mean) {
-    o.mean = (const float*)b->mean; o.invstd = (const float*)b->invstd; o.gamma = (const float*)b->gamma; o.beta = (const float*)b->beta;
-    o.relu = b->relu; o.infer = b->infer; o.eps = b->eps;
-  }
-  return o;
-}
-// the launches that can apply a BatchNormalization to their input: the thin 1x1 kernels (Cout <= 4) and the patch kernels (3x3,
 // stride 1, SAME, 32 / 64 input channels: conv_x6p.h forward, conv_x6wp.h filter gradient), fp32 storage.  Forward AND filter
 // gradient must both take the operand: the filter gradient's plan answers for the pair
 static bool bn_in_geom(const sg_ctx* ctx, int dtype, const sg_conv_desc* d) {
@@ -2280,10 +1946,7 @@ int sg_prepare_planes(sg_ctx* ctx, void* stream, const void* w_arena, void* plan
                       int njobs, int total_blocks) {
   SG_CHECK_ARG(ctx && w_arena && planes_arena && jobs_dev && njobs > 0 && total_blocks > 0, "sg_prepare_planes: bad argument");
   SG_CHECK_ARG(aligned16(planes_arena), "sg_prepare_planes: planes arena must be 16-byte aligned");
-  hipLaunchKernelGGL(prepare_planes_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, (const float*)w_arena,
-                     (char*)planes_arena, jobs_dev, njobs);
-  SG_LAUNCH_CHECK("prepare_planes_kernel");
-  return 0;
+  return launch_prepare_planes((const float*)w_arena, (char*)planes_arena, jobs_dev, njobs, total_blocks, (hipStream_t)stream);
 }
 
 size_t sg_bn_tiles_ws_bytes(const sg_ctx* ctx, int tiles, int C) {
@@ -2697,8 +2360,7 @@ static int launch_wgrad_plan(sg_ctx* ctx, hipStream_t st, int dtype, const sg_co
     case SG_WG_WIDE:
       return b16 ? launch_wgrad_pw_wide_b16(p, f.S, st) : launch_wgrad_pw_wide(p, f.S, st);
     case SG_WG_PATCH:
-      if (b16) return launch_x6wp<1, bf16_t>(p, f.S, st);
-      return f.planes == 1 ? launch_x6wp<1, float>(p, f.S, st) : launch_x6wp<3, float>(p, f.S, st);
+      return launch_x6wp(p, f.S, b16, f.planes, st);
     case SG_WG_SLAB_X6:
       if (b16) return WG_TILE(launch_wgrad_x6, 1, 1, bf16_t);
       return f.planes == 1 ? WG_TILE(launch_wgrad_x6, 1, 1, float) : WG_TILE(launch_wgrad_x6, 1);

@@ -38,10 +38,7 @@ struct PwGeom {
   __device__ static __forceinline__ int swz(int row) { return (row >> WSH) & (CPR - 1); }
 };
 
-__device__ __forceinline__ void pw_lds_dma16(const __amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, unsigned voff, int soff) {
-  // 64 lanes x 16 bytes -> lds_wave_base + 16 * lane (the LDS address is wave-uniform: M0); out-of-range lanes write zeros
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (void __attribute__((address_space(3)))*)lds_wave_base, 16, (int)voff, soff, 0, 0);
-}
+// (pw_lds_dma16: conv_common.h)
 
 // BN: columns of the tile - 384 (8 waves of 64 x 96) or 256 (64 x 64: the 1024- and 2048-wide layers of the exit flow and the
 // 256-wide ones at many rows, whose last 384-wide tile would be two thirds / one third empty; round 4)

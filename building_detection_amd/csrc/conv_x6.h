@@ -21,12 +21,6 @@
 //   MFMA; the LDS array saturates at 2).
 #pragma once
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-
 // LDS rows of a plane slab are the bare 64 bytes (32 k as bf16); the four 16-byte chunks of row r are stored at
 // slot (chunk ^ xswz(r)).  Reads: the 16 lanes of a ds_read_b128 group (rows {0-3,12-15,20-27} or {4-11,16-19,28-31})
 // then hit 16 distinct 16-byte bank groups; writes: two consecutive rows fill the 32 write banks exactly once
@@ -38,17 +32,7 @@ typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 constexpr int XPITCH = 64;
 __device__ __forceinline__ int xswz(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }
 
-// (x0, x1) -> three packed bf16 pairs (element 0 in the low half), x = h + m + l up to 2^-25 |x|
-__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-  f32x2_t v = {x0, x1};
-  h = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-  f32x2_t hf = {__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};
-  f32x2_t r = v - hf;
-  m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_t));
-  f32x2_t mf = {__uint_as_float(m << 16), __uint_as_float(m & 0xffff0000u)};
-  f32x2_t s = r - mf;
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(s, bf16x2_t));
-}
+// (bf16x8_t and the other vector types, split3_pair and tr_frag: conv_common.h - the patch unit uses them too)
 
 // B[k][n] = w[tap*s_tap + kk*s_k + n*s_n]  (k = tap*Ck + kk)  ->  planes[3][Npad][Kpad] bf16, zero padded.
 //   forward: Ck = Cin,  s_tap = Cin*Cout, s_k = Cout, s_n = 1      (w is HWIO)
@@ -804,13 +788,13 @@ inline int x6_variant() {
 // Convolution arithmetic on fp32 storage (sg_set_conv_x6 / SG_CONV_X6): 0 = native fp32 MFMA, 1 = the exact
 // six-pass emulation (default), 2 = bf16 products, one pass (fp32 tensors rounded to bf16 on the way into LDS, fp32
 // accumulation: the arithmetic of the SG_BF16 path on fp32 tensors).
-int g_x6_enabled = -1;  // -1: not yet read from the environment; set by sg_set_conv_x6()
+// (the state is a variable of conv_igemm.hip, not of this header)
 inline int x6_mode() {
-  if (g_x6_enabled < 0) {
-    g_x6_enabled = sg_switch<SW_CONV_X6>();
-    if (g_x6_enabled < 0 || g_x6_enabled > 2) g_x6_enabled = 1;
+  if (g_x6_mode < 0) {
+    g_x6_mode = sg_switch<SW_CONV_X6>();
+    if (g_x6_mode < 0 || g_x6_mode > 2) g_x6_mode = 1;
   }
-  return g_x6_enabled;
+  return g_x6_mode;
 }
 inline bool x6_enabled() { return x6_mode() != 0; }
 inline bool x6_vpad_on() { return sg_switch<SW_X6_VPAD>() != 0; }
@@ -835,17 +819,6 @@ inline bool x6_ok(const IgemmParams& p, bool vec, bool force = false) {
 // Loads follow the aligned-slab scheme of igemm_wgrad_kernel<FAST = 2>: constant per-thread voffsets (which here
 // also carry the thread's tap shift, so a 128-row tile may span several taps: Cin = 32, 64), the slab's position
 // and image row on the scalar unit.  Requires OW % 32 == 0, stride 1 and "same" geometry.
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_ptr;
-
-__device__ __forceinline__ bf16x8_t tr_frag(const char* lds_addr_a, const char* lds_addr_b) {
-  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(lds_addr_a));
-  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(lds_addr_b));
-  typedef short s16x8_t __attribute__((ext_vector_type(8)));
-  const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-
 template <int BN>
 struct X6WPitch {
   static constexpr int A = 2 * BM + 64;                       // 320

@@ -9,7 +9,8 @@
 //   sg_switch_f<SW_NAME>()    the value of a DBL switch
 //
 // The table is immutable once read, so it does not matter that every translation unit could hold its own copy.  State that can be
-// SET at run time (x6_mode() / sg_set_conv_x6()) is not kept here: it lives in one translation unit, conv_x6.h.
+// SET at run time (x6_mode() / sg_set_conv_x6()) is not kept here: it is a file-local variable of ONE translation unit, conv_igemm.hip
+// (g_x6_mode, behind x6_mode()) - not a variable in a header.
 #pragma once
 #include <stdlib.h>
 

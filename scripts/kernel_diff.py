@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of two builds of libsegengine.so (CPU only; needs llvm-objdump and llvm-readelf; llvm-cxxfilt or c++filt for readable names).
 
-    python scripts/kernel_diff.py OLD/libsegengine.so NEW/libsegengine.so
+    python scripts/kernel_diff.py [--by-name] OLD/libsegengine.so NEW/libsegengine.so
 
 Extracts the gfx950 code objects of both libraries (one per translation unit, in link order), lists their kernels - the functions
 that have a 64-byte kernel descriptor `<name>.kd` - and for every kernel present in both compares the code and the descriptor.
@@ -12,6 +12,10 @@ Two things move with the layout of a code object and say nothing about a kernel'
   * the literal of a pc-relative address of a device global (e.g. an arrival counter): where the bytes of a kernel differ, both
     versions are disassembled and must agree line by line except for single numeric literals, and each such literal must have
     changed by exactly the change of the distance between the kernel and ONE data object both code objects define.
+--by-name pairs the kernels by their demangled name with the namespace qualifiers removed instead of by their symbol: for a change
+that moves kernels, or the types in their signatures, into another namespace or another translation unit.  A kernel that several
+translation units define is numbered in link order among its namesakes; two different symbols of one library that collapse onto
+one name are an error (exit status 2).
 The script compares; it does not look for any particular instruction.  Objects in .bss have no file bytes and are not compared."""
 import os
 import re
@@ -72,16 +76,25 @@ def code_objects(lib, tmp):
     return [CodeObject(os.path.join(d, f)) for f in names]
 
 
+QUALIFIER = re.compile(r"(?:\(anonymous namespace\)|\b[A-Za-z_]\w*)::")
 NUM = re.compile(r"(?<![\w.])(-?(?:0x[0-9a-fA-F]+|\d+))(?![\w.])")
 
 
-def literal_moves(old, new, k):
-    """Both disassemblies agree except for literals that moved with the layout: the number of such literals, or None."""
-    a, b = old.disassembly(k), new.disassembly(k)
+def data_objects(co, by_name):
+    """name -> address of the data objects a code object defines (with by_name: demangled, namespace qualifiers removed)."""
+    names = [o for o in co.objects if not o.endswith(".kd")]
+    keys = [QUALIFIER.sub("", d) for d in demangle(names)] if by_name else names
+    return {key: co.objects[o][0] for key, o in zip(keys, names)}
+
+
+def literal_moves(old, new, k, kn, by_name=False):
+    """Both disassemblies (of `k` in old, `kn` in new) agree except for literals that moved with the layout: the number of such literals, or None."""
+    a, b = old.disassembly(k), new.disassembly(kn)
     if len(a) != len(b):
         return None
-    shift = new.funcs[k][0] - old.funcs[k][0]
-    allowed = {new.objects[o][0] - old.objects[o][0] - shift for o in old.objects if o in new.objects and not o.endswith(".kd")}
+    shift = new.funcs[kn][0] - old.funcs[k][0]
+    od, nd = data_objects(old, by_name), data_objects(new, by_name)
+    allowed = {nd[o] - od[o] - shift for o in od if o in nd}
     moved = 0
     for x, y in zip(a, b):
         if x == y:
@@ -107,6 +120,24 @@ def kernel_table(objs):
     return table
 
 
+def kernel_table_by_name(objs):
+    """demangled name without namespace qualifiers -> (code object, symbol); namesakes of several units are numbered in link order."""
+    syms = sorted({k for co in objs for k in co.kernels})
+    plain = {k: QUALIFIER.sub("", d) for k, d in zip(syms, demangle(syms))}
+    owner = {}
+    for k, name in plain.items():
+        if owner.setdefault(name, k) != k:
+            sys.exit(f"kernel_diff: two kernels collapse onto one name without namespaces: {name}\n    {owner[name]}\n    {k}")
+    count = {k: sum(k in co.kernels for co in objs) for k in syms}
+    seen, table = {}, {}
+    for co in objs:
+        for k in co.kernels:
+            n = seen.get(k, 0)
+            seen[k] = n + 1
+            table[plain[k] if count[k] == 1 else f"{plain[k]} #{n}"] = (co, k)
+    return table
+
+
 def demangle(names):
     if not names:
         return []
@@ -119,22 +150,26 @@ def demangle(names):
 
 
 def main():
-    if len(sys.argv) != 3:
+    by_name = "--by-name" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != "--by-name"]
+    if len(args) != 2:
         sys.exit(__doc__)
     with tempfile.TemporaryDirectory() as tmp:
-        old_objs, new_objs = code_objects(sys.argv[1], tmp), code_objects(sys.argv[2], tmp)
-        old, new = kernel_table(old_objs), kernel_table(new_objs)
+        old_objs, new_objs = code_objects(args[0], tmp), code_objects(args[1], tmp)
+        table = kernel_table_by_name if by_name else kernel_table
+        old, new = table(old_objs), table(new_objs)
+        show = (lambda keys: list(keys)) if by_name else demangle
         removed, added = sorted(set(old) - set(new)), sorted(set(new) - set(old))
         same = moved = 0
         differs = []
         for key in sorted(set(old) & set(new)):
-            (oc, k), (nc, _) = old[key], new[key]
-            if oc.descriptor(k) != nc.descriptor(k):
+            (oc, k), (nc, kn) = old[key], new[key]   # (the symbols differ only with --by-name)
+            if oc.descriptor(k) != nc.descriptor(kn):
                 differs.append((key, "kernel descriptor"))
-            elif oc.bytes_of(oc.funcs[k]) == nc.bytes_of(nc.funcs[k]):
+            elif oc.bytes_of(oc.funcs[k]) == nc.bytes_of(nc.funcs[kn]):
                 same += 1
             else:
-                n = literal_moves(oc, nc, k)
+                n = literal_moves(oc, nc, k, kn, by_name)
                 if n is None:
                     differs.append((key, "instruction stream"))
                 else:
@@ -142,8 +177,8 @@ def main():
 
         def text_bytes(objs):
             return sum(s[4] for co in objs for s in co.sections.values() if s[0] == ".text")
-        print(f"old: {len(old_objs)} code objects, {len(old)} kernels, {text_bytes(old_objs)} bytes of .text, library {os.path.getsize(sys.argv[1])} bytes")
-        print(f"new: {len(new_objs)} code objects, {len(new)} kernels, {text_bytes(new_objs)} bytes of .text, library {os.path.getsize(sys.argv[2])} bytes")
+        print(f"old: {len(old_objs)} code objects, {len(old)} kernels, {text_bytes(old_objs)} bytes of .text, library {os.path.getsize(args[0])} bytes")
+        print(f"new: {len(new_objs)} code objects, {len(new)} kernels, {text_bytes(new_objs)} bytes of .text, library {os.path.getsize(args[1])} bytes")
         for i, (a, b) in enumerate(zip(old_objs, new_objs)):
             if len(a.kernels) != len(b.kernels):
                 print(f"  code object {i}: {len(a.kernels)} -> {len(b.kernels)} kernels, {len(a.data)} -> {len(b.data)} bytes")
@@ -152,12 +187,12 @@ def main():
         print(f"  identical instructions, only address literals of device globals moved with the layout: {moved}")
         print(f"  DIFFERENT: {len(differs)}")
         for key, what in differs:
-            print(f"    {what}: {demangle([key])[0]}")
+            print(f"    {what}: {show([key])[0]}")
         print(f"added kernels: {len(added)}")
-        for d in demangle(added):
+        for d in show(added):
             print(f"    {d}")
         print(f"removed kernels: {len(removed)}")
-        for d in demangle(removed):
+        for d in show(removed):
             print(f"    {d}")
         return 1 if differs else 0
 

@@ -62,6 +62,12 @@ class RegionDesc(C.Structure):
                 [("class_w", C.c_float * SG_MAX_CLASSES), ("point_alpha", C.c_float * SG_MAX_CLASSES)])
 
 
+class MineDesc(C.Structure):
+    """Mirror of `sg_mine_desc` (include/segengine.h): a pointwise loss averaged over the hard rows only."""
+    _fields_ = ([(n, C.c_int32) for n in ("C", "y_cols", "kind", "reserved")] + [("rows", C.c_int64), ("min_kept", C.c_int64)] +
+                [("thresh", C.c_float), ("alpha", C.c_float * SG_MAX_CLASSES)])
+
+
 class OptimChunk(C.Structure):
     """Mirror of `sg_optim_chunk` (include/segengine.h): a 16-byte aligned run of one parameter's elements."""
     _fields_ = [("start", C.c_int64), ("length", C.c_int32), ("segment", C.c_int32)]
@@ -327,6 +333,9 @@ _SIGNATURES = {
     "sg_loss_region_ws_bytes": (_sz, [_vp, C.POINTER(RegionDesc)]),
     "sg_loss_region_fwd": (_i, [_vp, _vp, C.POINTER(RegionDesc), _vp, _vp, _vp, _vp, _vp, _sz]),
     "sg_loss_region_bwd": (_i, [_vp, _vp, C.POINTER(RegionDesc), _vp, _vp, _vp, _vp, _f]),
+    "sg_loss_mined_ws_bytes": (_sz, [_vp, C.POINTER(MineDesc)]),
+    "sg_loss_mined_fwd": (_i, [_vp, _vp, C.POINTER(MineDesc), _vp, _vp, _vp, _vp, _vp, _sz]),
+    "sg_loss_mined_bwd": (_i, [_vp, _vp, C.POINTER(MineDesc), _vp, _vp, _vp, _vp, _f]),
     "sg_adam_step": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f]),
     "sg_adam_step_lr": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f]),
     "sg_optim_norms_ws_bytes": (_sz, [_i]),

@@ -7,10 +7,9 @@
 // At C = 2 every kernel here evaluates the expressions of the 2-class kernels (softmax2_*_kernel, loss_*_kernel,
 // confusion_kernel, argmax_acc_kernel) in the same order; only the loss scalar's per-row sum is shaped differently.
 #include "sg_reduce.h"
+#include "loss_rows.h"
 
 namespace {
-
-constexpr float K_EPS = 1e-7f;  // tf.keras.backend.epsilon()
 
 struct ClassAlpha {
   float a[SG_MAX_CLASSES];
@@ -62,12 +61,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restric
   }
 }
 
-// a_c of the three losses; w = y_true[:, C:2C] (edge focal only, which the entry points take with y_cols == 2C alone)
-__device__ __forceinline__ float loss_coeff(int kind, float alpha, float y, float w) {
-  if (kind == SG_LOSS_CE2) return y;
-  if (kind == SG_LOSS_FOCAL) return alpha * y;
-  return alpha * w * y;
-}
+// loss_coeff, loss_row_term, loss_row_grad: loss_rows.h
 
 __device__ __forceinline__ float block_sum_256(float v, float* sm) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -97,8 +91,7 @@ __global__ __launch_bounds__(256) void lossn_fwd_kernel(int kind, int64_t rows, 
     float r = 0.f;
     MC_FOR(c) {
       const float a = loss_coeff(kind, al.a[c], y[c], w[c]);
-      const float f = kind == SG_LOSS_CE2 ? 1.f : (1.f - pv[c]) * (1.f - pv[c]);
-      r += a * f * logf(pv[c] + K_EPS);
+      r += loss_row_term(kind, a, pv[c]);
     }
     acc += r;
   }
@@ -131,13 +124,7 @@ __global__ __launch_bounds__(256) void lossn_bwd_kernel(int kind, int64_t rows, 
     }
     MC_FOR(c) {
       const float a = loss_coeff(kind, al.a[c], y[c], w[c]);
-      float g;
-      if (kind == SG_LOSS_CE2) {
-        g = 1.f / (pv[c] + K_EPS);
-      } else {
-        const float q = 1.f - pv[c];
-        g = -2.f * q * logf(pv[c] + K_EPS) + q * q / (pv[c] + K_EPS);
-      }
+      const float g = loss_row_grad(kind, pv[c]);
       dp[i * C + c] = k * a * g;
     }
   }

@@ -11,7 +11,8 @@ matrix (`metrics_from_matrix`).
 
 Beyond the reference: the region-overlap losses `dice_loss`, `jaccard_loss`, `tversky_loss(alpha, beta)` and
 `compound(pointwise, region)`, which adds one of them to one of the three losses above (`sg_loss_region_fwd/bwd`, at 2 ... 32
-classes).
+classes), and `hard_mining(pointwise, thresh, min_kept)`, one of the three averaged over the batch's hard pixels
+only (`sg_loss_mined_fwd/bwd`).
 """
 from __future__ import annotations
 
@@ -126,6 +127,54 @@ def tversky_loss(alpha, beta):
                        alpha, beta)
 
 
+class _MinedLoss(_Named):
+    """A pointwise loss averaged over the hard pixels of the batch only (online hard example mining)."""
+
+    def __init__(self, pointwise, thresh, min_kept):
+        super().__init__(f"hard_mining({pointwise.__name__})", self.__doc__)
+        self.pointwise, self.thresh, self.min_kept = pointwise, thresh, min_kept
+
+    def __repr__(self):
+        return f"<building_detection_amd hard_mining({self.pointwise!r}, thresh={self.thresh}, min_kept={self.min_kept})>"
+
+
+def hard_mining(pointwise, thresh=0.7, min_kept=0.1):
+    """`pointwise` (binary_crossentropy, focal_loss or edge_focal_loss, with or without with_alpha) averaged over the hard
+    pixels only.  A pixel's key q is the probability the network gives its TRUE class; with q_(k) the k-th smallest key of the
+    batch,
+
+        T = max(thresh, q_(k)),   a pixel is kept iff q <= T,   L = sum of the kept pixels' terms / number of kept pixels.
+
+    Every tie at T is kept, so at least k pixels always are and the set depends on no order.  (The published
+    OhemCrossEntropy / OHEMPixelSampler compare with `<` and can drop the k-th pixel itself: a deliberate difference.)
+    thresh in [0, 1]: 1 keeps every pixel (the plain loss), 0 is pure top-k.  min_kept: a float in (0, 1] is a fraction of the
+    batch's pixels, k = min(rows, max(1, ceil(f * rows))); an int >= 1 is a pixel count, k = min(rows, n)."""
+    if isinstance(pointwise, _MinedLoss) or not isinstance(pointwise, _Named) or pointwise.__name__ not in _LOSS_KINDS:
+        raise ValueError(f"hard_mining: pointwise = {pointwise!r} is not one of {sorted(_LOSS_KINDS)}")
+    t = None if isinstance(thresh, bool) else _finite(thresh)
+    if t is None or not 0.0 <= t <= 1.0:
+        raise ValueError(f"hard_mining: thresh = {thresh!r} must be finite and in [0, 1]")
+    if isinstance(min_kept, (bool, np.bool_)):
+        k = None
+    elif isinstance(min_kept, (int, np.integer)):
+        k = int(min_kept) if min_kept >= 1 else None
+    elif isinstance(min_kept, (float, np.floating)):
+        k = float(min_kept) if 0.0 < min_kept <= 1.0 else None      # a NaN fails both
+    else:
+        k = None
+    if k is None:
+        raise ValueError(f"hard_mining: min_kept = {min_kept!r} must be a float in (0, 1] (a fraction of the batch's pixels) or "
+                         "an int >= 1 (a pixel count)")
+    return _MinedLoss(pointwise, t, k)
+
+
+def mined_rows(min_kept, rows: int) -> int:
+    """k of a batch of `rows` pixels: a float is a fraction, k = min(rows, max(1, ceil(f * rows))); an int a count, min(rows, n)."""
+    if isinstance(min_kept, float):
+        return min(rows, max(1, int(np.ceil(min_kept * rows))))
+    return min(rows, int(min_kept))
+
+
 class _CompoundLoss(_Named):
     """pointwise_weight * pointwise + region_weight * region, evaluated by ONE forward and ONE backward pass."""
 
@@ -140,6 +189,8 @@ class _CompoundLoss(_Named):
 def compound(pointwise, region, region_weight=1.0, pointwise_weight=1.0):
     """`pointwise` is binary_crossentropy, focal_loss or edge_focal_loss (with or without with_alpha), `region` one of
     dice_loss / jaccard_loss / tversky_loss(...).  The weights are >= 0 and not both 0."""
+    if isinstance(pointwise, _MinedLoss):
+        raise ValueError(f"compound: pointwise = {pointwise!r}: a mined pointwise term inside a compound is not implemented")
     if not isinstance(pointwise, _Named) or pointwise.__name__ not in _LOSS_KINDS:
         raise ValueError(f"compound: pointwise = {pointwise!r} is not one of {sorted(_LOSS_KINDS)}")
     if not isinstance(region, _RegionLoss):
@@ -177,15 +228,16 @@ def _warn_foreign(fn, what, lines):
 
 def resolve_loss(loss) -> int:
     """The pointwise kind of `loss`: SG_LOSS_* for the reference's three names (and for the pointwise part of a compound),
-    NO_POINTWISE for a region loss on its own."""
-    if isinstance(loss, _CompoundLoss):
+    NO_POINTWISE for a region loss on its own; for hard_mining(pointwise) the kind of `pointwise`."""
+    if isinstance(loss, (_CompoundLoss, _MinedLoss)):
         return _LOSS_KINDS[loss.pointwise.__name__]
     if isinstance(loss, _RegionLoss):
         return NO_POINTWISE
     name = loss if isinstance(loss, str) else getattr(loss, "__name__", None)
     if name not in _LOSS_KINDS:
         raise ValueError(f"loss {loss!r}: the engine implements {sorted(_LOSS_KINDS)} (train_model/DeepLabv3plus.py:490-527), "
-                         "dice_loss, jaccard_loss, tversky_loss(alpha, beta) and compound(pointwise, region)")
+                         "dice_loss, jaccard_loss, tversky_loss(alpha, beta), compound(pointwise, region) and "
+                         "hard_mining(pointwise)")
     _warn_foreign(loss, "loss", "490-527")
     return _LOSS_KINDS[name]
 
@@ -217,10 +269,24 @@ def resolve_region(loss, num_classes: int):
                 per_image=region.per_image, point_kind=kind, point_alpha=alpha, point_weight=wp, region_weight=wr)
 
 
+def resolve_mining(loss, num_classes: int):
+    """The fields of `sg_mine_desc` that `loss` fixes for a `num_classes` model, or None for a loss that is not mined:
+    dict(kind, alpha, thresh, min_kept).  alpha is None (cross-entropy) or `num_classes` weights - at two classes without
+    with_alpha the reference's own, passed explicitly; min_kept is the fraction (float) or the count (int) as given:
+    `mined_rows` turns it into the k of a batch."""
+    if not isinstance(loss, _MinedLoss):
+        return None
+    kind = _LOSS_KINDS[loss.pointwise.__name__]
+    alpha = resolve_alpha(loss.pointwise, num_classes)
+    if alpha is None and kind != SG_LOSS_CE2:
+        alpha = _TWO_CLASS_ALPHA[kind]
+    return dict(kind=kind, alpha=alpha, thresh=loss.thresh, min_kept=loss.min_kept)
+
+
 def resolve_alpha(loss, num_classes: int):
     """The per-class weights `loss` trains a `num_classes` model with: None = what the 2-class kernels have built in
     (no weights given, 2 classes; cross-entropy has none at all), else a tuple of `num_classes` floats."""
-    if isinstance(loss, _CompoundLoss):
+    if isinstance(loss, (_CompoundLoss, _MinedLoss)):
         return resolve_alpha(loss.pointwise, num_classes)
     if isinstance(loss, _RegionLoss):
         return None

@@ -1029,6 +1029,48 @@ class Engine:
               "sg_loss_region_bwd")
         return dp
 
+    @staticmethod
+    def mine_desc(mine, p, y_true):
+        """`sg_mine_desc` of `mine` (the dict of losses.resolve_mining) for p [..., C] and y_true [..., C or 2C]: min_kept
+        becomes the row count k of this batch (losses.mined_rows)."""
+        from .losses import mined_rows
+        c, y_cols = int(p.shape[-1]), int(y_true.shape[-1])
+        rows = p.numel() // c
+        if y_true.numel() != rows * y_cols or y_cols not in (c, 2 * c):
+            raise ValueError(f"y_true {tuple(y_true.shape)} does not go with p {tuple(p.shape)}: C or 2C columns per pixel")
+        if mine["kind"] == _lib.SG_LOSS_EDGE_FOCAL and y_cols != 2 * c:
+            raise ValueError(f"edge_focal_loss needs y_true[..., {2 * c}] (one-hot, then one edge weight per class), got {y_cols} columns")
+        if mine["alpha"] is not None and len(mine["alpha"]) != c:
+            raise ValueError(f"the loss carries class weights for another class count than {c}")
+        d = _lib.MineDesc(C=c, y_cols=y_cols, kind=int(mine["kind"]), reserved=0, rows=rows,
+                          min_kept=mined_rows(mine["min_kept"], rows), thresh=mine["thresh"])
+        for i in range(c):
+            d.alpha[i] = 1.0 if mine["alpha"] is None else mine["alpha"][i]
+        return d
+
+    def loss_mined_fwd(self, mine, p, y_true):
+        """A pointwise loss averaged over the hard rows (sg_loss_mined_fwd).  Returns (loss[1], sel): sel is the int32 [4]
+        record {bits of T, 0, n_kept low, n_kept high} that loss_mined_bwd forms the gradient from."""
+        _chk32(p, "p"); _chk32(y_true, "y_true")
+        d = self.mine_desc(mine, p, y_true)
+        out, sel = self.empty(1), self.empty(4, dtype=torch.int32)
+        wsp, wsn = self.ws(self.lib.sg_loss_mined_ws_bytes(self.h, C.byref(d)))
+        check(self.lib.sg_loss_mined_fwd(self.h, self.stream, C.byref(d), _ptr(p), _ptr(y_true), _ptr(out), _ptr(sel), wsp, wsn),
+              "sg_loss_mined_fwd")
+        return out, sel
+
+    def loss_mined_bwd(self, mine, p, y_true, sel, scale=1.0, out=None):
+        """dL/dp of loss_mined_fwd's loss, times `scale`; `sel` is what the forward call returned for the same p and y_true."""
+        _chk32(p, "p"); _chk32(y_true, "y_true")
+        d = self.mine_desc(mine, p, y_true)
+        if not torch.is_tensor(sel) or tuple(sel.shape) != (4,) or sel.dtype != torch.int32 or not sel.is_cuda:
+            raise ValueError(f"sel {tuple(getattr(sel, 'shape', ()))} {getattr(sel, 'dtype', type(sel))} is not the forward call's "
+                             "int32 [4] device record")
+        dp = out if out is not None else torch.empty_like(p)
+        check(self.lib.sg_loss_mined_bwd(self.h, self.stream, C.byref(d), _ptr(p), _ptr(y_true), _ptr(sel), _ptr(dp), float(scale)),
+              "sg_loss_mined_bwd")
+        return dp
+
     def confusion_matrix(self, p, y_true, out=None):
         """out[t * C + q] += rows whose truth is class t and prediction class q (int64 [C * C], zeroed when created here)."""
         _chk32(p, "p"); _chk32(y_true, "y_true")

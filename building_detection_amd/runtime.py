@@ -242,7 +242,13 @@ class Model:
         loss: one of the reference's three, or a region-overlap loss (losses.dice_loss, jaccard_loss, tversky_loss(a, b)) or
         losses.compound(pointwise, region); logs["loss"] is then L = pointwise_weight * L_point + region_weight * L_region.
         Under data parallelism (model.dist) every rank computes the region term on its own batch; the gradients are averaged
-        as ever and the logged loss is the mean over the ranks."""
+        as ever and the logged loss is the mean over the ranks.
+
+        losses.hard_mining(pointwise, thresh, min_kept) averages `pointwise` over the hard pixels of the batch only: those whose
+        true-class probability is <= T = max(thresh, the k-th smallest of the batch), every tie at T kept (sg_loss_mined_*; the
+        selection runs on the device, so a captured step needs no host round trip).  last_hard_mining() reports T and the kept
+        count of the last step.  Under data parallelism every rank mines its OWN shard (k is taken of the shard's pixels); the
+        gradients are averaged as ever and the logged loss is the mean over the ranks."""
         if isinstance(optimizer, str):   # 'adam' (the reference's, DeepLabv3plus.py:835) | 'adamw' | 'sgd'; else a ValueError
             from . import optimizers
             optimizer = optimizers.get(optimizer)
@@ -256,6 +262,9 @@ class Model:
         # global batch.)
         self.loss_region = LS.resolve_region(loss, self.num_classes)
         self._loss_coef = None
+        # hard_mining(pointwise): the descriptor fields sg_loss_mined_* run by, else None; _loss_sel is the last step's record
+        self.loss_mining = LS.resolve_mining(loss, self.num_classes)
+        self._loss_sel = self._loss_sel_rows = None
         self.metric_names = [LS.resolve_metric(m) for m in (metrics or [])]
         self.jit_compile = bool(jit_compile)
         self._train_graphs = {}
@@ -279,7 +288,12 @@ class Model:
 
     # A region loss: one forward call leaves {L, L_point, L_region} and the per-class gradient coefficients `coef`, which the
     # backward call of the same step reads (self._loss_coef; a captured step keeps the tensor, GraphedTrainStep.coef).
+    # A mined loss: the forward call leaves the record {T, n_kept} (self._loss_sel; GraphedTrainStep.sel), the backward call reads it.
     def _loss_fwd(self, eng, p, y):
+        if getattr(self, "loss_mining", None) is not None:
+            out, self._loss_sel = eng.loss_mined_fwd(self.loss_mining, p, y)
+            self._loss_sel_rows = p.numel() // p.shape[-1]
+            return out
         if getattr(self, "loss_region", None) is not None:
             out, self._loss_coef = eng.loss_region_fwd(self.loss_region, p, y)
             return out[:1]
@@ -288,11 +302,22 @@ class Model:
         return eng.lossn_fwd(self.loss_kind, p, y, self.loss_alpha)
 
     def _loss_bwd(self, eng, p, y):
+        if getattr(self, "loss_mining", None) is not None:
+            return eng.loss_mined_bwd(self.loss_mining, p, y, self._loss_sel, 1.0)
         if getattr(self, "loss_region", None) is not None:
             return eng.loss_region_bwd(self.loss_region, p, y, self._loss_coef, 1.0)
         if self._two_class():
             return eng.loss_bwd(self.loss_kind, p, y, 1.0)
         return eng.lossn_bwd(self.loss_kind, p, y, self.loss_alpha, 1.0)
+
+    def last_hard_mining(self):
+        """dict(threshold=T, kept=n_kept, rows=rows) of the last train_on_batch / test_on_batch under a hard_mining loss (this
+        rank's shard under data parallelism): one host sync, taken only here.  None when the loss is not mined or no step ran."""
+        sel = getattr(self, "_loss_sel", None)
+        if getattr(self, "loss_mining", None) is None or sel is None:
+            return None
+        w = sel.cpu().numpy().view(np.uint32)
+        return dict(threshold=float(w[:1].view(np.float32)[0]), kept=int(w[2]) | (int(w[3]) << 32), rows=int(self._loss_sel_rows))
 
     def _counts(self, eng, p, y):
         if not self.metric_names:
@@ -366,6 +391,8 @@ class Model:
                         g = self._train_graphs[key] = GraphedTrainStep(self, xd, yd)
                 if g is not None:
                     loss, counts = g.run(xd, yd)
+                    if getattr(g, "sel", None) is not None:   # (a test_on_batch in between leaves its own record here)
+                        self._loss_sel, self._loss_sel_rows = g.sel, yd.numel() // yd.shape[-1]
                     return (loss, counts) if return_device_scalars else self._logs(loss, counts)
             p = rt.forward(xd, training=True)
             loss = self._loss_fwd(rt.eng, p, yd)
@@ -663,6 +690,7 @@ class GraphedTrainStep:
                 p = rt.forward(self.x, training=True)
                 self.loss = model._loss_fwd(eng, p, self.y)
                 self.coef = getattr(model, "_loss_coef", None)   # a region loss: the graph's backward pass reads this tensor
+                self.sel = getattr(model, "_loss_sel", None)     # a mined loss: likewise the record {T, n_kept}
                 self.counts = model._counts(eng, p, self.y)   # zeroed inside the graph, four counts or C x C
                 dp = model._loss_bwd(eng, p, self.y)
                 rt.backward(dp)

@@ -732,6 +732,41 @@ int sg_loss_region_fwd(sg_ctx* ctx, void* stream, const sg_region_desc* desc, co
                        void* loss_out, void* coef_out, void* ws, size_t ws_bytes);
 int sg_loss_region_bwd(sg_ctx* ctx, void* stream, const sg_region_desc* desc, const void* p, const void* y_true,
                        const void* coef, void* dp, float grad_scale);
+/* Hard-pixel mining (online hard example mining, OHEM) for the three pointwise losses above: the loss is averaged over the
+ * rows the network gets wrong or is unsure about.  p[rows,C], y_true[rows,y_cols] as for sg_lossn_*.  For row i
+ *   t_i = argmax y_true[i, :C] (ties to the lowest index, the truth of sg_confusion_matrix),
+ *   key q_i = p[i, t_i], a plain load, clamped to [0, 1]; a NaN key counts as 0 (the row is kept, the NaN shows in L),
+ *   l_i = the row's term of kind `kind` with alpha (what sg_lossn_fwd averages over all rows).
+ * With q_(k) the k-th smallest key, k = min_kept:   T = max(thresh, q_(k));   row i is kept iff q_i <= T;
+ *   n_kept = #kept;   L = sum_kept l_i / n_kept;   dL/dp[i, :] = grad_scale * dl_i/dp / n_kept on kept rows, +0.0f elsewhere.
+ * EVERY tie at T is kept: the kept set depends on no order and holds at least k rows.  (The published OhemCrossEntropy /
+ * OHEMPixelSampler keep q_i < T and may drop the k-th row itself; this is a deliberate difference.)  thresh = 1 keeps every
+ * row - the plain loss -, thresh = 0 is pure top-k.
+ * q_(k) is found on the device by an exact radix select on the key's bit pattern (non-negative floats order as unsigned
+ * integers, 0 and denormals included); integer histogram adds only.  sel (16 bytes of device memory, 4-byte aligned) is the
+ * record {uint32 bits of T, uint32 0, uint64 n_kept}: fwd writes it, bwd reads it together with p and y_true and recomputes
+ * the keys, so the workspace need not survive between the two calls.
+ * Domain: 2 <= C <= SG_MAX_CLASSES; y_cols = C or 2C (2C with kind 2); kind = SG_LOSS_*; reserved = 0;
+ * 1 <= rows <= 2^32 - 1; 1 <= min_kept <= rows; 0 <= thresh <= 1; alpha finite (read for kinds 1 and 2).  The descriptor is a
+ * HOST struct, read at the call and carried in the kernel arguments (a captured graph keeps it).  The workspace is
+ * 4 * (rows + 8 + 3 * 2048 + 2 * sg_loss_parts) bytes.  fp32, dense, 4-byte alignment is enough for every pointer.  No allocation,
+ * no synchronisation, no float atomics: two calls on the same inputs give the same bits.  A descriptor outside the domain, a
+ * null pointer or a short workspace is SG_EINVAL / SG_EWORKSPACE and nothing is launched or written; the workspace query then
+ * returns 0. */
+typedef struct sg_mine_desc {
+  int32_t C, y_cols;
+  int32_t kind;               /* SG_LOSS_CE2 | SG_LOSS_FOCAL | SG_LOSS_EDGE_FOCAL */
+  int32_t reserved;           /* 0 */
+  int64_t rows;
+  int64_t min_kept;           /* k */
+  float thresh;
+  float alpha[SG_MAX_CLASSES]; /* ignored for SG_LOSS_CE2 */
+} sg_mine_desc;
+size_t sg_loss_mined_ws_bytes(const sg_ctx* ctx, const sg_mine_desc* desc);
+int sg_loss_mined_fwd(sg_ctx* ctx, void* stream, const sg_mine_desc* desc, const void* p, const void* y_true,
+                      void* loss_out, void* sel_out, void* ws, size_t ws_bytes);
+int sg_loss_mined_bwd(sg_ctx* ctx, void* stream, const sg_mine_desc* desc, const void* p, const void* y_true,
+                      const void* sel, void* dp, float grad_scale);
 /* Keras-2 Adam (compile(optimizer='adam'), DeepLabv3plus.py:835) on one flat fp32
  * parameter arena: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; w -= lr_t * m / (sqrt(v) + eps) with
  * lr_t = lr*sqrt(1-b2^t)/(1-b1^t) precomputed by the host.  g is scaled by grad_scale first (1/world). */

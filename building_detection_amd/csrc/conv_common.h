@@ -2,7 +2,7 @@
 // kernel family uses, the planning helpers every launch comes through, ConvPlan and the filter gradient's plan types.
 //
 // Types that cross a translation-unit boundary live in namespace sgconv; kernels and file-local helpers stay in an anonymous
-// namespace inside their own unit.  A kernel family that is a unit of its own (today: the patch family, conv_x6p.hip) has
+// namespace inside their own unit.  A kernel family that is a unit of its own (today: native, thin and patch - conv_native.hip, conv_thin.hip, conv_x6p.hip) has
 //   conv_<family>.h    its geometry constants, the host predicates the plan and the plan queries ask, and the declarations of its
 //                      launch functions: plain host functions with run-time arguments (which template form a launch takes is
 //                      decided behind them, in the family's unit)

@@ -712,50 +712,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, PF == 2 ? (WGM * WGN + 3) / 4 : WGM
   }
 }
 
-// mean / variance over all rows from the per-tile (sum, centred sum of squares) pairs: a segmented column reduction
-// over the T tiles (rows of the reducer = tiles), pivoted on tile 0's mean so nothing cancels, combined in fp64, then
-// the BatchNormalization bookkeeping of BnStatsOp::finalize.
-struct BnTilesOp {
-  static constexpr int NOUT = 2;
-  const float* __restrict__ stats;  // [T][2][C]
-  int C;
-  int64_t rows;                     // pixels (not tiles)
-  float* moving_mean;
-  float* moving_var;
-  float* save_mean;
-  float* save_invstd;
-  float momentum, eps;
-  int unbiased;
-
-  template <int V>
-  __device__ __forceinline__ void accum(int, int64_t r, int c, float (&acc)[2][V]) const {
-    float s1[V], m2[V], s0[V];
-    ldv<V>(stats + (2 * r) * C + c, s1);
-    ldv<V>(stats + (2 * r + 1) * C + c, m2);
-    ldv<V>(stats + c, s0);
-    const int64_t left = rows - r * BM;
-    const float nt = (float)(left < BM ? left : BM), n0 = (float)(rows < BM ? rows : BM);
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      const float d = s1[i] / nt - s0[i] / n0;  // tile mean minus the pivot (tile 0's mean)
-      acc[0][i] = fmaf(nt, d, acc[0][i]);
-      acc[1][i] += fmaf(nt * d, d, m2[i]);
-    }
-  }
-  __device__ __forceinline__ void finalize(int, int c, const double (&s)[2]) const {
-    const double n = (double)rows, n0 = (double)(rows < BM ? rows : BM);
-    const double m1 = s[0] / n;
-    const double mean = (double)stats[c] / n0 + m1;
-    double var = s[1] / n - m1 * m1;
-    if (var < 0.0) var = 0.0;
-    save_mean[c] = (float)mean;
-    save_invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    const double var_u = (unbiased && rows > 1) ? var * (n / (n - 1.0)) : var;
-    moving_mean[c] = (float)((double)moving_mean[c] * momentum + mean * (1.0 - (double)momentum));
-    moving_var[c] = (float)((double)moving_var[c] * momentum + var_u * (1.0 - (double)momentum));
-  }
-};
-
 template <int BN, int WGM, int WGN, int PF, int NPL = 3, typename TA = float, int MF = 0>
 int launch_x6(const IgemmParams& p, hipStream_t st) {
   constexpr int NT = 64 * WGM * WGN;

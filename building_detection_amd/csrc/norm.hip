@@ -119,7 +119,7 @@ struct BnBwdOp {
 
 // ---- dy that is the input gradient of a thin 1x1 convolution (Cout = CO <= 4: the softmax head, the sSE gate), never written out ----
 // dy[r][c] = sum_o g[r][o] * w[c][o] is evaluated where the backward consumes it, with thin_dgrad_kernel's own expression
-// (csrc/conv_igemm.hip), so the sums and dx have the bits of thin dgrad + sg_bn_train_bwd without the C-wide tensor.  fp32 storage.
+// (csrc/conv_thin.hip), so the sums and dx have the bits of thin dgrad + sg_bn_train_bwd without the C-wide tensor.  fp32 storage.
 // The value is the result of explicit fmaf calls, which the compiler does not contract into their uses: it reaches them as the rounded
 // fp32 the other path stores.  (No asm fence: inline asm is convergent, and the reducer's row loop is then not unrolled.)
 template <int V, int CO>

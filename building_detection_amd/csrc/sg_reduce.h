@@ -327,60 +327,6 @@ static inline int seg_reduce_launch(const Op& op, const SegPlan& pl, int nseg, i
   return 0;
 }
 
-// vector load/store helpers (V = 4: 16-byte access; V = 1: scalar; V = 8: two 16-byte accesses)
-template <int V>
-__device__ __forceinline__ void ldv(const float* __restrict__ p, float (&o)[V]) {
-  if constexpr (V == 8) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
-  } else if constexpr (V == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = t[3];
-  } else {
-    o[0] = p[0];
-  }
-}
-template <int V>
-__device__ __forceinline__ void stv(float* __restrict__ p, const float (&o)[V]) {
-  if constexpr (V == 8) {
-    const f32x4 a = {o[0], o[1], o[2], o[3]}, b = {o[4], o[5], o[6], o[7]};
-    *reinterpret_cast<f32x4*>(p) = a;
-    *reinterpret_cast<f32x4*>(p + 4) = b;
-  } else if constexpr (V == 4) {
-    f32x4 t = {o[0], o[1], o[2], o[3]};
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    p[0] = o[0];
-  }
-}
-
-// bf16 storage: V = 4 is one 8-byte access, V = 1 a 2-byte one; values widen to fp32 in registers
-template <int V>
-__device__ __forceinline__ void ldv(const bf16_t* __restrict__ p, float (&o)[V]) {
-  if constexpr (V == 8) {
-    f32x4 a, b;
-    ld8_bf16(p, a, b);
-    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
-  } else if constexpr (V == 4) {
-    const f32x4 t = ld4<bf16_t>(p);
-    o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = t[3];
-  } else {
-    o[0] = ld1<bf16_t>(p);
-  }
-}
-template <int V>
-__device__ __forceinline__ void stv(bf16_t* __restrict__ p, const float (&o)[V]) {
-  if constexpr (V == 8) {
-    const f32x4 a = {o[0], o[1], o[2], o[3]}, b = {o[4], o[5], o[6], o[7]};
-    st8_bf16(p, a, b);
-  } else if constexpr (V == 4) {
-    const f32x4 t = {o[0], o[1], o[2], o[3]};
-    st4<bf16_t>(p, t);
-  } else {
-    st1<bf16_t>(p, o[0]);
-  }
-}
-
 static inline bool sg_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // "operands aligned" of plan_dw / plan_bn: every tensor the call passes (null: not passed) starts on a 16-byte boundary
 static inline bool sg_all_aligned16(std::initializer_list<const void*> ps) { return std::all_of(ps.begin(), ps.end(), sg_aligned16); }

@@ -1,5 +1,5 @@
 """The cases of tests/test_batchnorm_variants_gpu.py: one function per entry point of csrc/norm.hip and of the column sums built
-on csrc/sg_reduce.h in csrc/conv_igemm.hip (sg_bias_grad, sg_bn_train_fwd_tiles), each against plain float64 (tests/_guarded.py).
+on csrc/sg_reduce.h in csrc/conv_thin.hip (sg_bias_grad, sg_bn_train_fwd_tiles), each against plain float64 (tests/_guarded.py).
 
 A case states which kernels its launch takes - the reduction's V / TX / gx / row-split regime / finalize lanes and the apply
 pass's form - from the ENGINE's plan (sg_bn_plan; sg_seg_plan for the column sums), after checked_plan() has asserted that
@@ -28,7 +28,7 @@ from test_bandwidth_variants_gpu import BF16, DEV, F32, G, GO, call, done, gen, 
 REF_CUS = 256            # the CU count the shapes below were chosen at (MI355X)
 SG_EINVAL, SG_EUNSUPPORTED = -1, -3
 MOMENTUM, EPS = 0.5, 1e-3
-BM = 128                 # rows per statistics tile of the producing convolution (csrc/conv_igemm.hip)
+BM = 128                 # rows per statistics tile of the producing convolution (csrc/conv_common.h)
 COLS_ON = os.environ.get("SG_BN_COLS", "1") != "0"
 LANES16 = os.environ.get("SG_FINALIZE_LANES", "16") == "16"
 QUIET = False            # the child process prints its one line per case and nothing else

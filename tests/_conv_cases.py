@@ -1,4 +1,4 @@
-"""The cases of tests/test_conv_forms_gpu.py: sg_conv2d_fwd and sg_conv2d_dgrad (csrc/conv_igemm.hip and the kernels it includes)
+"""The cases of tests/test_conv_forms_gpu.py: sg_conv2d_fwd and sg_conv2d_dgrad (csrc/conv_igemm.hip, the kernels it includes, conv_native.hip, conv_thin.hip)
 through the C ABI on tests/_guarded.py arenas, each launch against oracle.tfops.conv2d in float64 (autograd for dx).
 
 A case states, at the end of its id, which kernel FORM its launch takes.  The name comes from the mirrors below of the dispatch

@@ -1,5 +1,5 @@
 """Every variant of the BatchNormalization kernels (csrc/norm.hip) and of the column sums built on csrc/sg_reduce.h in
-csrc/conv_igemm.hip (sg_bias_grad, sg_bn_train_fwd_tiles) against plain float64 torch on the CPU, through the C ABI itself.
+csrc/conv_thin.hip (sg_bias_grad, sg_bn_train_fwd_tiles) against plain float64 torch on the CPU, through the C ABI itself.
 The companion of tests/test_bandwidth_variants_gpu.py, with its machinery: operands are tests/_guarded.py arenas (NaN guard
 bands, NaN-prefilled outputs, inputs whose bits must survive, workspaces of exactly the queried size), their start 16-byte
 aligned or one element further.  The cases themselves are tests/_bn_cases.py (also run as a program, for the forms behind

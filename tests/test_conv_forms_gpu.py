@@ -1,5 +1,5 @@
 """Every kernel form of the forward convolution and of the input gradient (sg_conv2d_fwd, sg_conv2d_dgrad: csrc/conv_igemm.hip with
-conv_x6.h, conv_x6p.h, conv_x6w.h, conv_b16.h, conv_b16w.h and the forward / dgrad half of conv_pw.h) against float64, through the C
+conv_native.hip, conv_thin.hip, conv_x6.h, conv_x6p.h, conv_x6w.h, conv_b16.h, conv_b16w.h and the forward / dgrad half of conv_pw.h) against float64, through the C
 ABI on guarded operands.  The tables, the mirror of the dispatch rules, the reference and the runner are tests/_conv_cases.py; a
 case id ends in the name of the form its launch takes, asserted against the mirror and against sg_conv2d_plan before anything
 is launched.

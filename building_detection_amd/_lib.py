@@ -311,6 +311,7 @@ _SIGNATURES = {
     "sg_bam_fwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     "sg_bam_bwd_ws_bytes": (_sz, [_vp, _i, _i64, _i]),
     "sg_bam_bwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "sg_dropout": (_i, [_vp, _vp, _i, _i64, _i64, _i, _i64, C.c_uint32, C.c_uint32, _f, _vp, _vp, _vp]),
     "sg_maxpool_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sg_maxpool_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sg_maxpool_fwd_idx": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

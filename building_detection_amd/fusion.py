@@ -19,6 +19,13 @@ The order matters - a rule may read what an earlier one has marked:
    9 thin_grad          reads fused_away (3); up_src (2) must be unset
   10 scse_lowrank       reads bn_src (8) and up_src (2) of the sSE convolution: both must be unset
   11 bn_backward_in_pw  reads sums_from (5, 6)
+
+What is not fused:
+
+   - Dropout / SpatialDropout2D (layers._DropoutNode).  The rules match node types, and none names this one, so a dropout node
+     simply ends a pattern: a convolution followed by Dropout -> BatchNormalization keeps its bias gradient and hands over no
+     statistics, a BatchNormalization followed by Dropout is applied by its own pass.  The mask costs one element-wise launch in
+     each direction (sg_dropout); applying it inside BatchNormalization's apply pass or a convolution's epilogue is not done.
 """
 from . import layers as L
 from . import switches

@@ -9,6 +9,7 @@ reference's un-fused spelling onto the generic nodes.
 from __future__ import annotations
 
 
+import math
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -701,6 +702,100 @@ class Softmax(Layer):
     def __call__(self, x):
         self._once()
         return _ActNode(self._name, "softmax", self.axis).build(x)
+
+
+# ================================================================================================ dropout
+def dropout_threshold(rate: float) -> int:
+    """thr of sg_dropout: an element is kept iff its 32-bit mask word is >= min(floor(rate * 2^32), 2^32 - 1)."""
+    return min(int(math.floor(float(rate) * 4294967296.0)), 0xFFFFFFFF)
+
+
+def dropout_scale(rate: float) -> float:
+    """float32(1 / (1 - rate)): what a kept element is multiplied by."""
+    return float(np.float32(1.0 / (1.0 - float(rate))))
+
+
+def _check_rate(who, rate):
+    try:
+        r = float(rate)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: rate must be a float in [0, 1), got {rate!r}") from None
+    if not (math.isfinite(r) and 0.0 <= r < 1.0):
+        raise ValueError(f"{who}: rate must be a finite float in [0, 1), got {rate!r}")
+    return r
+
+
+class _DropoutNode(Node):
+    """Dropout / SpatialDropout2D.  The mask is a function of (model.seed, rank, optimizer step, this node's
+    stream word, element index): nothing is stored, the backward regenerates it with the forward's arguments."""
+
+    op = "dropout"
+
+    def __init__(self, name, rate, spatial=False, seed=None):
+        super().__init__(name)
+        self.rate, self.spatial = rate, bool(spatial)
+        self.seed = None if seed is None else int(seed)
+        self.thr, self.scale = dropout_threshold(rate), dropout_scale(rate)
+        # the layer's word of the generator's counter: seed mod 2^32 where the layer was given seed=, else the node's ordinal among
+        # the model's dropout nodes (set by Model, which knows the topological order)
+        self.rng_stream = None if self.seed is None else self.seed % (1 << 32)
+
+    def build(self, x):
+        if self.spatial and len(x.shape) != 4:
+            raise ValueError(f"{self.name}: the noise shape [N,1,1,C] needs an [N,H,W,C] input, got {x.shape}")
+        return self.connect([x], x.shape)
+
+    def _mask(self, rt, t):
+        hwc, c = (int(np.prod(t.shape[1:])), int(t.shape[-1])) if self.spatial else (0, 0)
+        return rt.eng.dropout(t, self.thr, self.scale, rt.rng_words(), self.rng_stream, hwc=hwc, c=c)
+
+    def forward(self, rt, xs, training):
+        if not training or self.rate == 0.0:
+            return xs[0]          # the input tensor itself: no launch, no copy
+        return self._mask(rt, xs[0])
+
+    def backward(self, rt, xs, y, dy):
+        if self.rate == 0.0:
+            return [rt.shared(dy)]
+        return [self._mask(rt, dy)]
+
+
+class Dropout(Layer):
+    """tf.keras.layers.Dropout.  noise_shape: None or the input's full shape (one decision per element), or (N | None, 1, 1, C)
+    (one per image and channel: SpatialDropout2D).  Active in the training forward only."""
+
+    def __init__(self, rate, noise_shape=None, seed=None, name=None, **kw):
+        super().__init__(name)
+        self.rate = _check_rate(type(self).__name__, rate)
+        self.noise_shape = None if noise_shape is None else tuple(noise_shape)
+        self.seed = seed
+
+    def _spatial(self, x) -> bool:
+        ns = self.noise_shape
+        if ns is None:
+            return False
+        shape = tuple(x.shape)
+        if len(ns) == len(shape) and (ns[0] is None or isinstance(ns[0], (int, np.integer))):   # (the batch size is free here)
+            if tuple(ns[1:]) == shape[1:]:
+                return False
+            if len(shape) == 4 and tuple(ns[1:]) == (1, 1, shape[3]):
+                return True
+        raise ValueError(f"Dropout: noise_shape {ns} on an input of shape {shape}: supported are the input's full shape and "
+                         f"(N | None, 1, 1, C) (SpatialDropout2D)")
+
+    def __call__(self, x):
+        self._once()
+        return _DropoutNode(self._name, self.rate, self._spatial(x), self.seed).build(x)
+
+
+class SpatialDropout2D(Dropout):
+    """tf.keras.layers.SpatialDropout2D: whole feature maps are dropped, noise shape [N,1,1,C]."""
+
+    def __init__(self, rate, name=None, **kw):
+        super().__init__(rate, name=name)
+
+    def _spatial(self, x) -> bool:
+        return True
 
 
 # ================================================================================================ pooling

@@ -704,6 +704,18 @@ class Engine:
               "sg_act_bwd")
         return dx
 
+    def dropout(self, x, thr, scale, rng, rng_stream, hwc=0, c=0, first=0, out=None):
+        """y = x * scale where the element's mask word is >= thr, +0 elsewhere (sg_dropout).  rng: four 32-bit words
+        on the device {k0, k1, step, 0}; rng_stream: the layer's word.  hwc = 0: one decision per element; hwc = H*W*C with c
+        channels: one per image and channel.  The backward is the same call on dy; out may be x."""
+        _chk(x, "x")
+        if not (rng.is_cuda and rng.element_size() == 4 and rng.numel() >= 4 and rng.is_contiguous()):
+            raise _lib.SgError("dropout: rng must be four 32-bit words on the device")
+        y = out if out is not None else torch.empty_like(x)
+        check(self.lib.sg_dropout(self.h, self.stream, _dt(x), x.numel(), int(hwc), int(c), int(first), int(rng_stream) & 0xffffffff,
+                                  int(thr) & 0xffffffff, float(scale), _ptr(rng), _ptr(x), _ptr(y)), "sg_dropout")
+        return y
+
     def add_n(self, xs: Sequence[torch.Tensor], relu=False, out=None):
         assert 1 <= len(xs) <= 8
         for t in xs:

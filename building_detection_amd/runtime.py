@@ -115,6 +115,11 @@ class Model:
         self.nodes: List[Node] = collect_nodes(self.outputs)
         for i, n in enumerate(self.nodes):
             n.index = i
+        # a dropout node's word of the generator's counter: its ordinal among the model's dropout nodes in topological order
+        # (a layer given seed= keeps seed mod 2^32, but still counts)
+        for k, n in enumerate(n for n in self.nodes if isinstance(n, L._DropoutNode)):
+            if n.seed is None:
+                n.rng_stream = k
         self.seed = seed
         self.stop_training = False
         self.optimizer: Optional[Optimizer] = None
@@ -394,6 +399,7 @@ class Model:
                     if getattr(g, "sel", None) is not None:   # (a test_on_batch in between leaves its own record here)
                         self._loss_sel, self._loss_sel_rows = g.sel, yd.numel() // yd.shape[-1]
                     return (loss, counts) if return_device_scalars else self._logs(loss, counts)
+            rt.write_rng(self.optimizer.iterations)   # (a model without dropout: nothing)
             p = rt.forward(xd, training=True)
             loss = self._loss_fwd(rt.eng, p, yd)
             counts = self._counts(rt.eng, p, yd)
@@ -731,6 +737,7 @@ class GraphedTrainStep:
         dist = self.model.dist
         self.x.copy_(xd, non_blocking=True)
         self.y.copy_(yd, non_blocking=True)
+        self.rt.write_rng(opt.iterations)   # the dropout masks' step word: the count BEFORE this step, as in the eager step
         opt.iterations += 1
         lr_t, lr = opt.step_scalars()
         self.lr.fill_(lr_t)
@@ -920,6 +927,13 @@ class _Runtime:
         self._planes_dirty = True
         self._w_version = 0   # bumped by weights_changed(): captured graphs compare it with the version their planes hold
         self._use_planes = switches.get("SG_PREPARED_PLANES")
+        # the seed words of the dropout masks {k0, k1, step, 0}, read by sg_dropout on the device; only a model with
+        # a dropout node of rate > 0 owns them.  Allocated here, never inside a capture.
+        self.rng = None
+        if any(isinstance(n, L._DropoutNode) and n.rate > 0 for n in model.nodes):
+            self.rng = torch.zeros(4, dtype=torch.int32, device=e.device)
+        self._rng_host = [None, None, None]
+        self.write_rng(0)   # a fresh runtime draws the masks of step 0
 
     # -- parameters ---------------------------------------------------------------------------------------
     def param(self, p: ParamSpec):
@@ -1085,6 +1099,26 @@ class _Runtime:
                                                C.c_void_p(self._planes_arena.data_ptr()), C.c_void_p(self._planes_jobs.data_ptr()),
                                                self._planes_launch[0], self._planes_launch[1]), "sg_prepare_planes")
         self._planes_dirty = False
+
+    # -- dropout seed words -------------------------------------------------------------------------------
+    def rng_words(self):
+        if self.rng is None:
+            raise RuntimeError("this runtime owns no dropout seed words: the model had no dropout node of rate > 0 when it was built")
+        return self.rng
+
+    def write_rng(self, step: int):
+        """{k0, k1, step} = {model.seed mod 2^32, data-parallel rank, optimizer.iterations before the step counts itself} into the
+        device words, with device fills (no copy from pageable host memory); a word that has not changed is not written again.
+        Model.train_on_batch and GraphedTrainStep.run call this before the forward / the replays.  A direct
+        forward(x, training=True) does not: it draws the masks of whatever the words hold (step 0 on a fresh runtime)."""
+        if self.rng is None:
+            return
+        m = self.model
+        words = (int(m.seed) % (1 << 32), (int(m.dist.rank) if m.dist is not None else 0) % (1 << 32), int(step) % (1 << 32))
+        for i, v in enumerate(words):
+            if self._rng_host[i] != v:
+                self.rng[i:i + 1].fill_(v - (1 << 32) if v >= (1 << 31) else v)   # (the same 32 bits in torch's signed type)
+                self._rng_host[i] = v
 
     # -- tape ---------------------------------------------------------------------------------------------
     def save(self, node, **kw):

@@ -303,7 +303,7 @@ _layer_names = dict(
     Activation=_Activation, ReLU=_wrap(L.ReLU), Softmax=_Softmax, MaxPooling2D=_wrap(L.MaxPooling2D),
     MaxPool2D=_wrap(L.MaxPooling2D), AveragePooling2D=_wrap(L.AveragePooling2D),
     GlobalAveragePooling2D=_wrap(L.GlobalAveragePooling2D), GlobalAvgPool2D=_wrap(L.GlobalAveragePooling2D),
-    UpSampling2D=_wrap(L.UpSampling2D), Reshape=_wrap(L.Reshape), RepeatVector=_RepeatVector, Cropping2D=_Cropping2D,
+    UpSampling2D=_wrap(L.UpSampling2D), Dropout=_wrap(L.Dropout), SpatialDropout2D=_wrap(L.SpatialDropout2D), Reshape=_wrap(L.Reshape), RepeatVector=_RepeatVector, Cropping2D=_Cropping2D,
     Add=_AddLayer, add=_layers_add, Multiply=_MultiplyLayer, multiply=_layers_multiply,
     Concatenate=_ConcatLayer, concatenate=lambda xs, axis=-1, name=None: _concat(list(xs), axis, name))
 

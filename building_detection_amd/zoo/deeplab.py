@@ -100,10 +100,25 @@ def _aspp(x, pool, upsampling="nearest"):
     return L.concatenate(outs)
 
 
-def _neck(c5, aspp_pool, upsampling="nearest"):
+def _rates(dropout):
+    """dropout=None | (p_aspp, p_head) of the two builders -> the pair; a zero adds no node."""
+    if dropout is None:
+        return 0.0, 0.0
+    try:
+        p_aspp, p_head = dropout
+    except (TypeError, ValueError):
+        raise ValueError(f"dropout must be None or a pair (p_aspp, p_head), got {dropout!r}") from None
+    return L._check_rate("dropout[0]", p_aspp), L._check_rate("dropout[1]", p_head)
+
+
+def _drop(x, p):
+    return L.Dropout(p)(x) if p else x
+
+
+def _neck(c5, aspp_pool, upsampling="nearest", p_aspp=0.0):
     sk = _sk_block(c5)   # its GAP broadcast (1x1 source) is the same tensor in both modes and stays a nearest node
     a = _aspp(c5, aspp_pool, upsampling)
-    y = _cbr(a, 256, 1)
+    y = _drop(_cbr(a, 256, 1), p_aspp)   # the ASPP's 1x1 projection, where the published recipes regularise
     y = L.concatenate([y, sk])
     y = _cbr(y, 256, 3)
     y = _cbr(y, 256, 3)
@@ -116,28 +131,32 @@ def _decode(y, filters):
     return L.scse_block(y)
 
 
-def Xception_DeepLabV3_Plus(shape=(512, 512, 3), num_classes=2, aspp_pool=32, upsampling="nearest"):
+def Xception_DeepLabV3_Plus(shape=(512, 512, 3), num_classes=2, aspp_pool=32, upsampling="nearest", dropout=None):
     """`upsampling` ("nearest", the reference's, or "bilinear") is the interpolation of the ASPP's and the decoder's
-    UpSampling2D layers; it changes no parameter."""
+    UpSampling2D layers; it changes no parameter.  `dropout` = (p_aspp, p_head) adds Dropout(p_aspp) on the output of the ASPP's
+    1x1 projection and Dropout(p_head) on the tensor entering the class convolution; None (the reference) and a zero add no node."""
+    p_aspp, p_head = _rates(dropout)
     inp = L.Input(shape=shape)
     c, c1, c2, c5 = _xception(inp, with_bam=False)
-    y = _neck(c5, aspp_pool, upsampling)
+    y = _neck(c5, aspp_pool, upsampling, p_aspp)
     y = _decode(L.concatenate([L.UpSampling2D(size=2, interpolation=upsampling)(y), c2]), 256)
     y = _decode(L.concatenate([L.Conv2DTranspose(128, 3, strides=2, padding="same")(y), c1]), 128)
     y = _decode(L.concatenate([c, L.Conv2DTranspose(64, 3, strides=2, padding="same")(y)]), 64)
     y = L.UpSampling2D(size=2, interpolation=upsampling)(y)
     y = _cbr(y, 32, 3)
     y = _cbr(y, 32, 3)
-    out = L.Conv2D(num_classes, 1, 1, activation="softmax")(y)
+    out = L.Conv2D(num_classes, 1, 1, activation="softmax")(_drop(y, p_head))
     return Model(inputs=inp, outputs=out, name="Xception_DeepLabV3_Plus")
 
 
-def Xception_DeepLabV3_Plus_bam(shape=(512, 512, 3), num_classes=2, aspp_pool=32, upsampling="nearest"):
+def Xception_DeepLabV3_Plus_bam(shape=(512, 512, 3), num_classes=2, aspp_pool=32, upsampling="nearest", dropout=None):
+    """`dropout` as Xception_DeepLabV3_Plus."""
+    p_aspp, p_head = _rates(dropout)
     inp = L.Input(shape=shape)
     _, c1, c2, c5 = _xception(inp, with_bam=True)
-    y = _neck(c5, aspp_pool, upsampling)
+    y = _neck(c5, aspp_pool, upsampling, p_aspp)
     y = _decode(L.concatenate([c2, L.UpSampling2D(size=2, interpolation=upsampling)(y)]), 128)
     y = _decode(L.concatenate([c1, L.UpSampling2D(size=2, interpolation=upsampling)(y)]), 64)
     y = L.UpSampling2D(size=4, interpolation=upsampling)(y)
-    out = L.Conv2D(num_classes, 1, 1, activation="softmax")(y)
+    out = L.Conv2D(num_classes, 1, 1, activation="softmax")(_drop(y, p_head))
     return Model(inputs=inp, outputs=out, name="Xception_DeepLabV3_Plus_bam")

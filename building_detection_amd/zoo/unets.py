@@ -7,9 +7,18 @@ from ..runtime import Model
 
 
 # ------------------------------------------------------------------------------------------------ SCSE-UNet
-def UNet(num_classes=2, input_shape=(512, 512, 3)):
+def _head_drop(x, dropout):
+    """dropout=None | p_head of UNet and HRNet: Dropout(p_head) on the tensor entering the class convolution; None and 0 add no node."""
+    if dropout is None:
+        return x
+    p = L._check_rate("dropout", dropout)
+    return L.Dropout(p)(x) if p else x
+
+
+def UNet(num_classes=2, input_shape=(512, 512, 3), dropout=None):
     """5-level VGG-style U-Net: conv3x3+ReLU pairs (no BN), 2x2 max-pool, Conv2DTranspose 3x3 s2 + ReLU,
-    scSE after every decoder stage, 1x1 softmax head.  Note the (num_classes, input_shape) argument order."""
+    scSE after every decoder stage, 1x1 softmax head.  Note the (num_classes, input_shape) argument order.
+    `dropout` = p_head: Dropout(p_head) in front of the head (None, the reference: no node)."""
     def pair(t, f):
         t = L.Conv2D(f, 3, padding="same", activation="relu")(t)
         return L.Conv2D(f, 3, padding="same", activation="relu")(t)
@@ -24,7 +33,7 @@ def UNet(num_classes=2, input_shape=(512, 512, 3)):
     for f, skip in zip((512, 256, 128, 64), reversed(skips)):
         up = L.Conv2DTranspose(f, 3, strides=2, padding="same", activation="relu")(x)
         x = L.scse_block(pair(L.concatenate([up, skip]), f))
-    out = L.Conv2D(num_classes, 1, padding="same", activation="softmax")(x)
+    out = L.Conv2D(num_classes, 1, padding="same", activation="softmax")(_head_drop(x, dropout))
     return Model(inputs=inp, outputs=out, name="UNet_scse")
 
 
@@ -151,7 +160,8 @@ def _fuse2(b):
     return g0, g1, g2
 
 
-def HRNet(shape=(512, 512, 3), num_classes=2):
+def HRNet(shape=(512, 512, 3), num_classes=2, dropout=None):
+    """`dropout` = p_head: Dropout(p_head) in front of the head (None, the reference: no node)."""
     inp = L.Input(shape=shape)
     x = _cbr(inp, 64, strides=2)
     x = _bottleneck(x, 256, project=True)
@@ -171,5 +181,5 @@ def HRNet(shape=(512, 512, 3), num_classes=2):
     b = [_branch(t[0], 32), _branch(t[1], 64), _branch(t[2], 128), _branch(t[3], 256)]
     y = L.concatenate([b[0], _up(b[1], 32, 2), _up(b[2], 32, 4), _up(b[3], 32, 8)])
     y = _cbr(L.UpSampling2D(size=2)(y), 64)
-    out = L.Conv2D(num_classes, 1, padding="same", activation="softmax")(y)
+    out = L.Conv2D(num_classes, 1, padding="same", activation="softmax")(_head_drop(y, dropout))
     return Model(inputs=inp, outputs=out, name="HRNet")

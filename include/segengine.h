@@ -607,6 +607,21 @@ int sg_bam_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int64_t HW, int C, c
                const void* mc, const void* ms, const void* dy, void* dx, void* dmc, void* dms, void* ws,
                size_t ws_bytes);
 
+/* Dropout(rate) and SpatialDropout2D(rate): y[i] = x[i] * scale where keep(idx_i) holds, +0 elsewhere, in fp32
+ * (bf16 storage is widened, multiplied and rounded to nearest even).  No mask is stored; the backward is the same call on dy.
+ *   idx_i = first + i                                (hwc == 0: one decision per element; i = flat NHWC index, n elements)
+ *   idx_i = first + (i div hwc) * c + i mod c        (hwc > 0: the spatial form, noise shape [N,1,1,C]; hwc = H*W*C)
+ *   keep(idx): word idx & 3 of Philox4x32-10 (multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 / BB67AE85) at counter
+ *              (q mod 2^32, q >> 32, rng_stream, step), q = idx >> 2 (idx as an unsigned 64-bit number), key (k0, k1), is >= thr
+ * thr = min(floor(rate * 2^32), 2^32 - 1) and scale = 1 / (1 - rate) come from the host; thr = 0 keeps everything.
+ * rng_dev: four uint32 in DEVICE memory {k0, k1, step, 0}, read by the kernel, so a captured launch sees the values of each
+ * replay.  y == x (in place) is allowed.  The result is a function of the arguments alone: the same bits for every alignment,
+ * grid and kernel form (four elements per generator call and one 16-byte access when x, y are 16-byte aligned, first % 4 == 0
+ * and, in the spatial form, c % 4 == 0; one call per element otherwise).  SG_EINVAL, with nothing written: n < 0, hwc < 0,
+ * hwc % c != 0, n % hwc != 0, an unknown dtype. */
+int sg_dropout(sg_ctx* ctx, void* stream, int dtype, int64_t n, int64_t hwc, int c, int64_t first, uint32_t rng_stream,
+               uint32_t thr, float scale, const void* rng_dev, const void* x, void* y);
+
 /* ------------------------------------------------------------------------------------------ pooling
  * MaxPooling2D (3x3 s2 'same' v3plus.py:192; 2x2 s2 scse.py:54-66, res34.py:152,154; 2x2 window stride 4
  * res34.py:153).  pad_t/pad_l = TF SAME pad before (0 for valid); padded cells are -inf.  The backward

@@ -232,6 +232,46 @@ def conv_form_name(pl: ConvPlan, la: ConvLaunch, dgrad: bool, dt: int, operands=
     return n
 
 
+def wgrad_form_name(pl: WgradPlan, la: WgradLaunch, dt: int, d: ConvDesc, wpw_var: int = 1) -> str:
+    """The name of one launch `la` of filter-gradient plan `pl` of convolution `d` (DESIGN.md, appendix "filter-gradient form names"):
+        wgrad.thin.CO<n>.<f32|b16|b16>f32>        wgrad.wide.<x6|b16>        wgrad.patch.C<cin>x<cout>.<x6|npl1|b16>
+        wgrad.slab.x6.BN<w>.<x6|npl1|b16>         wgrad.planes.BN<w>         wgrad.native.BN<w>.<scalar|vec|fast1|fast2>[.b16|.b16>f32]
+    then the modifiers .skip .tapin .S<n> .sub<nb>+<tail> .up2 .wv0.  dt: the call's dtype with its flags; wpw_var: SG_WPW_VAR of the
+    process (the one form a plan does not name: wgrad_pw_wide_kernel<0>)."""
+    b16, head = (dt & 0xff) == SG_BF16, bool(dt & SG_HEAD_F32)
+    st = "b16>f32" if head else ("b16" if b16 else "f32")
+    pipe = "b16" if b16 else ("npl1" if la.planes == 1 else "x6")
+    fam = la.family
+    if fam == SG_WG_THIN:
+        n = f"wgrad.thin.CO{d.Cout}.{st}"
+    elif fam == SG_WG_WIDE:
+        n = f"wgrad.wide.{pipe}"
+    elif fam == SG_WG_PATCH:
+        n = f"wgrad.patch.C{d.Cin}x{d.Cout}.{pipe}"
+    elif fam == SG_WG_SLAB_X6:
+        n = f"wgrad.slab.x6.BN{la.bn}.{pipe}"
+    elif fam == SG_WG_PLANES:
+        n = f"wgrad.planes.BN{la.bn}"
+    elif fam in (SG_WG_SLAB_NATIVE, SG_WG_HEAD32):
+        kind = {2: "fast2", 1: "fast1"}.get(la.fast, "vec" if la.vec else "scalar")
+        n = f"wgrad.native.BN{la.bn}.{kind}" + ("" if st == "f32" else "." + st)
+    else:
+        return "wgrad.none"
+    if la.skip_slabs:
+        n += ".skip"
+    if la.tap_inner:
+        n += ".tapin"
+    if la.S > 1:
+        n += f".S{la.S}"
+    if pl.chunks > 1:
+        n += f".sub{pl.nb}+{pl.tail_n}"
+    if (dt & SG_X_UP2) and pl.up2:
+        n += ".up2"
+    if fam == SG_WG_WIDE and not b16 and wpw_var != 1:
+        n += ".wv0"
+    return n
+
+
 class SegPlan(C.Structure):
     """Mirror of `sg_seg_plan_t` (include/segengine.h): the segment reducer's plan (sg_seg_plan)."""
 

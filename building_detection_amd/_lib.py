@@ -68,6 +68,13 @@ class MineDesc(C.Structure):
                 [("thresh", C.c_float), ("alpha", C.c_float * SG_MAX_CLASSES)])
 
 
+class LovaszDesc(C.Structure):
+    """Mirror of `sg_lovasz_desc` (include/segengine.h): the Lovasz-Softmax loss, alone or added to a pointwise loss."""
+    _fields_ = ([(n, C.c_int32) for n in ("C", "y_cols", "images", "classes_all")] + [("rows_per_image", C.c_int64)] +
+                [(n, C.c_int32) for n in ("point_kind", "reserved")] + [(n, C.c_float) for n in ("point_weight", "lovasz_weight")] +
+                [("point_alpha", C.c_float * SG_MAX_CLASSES)])
+
+
 class OptimChunk(C.Structure):
     """Mirror of `sg_optim_chunk` (include/segengine.h): a 16-byte aligned run of one parameter's elements."""
     _fields_ = [("start", C.c_int64), ("length", C.c_int32), ("segment", C.c_int32)]
@@ -377,6 +384,11 @@ _SIGNATURES = {
     "sg_loss_mined_ws_bytes": (_sz, [_vp, C.POINTER(MineDesc)]),
     "sg_loss_mined_fwd": (_i, [_vp, _vp, C.POINTER(MineDesc), _vp, _vp, _vp, _vp, _vp, _sz]),
     "sg_loss_mined_bwd": (_i, [_vp, _vp, C.POINTER(MineDesc), _vp, _vp, _vp, _vp, _f]),
+    "sg_sort_pairs_ws_bytes": (_sz, [_vp, _i64, _i64, _i]),
+    "sg_sort_pairs_u32": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "sg_loss_lovasz_ws_bytes": (_sz, [_vp, C.POINTER(LovaszDesc)]),
+    "sg_loss_lovasz_fwd": (_i, [_vp, _vp, C.POINTER(LovaszDesc), _vp, _vp, _vp, _vp, _vp, _sz]),
+    "sg_loss_lovasz_bwd": (_i, [_vp, _vp, C.POINTER(LovaszDesc), _vp, _vp, _vp, _vp, _f]),
     "sg_adam_step": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f]),
     "sg_adam_step_lr": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f]),
     "sg_optim_norms_ws_bytes": (_sz, [_i]),

@@ -12,7 +12,8 @@ matrix (`metrics_from_matrix`).
 Beyond the reference: the region-overlap losses `dice_loss`, `jaccard_loss`, `tversky_loss(alpha, beta)` and
 `compound(pointwise, region)`, which adds one of them to one of the three losses above (`sg_loss_region_fwd/bwd`, at 2 ... 32
 classes), and `hard_mining(pointwise, thresh, min_kept)`, one of the three averaged over the batch's hard pixels
-only (`sg_loss_mined_fwd/bwd`).
+only (`sg_loss_mined_fwd/bwd`), and `lovasz_loss`, the Lovasz-Softmax surrogate of the Jaccard index, alone or
+as the second term of `compound` (`sg_loss_lovasz_fwd/bwd` on a stable segmented radix sort).
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ import warnings
 
 import numpy as np
 
-from ._lib import SG_LOSS_CE2, SG_LOSS_FOCAL, SG_LOSS_EDGE_FOCAL
+from ._lib import SG_LOSS_CE2, SG_LOSS_FOCAL, SG_LOSS_EDGE_FOCAL, SG_MAX_CLASSES
 
 K_EPSILON = 1e-7
 
@@ -127,6 +128,34 @@ def tversky_loss(alpha, beta):
                        alpha, beta)
 
 
+class _LovaszLoss(_Named):
+    """Lovasz-Softmax (Berman, Triggs, Blaschko, CVPR 2018), the tight convex surrogate of the Jaccard index.
+    Per group g - the batch, or one image with `per_image` - and class c: the pixels' errors m = 1 - p (a pixel of class c) or
+    p (any other) are ranked in descending order, ties by ascending pixel index, and
+
+        l[g,c] = sum_k m_(k) (J_k - J_(k-1)),   J_k = the Jaccard loss of calling the first k ranked pixels wrong,
+        L = mean over the groups of the mean of l[g,c] over the classes.
+
+    classes="present" averages over the classes that occur in the group, "all" over every class."""
+
+    classes, per_image = "present", False
+
+    def with_options(self, classes="present", per_image=False):
+        if classes not in ("present", "all"):
+            raise ValueError(f"{self.__name__}.with_options: classes = {classes!r} is not 'present' or 'all'")
+        if not isinstance(per_image, (bool, np.bool_)):
+            raise ValueError(f"{self.__name__}.with_options: per_image = {per_image!r} is not a bool")
+        out = _LovaszLoss(self.__name__, self.__doc__)
+        out.classes, out.per_image = classes, bool(per_image)
+        return out
+
+    def __repr__(self):
+        return f"<building_detection_amd {self.__name__} classes={self.classes!r} per_image={self.per_image}>"
+
+
+lovasz_loss = _LovaszLoss("lovasz_loss", _LovaszLoss.__doc__)
+
+
 class _MinedLoss(_Named):
     """A pointwise loss averaged over the hard pixels of the batch only (online hard example mining)."""
 
@@ -188,13 +217,13 @@ class _CompoundLoss(_Named):
 
 def compound(pointwise, region, region_weight=1.0, pointwise_weight=1.0):
     """`pointwise` is binary_crossentropy, focal_loss or edge_focal_loss (with or without with_alpha), `region` one of
-    dice_loss / jaccard_loss / tversky_loss(...).  The weights are >= 0 and not both 0."""
+    dice_loss / jaccard_loss / tversky_loss(...) or lovasz_loss.  The weights are >= 0 and not both 0."""
     if isinstance(pointwise, _MinedLoss):
         raise ValueError(f"compound: pointwise = {pointwise!r}: a mined pointwise term inside a compound is not implemented")
     if not isinstance(pointwise, _Named) or pointwise.__name__ not in _LOSS_KINDS:
         raise ValueError(f"compound: pointwise = {pointwise!r} is not one of {sorted(_LOSS_KINDS)}")
-    if not isinstance(region, _RegionLoss):
-        raise ValueError(f"compound: region = {region!r} is not dice_loss, jaccard_loss or a tversky_loss(...)")
+    if not isinstance(region, (_RegionLoss, _LovaszLoss)):
+        raise ValueError(f"compound: region = {region!r} is not dice_loss, jaccard_loss, a tversky_loss(...) or lovasz_loss")
     wr, wp = _finite(region_weight), _finite(pointwise_weight)
     if wr is None or wp is None or wr < 0 or wp < 0 or wr + wp == 0:
         raise ValueError(f"compound: region_weight = {region_weight!r}, pointwise_weight = {pointwise_weight!r} must be finite, "
@@ -228,15 +257,15 @@ def _warn_foreign(fn, what, lines):
 
 def resolve_loss(loss) -> int:
     """The pointwise kind of `loss`: SG_LOSS_* for the reference's three names (and for the pointwise part of a compound),
-    NO_POINTWISE for a region loss on its own; for hard_mining(pointwise) the kind of `pointwise`."""
+    NO_POINTWISE for a region loss or lovasz_loss on its own; for hard_mining(pointwise) the kind of `pointwise`."""
     if isinstance(loss, (_CompoundLoss, _MinedLoss)):
         return _LOSS_KINDS[loss.pointwise.__name__]
-    if isinstance(loss, _RegionLoss):
+    if isinstance(loss, (_RegionLoss, _LovaszLoss)):
         return NO_POINTWISE
     name = loss if isinstance(loss, str) else getattr(loss, "__name__", None)
     if name not in _LOSS_KINDS:
         raise ValueError(f"loss {loss!r}: the engine implements {sorted(_LOSS_KINDS)} (train_model/DeepLabv3plus.py:490-527), "
-                         "dice_loss, jaccard_loss, tversky_loss(alpha, beta), compound(pointwise, region) and "
+                         "dice_loss, jaccard_loss, tversky_loss(alpha, beta), lovasz_loss, compound(pointwise, region) and "
                          "hard_mining(pointwise)")
     _warn_foreign(loss, "loss", "490-527")
     return _LOSS_KINDS[name]
@@ -250,6 +279,8 @@ def resolve_region(loss, num_classes: int):
     dict(a, b, smooth, gamma, class_w, per_image, point_kind, point_alpha, point_weight, region_weight).  class_w has
     `num_classes` entries (ones when none were given); point_alpha is None (no pointwise term, or cross-entropy) or
     `num_classes` weights - at two classes without with_alpha the reference's own, passed explicitly."""
+    if isinstance(loss, _CompoundLoss) and isinstance(loss.region, _LovaszLoss):
+        return None                                               # resolve_lovasz answers for it
     if isinstance(loss, _CompoundLoss):
         region, kind = loss.region, _LOSS_KINDS[loss.pointwise.__name__]
         alpha = resolve_alpha(loss.pointwise, num_classes)
@@ -267,6 +298,27 @@ def resolve_region(loss, num_classes: int):
         raise ValueError(f"the loss carries {len(w)} class weights, the model has {num_classes} classes")
     return dict(a=region.alpha, b=region.beta, smooth=region.smooth, gamma=region.gamma, class_w=tuple(w),
                 per_image=region.per_image, point_kind=kind, point_alpha=alpha, point_weight=wp, region_weight=wr)
+
+
+def resolve_lovasz(loss, num_classes: int):
+    """The fields of `sg_lovasz_desc` that `loss` fixes for a `num_classes` model, or None for a loss without a Lovasz term:
+    dict(classes_all, per_image, point_kind, point_alpha, point_weight, lovasz_weight).  point_alpha is None (no pointwise
+    term, or cross-entropy) or `num_classes` weights - at two classes without with_alpha the reference's own, passed
+    explicitly."""
+    if isinstance(loss, _CompoundLoss) and isinstance(loss.region, _LovaszLoss):
+        lov, kind = loss.region, _LOSS_KINDS[loss.pointwise.__name__]
+        alpha = resolve_alpha(loss.pointwise, num_classes)
+        if alpha is None and kind != SG_LOSS_CE2:
+            alpha = _TWO_CLASS_ALPHA[kind]
+        wp, wl = loss.pointwise_weight, loss.region_weight
+    elif isinstance(loss, _LovaszLoss):
+        lov, kind, alpha, wp, wl = loss, NO_POINTWISE, None, 0.0, 1.0
+    else:
+        return None
+    if not 2 <= int(num_classes) <= SG_MAX_CLASSES:
+        raise ValueError(f"lovasz_loss: the model has {num_classes} classes, the engine takes 2 ... {SG_MAX_CLASSES}")
+    return dict(classes_all=lov.classes == "all", per_image=lov.per_image, point_kind=kind, point_alpha=alpha, point_weight=wp,
+                lovasz_weight=wl)
 
 
 def resolve_mining(loss, num_classes: int):
@@ -288,7 +340,7 @@ def resolve_alpha(loss, num_classes: int):
     (no weights given, 2 classes; cross-entropy has none at all), else a tuple of `num_classes` floats."""
     if isinstance(loss, (_CompoundLoss, _MinedLoss)):
         return resolve_alpha(loss.pointwise, num_classes)
-    if isinstance(loss, _RegionLoss):
+    if isinstance(loss, (_RegionLoss, _LovaszLoss)):
         return None
     kind = _LOSS_KINDS[loss if isinstance(loss, str) else getattr(loss, "__name__", None)]
     alpha = getattr(loss, "alpha", None)

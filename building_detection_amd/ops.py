@@ -1083,6 +1083,70 @@ class Engine:
               "sg_loss_mined_bwd")
         return dp
 
+    def sort_pairs(self, keys, vals, key_bits=32):
+        """Stable ascending sort of (key, value) pairs by the low `key_bits` key bits (sg_sort_pairs_u32).  keys, vals: int32
+        device tensors of one shape, read as uint32; [len] is one segment, [segments, len] sorts every row on its own.
+        Returns (keys_out, vals_out); the inputs are left as they are."""
+        for t, name in ((keys, "keys"), (vals, "vals")):
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() not in (1, 2):
+                raise ValueError(f"{name} {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))} is not a contiguous int32 "
+                                 "device tensor [len] or [segments, len]")
+        if keys.shape != vals.shape or keys.numel() == 0:
+            raise ValueError(f"keys {tuple(keys.shape)} and vals {tuple(vals.shape)} must have one non-empty shape")
+        segments, n = (1, keys.shape[0]) if keys.dim() == 1 else (keys.shape[0], keys.shape[1])
+        ko, vo = torch.empty_like(keys), torch.empty_like(vals)
+        wsp, wsn = self.ws(self.lib.sg_sort_pairs_ws_bytes(self.h, segments, n, int(key_bits)))
+        check(self.lib.sg_sort_pairs_u32(self.h, self.stream, segments, n, int(key_bits), _ptr(keys), _ptr(vals), _ptr(ko), _ptr(vo),
+                                         wsp, wsn), "sg_sort_pairs_u32")
+        return ko, vo
+
+    @staticmethod
+    def lovasz_desc(lovasz, p, y_true):
+        """`sg_lovasz_desc` of `lovasz` (the dict of losses.resolve_lovasz) for p [N, ..., C] and y_true [N, ..., C or 2C]:
+        one group per image of the leading axis with per_image (p then has at least three axes: a flat [rows, C] names no
+        images and is a ValueError), else one for the batch."""
+        c, y_cols = int(p.shape[-1]), int(y_true.shape[-1])
+        rows = p.numel() // c
+        if y_true.numel() != rows * y_cols or y_cols not in (c, 2 * c):
+            raise ValueError(f"y_true {tuple(y_true.shape)} does not go with p {tuple(p.shape)}: C or 2C columns per pixel")
+        if lovasz["point_kind"] == _lib.SG_LOSS_EDGE_FOCAL and y_cols != 2 * c:
+            raise ValueError(f"edge_focal_loss needs y_true[..., {2 * c}] (one-hot, then one edge weight per class), got {y_cols} columns")
+        if lovasz["point_alpha"] is not None and len(lovasz["point_alpha"]) != c:
+            raise ValueError(f"the loss carries class weights for another class count than {c}")
+        if lovasz["per_image"] and p.dim() < 3:
+            raise ValueError(f"per_image needs p [N, ..., C] with the images on the leading axis, not {tuple(p.shape)}")
+        images = int(p.shape[0]) if lovasz["per_image"] else 1
+        d = _lib.LovaszDesc(C=c, y_cols=y_cols, images=images, classes_all=int(lovasz["classes_all"]), rows_per_image=rows // images,
+                            point_kind=int(lovasz["point_kind"]), reserved=0, point_weight=lovasz["point_weight"],
+                            lovasz_weight=lovasz["lovasz_weight"])
+        for i in range(c):
+            d.point_alpha[i] = 1.0 if lovasz["point_alpha"] is None else lovasz["point_alpha"][i]
+        return d
+
+    def loss_lovasz_fwd(self, lovasz, p, y_true):
+        """The Lovasz-Softmax loss, alone or with its pointwise term (sg_loss_lovasz_fwd).  Returns (out, g): out =
+        {L, L_point, L_lovasz}, g [rows, C] = dL_lovasz/dp, which loss_lovasz_bwd forms the gradient from."""
+        _chk32(p, "p"); _chk32(y_true, "y_true")
+        d = self.lovasz_desc(lovasz, p, y_true)
+        out, g = self.empty(3), self.empty(p.numel() // d.C, d.C)
+        wsp, wsn = self.ws(self.lib.sg_loss_lovasz_ws_bytes(self.h, C.byref(d)))
+        check(self.lib.sg_loss_lovasz_fwd(self.h, self.stream, C.byref(d), _ptr(p), _ptr(y_true), _ptr(out), _ptr(g), wsp, wsn),
+              "sg_loss_lovasz_fwd")
+        return out, g
+
+    def loss_lovasz_bwd(self, lovasz, p, y_true, g, scale=1.0, out=None):
+        """dL/dp of loss_lovasz_fwd's L, times `scale`; `g` is what the forward call returned for the same p and y_true."""
+        _chk32(p, "p"); _chk32(y_true, "y_true")
+        d = self.lovasz_desc(lovasz, p, y_true)
+        rows = p.numel() // d.C
+        if not torch.is_tensor(g) or tuple(g.shape) != (rows, d.C) or g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
+            raise ValueError(f"g {tuple(getattr(g, 'shape', ()))} {getattr(g, 'dtype', type(g))} is not the forward call's "
+                             f"float32 [{rows}, {d.C}] device tensor")
+        dp = out if out is not None else torch.empty_like(p)
+        check(self.lib.sg_loss_lovasz_bwd(self.h, self.stream, C.byref(d), _ptr(p), _ptr(y_true), _ptr(g), _ptr(dp), float(scale)),
+              "sg_loss_lovasz_bwd")
+        return dp
+
     def confusion_matrix(self, p, y_true, out=None):
         """out[t * C + q] += rows whose truth is class t and prediction class q (int64 [C * C], zeroed when created here)."""
         _chk32(p, "p"); _chk32(y_true, "y_true")

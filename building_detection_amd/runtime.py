@@ -253,7 +253,13 @@ class Model:
         true-class probability is <= T = max(thresh, the k-th smallest of the batch), every tie at T kept (sg_loss_mined_*; the
         selection runs on the device, so a captured step needs no host round trip).  last_hard_mining() reports T and the kept
         count of the last step.  Under data parallelism every rank mines its OWN shard (k is taken of the shard's pixels); the
-        gradients are averaged as ever and the logged loss is the mean over the ranks."""
+        gradients are averaged as ever and the logged loss is the mean over the ranks.
+
+        losses.lovasz_loss, alone or as losses.compound(pointwise, lovasz_loss): the Lovasz-Softmax surrogate of the Jaccard index
+        (sg_loss_lovasz_*: the pixels' errors are ranked per class by a stable radix sort on the device, so a captured step needs
+        no host round trip).  logs["loss"] is L = pointwise_weight * L_point + region_weight * L_lovasz; last_loss_terms()
+        reports the three.  Under data parallelism every rank ranks its OWN shard - ranks are not exchanged, the same documented
+        choice as for the region losses -; the gradients are averaged as ever and the logged loss is the mean over the ranks."""
         if isinstance(optimizer, str):   # 'adam' (the reference's, DeepLabv3plus.py:835) | 'adamw' | 'sgd'; else a ValueError
             from . import optimizers
             optimizer = optimizers.get(optimizer)
@@ -270,6 +276,10 @@ class Model:
         # hard_mining(pointwise): the descriptor fields sg_loss_mined_* run by, else None; _loss_sel is the last step's record
         self.loss_mining = LS.resolve_mining(loss, self.num_classes)
         self._loss_sel = self._loss_sel_rows = None
+        # lovasz_loss or compound(pointwise, lovasz_loss): the descriptor fields sg_loss_lovasz_* run by, else None; _loss_g is the
+        # last step's dL_lovasz/dp, _loss_terms its {L, L_point, L_lovasz}
+        self.loss_lovasz = LS.resolve_lovasz(loss, self.num_classes)
+        self._loss_g = self._loss_terms = None
         self.metric_names = [LS.resolve_metric(m) for m in (metrics or [])]
         self.jit_compile = bool(jit_compile)
         self._train_graphs = {}
@@ -294,7 +304,11 @@ class Model:
     # A region loss: one forward call leaves {L, L_point, L_region} and the per-class gradient coefficients `coef`, which the
     # backward call of the same step reads (self._loss_coef; a captured step keeps the tensor, GraphedTrainStep.coef).
     # A mined loss: the forward call leaves the record {T, n_kept} (self._loss_sel; GraphedTrainStep.sel), the backward call reads it.
+    # A Lovasz loss: the forward call leaves {L, L_point, L_lovasz} and g = dL_lovasz/dp (self._loss_g; GraphedTrainStep.lov_g).
     def _loss_fwd(self, eng, p, y):
+        if getattr(self, "loss_lovasz", None) is not None:
+            self._loss_terms, self._loss_g = eng.loss_lovasz_fwd(self.loss_lovasz, p, y)
+            return self._loss_terms[:1]
         if getattr(self, "loss_mining", None) is not None:
             out, self._loss_sel = eng.loss_mined_fwd(self.loss_mining, p, y)
             self._loss_sel_rows = p.numel() // p.shape[-1]
@@ -307,6 +321,8 @@ class Model:
         return eng.lossn_fwd(self.loss_kind, p, y, self.loss_alpha)
 
     def _loss_bwd(self, eng, p, y):
+        if getattr(self, "loss_lovasz", None) is not None:
+            return eng.loss_lovasz_bwd(self.loss_lovasz, p, y, self._loss_g, 1.0)
         if getattr(self, "loss_mining", None) is not None:
             return eng.loss_mined_bwd(self.loss_mining, p, y, self._loss_sel, 1.0)
         if getattr(self, "loss_region", None) is not None:
@@ -323,6 +339,16 @@ class Model:
             return None
         w = sel.cpu().numpy().view(np.uint32)
         return dict(threshold=float(w[:1].view(np.float32)[0]), kept=int(w[2]) | (int(w[3]) << 32), rows=int(self._loss_sel_rows))
+
+    def last_loss_terms(self):
+        """dict(loss=L, pointwise=L_point, lovasz=L_lovasz) of the last train_on_batch / test_on_batch under lovasz_loss or
+        compound(pointwise, lovasz_loss) (this rank's shard under data parallelism): one host sync, taken only here.  None when
+        the loss has no Lovasz term or no step ran."""
+        t = getattr(self, "_loss_terms", None)
+        if getattr(self, "loss_lovasz", None) is None or t is None:
+            return None
+        v = t.cpu().numpy()
+        return dict(loss=float(v[0]), pointwise=float(v[1]), lovasz=float(v[2]))
 
     def _counts(self, eng, p, y):
         if not self.metric_names:
@@ -398,6 +424,8 @@ class Model:
                     loss, counts = g.run(xd, yd)
                     if getattr(g, "sel", None) is not None:   # (a test_on_batch in between leaves its own record here)
                         self._loss_sel, self._loss_sel_rows = g.sel, yd.numel() // yd.shape[-1]
+                    if getattr(g, "lov_terms", None) is not None:   # likewise the Lovasz terms and g of THIS graph's step
+                        self._loss_terms, self._loss_g = g.lov_terms, g.lov_g
                     return (loss, counts) if return_device_scalars else self._logs(loss, counts)
             rt.write_rng(self.optimizer.iterations)   # (a model without dropout: nothing)
             p = rt.forward(xd, training=True)
@@ -697,6 +725,8 @@ class GraphedTrainStep:
                 self.loss = model._loss_fwd(eng, p, self.y)
                 self.coef = getattr(model, "_loss_coef", None)   # a region loss: the graph's backward pass reads this tensor
                 self.sel = getattr(model, "_loss_sel", None)     # a mined loss: likewise the record {T, n_kept}
+                self.lov_g = getattr(model, "_loss_g", None)     # a Lovasz loss: likewise dL_lovasz/dp, and the three terms
+                self.lov_terms = getattr(model, "_loss_terms", None)
                 self.counts = model._counts(eng, p, self.y)   # zeroed inside the graph, four counts or C x C
                 dp = model._loss_bwd(eng, p, self.y)
                 rt.backward(dp)

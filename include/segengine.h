@@ -782,6 +782,67 @@ int sg_loss_mined_fwd(sg_ctx* ctx, void* stream, const sg_mine_desc* desc, const
                       void* loss_out, void* sel_out, void* ws, size_t ws_bytes);
 int sg_loss_mined_bwd(sg_ctx* ctx, void* stream, const sg_mine_desc* desc, const void* p, const void* y_true,
                       const void* sel, void* dp, float grad_scale);
+/* Stable segmented sort of (key, value) pairs of uint32: `segments` contiguous segments of `len` elements each, every segment
+ * ordered ascending by the low key_bits bits of its keys (1 <= key_bits <= 32), equal keys in input order.  The bits above
+ * key_bits travel with the key and are not compared.  A least-significant-digit radix sort in ceil(key_bits /
+ * SG_SORT_DIGIT_BITS) passes over tiles of SG_SORT_TILE elements: a tile's digit counts, an exclusive scan of the
+ * (digit x tile) table, a scatter.  An element's place inside its tile comes from ballots and a fixed wave order and the
+ * histogram adds are integers, so no place depends on the order in which anything lands: the same bits every run.
+ * keys_in / vals_in are not modified; an output may alias neither an input nor the other output.  Domain: segments, len >= 1,
+ * segments * len <= 2^31 - 1.  The workspace is, with tiles = ceil(len / SG_SORT_TILE) and passes as above,
+ *   4 * (segments * 256 * (tiles + 1) + (passes > 1 ? 2 * segments * len : 0)) bytes
+ * and may hold anything at the call (nothing is cleared by a memset node).  4-byte alignment is enough for every pointer.  No
+ * allocation, no synchronisation; every launch can be captured.  Arguments outside the domain, a null pointer, aliased
+ * operands or a short workspace are SG_EINVAL / SG_EWORKSPACE and nothing is launched or written; the workspace query then
+ * returns 0. */
+#define SG_SORT_TILE 2048
+#define SG_SORT_DIGIT_BITS 8
+size_t sg_sort_pairs_ws_bytes(const sg_ctx* ctx, int64_t segments, int64_t len, int key_bits);
+int sg_sort_pairs_u32(sg_ctx* ctx, void* stream, int64_t segments, int64_t len, int key_bits, const void* keys_in,
+                      const void* vals_in, void* keys_out, void* vals_out, void* ws, size_t ws_bytes);
+/* Lovasz-Softmax loss (Berman, Triggs, Blaschko, CVPR 2018), the convex surrogate of the Jaccard index, alone or added to one of
+ * the three pointwise losses above.  p[rows,C], y_true[rows,y_cols] as for sg_lossn_*; rows = images * rows_per_image.  Row i has
+ * the truth class t_i = argmax y_true[i, :C] (ties to the lowest index) and the clamped probabilities q[i,c]: the bits of p[i,c]
+ * with NaN, negative and -0 -> +0 and above 1 -> 1 (the clamp of the mined loss's key).  A group g is the whole batch
+ * (images = 1) or one image.  Per group and class c, over the group's n pixels:
+ *   f_i = [t_i == c],  G = sum f_i,  m_i = f_i ? 1.0f - q[i,c] : q[i,c]  (one fp32 subtraction);
+ *   the pixels are ranked by descending m_i, ties by ascending pixel index: a stable ascending sort of the 30-bit key
+ *   0x3F800000 - bits(m_i) with sg_sort_pairs_u32's passes;  along that order, k = 1 ... n,  F_k = foreground pixels among the
+ *   first k,  I_k = G - F_k,  U_k = G + k - F_k,  J_k = 1 - I_k / U_k,  J_0 = 0,  g_k = J_k - J_(k-1), formed in double from
+ *   the integer counts (G > 0: 1 / U_k on a foreground pixel, I_k / (U_k (U_k - 1)) on a background one; G = 0: g_1 = 1, the
+ *   rest 0) and rounded once to fp32;   l[g,c] = sum_k m_(k) g_k, in double in a fixed order, m taken of the UNCLAMPED p (a
+ *   NaN row is ranked as if p were 0, and the NaN shows in L).
+ * classes_all = 0 averages over the classes with G > 0 in the group (n_c(g) of them, counted on the device), 1 over all C:
+ *   L_lovasz = (1 / images) sum_g (1 / n_c(g)) sum_c l[g,c],   L = point_weight * L_point + lovasz_weight * L_lovasz,
+ * L_point being what sg_lossn_fwd computes for point_kind with point_alpha (point_kind = -1: none, reported as 0).
+ *   fwd  loss_out[3] = {L, L_point, L_lovasz};  g_out[rows,C] = dL_lovasz/dp = (f_i ? -1 : +1) g_rank(i) / (images n_c(g)), written
+ *        everywhere, +0.0f for a class that was skipped.
+ *   bwd  one pass: dp = grad_scale * (point_weight * the gradient sg_lossn_bwd writes + lovasz_weight * g), g = fwd's g_out.
+ *        With lovasz_weight = 0 and point_weight = 1 the bits of sg_lossn_bwd.
+ * Domain: 2 <= C <= SG_MAX_CLASSES; y_cols = C or 2C (2C with point_kind 2); 1 <= images <= 65535; rows_per_image >= 1 and
+ * rows * C <= 2^31 - 1; classes_all 0 or 1; reserved = 0; the weights finite, >= 0 and not both 0 (lovasz_weight > 0 without a
+ * pointwise term); point_alpha finite (read for kinds 1 and 2).  The descriptor is a HOST struct, read at the call.  The
+ * workspace is, with N = rows * C, S = images * C, tiles = ceil(rows_per_image / SG_SORT_TILE),
+ *   4 * (4 N + S * 256 * (tiles + 1) + 3 * S * tiles + 3 * S + sg_loss_parts) bytes
+ * (two key / value buffer pairs, the sort's table, per tile a foreground count and a double partial sum, per segment G and a
+ * double sum, the pointwise partial sums).  fp32, dense, 4-byte alignment is enough for every pointer.  No allocation, no
+ * synchronisation, no float atomics: two calls on the same inputs give the same bits; every launch can be captured.  A
+ * descriptor outside the domain, a null pointer or a short workspace is SG_EINVAL / SG_EWORKSPACE and nothing is launched or
+ * written; the workspace query then returns 0. */
+typedef struct sg_lovasz_desc {
+  int32_t C, y_cols, images;         /* images == 1: the batch is one group */
+  int32_t classes_all;               /* 0: present classes only; 1: all C   */
+  int64_t rows_per_image;
+  int32_t point_kind;                /* -1, or SG_LOSS_* */
+  int32_t reserved;                  /* 0 */
+  float   point_weight, lovasz_weight;
+  float   point_alpha[SG_MAX_CLASSES];
+} sg_lovasz_desc;
+size_t sg_loss_lovasz_ws_bytes(const sg_ctx* ctx, const sg_lovasz_desc* desc);
+int sg_loss_lovasz_fwd(sg_ctx* ctx, void* stream, const sg_lovasz_desc* desc, const void* p, const void* y_true,
+                       void* loss_out, void* g_out, void* ws, size_t ws_bytes);
+int sg_loss_lovasz_bwd(sg_ctx* ctx, void* stream, const sg_lovasz_desc* desc, const void* p, const void* y_true,
+                       const void* g, void* dp, float grad_scale);
 /* Keras-2 Adam (compile(optimizer='adam'), DeepLabv3plus.py:835) on one flat fp32
  * parameter arena: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; w -= lr_t * m / (sqrt(v) + eps) with
  * lr_t = lr*sqrt(1-b2^t)/(1-b1^t) precomputed by the host.  g is scaled by grad_scale first (1/world). */

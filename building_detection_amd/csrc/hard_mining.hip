@@ -18,9 +18,8 @@
 // order.  No float atomics, no allocation, no synchronisation: the same bits from run to run, and every call can be captured.
 // fp32, dense rows, dword accesses to p and y_true (4-byte alignment is enough); the stored keys are read 16 bytes at a time
 // when the workspace is 16-byte aligned.
-#include <float.h>
 #include <string.h>
-#include "loss_rows.h"
+#include "loss_head.h"
 
 namespace {
 
@@ -30,36 +29,12 @@ constexpr int LEVELS = 3;
 enum { ST_PREFIX = 0, ST_RANK, ST_BELOW, ST_DONE, ST_WORDS = 8 };
 constexpr int TAB_WORDS = ST_WORDS + LEVELS * BINS;
 
-struct ClassVec {
-  float v[SG_MAX_CLASSES];
-};
-
-#define HM_FOR(c) _Pragma("unroll") for (int c = 0; c < CM; ++c) if (EX || c < C)
-
-// the key bits of one row: p at the first maximum of y_true[:C], NaN / negative / -0 -> +0, above 1 -> 1
+// the key bits of one row: p at the first maximum of y_true[:C], clamped to [0, 1] on the bits
 template <int CM, bool EX>
 __device__ __forceinline__ uint32_t row_key(const float* __restrict__ p_row, const float* __restrict__ y_row, int C) {
   float y[CM];
-  HM_FOR(c) y[c] = y_row[c];
-  float best = y[0];
-  int t = 0;
-  HM_FOR(c) if (c > 0 && y[c] > best) {
-    best = y[c];
-    t = c;
-  }
-  // on the bits, so that no floating-point mode touches a denormal: a set sign bit or a NaN lies above +inf's pattern
-  const uint32_t b = __float_as_uint(p_row[t]);
-  return b > 0x7f800000u ? 0u : (b < 0x3f800000u ? b : 0x3f800000u);
-}
-
-__device__ __forceinline__ float block_sum_256(float v, float* sm) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) sm[wave] = v;
-  __syncthreads();
-  float t = 0.f;
-  if (threadIdx.x == 0) t = sm[0] + sm[1] + sm[2] + sm[3];
-  return t;  // valid in thread 0
+  SG_CLASS_FOR(c) y[c] = y_row[c];
+  return clamp_bits(p_row[row_first_max<CM, EX>(y, C)]);
 }
 
 // the workgroup's LDS table -> the global one: one integer add per non-zero bin
@@ -94,11 +69,9 @@ __global__ __launch_bounds__(256) void mine_key_kernel(int64_t rows, int C, int 
     atomicAdd(&h[k >> 21], 1u);
     le += k <= thresh_bits ? 1u : 0u;
   }
-  for (int off = 32; off > 0; off >>= 1) le += __shfl_xor(le, off, 64);
-  if ((threadIdx.x & 63) == 0) wle[threadIdx.x >> 6] = le;
-  __syncthreads();
-  if (threadIdx.x == 0) lep[blockIdx.x] = wle[0] + wle[1] + wle[2] + wle[3];  // one word per workgroup: 8192 waves adding to
-  flush_bins(h, tab + ST_WORDS);                                               // one address took 60 us of a 107 us pass
+  le = block_sum_256(le, wle);
+  if (threadIdx.x == 0) lep[blockIdx.x] = le;  // one word per workgroup: 8192 waves adding to one address took 60 us of a
+  flush_bins(h, tab + ST_WORDS);               // 107 us pass
 }
 
 // one workgroup of 256 threads, eight bins each
@@ -205,7 +178,7 @@ __global__ __launch_bounds__(256) void mine_sum_kernel(int kind, int64_t rows, i
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
     if (row_key<CM, EX>(p + i * C, yt + i * y_cols, C) > T) continue;
     float r = 0.f;
-    HM_FOR(c) {
+    SG_CLASS_FOR(c) {
       const float pv = p[i * C + c], y = yt[i * y_cols + c];
       const float w = kind == SG_LOSS_EDGE_FOCAL ? yt[i * y_cols + C + c] : 1.f;
       r += loss_row_term(kind, loss_coeff(kind, al.v[c], y, w), pv);
@@ -225,11 +198,8 @@ __global__ __launch_bounds__(256) void mine_final_kernel(const float* __restrict
   const int t = threadIdx.x;
   double s = 0.0;
   for (int i = t; i < nparts; i += 256) s += (double)part[i];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-  if ((t & 63) == 0) ws[t >> 6] = s;
-  __syncthreads();
+  const double tot = block_sum_double(s, ws);
   if (t == 0) {
-    const double tot = ((ws[0] + ws[1]) + ws[2]) + ws[3];
     const unsigned long long n = (unsigned long long)sel[2] | ((unsigned long long)sel[3] << 32);
     out[0] = (float)(-tot / (double)n);
   }
@@ -246,10 +216,10 @@ __global__ __launch_bounds__(256) void mine_bwd_kernel(int kind, int64_t rows, i
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
     if (row_key<CM, EX>(p + i * C, yt + i * y_cols, C) > T) {
-      HM_FOR(c) dp[i * C + c] = 0.f;
+      SG_CLASS_FOR(c) dp[i * C + c] = 0.f;
       continue;
     }
-    HM_FOR(c) {
+    SG_CLASS_FOR(c) {
       const float pv = p[i * C + c], y = yt[i * y_cols + c];
       const float w = kind == SG_LOSS_EDGE_FOCAL ? yt[i * y_cols + C + c] : 1.f;
       dp[i * C + c] = k * loss_coeff(kind, al.v[c], y, w) * loss_row_grad(kind, pv);
@@ -257,45 +227,16 @@ __global__ __launch_bounds__(256) void mine_bwd_kernel(int kind, int64_t rows, i
   }
 }
 
-#undef HM_FOR
-
-#define HM_DISPATCH(C, LAUNCH)    \
-  do {                            \
-    switch (C) {                  \
-      case 2: LAUNCH(2, true); break; \
-      case 3: LAUNCH(3, true); break; \
-      case 4: LAUNCH(4, true); break; \
-      case 5: LAUNCH(5, true); break; \
-      case 6: LAUNCH(6, true); break; \
-      case 7: LAUNCH(7, true); break; \
-      case 8: LAUNCH(8, true); break; \
-      default:                    \
-        if ((C) <= 16) { LAUNCH(16, false); } else { LAUNCH(32, false); } \
-    }                             \
-  } while (0)
-
 // 0, or SG_EINVAL with the error text set
 inline int desc_ok(const char* who, const sg_mine_desc* d) {
   SG_CHECK_ARG(d, "%s: no descriptor", who);
-  SG_CHECK_ARG(d->C >= 2 && d->C <= SG_MAX_CLASSES, "%s: C = %d outside [2, %d]", who, d->C, SG_MAX_CLASSES);
-  SG_CHECK_ARG(d->y_cols == d->C || d->y_cols == 2 * d->C, "%s: y_true has %d columns, not C = %d or 2C", who, d->y_cols, d->C);
-  SG_CHECK_ARG(d->kind >= SG_LOSS_CE2 && d->kind <= SG_LOSS_EDGE_FOCAL, "%s: unknown loss %d", who, d->kind);
-  SG_CHECK_ARG(d->kind != SG_LOSS_EDGE_FOCAL || d->y_cols == 2 * d->C, "%s: edge_focal_loss needs y_true[..., 2C]", who);
+  if (const int rc = loss_head_ok(who, d->C, d->y_cols, d->kind, false, "loss", d->alpha, "alpha")) return rc;
   SG_CHECK_ARG(d->reserved == 0, "%s: reserved = %d", who, d->reserved);
   SG_CHECK_ARG(d->rows >= 1 && d->rows <= 0xffffffffll, "%s: rows = %lld outside [1, 2^32 - 1]", who, (long long)d->rows);
   SG_CHECK_ARG(d->min_kept >= 1 && d->min_kept <= d->rows, "%s: min_kept = %lld outside [1, rows = %lld]", who,
                (long long)d->min_kept, (long long)d->rows);
   SG_CHECK_ARG(d->thresh >= 0.f && d->thresh <= 1.f, "%s: thresh = %g outside [0, 1]", who, d->thresh);  // a NaN fails both
-  if (d->kind != SG_LOSS_CE2)
-    for (int c = 0; c < d->C; ++c)
-      SG_CHECK_ARG(d->alpha[c] >= -FLT_MAX && d->alpha[c] <= FLT_MAX, "%s: alpha[%d] is not finite", who, c);
   return 0;
-}
-
-inline ClassVec class_alpha(const sg_mine_desc* d) {
-  ClassVec al;
-  for (int c = 0; c < SG_MAX_CLASSES; ++c) al.v[c] = (d->kind > SG_LOSS_CE2 && c < d->C) ? d->alpha[c] : 1.f;
-  return al;
 }
 
 // keys[rows] | state and tables | #{key <= thresh} per workgroup [parts] | loss partials [parts]
@@ -330,7 +271,7 @@ int sg_loss_mined_fwd(sg_ctx* ctx, void* stream, const sg_mine_desc* desc, const
   const int parts = sg_loss_parts(rows);
   const uint32_t k = (uint32_t)desc->min_kept;
   const uint32_t thresh_bits = desc->thresh > 0.f ? float_bits(desc->thresh) : 0u;  // -0 is 0
-  const ClassVec al = class_alpha(desc);
+  const ClassVec al = class_vec(desc->kind, desc->C, desc->alpha);
   hipStream_t st = (hipStream_t)stream;
   uint32_t* keys = (uint32_t*)ws;
   uint32_t* tab = keys + rows;
@@ -343,7 +284,7 @@ int sg_loss_mined_fwd(sg_ctx* ctx, void* stream, const sg_mine_desc* desc, const
 #define L(CM, EX)                                                                                                      \
   hipLaunchKernelGGL((mine_key_kernel<CM, EX>), dim3(parts), dim3(256), 0, st, rows, C, y_cols, thresh_bits, (const float*)p, \
                      (const float*)y_true, keys, tab, lep)
-  HM_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("mine_key_kernel");
   for (int level = 0; level < LEVELS; ++level) {
@@ -361,7 +302,7 @@ int sg_loss_mined_fwd(sg_ctx* ctx, void* stream, const sg_mine_desc* desc, const
 #define L(CM, EX)                                                                                                            \
   hipLaunchKernelGGL((mine_sum_kernel<CM, EX>), dim3(parts), dim3(256), 0, st, kind, rows, C, y_cols, al, (const float*)p, \
                      (const float*)y_true, (const uint32_t*)sel, part)
-  HM_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("mine_sum_kernel");
   hipLaunchKernelGGL(mine_final_kernel, dim3(1), dim3(256), 0, st, (const float*)part, parts, (const uint32_t*)sel,
@@ -374,13 +315,11 @@ int sg_loss_mined_bwd(sg_ctx* ctx, void* stream, const sg_mine_desc* desc, const
                       void* dp, float grad_scale) {
   SG_CHECK_ARG(ctx && p && y_true && sel && dp, "sg_loss_mined_bwd: bad argument");
   if (const int rc = desc_ok("sg_loss_mined_bwd", desc)) return rc;
-  const ClassVec al = class_alpha(desc);
-  int64_t blocks = sg_cdiv(desc->rows, 256);
-  if (blocks > 8192) blocks = 8192;
+  const ClassVec al = class_vec(desc->kind, desc->C, desc->alpha);
 #define L(CM, EX)                                                                                                              \
-  hipLaunchKernelGGL((mine_bwd_kernel<CM, EX>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, desc->kind, desc->rows, \
+  hipLaunchKernelGGL((mine_bwd_kernel<CM, EX>), dim3(loss_bwd_blocks(desc->rows)), dim3(256), 0, (hipStream_t)stream, desc->kind, desc->rows, \
                      desc->C, desc->y_cols, al, (const float*)p, (const float*)y_true, (const uint32_t*)sel, (float*)dp, grad_scale)
-  HM_DISPATCH(desc->C, L);
+  SG_CLASS_DISPATCH(desc->C, L);
 #undef L
   SG_LAUNCH_CHECK("mine_bwd_kernel");
   return 0;

@@ -14,8 +14,7 @@
 //   lv_bwd_kernel     dp = grad_scale * (point_weight * pointwise gradient + lovasz_weight * g)
 // A double is kept in the workspace as two words, so 4-byte alignment is enough for every pointer.  No float atomics, no
 // allocation, no synchronisation: the same bits from run to run, and every launch is a kernel node.
-#include <float.h>
-#include "loss_rows.h"
+#include "loss_head.h"
 #include "sort_impl.h"
 
 namespace {
@@ -24,32 +23,12 @@ constexpr int MAX_IMAGES = 65535;
 constexpr uint32_t ONE_BITS = 0x3f800000u;
 constexpr uint32_t FG_BIT = 0x80000000u;
 
-struct ClassVec {
-  float v[SG_MAX_CLASSES];
-};
-
-#define LV_FOR(c) _Pragma("unroll") for (int c = 0; c < CM; ++c) if (EX || c < C)
-
-// NaN / negative / -0 -> +0, above 1 -> 1, on the bits (row_key of hard_mining.hip)
-__device__ __forceinline__ uint32_t clamp_bits(float p) {
-  const uint32_t b = __float_as_uint(p);
-  return b > 0x7f800000u ? 0u : (b < ONE_BITS ? b : ONE_BITS);
-}
-
 __device__ __forceinline__ void put_double(uint32_t* __restrict__ w, double v) {
   w[0] = (uint32_t)__double2loint(v);
   w[1] = (uint32_t)__double2hiint(v);
 }
 
 __device__ __forceinline__ double get_double(const uint32_t* __restrict__ w) { return __hiloint2double((int)w[1], (int)w[0]); }
-
-// the workgroup's sum of v in a fixed order: a wave's 64 by xor-shuffles, the four waves in wave order.  Valid in thread 0
-__device__ __forceinline__ double block_sum_double(double v, double* sm) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sm[0] + sm[1]) + sm[2]) + sm[3];
-}
 
 template <int CM, bool EX>
 __global__ __launch_bounds__(256) void lv_key_kernel(int kind, int64_t rows, int64_t n, int C, int y_cols, const ClassVec al,
@@ -62,18 +41,13 @@ __global__ __launch_bounds__(256) void lv_key_kernel(int kind, int64_t rows, int
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
     float pv[CM], y[CM];
-    LV_FOR(c) {
+    SG_CLASS_FOR(c) {
       pv[c] = p[i * C + c];
       y[c] = yt[i * y_cols + c];
     }
-    float best = y[0];
-    int t = 0;
-    LV_FOR(c) if (c > 0 && y[c] > best) {
-      best = y[c];
-      t = c;
-    }
+    const int t = row_first_max<CM, EX>(y, C);
     const int64_t g = i / n, r = i - g * n;
-    LV_FOR(c) {
+    SG_CLASS_FOR(c) {
       const uint32_t q = clamp_bits(pv[c]);
       const bool f = c == t;
       const uint32_t mb = f ? __float_as_uint(1.0f - __uint_as_float(q)) : q;   // in [0, 1]: at most ONE_BITS
@@ -83,17 +57,15 @@ __global__ __launch_bounds__(256) void lv_key_kernel(int kind, int64_t rows, int
     }
     if (kind >= 0) {
       float s = 0.f;
-      LV_FOR(c) {
+      SG_CLASS_FOR(c) {
         const float w = kind == SG_LOSS_EDGE_FOCAL ? yt[i * y_cols + C + c] : 1.f;
         s += loss_row_term(kind, loss_coeff(kind, al.v[c], y[c], w), pv[c]);
       }
       acc += s;
     }
   }
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
+  const float tot = block_sum_256(acc, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
 // grid = segments * ntiles
@@ -237,10 +209,7 @@ __global__ __launch_bounds__(256) void lv_final_kernel(const float* __restrict__
   __syncthreads();
   const double tl = block_sum_double(sl, sm);
   if (threadIdx.x == 0) {
-    const double lp = kind >= 0 ? -tp / (double)rows : 0.0, ll = tl / (double)images;
-    out[0] = (float)((kind >= 0 ? (double)point_weight * lp : 0.0) + (double)lovasz_weight * ll);
-    out[1] = (float)lp;
-    out[2] = (float)ll;
+    put_loss_terms(out, kind, point_weight, kind >= 0 ? -tp / (double)rows : 0.0, lovasz_weight, tl / (double)images);
   }
 }
 
@@ -257,16 +226,16 @@ __global__ __launch_bounds__(256) void lv_bwd_kernel(int kind, int64_t rows, int
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
     if (kind < 0) {
-      LV_FOR(c) dp[i * C + c] = sl * gl[i * C + c];
+      SG_CLASS_FOR(c) dp[i * C + c] = sl * gl[i * C + c];
       continue;
     }
     float pv[CM], y[CM], w[CM];
-    LV_FOR(c) {
+    SG_CLASS_FOR(c) {
       pv[c] = p[i * C + c];
       y[c] = yt[i * y_cols + c];
       w[c] = kind == SG_LOSS_EDGE_FOCAL ? yt[i * y_cols + C + c] : 1.f;
     }
-    LV_FOR(c) {
+    SG_CLASS_FOR(c) {
       const float a = loss_coeff(kind, al.v[c], y[c], w[c]);
       const float g = loss_row_grad(kind, pv[c]);
       const float pg = k * a * g;
@@ -275,54 +244,17 @@ __global__ __launch_bounds__(256) void lv_bwd_kernel(int kind, int64_t rows, int
   }
 }
 
-#undef LV_FOR
-
-#define LV_DISPATCH(C, LAUNCH)    \
-  do {                            \
-    switch (C) {                  \
-      case 2: LAUNCH(2, true); break; \
-      case 3: LAUNCH(3, true); break; \
-      case 4: LAUNCH(4, true); break; \
-      case 5: LAUNCH(5, true); break; \
-      case 6: LAUNCH(6, true); break; \
-      case 7: LAUNCH(7, true); break; \
-      case 8: LAUNCH(8, true); break; \
-      default:                    \
-        if ((C) <= 16) { LAUNCH(16, false); } else { LAUNCH(32, false); } \
-    }                             \
-  } while (0)
-
-inline bool nonneg(float v) { return v >= 0.f && v <= FLT_MAX; }  // finite and >= 0 (a NaN fails both)
-
 // 0, or SG_EINVAL with the error text set
 inline int desc_ok(const char* who, const sg_lovasz_desc* d) {
   SG_CHECK_ARG(d, "%s: no descriptor", who);
-  SG_CHECK_ARG(d->C >= 2 && d->C <= SG_MAX_CLASSES, "%s: C = %d outside [2, %d]", who, d->C, SG_MAX_CLASSES);
-  SG_CHECK_ARG(d->y_cols == d->C || d->y_cols == 2 * d->C, "%s: y_true has %d columns, not C = %d or 2C", who, d->y_cols, d->C);
+  if (const int rc = loss_head_ok(who, d->C, d->y_cols, d->point_kind, true, "pointwise loss", d->point_alpha, "point_alpha")) return rc;
   SG_CHECK_ARG(d->images >= 1 && d->images <= MAX_IMAGES, "%s: %d images outside [1, %d]", who, d->images, MAX_IMAGES);
   SG_CHECK_ARG(d->classes_all == 0 || d->classes_all == 1, "%s: classes_all = %d is not 0 or 1", who, d->classes_all);
   SG_CHECK_ARG(d->reserved == 0, "%s: reserved = %d", who, d->reserved);
   SG_CHECK_ARG(d->rows_per_image >= 1 && d->rows_per_image <= INT32_MAX / ((int64_t)d->images * d->C),
                "%s: rows_per_image = %lld: images * rows_per_image * C must lie in [1, 2^31 - 1]", who, (long long)d->rows_per_image);
-  SG_CHECK_ARG(d->point_kind >= -1 && d->point_kind <= SG_LOSS_EDGE_FOCAL, "%s: unknown pointwise loss %d", who, d->point_kind);
-  SG_CHECK_ARG(d->point_kind != SG_LOSS_EDGE_FOCAL || d->y_cols == 2 * d->C, "%s: edge_focal_loss needs y_true[..., 2C]", who);
-  SG_CHECK_ARG(nonneg(d->point_weight) && nonneg(d->lovasz_weight), "%s: point_weight = %g, lovasz_weight = %g must be finite and >= 0",
-               who, d->point_weight, d->lovasz_weight);
-  if (d->point_kind < 0) {
-    SG_CHECK_ARG(d->lovasz_weight > 0.f, "%s: lovasz_weight = 0 without a pointwise term", who);
-  } else {
-    SG_CHECK_ARG(d->point_weight > 0.f || d->lovasz_weight > 0.f, "%s: point_weight and lovasz_weight are both 0", who);
-    if (d->point_kind != SG_LOSS_CE2)
-      for (int c = 0; c < d->C; ++c)
-        SG_CHECK_ARG(d->point_alpha[c] >= -FLT_MAX && d->point_alpha[c] <= FLT_MAX, "%s: point_alpha[%d] is not finite", who, c);
-  }
+  if (const int rc = loss_weights_ok(who, d->point_kind, d->point_weight, d->lovasz_weight, "lovasz_weight")) return rc;
   return sort_pairs_shape_ok(who, (int64_t)d->images * d->C, d->rows_per_image, 30);
-}
-
-inline ClassVec point_alpha(const sg_lovasz_desc* d) {
-  ClassVec al;
-  for (int c = 0; c < SG_MAX_CLASSES; ++c) al.v[c] = (d->point_kind > SG_LOSS_CE2 && c < d->C) ? d->point_alpha[c] : 1.f;
-  return al;
 }
 
 // the workspace in words, in this order
@@ -372,7 +304,7 @@ int sg_loss_lovasz_fwd(sg_ctx* ctx, void* stream, const sg_lovasz_desc* desc, co
   const int C = desc->C, kind = desc->point_kind, images = desc->images, y_cols = desc->y_cols, all = desc->classes_all;
   const int64_t n = desc->rows_per_image, rows = n * images, ntiles = (int64_t)l.tiles, S = (int64_t)l.S;
   const int parts = (int)l.parts;
-  const ClassVec al = point_alpha(desc);
+  const ClassVec al = class_vec(desc->point_kind, desc->C, desc->point_alpha);
   hipStream_t st = (hipStream_t)stream;
   uint32_t* w = (uint32_t*)ws;
   uint32_t *ka = w + l.keys_a(), *va = w + l.vals_a(), *kb = w + l.keys_b(), *vb = w + l.vals_b();
@@ -381,7 +313,7 @@ int sg_loss_lovasz_fwd(sg_ctx* ctx, void* stream, const sg_lovasz_desc* desc, co
 #define L(CM, EX)                                                                                                           \
   hipLaunchKernelGGL((lv_key_kernel<CM, EX>), dim3(parts), dim3(256), 0, st, kind, rows, n, C, y_cols, al, (const float*)p, \
                      (const float*)y_true, ka, va, ppart)
-  LV_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("lv_key_kernel");
   // pass 0 reads pair a and writes pair b, pass 1 writes pair a, ...
@@ -408,14 +340,12 @@ int sg_loss_lovasz_bwd(sg_ctx* ctx, void* stream, const sg_lovasz_desc* desc, co
   SG_CHECK_ARG(ctx && p && y_true && g && dp, "sg_loss_lovasz_bwd: bad argument");
   if (const int rc = desc_ok("sg_loss_lovasz_bwd", desc)) return rc;
   const int64_t rows = desc->rows_per_image * desc->images;
-  const ClassVec al = point_alpha(desc);
-  int64_t blocks = sg_cdiv(rows, 256);
-  if (blocks > 8192) blocks = 8192;
+  const ClassVec al = class_vec(desc->point_kind, desc->C, desc->point_alpha);
 #define L(CM, EX)                                                                                                             \
-  hipLaunchKernelGGL((lv_bwd_kernel<CM, EX>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, desc->point_kind, rows, \
+  hipLaunchKernelGGL((lv_bwd_kernel<CM, EX>), dim3(loss_bwd_blocks(rows)), dim3(256), 0, (hipStream_t)stream, desc->point_kind, rows, \
                      desc->C, desc->y_cols, al, (const float*)p, (const float*)y_true, (const float*)g, (float*)dp, grad_scale,  \
                      desc->point_weight, desc->lovasz_weight)
-  LV_DISPATCH(desc->C, L);
+  SG_CLASS_DISPATCH(desc->C, L);
 #undef L
   SG_LAUNCH_CHECK("lv_bwd_kernel");
   return 0;

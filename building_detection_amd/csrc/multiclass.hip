@@ -7,18 +7,11 @@
 // At C = 2 every kernel here evaluates the expressions of the 2-class kernels (softmax2_*_kernel, loss_*_kernel,
 // confusion_kernel, argmax_acc_kernel) in the same order; only the loss scalar's per-row sum is shaped differently.
 #include "sg_reduce.h"
-#include "loss_rows.h"
+#include "loss_head.h"
 
 namespace {
 
-struct ClassAlpha {
-  float a[SG_MAX_CLASSES];
-};
-
 constexpr int64_t EW_CAP = 8192;   // ew_blocks: workgroups of this file's element-wise launches
-
-// CM: the unrolled trip count; EX: C == CM is known at compile time
-#define MC_FOR(c) _Pragma("unroll") for (int c = 0; c < CM; ++c) if (EX || c < C)
 
 template <int CM, bool EX>
 __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* z, float* p, int64_t rows, int C) {
@@ -26,16 +19,16 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* z, float*
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
     float v[CM];
-    MC_FOR(c) v[c] = z[i * C + c];
+    SG_CLASS_FOR(c) v[c] = z[i * C + c];
     float m = v[0];
-    MC_FOR(c) if (c > 0) m = fmaxf(m, v[c]);
+    SG_CLASS_FOR(c) if (c > 0) m = fmaxf(m, v[c]);
     float s = 0.f;
-    MC_FOR(c) {
+    SG_CLASS_FOR(c) {
       v[c] = expf(v[c] - m);
       s = c == 0 ? v[c] : s + v[c];
     }
     const float inv = 1.0f / s;
-    MC_FOR(c) p[i * C + c] = v[c] * inv;
+    SG_CLASS_FOR(c) p[i * C + c] = v[c] * inv;
   }
 }
 
@@ -46,7 +39,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restric
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
     float pv[CM], g[CM];
-    MC_FOR(c) {
+    SG_CLASS_FOR(c) {
       pv[c] = p[i * C + c];
       g[c] = dp[i * C + c];
     }
@@ -55,26 +48,14 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restric
       dot = g[0] * pv[0] + g[1] * pv[1];  // softmax2_bwd_kernel's expression, so that it contracts alike
     } else {
       dot = 0.f;
-      MC_FOR(c) dot += g[c] * pv[c];
+      SG_CLASS_FOR(c) dot += g[c] * pv[c];
     }
-    MC_FOR(c) dz[i * C + c] = pv[c] * (g[c] - dot);
+    SG_CLASS_FOR(c) dz[i * C + c] = pv[c] * (g[c] - dot);
   }
 }
 
-// loss_coeff, loss_row_term, loss_row_grad: loss_rows.h
-
-__device__ __forceinline__ float block_sum_256(float v, float* sm) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) sm[wave] = v;
-  __syncthreads();
-  float t = 0.f;
-  if (threadIdx.x == 0) t = sm[0] + sm[1] + sm[2] + sm[3];
-  return t;  // valid in thread 0
-}
-
 template <int CM, bool EX>
-__global__ __launch_bounds__(256) void lossn_fwd_kernel(int kind, int64_t rows, int C, int y_cols, const ClassAlpha al,
+__global__ __launch_bounds__(256) void lossn_fwd_kernel(int kind, int64_t rows, int C, int y_cols, const ClassVec al,
                                                         const float* __restrict__ p, const float* __restrict__ yt,
                                                         float* __restrict__ part) {
   if (EX) C = CM;
@@ -83,14 +64,14 @@ __global__ __launch_bounds__(256) void lossn_fwd_kernel(int kind, int64_t rows, 
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
     float pv[CM], y[CM], w[CM];
-    MC_FOR(c) {
+    SG_CLASS_FOR(c) {
       pv[c] = p[i * C + c];
       y[c] = yt[i * y_cols + c];
       w[c] = kind == SG_LOSS_EDGE_FOCAL ? yt[i * y_cols + C + c] : 1.f;
     }
     float r = 0.f;
-    MC_FOR(c) {
-      const float a = loss_coeff(kind, al.a[c], y[c], w[c]);
+    SG_CLASS_FOR(c) {
+      const float a = loss_coeff(kind, al.v[c], y[c], w[c]);
       r += loss_row_term(kind, a, pv[c]);
     }
     acc += r;
@@ -109,7 +90,7 @@ __global__ void lossn_final_kernel(const float* __restrict__ part, int nparts, i
 
 // dL/dp_c = -(scale/rows) * a_c * d/dp [ f(p) log(p+eps) ];  f = (1-p)^2 -> -2(1-p) log(p+eps) + (1-p)^2/(p+eps)
 template <int CM, bool EX>
-__global__ __launch_bounds__(256) void lossn_bwd_kernel(int kind, int64_t rows, int C, int y_cols, const ClassAlpha al,
+__global__ __launch_bounds__(256) void lossn_bwd_kernel(int kind, int64_t rows, int C, int y_cols, const ClassVec al,
                                                         const float* __restrict__ p, const float* __restrict__ yt,
                                                         float* __restrict__ dp, float scale) {
   if (EX) C = CM;
@@ -117,31 +98,24 @@ __global__ __launch_bounds__(256) void lossn_bwd_kernel(int kind, int64_t rows, 
   const float k = -scale / (float)rows;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
     float pv[CM], y[CM], w[CM];
-    MC_FOR(c) {
+    SG_CLASS_FOR(c) {
       pv[c] = p[i * C + c];
       y[c] = yt[i * y_cols + c];
       w[c] = kind == SG_LOSS_EDGE_FOCAL ? yt[i * y_cols + C + c] : 1.f;
     }
-    MC_FOR(c) {
-      const float a = loss_coeff(kind, al.a[c], y[c], w[c]);
+    SG_CLASS_FOR(c) {
+      const float a = loss_coeff(kind, al.v[c], y[c], w[c]);
       const float g = loss_row_grad(kind, pv[c]);
       dp[i * C + c] = k * a * g;
     }
   }
 }
 
-// first maximum while scanning upwards (strict >): ties go to the lowest index, as tf.argmax does
 template <int CM, bool EX>
 __device__ __forceinline__ int row_argmax(const float* __restrict__ r, int C) {
   float v[CM];
-  MC_FOR(c) v[c] = r[c];
-  float best = v[0];
-  int q = 0;
-  MC_FOR(c) if (c > 0 && v[c] > best) {
-    best = v[c];
-    q = c;
-  }
-  return q;
+  SG_CLASS_FOR(c) v[c] = r[c];
+  return row_first_max<CM, EX>(v, C);
 }
 
 // out[t * C + q] += #rows with argmax(y_true[:, :C]) == t and argmax(p) == q.  A workgroup counts into an LDS table of
@@ -198,34 +172,13 @@ __global__ __launch_bounds__(256) void argmax_max_kernel(const float* __restrict
   if ((unsigned char)q > old) *d = (unsigned char)q;
 }
 
-#undef MC_FOR
-
-// LAUNCH(CM, EX) for the instantiation that serves C
-#define MC_DISPATCH(C, LAUNCH)    \
-  do {                            \
-    switch (C) {                  \
-      case 2: LAUNCH(2, true); break; \
-      case 3: LAUNCH(3, true); break; \
-      case 4: LAUNCH(4, true); break; \
-      case 5: LAUNCH(5, true); break; \
-      case 6: LAUNCH(6, true); break; \
-      case 7: LAUNCH(7, true); break; \
-      case 8: LAUNCH(8, true); break; \
-      default:                    \
-        if ((C) <= 16) { LAUNCH(16, false); } else { LAUNCH(32, false); } \
-    }                             \
-  } while (0)
-
 inline bool classes_ok(int C) { return C >= 2 && C <= SG_MAX_CLASSES; }
 
-// kind, C, y_cols and alpha of the two loss calls; fills `al`
-inline int lossn_args(const char* who, int kind, int C, int y_cols, const float* alpha, ClassAlpha& al) {
-  SG_CHECK_ARG(kind >= SG_LOSS_CE2 && kind <= SG_LOSS_EDGE_FOCAL, "%s: unknown loss %d", who, kind);
-  SG_CHECK_ARG(classes_ok(C), "%s: C = %d outside [2, %d]", who, C, SG_MAX_CLASSES);
-  SG_CHECK_ARG(y_cols == C || y_cols == 2 * C, "%s: y_true has %d columns, not C = %d or 2C", who, y_cols, C);
-  SG_CHECK_ARG(kind != SG_LOSS_EDGE_FOCAL || y_cols == 2 * C, "%s: edge_focal_loss needs y_true[..., 2C]", who);
+// kind, C, y_cols and alpha of the two loss calls (the weights' values are taken as they come); fills `al`
+inline int lossn_args(const char* who, int kind, int C, int y_cols, const float* alpha, ClassVec& al) {
+  if (const int rc = loss_head_ok(who, C, y_cols, kind, false, "loss", nullptr, "alpha")) return rc;
   SG_CHECK_ARG(kind == SG_LOSS_CE2 || alpha, "%s: focal losses need the C class weights", who);
-  for (int c = 0; c < SG_MAX_CLASSES; ++c) al.a[c] = (alpha && c < C) ? alpha[c] : 1.f;
+  al = class_vec(kind, C, alpha);
   return 0;
 }
 
@@ -240,7 +193,7 @@ int sg_softmax_fwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, co
 #define L(CM, EX)                                                                                                     \
   hipLaunchKernelGGL((softmax_fwd_kernel<CM, EX>), dim3(ew_blocks(rows, EW_CAP)), dim3(256), 0, (hipStream_t)stream, (const float*)z, \
                      (float*)p, rows, C)
-  MC_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("softmax_fwd_kernel");
   return 0;
@@ -253,7 +206,7 @@ int sg_softmax_bwd(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, co
 #define L(CM, EX)                                                                                                     \
   hipLaunchKernelGGL((softmax_bwd_kernel<CM, EX>), dim3(ew_blocks(rows, EW_CAP)), dim3(256), 0, (hipStream_t)stream, (const float*)p, \
                      (const float*)dp, (float*)dz, rows, C)
-  MC_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("softmax_bwd_kernel");
   return 0;
@@ -264,7 +217,7 @@ size_t sg_lossn_ws_bytes(const sg_ctx*, int64_t rows) { return (size_t)sg_loss_p
 int sg_lossn_fwd(sg_ctx* ctx, void* stream, int kind, int64_t rows, int C, int y_cols, const float* alpha, const void* p,
                  const void* y_true, void* loss_out, void* ws, size_t ws_bytes) {
   SG_CHECK_ARG(ctx && p && y_true && loss_out && rows > 0, "sg_lossn_fwd: bad argument");
-  ClassAlpha al;
+  ClassVec al;
   if (const int rc = lossn_args("sg_lossn_fwd", kind, C, y_cols, alpha, al)) return rc;
   const int parts = sg_loss_parts(rows);
   if (!ws || ws_bytes < (size_t)parts * sizeof(float)) {
@@ -275,7 +228,7 @@ int sg_lossn_fwd(sg_ctx* ctx, void* stream, int kind, int64_t rows, int C, int y
 #define L(CM, EX)                                                                                                  \
   hipLaunchKernelGGL((lossn_fwd_kernel<CM, EX>), dim3(parts), dim3(256), 0, st, kind, rows, C, y_cols, al, (const float*)p, \
                      (const float*)y_true, (float*)ws)
-  MC_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("lossn_fwd_kernel");
   hipLaunchKernelGGL(lossn_final_kernel, dim3(1), dim3(64), 0, st, (const float*)ws, parts, rows, (float*)loss_out);
@@ -286,14 +239,12 @@ int sg_lossn_fwd(sg_ctx* ctx, void* stream, int kind, int64_t rows, int C, int y
 int sg_lossn_bwd(sg_ctx* ctx, void* stream, int kind, int64_t rows, int C, int y_cols, const float* alpha, const void* p,
                  const void* y_true, void* dp, float grad_scale) {
   SG_CHECK_ARG(ctx && p && y_true && dp && rows > 0, "sg_lossn_bwd: bad argument");
-  ClassAlpha al;
+  ClassVec al;
   if (const int rc = lossn_args("sg_lossn_bwd", kind, C, y_cols, alpha, al)) return rc;
-  int64_t blocks = sg_cdiv(rows, 256);
-  if (blocks > 8192) blocks = 8192;
 #define L(CM, EX)                                                                                                      \
-  hipLaunchKernelGGL((lossn_bwd_kernel<CM, EX>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, kind, rows, C, \
+  hipLaunchKernelGGL((lossn_bwd_kernel<CM, EX>), dim3(loss_bwd_blocks(rows)), dim3(256), 0, (hipStream_t)stream, kind, rows, C, \
                      y_cols, al, (const float*)p, (const float*)y_true, (float*)dp, grad_scale)
-  MC_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("lossn_bwd_kernel");
   return 0;
@@ -309,7 +260,7 @@ int sg_confusion_matrix(sg_ctx* ctx, void* stream, int64_t rows, int C, int y_co
 #define L(CM, EX)                                                                                                        \
   hipLaunchKernelGGL((confusion_matrix_kernel<CM, EX>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rows, C, \
                      y_cols, (const float*)p, (const float*)y_true, (unsigned long long*)out_i64)
-  MC_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("confusion_matrix_kernel");
   return 0;
@@ -324,7 +275,7 @@ int sg_argmax_max_u8(sg_ctx* ctx, void* stream, const void* p, int C, int TH, in
 #define L(CM, EX)                                                                                                      \
   hipLaunchKernelGGL((argmax_max_kernel<CM, EX>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)p, \
                      C, TH, TW, (unsigned char*)canvas_u8, CH, CW, y0, x0)
-  MC_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("argmax_max_kernel");
   return 0;

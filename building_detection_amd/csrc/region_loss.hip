@@ -10,18 +10,12 @@
 //   region_total_kernel  more than one image: the per-image sums in image order -> the three loss scalars
 //   region_bwd_kernel    dp = grad_scale * (lambda_p * pointwise gradient + A y + B), {A, B} read from device memory
 // No float atomics anywhere: the same bits from run to run.  fp32, dense rows, dword accesses (4-byte alignment is enough).
-#include <float.h>
-#include "sg_common.h"
+#include "loss_head.h"
 
 namespace {
 
-constexpr float K_EPS = 1e-7f;  // tf.keras.backend.epsilon()
 constexpr int MAX_COLS = 1 + 3 * SG_MAX_CLASSES;
 constexpr int MAX_IMAGES = 65535;  // gridDim.y
-
-struct ClassVec {
-  float v[SG_MAX_CLASSES];
-};
 
 // what the final kernel needs of the descriptor
 struct RegionTerm {
@@ -30,15 +24,6 @@ struct RegionTerm {
   double inv_gw;  // 1 / (G * sum_c w_c)
   ClassVec w;
 };
-
-#define RG_FOR(c) _Pragma("unroll") for (int c = 0; c < CM; ++c) if (EX || c < C)
-
-// a_c of the three pointwise losses, as in multiclass.hip
-__device__ __forceinline__ float point_coeff(int kind, float alpha, float y, float w) {
-  if (kind == SG_LOSS_CE2) return y;
-  if (kind == SG_LOSS_FOCAL) return alpha * y;
-  return alpha * w * y;
-}
 
 __device__ __forceinline__ float wave_sum(float v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -53,27 +38,25 @@ __global__ __launch_bounds__(256) void region_fwd_kernel(int kind, int64_t rows_
   if (EX) C = CM;
   __shared__ float sm[4][MAX_COLS];
   float acc = 0.f, si[CM], sp[CM], sy[CM];
-  RG_FOR(c) si[c] = sp[c] = sy[c] = 0.f;
+  SG_CLASS_FOR(c) si[c] = sp[c] = sy[c] = 0.f;
   const int64_t row0 = (int64_t)blockIdx.y * rows_per_image;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows_per_image; r += stride) {
     const int64_t i = row0 + r;
     float pv[CM], y[CM];
-    RG_FOR(c) {
+    SG_CLASS_FOR(c) {
       pv[c] = p[i * C + c];
       y[c] = yt[i * y_cols + c];
     }
     if (kind >= 0) {
       float t = 0.f;
-      RG_FOR(c) {
+      SG_CLASS_FOR(c) {
         const float w = kind == SG_LOSS_EDGE_FOCAL ? yt[i * y_cols + C + c] : 1.f;
-        const float a = point_coeff(kind, al.v[c], y[c], w);
-        const float f = kind == SG_LOSS_CE2 ? 1.f : (1.f - pv[c]) * (1.f - pv[c]);
-        t += a * f * logf(pv[c] + K_EPS);
+        t += loss_row_term(kind, loss_coeff(kind, al.v[c], y[c], w), pv[c]);
       }
       acc += t;
     }
-    RG_FOR(c) {
+    SG_CLASS_FOR(c) {
       si[c] += pv[c] * y[c];
       sp[c] += pv[c];
       sy[c] += y[c];
@@ -82,7 +65,7 @@ __global__ __launch_bounds__(256) void region_fwd_kernel(int kind, int64_t rows_
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   acc = wave_sum(acc);
   if (lane == 0) sm[wave][0] = acc;
-  RG_FOR(c) {
+  SG_CLASS_FOR(c) {
     const float ti = wave_sum(si[c]), tp = wave_sum(sp[c]), ty = wave_sum(sy[c]);
     if (lane == 0) {
       sm[wave][1 + c] = ti;
@@ -141,10 +124,7 @@ __global__ __launch_bounds__(256) void region_final_kernel(const float* __restri
     double s = 0.0;
     for (int c = 0; c < C; ++c) s += term[c];
     if (images == 1) {
-      const double lp = kind >= 0 ? -tot[0] / (double)rows : 0.0, lr = s * rt.inv_gw;
-      loss_out[0] = (float)((kind >= 0 ? (double)rt.point_weight * lp : 0.0) + (double)rt.region_weight * lr);
-      loss_out[1] = (float)lp;
-      loss_out[2] = (float)lr;
+      put_loss_terms(loss_out, kind, rt.point_weight, kind >= 0 ? -tot[0] / (double)rows : 0.0, rt.region_weight, s * rt.inv_gw);
     } else {
       img_sums[2 * img] = (float)tot[0];
       img_sums[2 * img + 1] = (float)s;
@@ -160,10 +140,7 @@ __global__ void region_total_kernel(const float* __restrict__ img_sums, int imag
       sp += (double)img_sums[2 * g];
       sr += (double)img_sums[2 * g + 1];
     }
-    const double lp = kind >= 0 ? -sp / (double)rows : 0.0, lr = sr * rt.inv_gw;
-    loss_out[0] = (float)((kind >= 0 ? (double)rt.point_weight * lp : 0.0) + (double)rt.region_weight * lr);
-    loss_out[1] = (float)lp;
-    loss_out[2] = (float)lr;
+    put_loss_terms(loss_out, kind, rt.point_weight, kind >= 0 ? -sp / (double)rows : 0.0, rt.region_weight, sr * rt.inv_gw);
   }
 }
 
@@ -176,7 +153,7 @@ __global__ __launch_bounds__(256) void region_bwd_kernel(int kind, int64_t rows_
                                                          float* __restrict__ dp, float scale, float point_weight) {
   if (EX) C = CM;
   float A[CM], B[CM];
-  RG_FOR(c) {
+  SG_CLASS_FOR(c) {
     A[c] = scale * coef[(int64_t)blockIdx.y * 2 * C + c];
     B[c] = scale * coef[(int64_t)blockIdx.y * 2 * C + C + c];
   }
@@ -186,54 +163,28 @@ __global__ __launch_bounds__(256) void region_bwd_kernel(int kind, int64_t rows_
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows_per_image; r += stride) {
     const int64_t i = row0 + r;
     float pv[CM], y[CM];
-    RG_FOR(c) {
+    SG_CLASS_FOR(c) {
       pv[c] = p[i * C + c];
       y[c] = yt[i * y_cols + c];
     }
     if (kind >= 0) {
-      RG_FOR(c) {
+      SG_CLASS_FOR(c) {
         const float w = kind == SG_LOSS_EDGE_FOCAL ? yt[i * y_cols + C + c] : 1.f;
-        const float a = point_coeff(kind, al.v[c], y[c], w);
-        float g;
-        if (kind == SG_LOSS_CE2) {
-          g = 1.f / (pv[c] + K_EPS);
-        } else {
-          const float q = 1.f - pv[c];
-          g = -2.f * q * logf(pv[c] + K_EPS) + q * q / (pv[c] + K_EPS);
-        }
+        const float a = loss_coeff(kind, al.v[c], y[c], w);
+        const float g = loss_row_grad(kind, pv[c]);
         const float pg = k * a * g;
         dp[i * C + c] = pg + (A[c] * y[c] + B[c]);
       }
     } else {
-      RG_FOR(c) dp[i * C + c] = A[c] * y[c] + B[c];
+      SG_CLASS_FOR(c) dp[i * C + c] = A[c] * y[c] + B[c];
     }
   }
 }
 
-#undef RG_FOR
-
-#define RG_DISPATCH(C, LAUNCH)    \
-  do {                            \
-    switch (C) {                  \
-      case 2: LAUNCH(2, true); break; \
-      case 3: LAUNCH(3, true); break; \
-      case 4: LAUNCH(4, true); break; \
-      case 5: LAUNCH(5, true); break; \
-      case 6: LAUNCH(6, true); break; \
-      case 7: LAUNCH(7, true); break; \
-      case 8: LAUNCH(8, true); break; \
-      default:                    \
-        if ((C) <= 16) { LAUNCH(16, false); } else { LAUNCH(32, false); } \
-    }                             \
-  } while (0)
-
-inline bool nonneg(float v) { return v >= 0.f && v <= FLT_MAX; }  // finite and >= 0 (a NaN fails both)
-
 // 0, or SG_EINVAL with the error text set
 inline int desc_ok(const char* who, const sg_region_desc* d) {
   SG_CHECK_ARG(d, "%s: no descriptor", who);
-  SG_CHECK_ARG(d->C >= 2 && d->C <= SG_MAX_CLASSES, "%s: C = %d outside [2, %d]", who, d->C, SG_MAX_CLASSES);
-  SG_CHECK_ARG(d->y_cols == d->C || d->y_cols == 2 * d->C, "%s: y_true has %d columns, not C = %d or 2C", who, d->y_cols, d->C);
+  if (const int rc = loss_head_ok(who, d->C, d->y_cols, d->point_kind, true, "pointwise loss", d->point_alpha, "point_alpha")) return rc;
   SG_CHECK_ARG(d->images >= 1 && d->images <= MAX_IMAGES, "%s: %d images outside [1, %d]", who, d->images, MAX_IMAGES);
   SG_CHECK_ARG(d->rows_per_image > 0 && d->rows_per_image <= INT64_MAX / ((int64_t)d->images * 4 * SG_MAX_CLASSES),
                "%s: rows_per_image = %lld", who, (long long)d->rows_per_image);
@@ -246,25 +197,7 @@ inline int desc_ok(const char* who, const sg_region_desc* d) {
     sw += d->class_w[c];
   }
   SG_CHECK_ARG(sw > 0.0, "%s: the class weights sum to 0", who);
-  SG_CHECK_ARG(d->point_kind >= -1 && d->point_kind <= SG_LOSS_EDGE_FOCAL, "%s: unknown pointwise loss %d", who, d->point_kind);
-  SG_CHECK_ARG(d->point_kind != SG_LOSS_EDGE_FOCAL || d->y_cols == 2 * d->C, "%s: edge_focal_loss needs y_true[..., 2C]", who);
-  SG_CHECK_ARG(nonneg(d->point_weight) && nonneg(d->region_weight), "%s: point_weight = %g, region_weight = %g must be finite and >= 0",
-               who, d->point_weight, d->region_weight);
-  if (d->point_kind < 0) {
-    SG_CHECK_ARG(d->region_weight > 0.f, "%s: region_weight = 0 without a pointwise term", who);
-  } else {
-    SG_CHECK_ARG(d->point_weight > 0.f || d->region_weight > 0.f, "%s: point_weight and region_weight are both 0", who);
-    if (d->point_kind != SG_LOSS_CE2)
-      for (int c = 0; c < d->C; ++c)
-        SG_CHECK_ARG(d->point_alpha[c] >= -FLT_MAX && d->point_alpha[c] <= FLT_MAX, "%s: point_alpha[%d] is not finite", who, c);
-  }
-  return 0;
-}
-
-inline ClassVec point_alpha(const sg_region_desc* d) {
-  ClassVec al;
-  for (int c = 0; c < SG_MAX_CLASSES; ++c) al.v[c] = (d->point_kind > SG_LOSS_CE2 && c < d->C) ? d->point_alpha[c] : 1.f;
-  return al;
+  return loss_weights_ok(who, d->point_kind, d->point_weight, d->region_weight, "region_weight");
 }
 
 inline size_t part_floats(const sg_region_desc* d) {
@@ -294,7 +227,7 @@ int sg_loss_region_fwd(sg_ctx* ctx, void* stream, const sg_region_desc* desc, co
   const int C = desc->C, kind = desc->point_kind, images = desc->images;
   const int parts = sg_loss_parts(desc->rows_per_image);
   const int64_t rows = desc->rows_per_image * images;
-  const ClassVec al = point_alpha(desc);
+  const ClassVec al = class_vec(desc->point_kind, desc->C, desc->point_alpha);
   RegionTerm rt;
   rt.a = desc->a, rt.b = desc->b, rt.smooth = desc->smooth, rt.gamma = desc->gamma;
   rt.point_weight = desc->point_weight, rt.region_weight = desc->region_weight;
@@ -310,7 +243,7 @@ int sg_loss_region_fwd(sg_ctx* ctx, void* stream, const sg_region_desc* desc, co
 #define L(CM, EX)                                                                                                        \
   hipLaunchKernelGGL((region_fwd_kernel<CM, EX>), dim3(parts, images), dim3(256), 0, st, kind, desc->rows_per_image, C, \
                      desc->y_cols, al, (const float*)p, (const float*)y_true, part)
-  RG_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("region_fwd_kernel");
   hipLaunchKernelGGL(region_final_kernel, dim3(images), dim3(256), 0, st, (const float*)part, parts, C, kind, images, rows, rt,
@@ -330,14 +263,12 @@ int sg_loss_region_bwd(sg_ctx* ctx, void* stream, const sg_region_desc* desc, co
   if (const int rc = desc_ok("sg_loss_region_bwd", desc)) return rc;
   const int C = desc->C, images = desc->images;
   const int64_t rows = desc->rows_per_image * images;
-  const ClassVec al = point_alpha(desc);
-  int64_t blocks = sg_cdiv(desc->rows_per_image, 256);
-  if (blocks > 8192) blocks = 8192;
+  const ClassVec al = class_vec(desc->point_kind, desc->C, desc->point_alpha);
 #define L(CM, EX)                                                                                                            \
-  hipLaunchKernelGGL((region_bwd_kernel<CM, EX>), dim3((unsigned)blocks, images), dim3(256), 0, (hipStream_t)stream,         \
+  hipLaunchKernelGGL((region_bwd_kernel<CM, EX>), dim3(loss_bwd_blocks(desc->rows_per_image), images), dim3(256), 0, (hipStream_t)stream,         \
                      desc->point_kind, desc->rows_per_image, rows, C, desc->y_cols, al, (const float*)p, (const float*)y_true, \
                      (const float*)coef, (float*)dp, grad_scale, desc->point_weight)
-  RG_DISPATCH(C, L);
+  SG_CLASS_DISPATCH(C, L);
 #undef L
   SG_LAUNCH_CHECK("region_bwd_kernel");
   return 0;

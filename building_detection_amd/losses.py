@@ -274,6 +274,15 @@ def resolve_loss(loss) -> int:
 _TWO_CLASS_ALPHA = {SG_LOSS_FOCAL: (0.5, 0.5), SG_LOSS_EDGE_FOCAL: (0.35, 0.65)}   # what the 2-class kernels have built in
 
 
+def _pointwise(pointwise, num_classes: int):
+    """(kind, alpha) of a compound's or mined loss's pointwise term; alpha: None (cross-entropy) or `num_classes` weights."""
+    kind = _LOSS_KINDS[pointwise.__name__]
+    alpha = resolve_alpha(pointwise, num_classes)
+    if alpha is None and kind != SG_LOSS_CE2:
+        alpha = _TWO_CLASS_ALPHA[kind]
+    return kind, alpha
+
+
 def resolve_region(loss, num_classes: int):
     """The fields of `sg_region_desc` that `loss` fixes for a `num_classes` model, or None for a loss without a region term:
     dict(a, b, smooth, gamma, class_w, per_image, point_kind, point_alpha, point_weight, region_weight).  class_w has
@@ -282,10 +291,7 @@ def resolve_region(loss, num_classes: int):
     if isinstance(loss, _CompoundLoss) and isinstance(loss.region, _LovaszLoss):
         return None                                               # resolve_lovasz answers for it
     if isinstance(loss, _CompoundLoss):
-        region, kind = loss.region, _LOSS_KINDS[loss.pointwise.__name__]
-        alpha = resolve_alpha(loss.pointwise, num_classes)
-        if alpha is None and kind != SG_LOSS_CE2:
-            alpha = _TWO_CLASS_ALPHA[kind]
+        region, (kind, alpha) = loss.region, _pointwise(loss.pointwise, num_classes)
         wp, wr = loss.pointwise_weight, loss.region_weight
     elif isinstance(loss, _RegionLoss):
         region, kind, alpha, wp, wr = loss, NO_POINTWISE, None, 0.0, 1.0
@@ -306,10 +312,7 @@ def resolve_lovasz(loss, num_classes: int):
     term, or cross-entropy) or `num_classes` weights - at two classes without with_alpha the reference's own, passed
     explicitly."""
     if isinstance(loss, _CompoundLoss) and isinstance(loss.region, _LovaszLoss):
-        lov, kind = loss.region, _LOSS_KINDS[loss.pointwise.__name__]
-        alpha = resolve_alpha(loss.pointwise, num_classes)
-        if alpha is None and kind != SG_LOSS_CE2:
-            alpha = _TWO_CLASS_ALPHA[kind]
+        lov, (kind, alpha) = loss.region, _pointwise(loss.pointwise, num_classes)
         wp, wl = loss.pointwise_weight, loss.region_weight
     elif isinstance(loss, _LovaszLoss):
         lov, kind, alpha, wp, wl = loss, NO_POINTWISE, None, 0.0, 1.0
@@ -328,10 +331,7 @@ def resolve_mining(loss, num_classes: int):
     `mined_rows` turns it into the k of a batch."""
     if not isinstance(loss, _MinedLoss):
         return None
-    kind = _LOSS_KINDS[loss.pointwise.__name__]
-    alpha = resolve_alpha(loss.pointwise, num_classes)
-    if alpha is None and kind != SG_LOSS_CE2:
-        alpha = _TWO_CLASS_ALPHA[kind]
+    kind, alpha = _pointwise(loss.pointwise, num_classes)
     return dict(kind=kind, alpha=alpha, thresh=loss.thresh, min_kept=loss.min_kept)
 
 

@@ -999,24 +999,36 @@ class Engine:
         return dp
 
     @staticmethod
-    def region_desc(region, p, y_true):
-        """`sg_region_desc` of `region` (the dict of losses.resolve_region) for p [N, ..., C] and y_true [N, ..., C or 2C]:
-        one group per image of the leading axis with per_image, else one for the batch."""
+    def _head_desc(kind, p, y_true, *weights):
+        """What the three descriptors share: (C, y_cols, rows) of p [..., C] and y_true [..., C or 2C] after the shape checks,
+        edge focal's 2C columns and the length of every per-class vector in `weights` (None: not given) included."""
         c, y_cols = int(p.shape[-1]), int(y_true.shape[-1])
         rows = p.numel() // c
         if y_true.numel() != rows * y_cols or y_cols not in (c, 2 * c):
             raise ValueError(f"y_true {tuple(y_true.shape)} does not go with p {tuple(p.shape)}: C or 2C columns per pixel")
-        if region["point_kind"] == _lib.SG_LOSS_EDGE_FOCAL and y_cols != 2 * c:
+        if kind == _lib.SG_LOSS_EDGE_FOCAL and y_cols != 2 * c:
             raise ValueError(f"edge_focal_loss needs y_true[..., {2 * c}] (one-hot, then one edge weight per class), got {y_cols} columns")
-        if len(region["class_w"]) != c or (region["point_alpha"] is not None and len(region["point_alpha"]) != c):
+        if any(w is not None and len(w) != c for w in weights):
             raise ValueError(f"the loss carries class weights for another class count than {c}")
+        return c, y_cols, rows
+
+    @staticmethod
+    def _fill(field, values, c):
+        """A descriptor's per-class array: `values`, or ones where the loss has none."""
+        for i in range(c):
+            field[i] = 1.0 if values is None else values[i]
+
+    @staticmethod
+    def region_desc(region, p, y_true):
+        """`sg_region_desc` of `region` (the dict of losses.resolve_region) for p [N, ..., C] and y_true [N, ..., C or 2C]:
+        one group per image of the leading axis with per_image, else one for the batch."""
+        c, y_cols, rows = Engine._head_desc(region["point_kind"], p, y_true, region["class_w"], region["point_alpha"])
         images = int(p.shape[0]) if region["per_image"] and p.dim() > 1 else 1
         d = _lib.RegionDesc(C=c, y_cols=y_cols, images=images, point_kind=int(region["point_kind"]), rows_per_image=rows // images,
                             a=region["a"], b=region["b"], smooth=region["smooth"], gamma=region["gamma"],
                             point_weight=region["point_weight"], region_weight=region["region_weight"])
-        for i in range(c):
-            d.class_w[i] = region["class_w"][i]
-            d.point_alpha[i] = 1.0 if region["point_alpha"] is None else region["point_alpha"][i]
+        Engine._fill(d.class_w, region["class_w"], c)
+        Engine._fill(d.point_alpha, region["point_alpha"], c)
         return d
 
     def loss_region_fwd(self, region, p, y_true):
@@ -1046,18 +1058,10 @@ class Engine:
         """`sg_mine_desc` of `mine` (the dict of losses.resolve_mining) for p [..., C] and y_true [..., C or 2C]: min_kept
         becomes the row count k of this batch (losses.mined_rows)."""
         from .losses import mined_rows
-        c, y_cols = int(p.shape[-1]), int(y_true.shape[-1])
-        rows = p.numel() // c
-        if y_true.numel() != rows * y_cols or y_cols not in (c, 2 * c):
-            raise ValueError(f"y_true {tuple(y_true.shape)} does not go with p {tuple(p.shape)}: C or 2C columns per pixel")
-        if mine["kind"] == _lib.SG_LOSS_EDGE_FOCAL and y_cols != 2 * c:
-            raise ValueError(f"edge_focal_loss needs y_true[..., {2 * c}] (one-hot, then one edge weight per class), got {y_cols} columns")
-        if mine["alpha"] is not None and len(mine["alpha"]) != c:
-            raise ValueError(f"the loss carries class weights for another class count than {c}")
+        c, y_cols, rows = Engine._head_desc(mine["kind"], p, y_true, mine["alpha"])
         d = _lib.MineDesc(C=c, y_cols=y_cols, kind=int(mine["kind"]), reserved=0, rows=rows,
                           min_kept=mined_rows(mine["min_kept"], rows), thresh=mine["thresh"])
-        for i in range(c):
-            d.alpha[i] = 1.0 if mine["alpha"] is None else mine["alpha"][i]
+        Engine._fill(d.alpha, mine["alpha"], c)
         return d
 
     def loss_mined_fwd(self, mine, p, y_true):
@@ -1105,22 +1109,14 @@ class Engine:
         """`sg_lovasz_desc` of `lovasz` (the dict of losses.resolve_lovasz) for p [N, ..., C] and y_true [N, ..., C or 2C]:
         one group per image of the leading axis with per_image (p then has at least three axes: a flat [rows, C] names no
         images and is a ValueError), else one for the batch."""
-        c, y_cols = int(p.shape[-1]), int(y_true.shape[-1])
-        rows = p.numel() // c
-        if y_true.numel() != rows * y_cols or y_cols not in (c, 2 * c):
-            raise ValueError(f"y_true {tuple(y_true.shape)} does not go with p {tuple(p.shape)}: C or 2C columns per pixel")
-        if lovasz["point_kind"] == _lib.SG_LOSS_EDGE_FOCAL and y_cols != 2 * c:
-            raise ValueError(f"edge_focal_loss needs y_true[..., {2 * c}] (one-hot, then one edge weight per class), got {y_cols} columns")
-        if lovasz["point_alpha"] is not None and len(lovasz["point_alpha"]) != c:
-            raise ValueError(f"the loss carries class weights for another class count than {c}")
+        c, y_cols, rows = Engine._head_desc(lovasz["point_kind"], p, y_true, lovasz["point_alpha"])
         if lovasz["per_image"] and p.dim() < 3:
             raise ValueError(f"per_image needs p [N, ..., C] with the images on the leading axis, not {tuple(p.shape)}")
         images = int(p.shape[0]) if lovasz["per_image"] else 1
         d = _lib.LovaszDesc(C=c, y_cols=y_cols, images=images, classes_all=int(lovasz["classes_all"]), rows_per_image=rows // images,
                             point_kind=int(lovasz["point_kind"]), reserved=0, point_weight=lovasz["point_weight"],
                             lovasz_weight=lovasz["lovasz_weight"])
-        for i in range(c):
-            d.point_alpha[i] = 1.0 if lovasz["point_alpha"] is None else lovasz["point_alpha"][i]
+        Engine._fill(d.point_alpha, lovasz["point_alpha"], c)
         return d
 
     def loss_lovasz_fwd(self, lovasz, p, y_true):

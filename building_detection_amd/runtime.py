@@ -15,6 +15,7 @@ launch over the whole arena.  Under data parallelism the gradient arena is all-r
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 import time
@@ -103,6 +104,43 @@ class History:
         self.epoch: List[int] = []
 
 
+# What a loss's forward call leaves.  carry: the one tensor its backward call reads (region: coef [images, 2C]; mined: the int32
+# [4] record {T, n_kept}; Lovasz: g = dL_lovasz/dp [rows, C]; else None).  terms: the Lovasz {L, L_point, L_lovasz}; rows: mined rows
+_LossState = collections.namedtuple("_LossState", "carry terms rows", defaults=(None, None, None))
+
+
+class _LossHead:
+    """The loss side of a step, chosen once in compile().  route: "lovasz", "mined" or "region" (in this order of precedence;
+    desc = the descriptor fields the sg_loss_<route>_fwd/bwd pair runs by), else "two_class" (two classes with the reference's
+    weights: the 2-class entry points) or "n_class" (sg_lossn_* with the per-class weights).  fwd returns the loss scalar [1] and
+    leaves `state`, which bwd reads: a captured step keeps ITS state (GraphedTrainStep.loss_state) for after every replay."""
+
+    def __init__(self, model):
+        named = (("lovasz", model.loss_lovasz), ("mined", model.loss_mining), ("region", model.loss_region))
+        self.route, self.desc = next((rd for rd in named if rd[1] is not None),
+                                     ("two_class" if model._two_class() else "n_class", None))
+        self.kind, self.alpha = model.loss_kind, model.loss_alpha
+        self.state = _LossState()
+
+    def fwd(self, eng, p, y):
+        if self.desc is None:
+            return eng.loss_fwd(self.kind, p, y) if self.route == "two_class" else eng.lossn_fwd(self.kind, p, y, self.alpha)
+        if self.route == "mined":
+            out, sel = eng.loss_mined_fwd(self.desc, p, y)
+            self.state = _LossState(sel, rows=p.numel() // p.shape[-1])
+            return out
+        lovasz = self.route == "lovasz"
+        terms, carry = (eng.loss_lovasz_fwd if lovasz else eng.loss_region_fwd)(self.desc, p, y)
+        self.state = _LossState(carry, terms if lovasz else None)
+        return terms[:1]
+
+    def bwd(self, eng, p, y):
+        if self.desc is None:
+            return eng.loss_bwd(self.kind, p, y, 1.0) if self.route == "two_class" else eng.lossn_bwd(self.kind, p, y, self.alpha, 1.0)
+        call = {"lovasz": eng.loss_lovasz_bwd, "mined": eng.loss_mined_bwd, "region": eng.loss_region_bwd}[self.route]
+        return call(self.desc, p, y, self.state.carry, 1.0)
+
+
 class Model:
     def __init__(self, inputs, outputs, name=None, seed: int = 1103, dtype=None):
         """dtype: "float32" (the reference's precision) or "mixed_bfloat16" / "bfloat16" = bf16 storage of every
@@ -124,6 +162,7 @@ class Model:
         self.stop_training = False
         self.optimizer: Optional[Optimizer] = None
         self.loss_kind: Optional[int] = None
+        self._head: Optional[_LossHead] = None   # compile() chooses it
         self.metric_names: List[str] = []
         self._rt = None
         from . import mixed_precision
@@ -272,14 +311,10 @@ class Model:
         # parallelism the sums I, P, Y are not exchanged: the mean of the ranks' region losses is not the region loss of the
         # global batch.)
         self.loss_region = LS.resolve_region(loss, self.num_classes)
-        self._loss_coef = None
-        # hard_mining(pointwise): the descriptor fields sg_loss_mined_* run by, else None; _loss_sel is the last step's record
+        # hard_mining(pointwise); lovasz_loss or compound(pointwise, lovasz_loss): the fields sg_loss_mined_* / sg_loss_lovasz_* run by
         self.loss_mining = LS.resolve_mining(loss, self.num_classes)
-        self._loss_sel = self._loss_sel_rows = None
-        # lovasz_loss or compound(pointwise, lovasz_loss): the descriptor fields sg_loss_lovasz_* run by, else None; _loss_g is the
-        # last step's dL_lovasz/dp, _loss_terms its {L, L_point, L_lovasz}
         self.loss_lovasz = LS.resolve_lovasz(loss, self.num_classes)
-        self._loss_g = self._loss_terms = None
+        self._head = _LossHead(self)   # the route these fields select, and the last step's state
         self.metric_names = [LS.resolve_metric(m) for m in (metrics or [])]
         self.jit_compile = bool(jit_compile)
         self._train_graphs = {}
@@ -296,58 +331,27 @@ class Model:
         """C of the softmax head: the last axis of the model's output."""
         return int(self.outputs[0].shape[-1])
 
-    # The head side of a step.  Two classes with the reference's weights: the 2-class entry points and the four counts
-    # {TP, TN, FP, FN}, as ever.  Otherwise sg_lossn_* with the per-class weights, and for C > 2 the C x C count matrix.
+    # two classes with the reference's weights: the 2-class entry points (and the four counts {TP, TN, FP, FN}), as ever
     def _two_class(self):
         return self.num_classes == 2 and getattr(self, "loss_alpha", None) is None
-
-    # A region loss: one forward call leaves {L, L_point, L_region} and the per-class gradient coefficients `coef`, which the
-    # backward call of the same step reads (self._loss_coef; a captured step keeps the tensor, GraphedTrainStep.coef).
-    # A mined loss: the forward call leaves the record {T, n_kept} (self._loss_sel; GraphedTrainStep.sel), the backward call reads it.
-    # A Lovasz loss: the forward call leaves {L, L_point, L_lovasz} and g = dL_lovasz/dp (self._loss_g; GraphedTrainStep.lov_g).
-    def _loss_fwd(self, eng, p, y):
-        if getattr(self, "loss_lovasz", None) is not None:
-            self._loss_terms, self._loss_g = eng.loss_lovasz_fwd(self.loss_lovasz, p, y)
-            return self._loss_terms[:1]
-        if getattr(self, "loss_mining", None) is not None:
-            out, self._loss_sel = eng.loss_mined_fwd(self.loss_mining, p, y)
-            self._loss_sel_rows = p.numel() // p.shape[-1]
-            return out
-        if getattr(self, "loss_region", None) is not None:
-            out, self._loss_coef = eng.loss_region_fwd(self.loss_region, p, y)
-            return out[:1]
-        if self._two_class():
-            return eng.loss_fwd(self.loss_kind, p, y)
-        return eng.lossn_fwd(self.loss_kind, p, y, self.loss_alpha)
-
-    def _loss_bwd(self, eng, p, y):
-        if getattr(self, "loss_lovasz", None) is not None:
-            return eng.loss_lovasz_bwd(self.loss_lovasz, p, y, self._loss_g, 1.0)
-        if getattr(self, "loss_mining", None) is not None:
-            return eng.loss_mined_bwd(self.loss_mining, p, y, self._loss_sel, 1.0)
-        if getattr(self, "loss_region", None) is not None:
-            return eng.loss_region_bwd(self.loss_region, p, y, self._loss_coef, 1.0)
-        if self._two_class():
-            return eng.loss_bwd(self.loss_kind, p, y, 1.0)
-        return eng.lossn_bwd(self.loss_kind, p, y, self.loss_alpha, 1.0)
 
     def last_hard_mining(self):
         """dict(threshold=T, kept=n_kept, rows=rows) of the last train_on_batch / test_on_batch under a hard_mining loss (this
         rank's shard under data parallelism): one host sync, taken only here.  None when the loss is not mined or no step ran."""
-        sel = getattr(self, "_loss_sel", None)
-        if getattr(self, "loss_mining", None) is None or sel is None:
+        st = getattr(self._head, "state", _LossState())   # (rows: set by a mined step alone)
+        if st.rows is None:
             return None
-        w = sel.cpu().numpy().view(np.uint32)
-        return dict(threshold=float(w[:1].view(np.float32)[0]), kept=int(w[2]) | (int(w[3]) << 32), rows=int(self._loss_sel_rows))
+        w = st.carry.cpu().numpy().view(np.uint32)
+        return dict(threshold=float(w[:1].view(np.float32)[0]), kept=int(w[2]) | (int(w[3]) << 32), rows=int(st.rows))
 
     def last_loss_terms(self):
         """dict(loss=L, pointwise=L_point, lovasz=L_lovasz) of the last train_on_batch / test_on_batch under lovasz_loss or
         compound(pointwise, lovasz_loss) (this rank's shard under data parallelism): one host sync, taken only here.  None when
         the loss has no Lovasz term or no step ran."""
-        t = getattr(self, "_loss_terms", None)
-        if getattr(self, "loss_lovasz", None) is None or t is None:
+        st = getattr(self._head, "state", _LossState())   # (terms: set by a Lovasz step alone)
+        if st.terms is None:
             return None
-        v = t.cpu().numpy()
+        v = st.terms.cpu().numpy()
         return dict(loss=float(v[0]), pointwise=float(v[1]), lovasz=float(v[2]))
 
     def _counts(self, eng, p, y):
@@ -422,16 +426,13 @@ class Model:
                         g = self._train_graphs[key] = GraphedTrainStep(self, xd, yd)
                 if g is not None:
                     loss, counts = g.run(xd, yd)
-                    if getattr(g, "sel", None) is not None:   # (a test_on_batch in between leaves its own record here)
-                        self._loss_sel, self._loss_sel_rows = g.sel, yd.numel() // yd.shape[-1]
-                    if getattr(g, "lov_terms", None) is not None:   # likewise the Lovasz terms and g of THIS graph's step
-                        self._loss_terms, self._loss_g = g.lov_terms, g.lov_g
+                    self._head.state = g.loss_state   # of THIS graph's step (a test_on_batch in between leaves its own here)
                     return (loss, counts) if return_device_scalars else self._logs(loss, counts)
             rt.write_rng(self.optimizer.iterations)   # (a model without dropout: nothing)
             p = rt.forward(xd, training=True)
-            loss = self._loss_fwd(rt.eng, p, yd)
+            loss = self._head.fwd(rt.eng, p, yd)
             counts = self._counts(rt.eng, p, yd)
-            dp = self._loss_bwd(rt.eng, p, yd)
+            dp = self._head.bwd(rt.eng, p, yd)
             rt.backward(dp)
             grad_scale = 1.0
             if self.dist is not None:
@@ -451,7 +452,7 @@ class Model:
         with rt.eng.lock:
             xd, yd = rt.to_device(x), rt.to_device(y)
             p = rt.forward(xd, training=False)
-            loss = self._loss_fwd(rt.eng, p, yd)
+            loss = self._head.fwd(rt.eng, p, yd)
             counts = self._counts(rt.eng, p, yd)
             if self.dist is not None:  # val_* logs describe the GLOBAL validation batch on every rank, as the training
                 loss, counts = self.dist.reduce_step_scalars(loss, counts)  # logs do: callbacks then decide alike
@@ -722,13 +723,10 @@ class GraphedTrainStep:
                 eng.lane = lane
                 begin()
                 p = rt.forward(self.x, training=True)
-                self.loss = model._loss_fwd(eng, p, self.y)
-                self.coef = getattr(model, "_loss_coef", None)   # a region loss: the graph's backward pass reads this tensor
-                self.sel = getattr(model, "_loss_sel", None)     # a mined loss: likewise the record {T, n_kept}
-                self.lov_g = getattr(model, "_loss_g", None)     # a Lovasz loss: likewise dL_lovasz/dp, and the three terms
-                self.lov_terms = getattr(model, "_loss_terms", None)
+                self.loss = model._head.fwd(eng, p, self.y)
+                self.loss_state = model._head.state   # the graph's backward pass reads its tensor; the reports read the rest
                 self.counts = model._counts(eng, p, self.y)   # zeroed inside the graph, four counts or C x C
-                dp = model._loss_bwd(eng, p, self.y)
+                dp = model._head.bwd(eng, p, self.y)
                 rt.backward(dp)
                 if not segmented:  # the optimizer rides in the same graph
                     opt.apply(rt, eng, 1.0, lr_dev=self.lr)

@@ -22,7 +22,7 @@ F32 = torch.float32
 TOL, TOL_RED = 2e-5, 1e-4
 OFFS = [pytest.param(False, id="aligned"), pytest.param(True, id="offset")]
 ROWS = (1, 63, 64, 65, 257, 2049, 70001)
-CLASSES = (2, 3, 5, 32)
+CLASSES = (2, 3, 5, 11, 32)   # 11: the bounded C <= 16 form of the kernels
 RED_CAP = 2048 * 1024                 # rows after which the 2048 workgroups take a second trip
 TAB_WORDS = 8 + 3 * 2048              # the state words and the three digit tables of the workspace
 DENORMAL = 1e-40
@@ -422,7 +422,8 @@ def test_mined_loss_in_a_model_eager_and_captured(engine, C):
     assert torch.equal(la, lb) and torch.equal(ca, cb) and ha == hb, (la, lb, ha, hb)
     assert ha["threshold"] >= f32(thresh) and ha["kept"] >= rows // 4
     assert len(mb._train_graphs) == 1 and isinstance(next(iter(mb._train_graphs.values())), GraphedTrainStep)
-    assert next(iter(mb._train_graphs.values())).sel is not None and not getattr(ma, "_train_graphs", None)
+    sel = next(iter(mb._train_graphs.values())).loss_state.carry   # the record the graph's backward pass reads
+    assert sel.is_cuda and sel.dtype == torch.int32 and tuple(sel.shape) == (4,) and not getattr(ma, "_train_graphs", None)
     for wa, wb in zip(ma.get_weights(), mb.get_weights()):
         assert np.array_equal(wa, wb)
     assert any(not np.array_equal(w0, w1) for w0, w1 in zip(build(C).get_weights(), ma.get_weights()))

@@ -215,7 +215,7 @@ INPUTS = ("random", "quantised", "absent", "absent_in_one_image", "one_class", "
 
 # ================================================================================================ loss and gradient
 @pytest.mark.parametrize("off", OFFS)
-@pytest.mark.parametrize("C", (2, 3, 5, 32))
+@pytest.mark.parametrize("C", (2, 3, 5, 11, 32))   # 11: the bounded C <= 16 form of the kernels
 def test_loss_and_gradient(engine, C, off):
     for j, rows in enumerate(ROWS):
         if C == 32 and rows > 2049:
@@ -271,7 +271,7 @@ def test_all_against_present_on_an_absent_class(engine, C):
 
 
 @pytest.mark.parametrize("off", OFFS)
-@pytest.mark.parametrize("C", (2, 3, 32))
+@pytest.mark.parametrize("C", (2, 3, 11, 32))
 def test_lovasz_weight_zero_gives_the_bits_of_lossn_bwd(engine, C, off):
     for rows, y_cols in ((257, 2 * C), (2049, C)):
         g = gen(f"zero{rows}{C}")
@@ -455,7 +455,11 @@ def test_lovasz_loss_in_a_model_eager_and_captured(engine, C):
     (la, ca, ta), (lb, cb, tb) = queued
     assert torch.equal(la, lb) and torch.equal(ca, cb) and ta == tb, (la, lb, ta, tb)
     assert len(mb._train_graphs) == 2 and all(isinstance(s, GraphedTrainStep) for s in mb._train_graphs.values())
-    assert all(s.lov_g is not None and s.lov_terms is not None for s in mb._train_graphs.values())
+    for s in mb._train_graphs.values():   # each graph keeps the state of ITS forward call: g [rows, C] and the three terms
+        rows = s.y.numel() // s.y.shape[-1]
+        g, terms = s.loss_state.carry, s.loss_state.terms
+        assert g.is_cuda and g.dtype == torch.float32 and tuple(g.shape) == (rows, C) and g.is_contiguous()
+        assert terms.is_cuda and terms.dtype == torch.float32 and tuple(terms.shape) == (3,)
     assert not getattr(ma, "_train_graphs", None)
     for wa, wb in zip(ma.get_weights(), mb.get_weights()):
         assert np.array_equal(wa, wb)

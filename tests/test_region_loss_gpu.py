@@ -122,7 +122,7 @@ def alpha_for(C):
 
 # ================================================================================================ rows, classes, widths, parameters
 @pytest.mark.parametrize("off", OFFS)
-@pytest.mark.parametrize("C", (2, 3, 5, 32))
+@pytest.mark.parametrize("C", (2, 3, 5, 11, 32))   # 11: the bounded C <= 16 form of the kernels
 def test_row_tails_classes_and_parameter_sets(engine, C, off):
     for n, rows in enumerate((1, 63, 255, 257, 1023, 1025)):                 # 1025: two parts
         gamma, a, b = PARAMS[n % len(PARAMS)]
@@ -201,7 +201,7 @@ def test_absent_class_and_zero_class_weight(engine, off):
 
 # ================================================================================================ the pointwise part is sg_lossn_*
 @pytest.mark.parametrize("off", OFFS)
-@pytest.mark.parametrize("C", (2, 3, 5, 32))
+@pytest.mark.parametrize("C", (2, 3, 5, 11, 32))   # 11: the bounded C <= 16 form of the kernels
 def test_without_region_weight_the_pointwise_calls(engine, C, off):
     for rows, y_cols in ((257, 2 * C), (1025, C), (4099, 2 * C)):
         g = gen(f"pw{rows}{C}")
@@ -340,7 +340,8 @@ def test_compound_loss_in_a_model_eager_and_captured(engine, C):
         assert la.numel() == 1 and torch.equal(la, lb) and torch.equal(ca, cb), (i, la, lb, ca, cb)     # steps 3 and 4 are replays
         assert ma._logs(la, ca) == mb._logs(lb, cb) and np.isfinite(la.item())
     assert len(mb._train_graphs) == 1 and isinstance(next(iter(mb._train_graphs.values())), GraphedTrainStep)
-    assert next(iter(mb._train_graphs.values())).coef is not None and not getattr(ma, "_train_graphs", None)
+    coef = next(iter(mb._train_graphs.values())).loss_state.carry   # {A, B} per class, which the graph's backward pass reads
+    assert coef.is_cuda and coef.dtype == torch.float32 and tuple(coef.shape) == (1, 2 * C) and not getattr(ma, "_train_graphs", None)
     for wa, wb in zip(ma.get_weights(), mb.get_weights()):
         assert np.array_equal(wa, wb)
     assert any(not np.array_equal(w0, w1) for w0, w1 in zip(build(C).get_weights(), ma.get_weights()))

@@ -23,6 +23,9 @@ SG_LOSS_CE2, SG_LOSS_FOCAL, SG_LOSS_EDGE_FOCAL = 0, 1, 2
 SG_MAX_CLASSES = 32   # the C-class head: sg_softmax_*, sg_lossn_*, sg_confusion_matrix, sg_argmax_max_u8
 SG_AUGMENT_MAX_ITEMS = 64
 SG_AUG_FLIP_UD, SG_AUG_FLIP_LR, SG_AUG_SWAP_RB, SG_AUG_THRESHOLD = 1, 2, 4, 8
+SG_WARP_MAX_ITEMS = 32
+SG_WARP_NEAREST, SG_WARP_REFLECT, SG_WARP_COLOR = 1, 2, 4
+SG_WARP_NOISE_STREAM, SG_WARP_NOISE_KEY = 0x6E6F6973, 0x77617270
 SG_SCENE_MAX_ITEMS = 64
 SG_SYM_FLIP_UD, SG_SYM_FLIP_LR, SG_SYM_TRANSPOSE = 1, 2, 4
 SG_OPT_ADAM, SG_OPT_SGD = 0, 1
@@ -48,6 +51,21 @@ SG_WS_PREPARED = C.c_size_t(-1).value
 class AugmentItem(C.Structure):
     """Mirror of `sg_augment_item` (include/segengine.h): one output tile of sg_augment_u8."""
     _fields_ = [(n, C.c_int32) for n in ("src", "n", "shift", "flags")]
+
+
+class WarpItem(C.Structure):
+    """Mirror of `sg_warp_item` (include/segengine.h): one output tile of sg_warp_u8."""
+    _fields_ = ([(n, C.c_int32) for n in ("src", "sh", "sw", "flags", "a00", "a01", "a10", "a11")] +
+                [("b0", C.c_int64), ("b1", C.c_int64), ("sample", C.c_uint64), ("fill", C.c_int32), ("noise_q12", C.c_int32),
+                 ("m", C.c_int32 * 9), ("off", C.c_int32 * 3)])
+
+
+def warp_item(src=0, sh=0, sw=0, flags=0, a=(65536, 0, 0, 65536), b=(0, 0), sample=0, fill=0, noise_q12=0,
+              m=(4096, 0, 0, 0, 4096, 0, 0, 0, 4096), off=(0, 0, 0)):
+    """A WarpItem from Python values; the defaults are the identity map and the identity colour matrix."""
+    a, b = [int(v) for v in a], [int(v) for v in b]
+    return WarpItem(int(src), int(sh), int(sw), int(flags), a[0], a[1], a[2], a[3], b[0], b[1], int(sample) & (2 ** 64 - 1),
+                    int(fill), int(noise_q12), (C.c_int32 * 9)(*[int(v) for v in m]), (C.c_int32 * 3)(*[int(v) for v in off]))
 
 
 class SceneItem(C.Structure):
@@ -397,6 +415,7 @@ _SIGNATURES = {
     "sg_edge_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sg_resize_linear_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "sg_augment_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "sg_warp_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, C.c_uint64, _i, _i, _vp]),
     "sg_argmax_accumulate_i8": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i]),
     "sg_argmax_max_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i]),
     "sg_scene_tiles_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp]),

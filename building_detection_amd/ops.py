@@ -1373,6 +1373,37 @@ class Engine:
                                          _ptr(dst[i0:i0 + len(chunk)])), "sg_augment_u8")
         return dst
 
+    def warp_u8(self, src, items, luts=None, seed=0, out_hw=None, extents=None):
+        """Affine warps and colour jitter (sg_warp_u8): uint8 sources [S,H,W,3] or [S,H,W] -> [N,OH,OW(,3)].  items[i] is a
+        mapping with the fields of `sg_warp_item` (see _lib.warp_item for the defaults: the identity, no colour); an item without
+        sh / sw takes extents[src] = (sh, sw) when `extents` is given, else the whole H x W slot.  luts: uint8 device tensor
+        [N,3,256] or None; seed: the 64-bit key of the noise.  out_hw defaults to (H, W); more than SG_WARP_MAX_ITEMS items take
+        several calls (the noise does not depend on the split)."""
+        assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() in (3, 4)
+        s, h, w = src.shape[:3]
+        c = src.shape[3] if src.dim() == 4 else 1
+        oh, ow = (h, w) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        items = [dict(it) for it in items]
+        for it in items:
+            if it.get("sh") is None or it.get("sw") is None:
+                k = int(it.get("src", 0))
+                if extents is not None and not 0 <= k < len(extents):
+                    raise _lib.SgError(f"sg_warp_u8: source {k} has no entry in extents ({len(extents)} given)")
+                it["sh"], it["sw"] = (h, w) if extents is None else extents[k]
+        if luts is not None:
+            assert luts.is_cuda and luts.dtype == torch.uint8 and luts.is_contiguous()
+            if tuple(luts.shape) != (len(items), 3, 256):
+                raise _lib.SgError(f"luts: expected [{len(items)},3,256], got {tuple(luts.shape)}")
+        dst = torch.empty((len(items), oh, ow) + tuple(src.shape[3:]), dtype=torch.uint8, device=self.device)
+        cap = _lib.SG_WARP_MAX_ITEMS
+        for i0 in range(0, len(items), cap):
+            chunk = items[i0:i0 + cap]
+            table = (_lib.WarpItem * len(chunk))(*[_lib.warp_item(**it) for it in chunk])
+            check(self.lib.sg_warp_u8(self.h, self.stream, s, h, w, c, _ptr(src), len(chunk), table,
+                                      _ptr(None if luts is None else luts[i0:i0 + len(chunk)]), int(seed) & (2 ** 64 - 1),
+                                      oh, ow, _ptr(dst[i0:i0 + len(chunk)])), "sg_warp_u8")
+        return dst
+
     def scale(self, t, a):
         check(self.lib.sg_scale_f32(self.h, self.stream, _ptr(t), t.numel(), float(a)), "sg_scale_f32")
         return t

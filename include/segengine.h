@@ -946,6 +946,63 @@ typedef struct sg_augment_item {
 } sg_augment_item;
 int sg_augment_u8(sg_ctx* ctx, void* stream, int S, int H, int W, int C, const void* src_u8, int N,
                   const sg_augment_item* items, int OH, int OW, int fill, void* dst_u8);
+/* Online augmentation (no counterpart in the reference, which augments offline): affine warps and colour jitter of uint8
+ * tiles in one call, src_u8[S,H,W,C] -> dst_u8[N,OH,OW,C], C = 1 or 3.  Source s occupies the top-left sh x sw corner of
+ * its H x W slot (sources of different sizes share one array); output tile i is described by items[i].  All arithmetic is
+ * integer, stated here to the bit (tests/_warp_ref.py restates this comment in numpy).
+ *
+ * Geometry.  For output pixel (ox, oy) the source position in 1/65536 pixel is
+ *     X = a00 * ox + a01 * oy + b0,   Y = a10 * ox + a11 * oy + b1      (int64 sums; a** int32 Q16, b* int64)
+ * and the host bakes every centre convention into b.  Bilinear (the default): x0 = X >> 16, y0 = Y >> 16 (floor),
+ * wx = (X & 0xFFFF) >> 8, wy likewise (0 .. 255), and with p00 = tap (x0, y0), p01 = (x0 + 1, y0), p10 = (x0, y0 + 1),
+ * p11 = (x0 + 1, y0 + 1), per channel
+ *     v = ((256-wx) (256-wy) p00 + wx (256-wy) p01 + (256-wx) wy p10 + wx wy p11 + 32768) >> 16.
+ * SG_WARP_NEAREST: v = the tap ((X + 32768) >> 16, (Y + 32768) >> 16) alone, so every output value is a source value or
+ * the fill (class maps and 0 / 255 masks stay valid).  A tap (x, y) outside [0, sw) x [0, sh) reads the item's `fill`;
+ * with SG_WARP_REFLECT it reads (r(x, sw), r(y, sh)) instead, r(i, n) the reflect-101 index: j = i mod 2 (n - 1) taken
+ * non-negative, r = j < n ? j : 2 (n - 1) - j, for any distance outside.  A tap of weight 0 contributes 0 wherever it lies,
+ * so the identity, the eight symmetries of the square and whole-pixel shifts reproduce source bytes exactly.
+ *
+ * Colour (items with SG_WARP_COLOR; C = 3 only), after the interpolation, in this order:
+ *   1. u_c = clamp((m[3c] v_0 + m[3c+1] v_1 + m[3c+2] v_2 + off[c] + 2048) >> 12, 0, 255), the shift arithmetic; m is a
+ *      row-major Q12 3 x 3 matrix (saturation, hue rotation, channel permutations such as the R-B swap).
+ *   2. luts_u8 != NULL: u_c = luts_u8[i][c][u_c], luts_u8[N][3][256] in device memory, row i for items[i] (brightness,
+ *      contrast and gamma, tabulated by the host).  Items without SG_WARP_COLOR do not read their rows.
+ *   3. noise_q12 > 0: (w_0, w_1, w_2, w_3) = Philox4x32-10 of counter (oy * OW + ox, sample mod 2^32, sample >> 32,
+ *      SG_WARP_NOISE_STREAM) and key (seed mod 2^32, (seed >> 32) xor SG_WARP_NOISE_KEY); t_c = the sum of the four bytes of
+ *      w_c minus 510 (mean 0, standard deviation sqrt(4 (256^2 - 1) / 12) = 147.80: four added bytes make a cheap bell
+ *      shape); u_c = clamp(u_c + ((noise_q12 * t_c + 2048) >> 12), 0, 255).  The noise of a sample depends on (seed, sample,
+ *      pixel, channel) only: not on the item's slot in the table, nor on how items are split into calls.
+ * Without SG_WARP_COLOR m, off, noise_q12 and sample are not read.
+ *
+ * Checked on the host before anything is launched (SG_EINVAL, the message naming the item; nothing is written):
+ * 1 <= N <= SG_WARP_MAX_ITEMS; C = 1 or 3; 1 <= OH, OW <= 2^14; both tensors under 2 GiB; per item 0 <= src < S,
+ * 1 <= sh <= H, 1 <= sw <= W, no unknown flag, 0 <= fill <= 255, |a**| <= 2^24, |b*| < 2^46 (with OH, OW <= 2^14 the int64
+ * sums stay below 2^47 and X >> 16 fits 32 bits); SG_WARP_REFLECT needs sh, sw >= 2; SG_WARP_COLOR needs C = 3,
+ * |m[k]| <= 2^18, |off[c]| <= 2^24 and 0 <= noise_q12 <= 2^16 (the 32-bit sums of steps 1 and 3 cannot overflow).
+ * The call neither allocates nor synchronises; the table travels as a kernel argument.  Items of one call that differ in
+ * (NEAREST, REFLECT, COLOR) take one launch per combination present; rows are stored as whole 32-bit words when OW is a
+ * multiple of 4 and dst_u8 is 4-byte aligned, byte by byte otherwise. */
+#define SG_WARP_MAX_ITEMS 32
+#define SG_WARP_NEAREST 1
+#define SG_WARP_REFLECT 2
+#define SG_WARP_COLOR   4
+#define SG_WARP_NOISE_STREAM 0x6E6F6973u   /* "nois": counter word 3 of the noise draws */
+#define SG_WARP_NOISE_KEY    0x77617270u   /* "warp": xor-ed into the high key word */
+typedef struct sg_warp_item {
+  int32_t src;                 /* source slot, 0 <= src < S */
+  int32_t sh, sw;              /* the source's extent inside its H x W slot */
+  int32_t flags;               /* SG_WARP_* */
+  int32_t a00, a01, a10, a11;  /* Q16 */
+  int64_t b0, b1;              /* 1/65536 pixel */
+  uint64_t sample;             /* the sample's number in the stream (noise counter) */
+  int32_t fill;                /* 0 .. 255 */
+  int32_t noise_q12;           /* Q12 factor of t; sigma in grey levels = 147.80 * noise_q12 / 4096 */
+  int32_t m[9];                /* Q12 colour matrix, row-major */
+  int32_t off[3];              /* Q12 colour offsets */
+} sg_warp_item;                /* 112 bytes */
+int sg_warp_u8(sg_ctx* ctx, void* stream, int S, int H, int W, int C, const void* src_u8, int N, const sg_warp_item* items,
+               const void* luts_u8, uint64_t seed, int OH, int OW, void* dst_u8);
 
 /* ------------------------------------------------------------------------------------ inference tail
  * predict.py:110-114: mask = argmax(p) (ties -> 0) added as int8 into the canvas window at (y0,x0) of a

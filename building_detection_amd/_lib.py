@@ -28,6 +28,8 @@ SG_WARP_NEAREST, SG_WARP_REFLECT, SG_WARP_COLOR = 1, 2, 4
 SG_WARP_NOISE_STREAM, SG_WARP_NOISE_KEY = 0x6E6F6973, 0x77617270
 SG_SCENE_MAX_ITEMS = 64
 SG_SYM_FLIP_UD, SG_SYM_FLIP_LR, SG_SYM_TRANSPOSE = 1, 2, 4
+SG_RESIZE_BILINEAR, SG_RESIZE_NEAREST = 0, 1
+SG_RESIZE_MAX_EXTENT = 16384   # sg_resize_*, sg_prob_resize_accumulate: every extent
 SG_OPT_ADAM, SG_OPT_SGD = 0, 1
 SG_OPT_AMSGRAD, SG_OPT_NESTEROV, SG_OPT_EMA = 1, 2, 4
 SG_OPT_CLIP_NONE, SG_OPT_CLIP_VALUE, SG_OPT_CLIP_NORM, SG_OPT_CLIP_GLOBAL = 0, 1, 2, 3
@@ -388,6 +390,8 @@ _SIGNATURES = {
     "sg_upsample_nearest_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i]),
     "sg_upsample_bilinear_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i]),
     "sg_upsample_bilinear_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i]),
+    "sg_resize_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i]),
+    "sg_resize_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i]),
     "sg_loss_ws_bytes": (_sz, [_vp, _i64]),
     "sg_loss_fwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _sz]),
     "sg_loss_bwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _f]),
@@ -421,6 +425,7 @@ _SIGNATURES = {
     "sg_scene_tiles_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
     "sg_prob_accumulate": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i]),
     "sg_prob_finalize": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
+    "sg_prob_resize_accumulate": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _i, _i]),
     "sg_vote_ge": (_i, [_vp, _vp, _i, _pp, _i64, _i, _vp]),
     "sg_mask_objects_ws_bytes": (_sz, [_i, _i]),
     "sg_mask_objects": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp]),

@@ -1,10 +1,12 @@
 // HBM-bound kernels that change a map's resolution (NHWC, channels innermost so every access is a coalesced run of 16-byte
-// channel chunks): max pooling (plain and with recorded cells), average pooling, nearest and bilinear up-sampling.  Each
+// channel chunks): max pooling (plain and with recorded cells), average pooling, nearest and bilinear up-sampling by an
+// integer factor, and the resize between arbitrary sizes (bilinear or nearest, up or down).  Each
 // is a small op under one of two skeletons: pixel_kernel (one work item = one pixel x V channels) or window_kernel (one
 // workgroup = one dx pixel of a large-factor up-sampling gradient).
 #include <limits.h>
 #include <type_traits>
 #include "sg_reduce.h"
+#include "resize_coords.h"
 
 namespace {
 
@@ -507,7 +509,125 @@ struct BilinearBwd {
   }
 };
 
+// ---------------------------------------------------------------------------------------- arbitrary-size resize
+// sg_resize_fwd / _bwd: any (H, W) -> (OH, OW) with extents up to RS_MAX_EXTENT, by the integer arithmetic of resize_coords.h.
+// The per-column (lo, hi, f) of a row depend on neither the row nor the channel, but a table of them would be OW entries of
+// eight bytes (up to 128 KB: more than a workgroup's LDS at the largest extent, and a second launch if it lived in a
+// workspace), while recomputing them is one multiply-high division by a host-prepared FastDiv and one float division per axis
+// per work item, hidden under the four loads.  So the taps are recomputed.  num + den > 0 (num >= n - m > -2m), which makes the
+// floor an unsigned division: fl = (num + den) / den - 1.
+struct ResizeAxis {
+  int n, m;          // input and output extent
+  FastDiv fd_2m;     // forward: fl and the nearest source of an output index
+  FastDiv fd_2n;     // backward: first() of an input index
+  __device__ __forceinline__ RsTap taps(int o) const {
+    return rs_taps_from_fl(o, n, m, (int)fd_div((uint32_t)((2 * o + 1) * n + m), fd_2m) - 1);
+  }
+  __device__ __forceinline__ int nearest(int o) const { return min((int)fd_div((uint32_t)((2 * o + 1) * n), fd_2m), n - 1); }
+  __device__ __forceinline__ int first(int k) const { return rs_clamp_first((int)fd_div((uint32_t)rs_first_num(k, n, m), fd_2n), m); }
+  __device__ __forceinline__ int nfirst(int i) const { return rs_clamp_first((int)fd_div((uint32_t)rs_nfirst_num(i, n, m), fd_2n), m); }
+  // outputs [o0, o1) that can reach input i
+  template <int METHOD>
+  __device__ __forceinline__ void span(int i, int& o0, int& o1) const {
+    if (METHOD == SG_RESIZE_NEAREST) {
+      o0 = nfirst(i);
+      o1 = nfirst(i + 1);
+    } else {
+      rs_span_from_first(i, n, m, i == 0 ? 0 : first(i - 1), i == n - 1 ? m : first(i + 1), o0, o1);
+    }
+  }
+};
+
+inline ResizeAxis resize_axis(int n, int m) {
+  return ResizeAxis{n, m, make_fastdiv((uint32_t)(2 * m)), make_fastdiv((uint32_t)(2 * n))};
+}
+
+// One work item = one output pixel x V channels.  Bilinear: BilinearFwd's four loads and three fmaf, columns first, then rows.
+template <typename T, int METHOD>
+struct ResizeFwd {
+  const T* __restrict__ x;
+  T* __restrict__ y;
+  int C, y_ld;
+  ResizeAxis ah, aw;
+  template <int V>
+  __device__ __forceinline__ void apply(uint32_t pix, uint32_t n, uint32_t oh, uint32_t ow, int c) const {
+    const int H = ah.n, W = aw.n;
+    float o[V];
+    if (METHOD == SG_RESIZE_NEAREST) {
+      ldv<V>(x + (((int64_t)n * H + ah.nearest((int)oh)) * W + aw.nearest((int)ow)) * C + c, o);
+    } else {
+      const RsTap th = ah.taps((int)oh), tw = aw.taps((int)ow);
+      const float fy = rs_frac(th), fx = rs_frac(tw);
+      const T* r0 = x + ((int64_t)n * H + th.lo) * W * C + c;
+      const T* r1 = x + ((int64_t)n * H + th.hi) * W * C + c;
+      float tl[V], tr[V], bl[V], br[V];
+      ldv<V>(r0 + (int64_t)tw.lo * C, tl);
+      ldv<V>(r0 + (int64_t)tw.hi * C, tr);
+      ldv<V>(r1 + (int64_t)tw.lo * C, bl);
+      ldv<V>(r1 + (int64_t)tw.hi * C, br);
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        const float top = fmaf(tr[k] - tl[k], fx, tl[k]), bot = fmaf(br[k] - bl[k], fx, bl[k]);
+        o[k] = fmaf(bot - top, fy, top);
+      }
+    }
+    stv<V>(y + (int64_t)pix * y_ld + c, o);
+  }
+};
+
+// The transpose as a gather: one work item = one dx pixel x V channels walks the outputs of its span, rows outer, columns
+// inner, ascending (no atomics; the same bits in every run and for every batch slice).  An empty span (down-sampling) leaves
+// dx = 0, or dx as it is under `accumulate`.
+template <typename T, int METHOD>
+struct ResizeBwd {
+  const T* __restrict__ dy;
+  T* __restrict__ dx;
+  int C, dy_ld, accumulate;
+  ResizeAxis ah, aw;
+  template <int V>
+  __device__ __forceinline__ void apply(uint32_t pix, uint32_t n, uint32_t ih, uint32_t iw, int c) const {
+    const int OH = ah.m, OW = aw.m;
+    int a0, a1, b0, b1;
+    ah.template span<METHOD>((int)ih, a0, a1);
+    aw.template span<METHOD>((int)iw, b0, b1);
+    T* out = dx + (int64_t)pix * C + c;
+    if ((a0 >= a1 || b0 >= b1) && accumulate) return;
+    float acc[V] = {};
+    for (int a = a0; a < a1; ++a) {
+      const float wy = METHOD == SG_RESIZE_NEAREST ? 1.f : rs_weight(ah.taps(a), (int)ih);
+      const T* rowp = dy + ((int64_t)n * OH + a) * OW * dy_ld + c;
+      for (int b = b0; b < b1; ++b) {
+        float g[V];
+        ldv<V>(rowp + (int64_t)b * dy_ld, g);
+        if (METHOD == SG_RESIZE_NEAREST) {
+#pragma unroll
+          for (int k = 0; k < V; ++k) acc[k] += g[k];
+        } else {
+          const float wgt = wy * rs_weight(aw.taps(b), (int)iw);
+#pragma unroll
+          for (int k = 0; k < V; ++k) acc[k] = fmaf(g[k], wgt, acc[k]);
+        }
+      }
+    }
+    store_grad<V>(out, acc, accumulate);
+  }
+};
+
 // ------------------------------------------------------------------------------------------------- host checks
+// the two sg_resize_* entry points: extents, the wide tensor's pixel stride ld (0 means C), both element counts, the method
+int resize_check(const char* who, bool args_ok, int method, int N, int H, int W, int C, int OH, int OW, const char* ld_name, int& ld) {
+  SG_CHECK_ARG(args_ok, "%s: null argument", who);
+  SG_CHECK_ARG(method == SG_RESIZE_BILINEAR || method == SG_RESIZE_NEAREST, "%s: method %d", who, method);
+  SG_CHECK_ARG(N > 0 && C > 0, "%s: N = %d, C = %d", who, N, C);
+  SG_CHECK_ARG(H >= 1 && H <= RS_MAX_EXTENT && W >= 1 && W <= RS_MAX_EXTENT && OH >= 1 && OH <= RS_MAX_EXTENT && OW >= 1 &&
+                   OW <= RS_MAX_EXTENT,
+               "%s: %d x %d -> %d x %d: an extent outside [1, %d]", who, H, W, OH, OW, RS_MAX_EXTENT);
+  if (ld == 0) ld = C;
+  SG_CHECK_ARG(ld >= C, "%s: %s < C", who, ld_name);
+  SG_CHECK_ARG((int64_t)N * H * W * C < (1ll << 31) && (int64_t)N * OH * OW * ld < (1ll << 31), "%s: tensor exceeds 2^31 elements", who);
+  return 0;
+}
+
 // the four sg_maxpool_* entry points (kmax: the index forms keep the cell in one byte)
 int maxpool_check(const char* who, bool args_ok, int N, const PoolGeom& g, int kmax) {
   SG_CHECK_ARG(args_ok, "%s: bad argument", who);
@@ -674,6 +794,38 @@ int sg_upsample_bilinear_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H,
     const BilinearBwd<T> op = {(const T*)dy, (T*)dx, H, W, C, sh, sw, dy_ld, accumulate};
     if (window_ok(vec, N, H, W, sh, sw)) return launch_window(op, N, H, W, C, lds, (hipStream_t)stream, "upsample_bilinear_bwd_window");
     return launch_pixels(op, N, H, W, C, vec, lds, (hipStream_t)stream, "upsample_bilinear_bwd");
+  });
+  return 0;
+}
+
+int sg_resize_fwd(sg_ctx* ctx, void* stream, int dtype, int method, int N, int H, int W, int C, int OH, int OW, const void* x,
+                  void* y, int y_ld) {
+  if (int rc = resize_check("sg_resize_fwd", ctx && x && y, method, N, H, W, C, OH, OW, "y_ld", y_ld)) return rc;
+  const bool vec = (C % 4 == 0) && (y_ld % 4 == 0) && sg_aligned16(x) && sg_aligned16(y);
+  const ResizeAxis ah = resize_axis(H, OH), aw = resize_axis(W, OW);
+  SG_DTYPE_SWITCH(dtype, "sg_resize_fwd", {
+    if (method == SG_RESIZE_NEAREST) {
+      const ResizeFwd<T, SG_RESIZE_NEAREST> op = {(const T*)x, (T*)y, C, y_ld, ah, aw};
+      return launch_pixels(op, N, OH, OW, C, vec, 0, (hipStream_t)stream, "resize_nearest_fwd");
+    }
+    const ResizeFwd<T, SG_RESIZE_BILINEAR> op = {(const T*)x, (T*)y, C, y_ld, ah, aw};
+    return launch_pixels(op, N, OH, OW, C, vec, 0, (hipStream_t)stream, "resize_bilinear_fwd");
+  });
+  return 0;
+}
+
+int sg_resize_bwd(sg_ctx* ctx, void* stream, int dtype, int method, int N, int H, int W, int C, int OH, int OW, const void* dy,
+                  int dy_ld, void* dx, int accumulate) {
+  if (int rc = resize_check("sg_resize_bwd", ctx && dy && dx, method, N, H, W, C, OH, OW, "dy_ld", dy_ld)) return rc;
+  const bool vec = (C % 4 == 0) && (dy_ld % 4 == 0) && sg_aligned16(dy) && sg_aligned16(dx);
+  const ResizeAxis ah = resize_axis(H, OH), aw = resize_axis(W, OW);
+  SG_DTYPE_SWITCH(dtype, "sg_resize_bwd", {
+    if (method == SG_RESIZE_NEAREST) {
+      const ResizeBwd<T, SG_RESIZE_NEAREST> op = {(const T*)dy, (T*)dx, C, dy_ld, accumulate, ah, aw};
+      return launch_pixels(op, N, H, W, C, vec, 0, (hipStream_t)stream, "resize_nearest_bwd");
+    }
+    const ResizeBwd<T, SG_RESIZE_BILINEAR> op = {(const T*)dy, (T*)dx, C, dy_ld, accumulate, ah, aw};
+    return launch_pixels(op, N, H, W, C, vec, 0, (hipStream_t)stream, "resize_bilinear_bwd");
   });
   return 0;
 }

@@ -6,6 +6,7 @@
 // of a T x T tile, (a, b) = transpose ? (c, r) : (r, c), u = flip_ud ? T-1-a : a, v = flip_lr ? T-1-b : b, and the tile
 // element corresponds to scene / canvas pixel (y0+u, x0+v).  A window is the T x T square at (y0, x0) under every symmetry.
 #include "sg_common.h"
+#include "resize_coords.h"
 
 namespace {
 
@@ -159,6 +160,38 @@ __global__ __launch_bounds__(256) void prob_finalize_kernel(const float* acc, co
   }
 }
 
+// One thread per base canvas element (y, x, k): blockIdx.y is the canvas row (CH <= 16384), the x grid covers the row's CW * C
+// floats.  The bilinear taps of resize_coords.h from the scaled canvases (HS, WS) to the base ones (CH, CW), each tap
+// normalised by its own wsum_s before the blend (a pixel the scaled pass never reached counts as probability 0), the blend in
+// sg_resize_fwd's order, one fma into acc.  The thread of class 0 carries wsum.  Canvas offsets are 64-bit.
+__global__ __launch_bounds__(256) void prob_resize_accumulate_kernel(const float* __restrict__ acc_s, const float* __restrict__ wsum_s,
+                                                                     float* __restrict__ acc, float* __restrict__ wsum, int C, int HS,
+                                                                     int WS, int CH, int CW, float weight, FastDiv dC, FastDiv d2h,
+                                                                     FastDiv d2w) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= (uint32_t)CW * (uint32_t)C) return;   // < 16384 * 32
+  const int y = (int)blockIdx.y;
+  uint32_t x, k;
+  fd_divmod(j, dC, x, k);
+  const RsTap th = rs_taps_from_fl(y, HS, CH, (int)fd_div((uint32_t)((2 * y + 1) * HS + CH), d2h) - 1);
+  const RsTap tw = rs_taps_from_fl((int)x, WS, CW, (int)fd_div((uint32_t)((2 * (int)x + 1) * WS + CW), d2w) - 1);
+  const float fy = rs_frac(th), fx = rs_frac(tw);
+  float q[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int64_t sp = (int64_t)(a ? th.hi : th.lo) * WS + (b ? tw.hi : tw.lo);
+      const float ws = wsum_s[sp];
+      q[a][b] = ws > 0.f ? __fdiv_rn(acc_s[sp * C + k], ws) : 0.f;
+    }
+  const float top = fmaf(q[0][1] - q[0][0], fx, q[0][0]), bot = fmaf(q[1][1] - q[1][0], fx, q[1][0]);
+  const float v = fmaf(bot - top, fy, top);
+  const int64_t pix = (int64_t)y * CW + x;
+  acc[pix * C + k] = fmaf(weight, v, acc[pix * C + k]);
+  if (k == 0) wsum[pix] = __fadd_rn(wsum[pix], weight);
+}
+
 // the checks both table-taking entry points share; fills `tab`
 inline int scene_table(const char* who, int N, const sg_scene_item* items, SceneTable& tab) {
   SG_CHECK_ARG(N >= 1 && N <= SG_SCENE_MAX_ITEMS, "%s: N = %d outside [1, %d]", who, N, SG_SCENE_MAX_ITEMS);
@@ -234,6 +267,23 @@ int sg_prob_finalize(sg_ctx* ctx, void* stream, int C, const void* acc_f32, cons
   hipLaunchKernelGGL(prob_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)acc_f32,
                      (const float*)wsum_f32, (float*)probs_out_f32, (unsigned char*)map_u8, npix, C, out_scale);
   SG_LAUNCH_CHECK("prob_finalize_kernel");
+  return 0;
+}
+
+int sg_prob_resize_accumulate(sg_ctx* ctx, void* stream, int C, const void* acc_s_f32, const void* wsum_s_f32, int HS, int WS,
+                              float weight, void* acc_f32, void* wsum_f32, int CH, int CW) {
+  SG_CHECK_ARG(ctx && acc_s_f32 && wsum_s_f32 && acc_f32 && wsum_f32, "sg_prob_resize_accumulate: null argument");
+  SG_CHECK_ARG(C >= 2 && C <= SG_MAX_CLASSES, "sg_prob_resize_accumulate: C = %d outside [2, %d]", C, SG_MAX_CLASSES);
+  SG_CHECK_ARG(HS >= 1 && HS <= RS_MAX_EXTENT && WS >= 1 && WS <= RS_MAX_EXTENT && CH >= 1 && CH <= RS_MAX_EXTENT && CW >= 1 &&
+                   CW <= RS_MAX_EXTENT,
+               "sg_prob_resize_accumulate: %d x %d -> %d x %d: an extent outside [1, %d]", HS, WS, CH, CW, RS_MAX_EXTENT);
+  SG_CHECK_ARG(weight > 0.f && weight <= 3.402823466e38f, "sg_prob_resize_accumulate: weight %g is not positive and finite",
+               (double)weight);
+  const dim3 grid((unsigned)sg_cdiv((int64_t)CW * C, 256), (unsigned)CH);
+  hipLaunchKernelGGL(prob_resize_accumulate_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float*)acc_s_f32,
+                     (const float*)wsum_s_f32, (float*)acc_f32, (float*)wsum_f32, C, HS, WS, CH, CW, weight,
+                     make_fastdiv((uint32_t)C), make_fastdiv((uint32_t)(2 * CH)), make_fastdiv((uint32_t)(2 * CW)));
+  SG_LAUNCH_CHECK("prob_resize_accumulate_kernel");
   return 0;
 }
 

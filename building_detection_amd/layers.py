@@ -947,6 +947,47 @@ class UpSampling2D(Layer):
         return _UpNode(self._name, self.size, self.interpolation).build(x)
 
 
+class _ResizeNode(Node):
+    """tf.keras.layers.Resizing: the map brought to (height, width) by sg_resize_fwd, up or down; no fusion rule reads it, so
+    like _UpNode it ends every chain it stands in."""
+    op = "resizing"
+
+    def __init__(self, name, height, width, interpolation="bilinear"):
+        super().__init__(name)
+        self.height, self.width, self.interpolation = height, width, interpolation
+
+    def build(self, x):
+        if len(x.shape) != 4:
+            raise ValueError(f"Resizing: expected a [N,H,W,C] input, got {tuple(x.shape)}")
+        return self.connect([x], (None, self.height, self.width, x.shape[3]))
+
+    def forward(self, rt, xs, training):
+        return rt.eng.resize_fwd(xs[0], self.height, self.width, self.interpolation)
+
+    def backward(self, rt, xs, y, dy):
+        return [rt.eng.resize_bwd(dy, tuple(xs[0].shape), self.interpolation)]
+
+
+class Resizing(Layer):
+    """tf.keras.layers.Resizing(height, width, interpolation): tf.image.resize without antialiasing, half-pixel centres, to
+    any size (include/segengine.h, sg_resize_fwd).  'bilinear' and 'nearest' only; no cropping."""
+
+    def __init__(self, height, width, interpolation="bilinear", crop_to_aspect_ratio=False, name=None, **kw):
+        super().__init__(name)
+        if crop_to_aspect_ratio:
+            raise ValueError("Resizing: crop_to_aspect_ratio=True is not supported")
+        if interpolation not in ("bilinear", "nearest"):
+            raise ValueError(f"Resizing: interpolation {interpolation!r} is not supported (use 'bilinear' or 'nearest')")
+        self.height, self.width = int(height), int(width)
+        if not (1 <= self.height <= 16384 and 1 <= self.width <= 16384):
+            raise ValueError(f"Resizing: height {height} / width {width} outside [1, 16384]")
+        self.interpolation = interpolation
+
+    def __call__(self, x):
+        self._once()
+        return _ResizeNode(self._name, self.height, self.width, self.interpolation).build(x)
+
+
 # ====================================================================================== structural nodes
 class _ReshapeNode(Node):
     op = "reshape"

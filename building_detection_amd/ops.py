@@ -947,6 +947,39 @@ class Engine:
                                                 int(accumulate)), "sg_upsample_bilinear_bwd")
         return dx
 
+    @staticmethod
+    def _resize_method(method):
+        try:
+            return {"bilinear": _lib.SG_RESIZE_BILINEAR, "nearest": _lib.SG_RESIZE_NEAREST}[method]
+        except (KeyError, TypeError):
+            raise ValueError(f"method={method!r}: 'bilinear' or 'nearest'") from None
+
+    def resize_fwd(self, x, oh, ow, method="bilinear", out=None, out_ld=0):
+        """tf.image.resize(x, (oh, ow), method, antialias=False) of [N,H,W,C] between arbitrary sizes, up or down (half-pixel
+        centres; sg_resize_fwd).  out / out_ld as upsample_fwd."""
+        m = self._resize_method(method)
+        n, h, w, c = x.shape
+        oh, ow = int(oh), int(ow)
+        y = out if out is not None else self.empty(n, oh, ow, c, dtype=x.dtype)
+        check(self.lib.sg_resize_fwd(self.h, self.stream, _dt(x), m, n, h, w, c, oh, ow, _ptr(x), _ptr(y), out_ld), "sg_resize_fwd")
+        return y
+
+    def resize_bwd(self, dy, x_shape, method="bilinear", accumulate_into=None, dy_ld=0, out=None):
+        """The gradient of resize_fwd with respect to x of shape x_shape = (N,H,W,C): a new tensor (or `out`, overwritten), or
+        added into `accumulate_into` (which is returned)."""
+        m = self._resize_method(method)
+        n, h, w, c = (int(v) for v in x_shape)
+        oh, ow = int(dy.shape[1]), int(dy.shape[2])
+        if accumulate_into is not None and (tuple(accumulate_into.shape) != (n, h, w, c) or accumulate_into.dtype != dy.dtype):
+            raise _lib.SgError(f"accumulate_into {tuple(accumulate_into.shape)} {accumulate_into.dtype} is not x's "
+                               f"{(n, h, w, c)} {dy.dtype}")
+        if accumulate_into is not None and out is not None:
+            raise _lib.SgError("resize_bwd: accumulate_into and out exclude each other")
+        dx = accumulate_into if accumulate_into is not None else (out if out is not None else self.empty(n, h, w, c, dtype=dy.dtype))
+        check(self.lib.sg_resize_bwd(self.h, self.stream, _dt(dy), m, n, h, w, c, oh, ow, _ptr(dy), dy_ld, _ptr(dx),
+                                     int(accumulate_into is not None)), "sg_resize_bwd")
+        return dx
+
     # ------------------------------------------------------------------------------ loss / metrics / Adam
     def loss_fwd(self, kind, p, y_true):
         _chk32(p, "p"); _chk32(y_true, "y_true")
@@ -1325,6 +1358,21 @@ class Engine:
         check(self.lib.sg_prob_finalize(self.h, self.stream, c, _ptr(acc), _ptr(wsum), ch, cw, _ptr(probs_out), int(out_scale),
                                         _ptr(out)), "sg_prob_finalize")
         return out
+
+    def prob_resize_accumulate(self, acc_s, wsum_s, acc, wsum, weight=1.0):
+        """sg_prob_resize_accumulate: folds the canvases acc_s [HS,WS,C] / wsum_s [HS,WS] of a scene stitched at another scale
+        into the base canvases acc [CH,CW,C] / wsum [CH,CW]: acc += weight * resize(acc_s / wsum_s), wsum += weight, with the
+        bilinear taps of resize_fwd and every tap normalised before the blend."""
+        for t, name in ((acc_s, "acc_s"), (wsum_s, "wsum_s"), (acc, "acc"), (wsum, "wsum")):
+            _chk32(t, name)
+        if (acc_s.dim() != 3 or acc.dim() != 3 or acc_s.shape[2] != acc.shape[2] or tuple(wsum_s.shape) != tuple(acc_s.shape[:2])
+                or tuple(wsum.shape) != tuple(acc.shape[:2])):
+            raise _lib.SgError(f"acc_s {tuple(acc_s.shape)} / wsum_s {tuple(wsum_s.shape)} / acc {tuple(acc.shape)} / wsum "
+                               f"{tuple(wsum.shape)}: expected [HS,WS,C], [HS,WS], [CH,CW,C], [CH,CW]")
+        hs, ws, c = acc_s.shape
+        ch, cw = acc.shape[:2]
+        check(self.lib.sg_prob_resize_accumulate(self.h, self.stream, c, _ptr(acc_s), _ptr(wsum_s), hs, ws, float(weight), _ptr(acc),
+                                                 _ptr(wsum), ch, cw), "sg_prob_resize_accumulate")
 
     def vote_ge(self, masks: Sequence[torch.Tensor], k: int):
         arr = (C.c_void_p * len(masks))(*[m.data_ptr() for m in masks])

@@ -142,6 +142,32 @@ def tta_symmetries(tta) -> List[int]:
     return syms
 
 
+SCALE_RANGE = (0.25, 4.0)      # of a multi-scale pass
+SCENE_MAX_EXTENT = 16384       # ... and its limit on every scene and scaled-scene axis (sg_prob_resize_accumulate)
+
+
+def check_scales(scales):
+    """The scales of a multi-scale pass as floats: a non-empty sequence of finite values in SCALE_RANGE."""
+    try:
+        out = [float(s) for s in scales]
+    except TypeError:
+        raise ValueError(f"scales={scales!r}: a sequence of floats in {list(SCALE_RANGE)}") from None
+    if not out or any(not (SCALE_RANGE[0] <= s <= SCALE_RANGE[1]) for s in out):   # also refuses NaN
+        raise ValueError(f"scales={scales!r}: a non-empty sequence of floats in {list(SCALE_RANGE)}")
+    return out
+
+
+def scaled_size(h: int, w: int, s: float):
+    """(hs, ws) of an h x w scene at scale s: max(1, floor(d * s + 1/2)) per axis.  ValueError beyond the limits of the resize
+    (one image below 2^31 bytes) and of the fold (every extent at most SCENE_MAX_EXTENT)."""
+    hs, ws = (max(1, int(math.floor(d * float(s) + 0.5))) for d in (h, w))
+    if max(h, w, hs, ws) > SCENE_MAX_EXTENT:
+        raise ValueError(f"scene {h} x {w} at scale {s} = {hs} x {ws}: an extent above the multi-scale limit {SCENE_MAX_EXTENT}")
+    if max(h * w, hs * ws) * 3 >= 2 ** 31:
+        raise ValueError(f"scene {h} x {w} at scale {s} = {hs} x {ws}: an image of 2^31 bytes or more (resize_linear_u8's limit)")
+    return hs, ws
+
+
 class SoftScene:
     """Probability canvases of one scene: `acc` [h,w,C] = sum of w * p and `wsum` [h,w] = sum of w on the device, filled by
     add() model by model and read by result().  The image is uploaded once as uint8; overhanging tiles are clipped by the
@@ -164,19 +190,54 @@ class SoftScene:
         self.win = torch.from_numpy(make_window(window, self.tile)).to(dev)
         self.acc = torch.zeros(self.h, self.w, self.num_classes, dtype=torch.float32, device=dev)
         self.wsum = torch.zeros(self.h, self.w, dtype=torch.float32, device=dev)
+        self._kind = None   # "plain" | "scaled": what add() has put on the canvases
+
+    @classmethod
+    def _on_device(cls, scene, like):
+        """A scene of its own canvases around a uint8 [h,w,3] device tensor, with `like`'s classes, tile, stride and window."""
+        import torch
+        self = cls.__new__(cls)
+        self.eng, self.num_classes, self.tile, self.stride, self.win = like.eng, like.num_classes, like.tile, like.stride, like.win
+        self.h, self.w = int(scene.shape[0]), int(scene.shape[1])
+        _, self.origins = scene_origins(self.h, self.w, self.tile, self.stride)
+        self.scene = scene
+        self.acc = torch.zeros(self.h, self.w, self.num_classes, dtype=torch.float32, device=scene.device)
+        self.wsum = torch.zeros(self.h, self.w, dtype=torch.float32, device=scene.device)
+        self._kind = None
+        return self
 
     def work_list(self, tta=1):
         """[(y0, x0, sym), ...]: origins-major, then symmetries."""
         syms = tta_symmetries(tta)
         return [(i, j, s) for i, j in self.origins for s in syms]
 
-    def add(self, model, tta=1, weight: float = 1.0, batch: int = 8):
+    def add(self, model, tta=1, weight: float = 1.0, batch: int = 8, scale=None):
+        """Adds one model's pass over the scene.  scale=None: its windowed tile probabilities go straight onto the canvases.
+        scale=s (SCALE_RANGE, 1.0 included): the pass runs on the scene resized to scaled_size(h, w, s), is stitched on canvases
+        of that size, and enters as a normalised probability map under `weight` (sg_prob_resize_accumulate); a scene takes
+        passes of one kind only, since raw window sums and normalised maps must not meet on one canvas."""
         import torch
         shape = tuple(model.inputs[0].shape[1:])
         if shape != (self.tile, self.tile, 3):
             raise ValueError(f"model input {shape} is not the scene's tile {(self.tile, self.tile, 3)}")
         if model.num_classes != self.num_classes:
             raise ValueError(f"model has {model.num_classes} classes, the scene {self.num_classes}")
+        kind = "plain" if scale is None else "scaled"
+        if self._kind not in (None, kind):
+            raise ValueError(f"SoftScene.add: a {kind} pass on a scene that holds {self._kind} passes (give every pass a scale, "
+                             "1.0 included, or none)")
+        if scale is not None:
+            s = check_scales([scale])[0]
+            weight = float(weight)
+            if not (weight > 0 and math.isfinite(weight)):
+                raise ValueError(f"SoftScene.add: weight {weight} is not positive and finite")
+            hs, ws = scaled_size(self.h, self.w, s)
+            sub = SoftScene._on_device(self.eng.resize_linear_u8(self.scene[None], hs, ws)[0], self)
+            sub.add(model, tta=tta, weight=1.0, batch=batch)
+            self.eng.prob_resize_accumulate(sub.acc, sub.wsum, self.acc, self.wsum, weight)
+            self._kind = kind
+            return self
+        self._kind = kind
         eng = self.eng
         work = self.work_list(tta)
         for s in range(0, len(work), batch):
@@ -197,9 +258,13 @@ class SoftScene:
 
 
 def detection_soft(img, user_path=None, models=None, save_name="model", batch: int = 8, tta=1, window="flat", weights=None,
-                   tile=None, stride=None, return_probs: bool = False):
+                   tile=None, stride=None, return_probs: bool = False, scales=None, scale_weights=None):
     """Soft counterpart of detection(): `models` is one model or a sequence (the soft ensemble: the mean of the models'
     probabilities under `weights`, default all 1).  tile defaults to the model's input height; stride to 360 at tile 512.
+    scales (a sequence of floats in SCALE_RANGE, e.g. (0.75, 1.0, 1.25)) adds the scale axis: every (model, scale) pass runs
+    on the scene resized by cv.resize's INTER_LINEAR (Engine.resize_linear_u8), is stitched at its own size with the same
+    tile, stride, window and tta, and enters as a normalised probability map under weight_model * weight_scale
+    (scale_weights, default all 1), so the result is sum(w P) / sum(w); scales=None is the single-scale path.
     Returns the uint8 array (and the probabilities with return_probs); writes `<user_path>/<save_name>.png` when given."""
     models = list(models) if isinstance(models, (list, tuple)) else [models]
     if not models or models[0] is None:
@@ -207,6 +272,18 @@ def detection_soft(img, user_path=None, models=None, save_name="model", batch: i
     weights = [1.0] * len(models) if weights is None else [float(v) for v in weights]
     if len(weights) != len(models):
         raise ValueError(f"{len(weights)} weights for {len(models)} models")
+    if scales is None:
+        if scale_weights is not None:
+            raise ValueError("scale_weights without scales")
+        passes = [(None, 1.0)]
+    else:
+        scales = check_scales(scales)
+        scale_weights = [1.0] * len(scales) if scale_weights is None else [float(v) for v in scale_weights]
+        if len(scale_weights) != len(scales):
+            raise ValueError(f"{len(scale_weights)} scale_weights for {len(scales)} scales")
+        if any(not (v > 0 and math.isfinite(v)) for v in scale_weights):
+            raise ValueError(f"scale_weights={scale_weights!r}: positive and finite values")
+        passes = list(zip(scales, scale_weights))
     tile = int(models[0].inputs[0].shape[1]) if tile is None else int(tile)
     if stride is None:
         if tile != TILE:
@@ -214,7 +291,8 @@ def detection_soft(img, user_path=None, models=None, save_name="model", batch: i
         stride = STRIDE
     scene = SoftScene(img, models[0].num_classes, tile, stride, window, engine=models[0]._runtime().eng)
     for m, wt in zip(models, weights):
-        scene.add(m, tta=tta, weight=wt, batch=batch)
+        for sc, swt in passes:
+            scene.add(m, tta=tta, weight=wt * swt, batch=batch, scale=sc)
     res = scene.result(return_probs)
     if user_path is not None:
         from PIL import Image

@@ -155,7 +155,8 @@ def reshape(t, shape, name=None):
 
 def _image_resize(images, size, method="bilinear", name=None, **kw):
     """tf.image.resize on a symbolic [N,H,W,C] tensor, for sizes that are the same integer multiple of the input's height
-    and width (the case UpSampling2D covers): it becomes that layer's node.  Other sizes have no kernel here."""
+    and width (the case UpSampling2D covers): it becomes that layer's node.  Other sizes are refused here; the arbitrary-size
+    surface, up or down, is the layer tf.keras.layers.Resizing(height, width, interpolation) (layers.Resizing)."""
     x = _r(images)
     if method not in ("bilinear", "nearest"):
         raise ValueError(f"tf.image.resize: method {method!r} is not supported (use 'bilinear' or 'nearest')")
@@ -303,7 +304,7 @@ _layer_names = dict(
     Activation=_Activation, ReLU=_wrap(L.ReLU), Softmax=_Softmax, MaxPooling2D=_wrap(L.MaxPooling2D),
     MaxPool2D=_wrap(L.MaxPooling2D), AveragePooling2D=_wrap(L.AveragePooling2D),
     GlobalAveragePooling2D=_wrap(L.GlobalAveragePooling2D), GlobalAvgPool2D=_wrap(L.GlobalAveragePooling2D),
-    UpSampling2D=_wrap(L.UpSampling2D), Dropout=_wrap(L.Dropout), SpatialDropout2D=_wrap(L.SpatialDropout2D), Reshape=_wrap(L.Reshape), RepeatVector=_RepeatVector, Cropping2D=_Cropping2D,
+    UpSampling2D=_wrap(L.UpSampling2D), Resizing=_wrap(L.Resizing), Dropout=_wrap(L.Dropout), SpatialDropout2D=_wrap(L.SpatialDropout2D), Reshape=_wrap(L.Reshape), RepeatVector=_RepeatVector, Cropping2D=_Cropping2D,
     Add=_AddLayer, add=_layers_add, Multiply=_MultiplyLayer, multiply=_layers_multiply,
     Concatenate=_ConcatLayer, concatenate=lambda xs, axis=-1, name=None: _concat(list(xs), axis, name))
 

@@ -666,6 +666,28 @@ int sg_upsample_bilinear_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int H,
                              int sw, const void* x, void* y, int y_ld);
 int sg_upsample_bilinear_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int H, int W, int C, int sh,
                              int sw, const void* dy, int dy_ld, void* dx, int accumulate);
+/* tf.keras.layers.Resizing / tf.image.resize(antialias=False) between arbitrary sizes, up or down: x[N,H,W,C] ->
+ * y[N,OH,OW,C], each axis on its own and all coordinates in integers (csrc/resize_coords.h).  For output index o, input
+ * extent n and output extent m:
+ *   num = (2o + 1) n - m     den = 2m     fl = floor(num / den)     r = num - fl den           (0 <= r < den)
+ *   SG_RESIZE_BILINEAR:  lo = max(fl, 0)    hi = min(max(fl + (r != 0), 0), n - 1)    f = (float)r / (float)den
+ *                        y = x[lo] + (x[hi] - x[lo]) * f         (columns first, then rows; arithmetic in fp32)
+ *   SG_RESIZE_NEAREST:   y = x[min(floor((2o + 1) n / (2m)), n - 1)]
+ * i.e. half-pixel centres, in = (o + 1/2) n / m - 1/2, the rule of the integer-factor pair above with 1/s replaced by n/m;
+ * m == n is the identity, bit for bit.  y_ld / dy_ld: pixel stride of the OH x OW tensor, 0 = C; accumulate != 0 adds into dx.
+ * The backward is the transpose as a gather.  With first(k) = clamp(ceil(((2k + 1) m - n) / (2n)), 0, m), dx[i] sums
+ * ((lo(o) == i ? 1 - f : 0) + (hi(o) == i ? f : 0)) dy[o] over o in [i == 0 ? 0 : first(i - 1), i == n - 1 ? m - 1 :
+ * first(i + 1) - 1], at most floor(2m / n) + 1 outputs per axis and possibly none when down-sampling (dx[i] = 0 then, or
+ * untouched under accumulate); nearest sums dy[o] over the contiguous run of o whose source is i.  Rows outer, columns inner,
+ * ascending: no atomics, bit-identical from run to run and for every batch slice.
+ * Checked on the host before any launch (SG_EINVAL, nothing written): H, W, OH, OW in [1, 16384]; N, C > 0; N*H*W*C and
+ * N*OH*OW*ld < 2^31; ld >= C; non-null pointers; a known method and dtype (SG_F32, SG_BF16). */
+#define SG_RESIZE_BILINEAR 0
+#define SG_RESIZE_NEAREST  1
+int sg_resize_fwd(sg_ctx* ctx, void* stream, int dtype, int method, int N, int H, int W, int C, int OH, int OW,
+                  const void* x, void* y, int y_ld);
+int sg_resize_bwd(sg_ctx* ctx, void* stream, int dtype, int method, int N, int H, int W, int C, int OH, int OW,
+                  const void* dy, int dy_ld, void* dx, int accumulate);
 
 /* -------------------------------------------------------------------------------- loss / metrics / Adam
  * The three losses of train_model/DeepLabv3plus.py:490-527 on softmax probabilities p[rows,2] and
@@ -1034,7 +1056,16 @@ int sg_argmax_max_u8(sg_ctx* ctx, void* stream, const void* p, int C, int TH, in
  *                       the canvases are indexed in 64 bits.
  *   sg_prob_finalize    map_u8[CH,CW] = out_scale * argmax_k acc[y,x,k] (ties -> lowest index; out_scale >= 1 and
  *                       out_scale * (C-1) <= 255), probs_out_f32[CH,CW,C] = acc / wsum when given (may be acc itself);
- *                       where wsum == 0 both are 0. */
+ *                       where wsum == 0 both are 0.
+ *   sg_prob_resize_accumulate  folds a scene stitched at another scale, acc_s_f32[HS,WS,C] / wsum_s_f32[HS,WS], into the base
+ *                       canvases acc_f32[CH,CW,C] / wsum_f32[CH,CW] as a normalised probability map: for canvas pixel (y, x)
+ *                       the SG_RESIZE_BILINEAR taps of sg_resize_fwd from (HS, WS) to (CH, CW) are taken, each tap is
+ *                       normalised first, q = wsum_s > 0 ? acc_s[.., k] / wsum_s : 0, the four q are blended as sg_resize_fwd
+ *                       blends (columns first, then rows), and acc[y,x,k] = fmaf(weight, blend, acc[y,x,k]); wsum[y,x] +=
+ *                       weight.  One thread owns a canvas element: no float atomics, bitwise reproducible; the canvases
+ *                       are indexed in 64 bits.  At HS == CH, WS == CW it is normalise-and-add, exactly.  2 <= C <=
+ *                       SG_MAX_CLASSES; HS, WS, CH, CW in [1, 16384]; weight positive and finite; the source and the base
+ *                       canvases must not overlap. */
 #define SG_SCENE_MAX_ITEMS 64
 #define SG_SYM_FLIP_UD   1      /* same bits as SG_AUG_FLIP_UD / _LR */
 #define SG_SYM_FLIP_LR   2
@@ -1050,6 +1081,8 @@ int sg_prob_accumulate(sg_ctx* ctx, void* stream, int C, int T, const void* p_f3
                        const void* win_f32, float scale, void* acc_f32, void* wsum_f32, int CH, int CW);
 int sg_prob_finalize(sg_ctx* ctx, void* stream, int C, const void* acc_f32, const void* wsum_f32, int CH, int CW,
                      void* probs_out_f32, int out_scale, void* map_u8);
+int sg_prob_resize_accumulate(sg_ctx* ctx, void* stream, int C, const void* acc_s_f32, const void* wsum_s_f32, int HS, int WS,
+                              float weight, void* acc_f32, void* wsum_f32, int CH, int CW);
 /* model_fuse.py:315,323: out = 255 where sum_i (masks[i] // 255) >= k else 0; masks are u8 [n]. */
 int sg_vote_ge(sg_ctx* ctx, void* stream, int nmasks, const void* const* masks, int64_t n, int k,
                void* out_u8);

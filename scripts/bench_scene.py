@@ -13,7 +13,11 @@ Per scene size it reports
     back-to-back between two device events (launch gaps included), and their shares of the soft path's time.
 Imports the engine only; needs the GPU (no time is reported without one).  One JSON line per row, then the file.
 
-    python scripts/bench_scene.py [--sizes 2048 4096] [--reps 3] [--batch 8] [--out profiles/scene_bench.json]
+With --scales it also times the tta-1 soft path over that list of scales (pipeline.detection_soft(scales=...)) against the
+single-scale time, with the passes' pixel and tile counts beside it, and the device time of the folds
+(sg_prob_resize_accumulate) and of the scene resizes (sg_resize_linear_u8).
+
+    python scripts/bench_scene.py [--sizes 2048 4096] [--reps 3] [--batch 8] [--scales 0.75 1.0 1.25] [--out profiles/scene_bench.json]
 """
 import argparse
 import json
@@ -76,6 +80,8 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[2048, 4096])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--scales", type=float, nargs="*", default=None,
+                    help="also time detection_soft(tta=1, flat) over these scales, e.g. 0.75 1.0 1.25")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -104,6 +110,31 @@ def main():
         ntiles = len(PL.scene_origins(size, size)[1])
         for k, ms in times.items():
             emit({"scene": size, "what": k, "tiles": ntiles * (8 if "tta8" in k else 1), **stats(ms)})
+        if a.scales:
+            # the scale axis: every pass on a resized scene, stitched at its size, folded in as a normalised map.  Against the
+            # single-scale soft path above times the passes' pixel count (sum of s^2), and the fold's own device time.
+            multi = lambda: PL.detection_soft(img, None, model, batch=a.batch, tta=1, window="flat", scales=a.scales)   # noqa: E731
+            multi()
+            ms = [wall(multi) for _ in range(a.reps)]
+            single = statistics.median(times["soft_tta1_flat"])
+            area = sum(s * s for s in a.scales)
+            tiles_ms = sum(len(PL.scene_origins(*PL.scaled_size(size, size, s))[1]) for s in a.scales)
+            emit({"scene": size, "what": "soft_tta1_flat, scales " + " ".join(str(s) for s in a.scales), "tiles": tiles_ms, **stats(ms),
+                  "x_single_scale": round(statistics.median(ms) / single, 3), "pixel_count_x": round(area, 4),
+                  "tiles_x": round(tiles_ms / ntiles, 3)})
+            base = PL.SoftScene(img, 2, window="flat", engine=eng)
+            fold, resize = 0.0, 0.0
+            for s in a.scales:
+                hs, ws = PL.scaled_size(size, size, s)
+                sub_acc = torch.rand(hs, ws, 2, device=eng.device)
+                sub_w = torch.rand(hs, ws, device=eng.device) + 0.5
+                fold += device_ms(lambda: eng.prob_resize_accumulate(sub_acc, sub_w, base.acc, base.wsum, 1.0))
+                resize += device_ms(lambda: eng.resize_linear_u8(base.scene[None], hs, ws))
+            emit({"scene": size, "what": "scales: sg_prob_resize_accumulate, all folds", "launches": len(a.scales),
+                  "device_ms": round(fold, 3), "share_of_path": round(fold / statistics.median(ms), 4)})
+            emit({"scene": size, "what": "scales: sg_resize_linear_u8, all scenes", "launches": len(a.scales),
+                  "device_ms": round(resize, 3), "share_of_path": round(resize / statistics.median(ms), 4)})
+            del base
         host_prep(img, a.batch, eng.device)
         prep = stats([wall(lambda: host_prep(img, a.batch, eng.device)) for _ in range(a.reps)])
         emit({"scene": size, "what": "detection: host cut + upload", **prep,

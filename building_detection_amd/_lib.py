@@ -355,6 +355,9 @@ _SIGNATURES = {
     "sg_bn_train_bwd_thin": (_i, [_vp, _vp, _i, _i64, _i, _i, _i] + [_vp] * 10 + [_i, _vp, _sz]),
     "sg_bn_infer": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i]),
     "sg_add2_bn": (_i, [_vp, _vp, _i, _i64, _i] + [_vp] * 11 + [_i, _i, _f, _i, _i]),
+    "sg_gn_ws_bytes": (_sz, [_vp, _i, _i, _i64, _i, _i]),
+    "sg_gn_fwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _i] + [_vp] * 6 + [_f, _i, _vp, _sz]),
+    "sg_gn_bwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _i] + [_vp] * 9 + [_i, _vp, _sz]),
     "sg_bn_plan": (_i, [_vp, _i, _i64, _i, _i, _i, C.POINTER(BnPlan)]),
     "sg_seg_plan": (_i, [_vp, _i, _i, _i64, _i, _i, _i, C.POINTER(SegPlan)]),
     "sg_act_fwd": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp]),

@@ -84,6 +84,7 @@ def up2_conv(nodes, outs):
 
 def absorb_relu(nodes, outs):
     """BN -> ReLU   => BN kernel applies ReLU (and masks in backward);
+    GN -> ReLU   => the same through the GroupNormalization kernels' relu flag (the only rule that looks at that layer);
     Add -> ReLU  => add_n applies ReLU;
     ReLU -> SeparableConv2D => depthwise gather applies ReLU (pre_relu).
     A ReLU is absorbed only if its output has exactly one consumer (or, for producers, it is the only
@@ -94,7 +95,7 @@ def absorb_relu(nodes, outs):
         src = n.inputs[0]
         prod = src.node
         if (prod is not None and len(src.consumers) == 1 and id(src) not in outs
-                and isinstance(prod, (L._BNNode, L._AddNode)) and not prod.relu):
+                and isinstance(prod, (L._BNNode, L._GNNode, L._AddNode)) and not prod.relu):
             prod.relu, n.fused_away = True, True
             continue
         cons = n.output.consumers

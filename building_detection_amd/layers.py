@@ -631,6 +631,102 @@ class BatchNormalization(Layer):
         return _BNNode(self._name, self.momentum, self.epsilon).build(x)
 
 
+class _GNNode(Node):
+    """GroupNormalization: statistics per image and channel group, the same function in training and inference.  Deliberately
+    not a _BNNode: the fusion rules select by isinstance, and none of BatchNormalization's applies (a bias in front of this
+    layer has a non-zero gradient, no convolution emits tile statistics for it, no consumer applies it)."""
+    op = "group_normalization"
+
+    def __init__(self, name, groups, epsilon, center, scale):
+        super().__init__(name)
+        self.groups, self.epsilon, self.center, self.scale = groups, epsilon, center, scale
+        self.gamma = self.beta = None
+        self.relu = False       # absorb_relu: followed by a single-consumer ReLU, applied here (the kernel's relu flag)
+
+    def build(self, x):
+        c = x.shape[-1]
+        if self.groups == -1:
+            self.groups = c
+        if self.groups < 1 or c % self.groups:
+            raise ValueError(f"GroupNormalization: the number of groups ({self.groups}) must divide the number of channels ({c})")
+        if self.scale:
+            self.gamma = self.add_param("gamma", (c,), "ones", kind="gamma")
+        if self.center:
+            self.beta = self.add_param("beta", (c,), "zeros", kind="beta")
+        return self.connect([x], x.shape)
+
+    def forward(self, rt, xs, training):
+        (x,) = xs
+        y, mean, invstd = rt.eng.gn_fwd(x, None if self.gamma is None else rt.param(self.gamma),
+                                        None if self.beta is None else rt.param(self.beta), self.groups, relu=self.relu,
+                                        eps=self.epsilon)
+        rt.save(self, mean=mean, invstd=invstd)
+        return y
+
+    def backward(self, rt, xs, y, dy):
+        (x,) = xs
+        s = rt.saved(self)
+        dx, _, _ = rt.eng.gn_bwd(x, dy, None if self.gamma is None else rt.param(self.gamma),
+                                 None if self.beta is None else rt.param(self.beta), s["mean"], s["invstd"], self.groups,
+                                 relu=self.relu, dgamma=None if self.gamma is None else rt.grad(self.gamma),
+                                 dbeta=None if self.beta is None else rt.grad(self.beta))
+        return [dx]
+
+
+class GroupNormalization(Layer):
+    """tf.keras.layers.GroupNormalization: groups=-1 is one channel per group (instance normalisation), groups=1 normalises
+    over (H, W, C)."""
+
+    def __init__(self, groups=32, axis=-1, epsilon=1e-3, center=True, scale=True, name=None, **kw):
+        super().__init__(name)
+        assert axis in (-1, 3, 1), "GroupNormalization on this path normalises the last axis"
+        self.groups, self.epsilon, self.center, self.scale = int(groups), epsilon, bool(center), bool(scale)
+
+    def __call__(self, x):
+        self._once()
+        return _GNNode(self._name, self.groups, self.epsilon, self.center, self.scale).build(x)
+
+
+# The zoo builders' `norm=` argument: every normalisation site of a builder goes through Normalization(), which makes the layer
+# the enclosing norm_scope asks for.  "batch" (the default, and what the reference builds) is BatchNormalization() itself.
+_NORM = [("batch", None)]
+
+
+def parse_norm(norm):
+    """norm = "batch" | "group" | ("group", G) -> (kind, G or None)"""
+    if norm in ("batch", "group"):
+        return norm, None
+    if isinstance(norm, (tuple, list)) and len(norm) == 2 and norm[0] == "group" and isinstance(norm[1], int) and norm[1] >= 1:
+        return "group", int(norm[1])
+    raise ValueError(f'norm must be "batch", "group" or ("group", G), got {norm!r}')
+
+
+class norm_scope:
+    def __init__(self, norm):
+        self.norm = parse_norm(norm)
+
+    def __enter__(self):
+        _NORM.append(self.norm)
+
+    def __exit__(self, *exc):
+        _NORM.pop()
+
+
+class Normalization(Layer):
+    """A builder's normalisation site: BatchNormalization(), or under norm_scope("group") a GroupNormalization of gcd(C, 32)
+    groups (728 channels: 8 groups of 91; 48: 16 of 3), under ("group", G) of G groups (ValueError where C % G != 0)."""
+
+    def __init__(self, name=None):
+        super().__init__(name)
+
+    def __call__(self, x):
+        self._once()
+        kind, g = _NORM[-1]
+        if kind == "batch":
+            return BatchNormalization(name=self._name)(x)
+        return GroupNormalization(groups=g if g is not None else math.gcd(x.shape[-1], 32), name=self._name)(x)
+
+
 # ============================================================================================ activations
 class _ActNode(Node):
     op = "activation"
@@ -1257,12 +1353,12 @@ def bam_block(x: KTensor, rate=16, d=4) -> KTensor:
     c = x.shape[-1]
     r = c // rate
     a = GlobalAveragePooling2D()(x)
-    a = Activation("relu")(BatchNormalization()(Dense(r)(a)))
-    a = Activation("relu")(BatchNormalization()(Dense(r)(a)))
+    a = Activation("relu")(Normalization()(Dense(r)(a)))
+    a = Activation("relu")(Normalization()(Dense(r)(a)))
     mc = Dense(c)(a)
-    s = Activation("relu")(BatchNormalization()(Conv2D(r, 1)(x)))
-    s = Activation("relu")(BatchNormalization()(Conv2D(r, 3, dilation_rate=d, padding="same")(s)))
-    s = Activation("relu")(BatchNormalization()(Conv2D(r, 3, dilation_rate=d, padding="same")(s)))
+    s = Activation("relu")(Normalization()(Conv2D(r, 1)(x)))
+    s = Activation("relu")(Normalization()(Conv2D(r, 3, dilation_rate=d, padding="same")(s)))
+    s = Activation("relu")(Normalization()(Conv2D(r, 3, dilation_rate=d, padding="same")(s)))
     ms = Conv2D(1, 1)(s)
     return _BamCombineNode().build(x, mc, ms)
 

@@ -6,7 +6,7 @@
 
 "mixed_bfloat16": every activation and activation gradient is stored in bf16 (half the HBM traffic of the
 bandwidth-bound layers), convolutions multiply bf16 operands on the matrix pipe in ONE pass with fp32 accumulation,
-all other kernels widen to fp32 on load; weights (fp32 master copies), BatchNormalization parameters and statistics,
+all other kernels widen to fp32 on load; weights (fp32 master copies), BatchNormalization / GroupNormalization parameters and statistics,
 the softmax head with its logits / probabilities, the loss, weight gradients and Adam stay fp32.  "float32" is the
 reference's precision and the default.  BASELINE.json configs[2].
 """

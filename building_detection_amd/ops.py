@@ -661,6 +661,43 @@ class Engine:
               "sg_bn_train_bwd")
         return dx, dgamma, dbeta
 
+    # ---------------------------------------------------------------------------------------------- GroupNormalization
+    @staticmethod
+    def _gn_geom(x, groups):
+        """(N, HW, C) of an [N, ..., C] tensor; the group count must divide C."""
+        c = x.shape[-1]
+        n = x.shape[0]
+        if groups < 1 or c % groups:
+            raise _lib.SgError(f"group normalisation: {c} channels do not divide into {groups} groups")
+        return n, x.numel() // (n * c), c
+
+    def gn_fwd(self, x, gamma, beta, groups, relu=False, eps=1e-3, out=None):
+        """GroupNormalization of x [N, ..., C] (statistics per image and group of C / groups adjacent channels); gamma / beta None:
+        no scale / no offset.  -> y, mean [N * groups], invstd [N * groups].  The same call in training and inference."""
+        _chk(x, "x")
+        n, hw, c = self._gn_geom(x, groups)
+        y = out if out is not None else torch.empty_like(x)
+        mean, invstd = self.empty(n * groups), self.empty(n * groups)
+        wsp, wsn = self.ws(self.lib.sg_gn_ws_bytes(self.h, _dt(x), n, hw, c, groups))
+        check(self.lib.sg_gn_fwd(self.h, self.stream, _dt(x), n, hw, c, groups, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y),
+                                 _ptr(mean), _ptr(invstd), eps, int(relu), wsp, wsn), "sg_gn_fwd")
+        return y, mean, invstd
+
+    def gn_bwd(self, x, dy, gamma, beta, mean, invstd, groups, relu=False, out=None, dgamma=None, dbeta=None):
+        """-> dx, dgamma, dbeta (None where gamma / beta is None).  The fused ReLU's mask is recomputed from x; y is not read."""
+        _chk(x, "x")
+        _chk(dy, "dy")
+        n, hw, c = self._gn_geom(x, groups)
+        dx = out if out is not None else torch.empty_like(x)
+        if gamma is not None and dgamma is None:
+            dgamma = self.empty(c)
+        if beta is not None and dbeta is None:
+            dbeta = self.empty(c)
+        wsp, wsn = self.ws(self.lib.sg_gn_ws_bytes(self.h, _dt(x), n, hw, c, groups))
+        check(self.lib.sg_gn_bwd(self.h, self.stream, _dt(x), n, hw, c, groups, _ptr(x), _ptr(dy), _ptr(gamma), _ptr(beta),
+                                 _ptr(mean), _ptr(invstd), _ptr(dx), _ptr(dgamma), _ptr(dbeta), int(relu), wsp, wsn), "sg_gn_bwd")
+        return dx, dgamma, dbeta
+
     def bn_train_bwd_thin_ok(self, x, g, w) -> bool:
         """Can bn_train_bwd_thin take the gradient g of a thin 1x1 convolution (kernel w) for the BatchNormalization input x?"""
         c = x.shape[-1]

@@ -300,7 +300,7 @@ def _module(name, **attrs):
 
 _layer_names = dict(
     Input=L.Input, Conv2D=_wrap(L.Conv2D), SeparableConv2D=_wrap(L.SeparableConv2D),
-    Conv2DTranspose=_wrap(L.Conv2DTranspose), Dense=_wrap(L.Dense), BatchNormalization=_wrap(L.BatchNormalization),
+    Conv2DTranspose=_wrap(L.Conv2DTranspose), Dense=_wrap(L.Dense), BatchNormalization=_wrap(L.BatchNormalization), GroupNormalization=_wrap(L.GroupNormalization),
     Activation=_Activation, ReLU=_wrap(L.ReLU), Softmax=_Softmax, MaxPooling2D=_wrap(L.MaxPooling2D),
     MaxPool2D=_wrap(L.MaxPooling2D), AveragePooling2D=_wrap(L.AveragePooling2D),
     GlobalAveragePooling2D=_wrap(L.GlobalAveragePooling2D), GlobalAvgPool2D=_wrap(L.GlobalAveragePooling2D),

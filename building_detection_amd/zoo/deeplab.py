@@ -15,7 +15,7 @@ from ..runtime import Model
 def _cbr(x, filters, k, stride=1, dilate=1, activate=True):
     """conv_bn_relu of v3plus.py:288-293."""
     x = L.Conv2D(filters, k, stride, padding="same", dilation_rate=dilate)(x)
-    x = L.BatchNormalization()(x)
+    x = L.Normalization()(x)
     return L.Activation("relu")(x) if activate else x
 
 
@@ -23,12 +23,12 @@ def _sep_bn(x, filters, stride=1, pre_relu=False, post_relu=False):
     if pre_relu:
         x = L.Activation("relu")(x)
     x = L.SeparableConv2D(filters, 3, strides=stride, padding="same")(x)
-    x = L.BatchNormalization()(x)
+    x = L.Normalization()(x)
     return L.Activation("relu")(x) if post_relu else x
 
 
 def _shortcut(x, filters, stride):
-    return L.BatchNormalization()(L.Conv2D(filters, 1, strides=stride, padding="same")(x))
+    return L.Normalization()(L.Conv2D(filters, 1, strides=stride, padding="same")(x))
 
 
 def _xception(inp, with_bam):
@@ -88,7 +88,7 @@ def _sk_block(x, reduce=16):
     t = _cbr(t, 256 // reduce, 1)
     logits = [L.Conv2D(256, 1, strides=1, padding="same")(t) for _ in range(5)]
     y = L.sk_fuse(branches, logits)
-    return L.Activation("relu")(L.BatchNormalization()(y))
+    return L.Activation("relu")(L.Normalization()(y))
 
 
 def _aspp(x, pool, upsampling="nearest"):
@@ -131,10 +131,16 @@ def _decode(y, filters):
     return L.scse_block(y)
 
 
-def Xception_DeepLabV3_Plus(shape=(512, 512, 3), num_classes=2, aspp_pool=32, upsampling="nearest", dropout=None):
-    """`upsampling` ("nearest", the reference's, or "bilinear") is the interpolation of the ASPP's and the decoder's
+def Xception_DeepLabV3_Plus(shape=(512, 512, 3), num_classes=2, aspp_pool=32, upsampling="nearest", dropout=None, norm="batch"):
+    """`norm`: "batch" (the reference's graph), "group" (GroupNormalization of gcd(C, 32) groups at every BatchNormalization
+    site) or ("group", G).  `upsampling` ("nearest", the reference's, or "bilinear") is the interpolation of the ASPP's and the decoder's
     UpSampling2D layers; it changes no parameter.  `dropout` = (p_aspp, p_head) adds Dropout(p_aspp) on the output of the ASPP's
     1x1 projection and Dropout(p_head) on the tensor entering the class convolution; None (the reference) and a zero add no node."""
+    with L.norm_scope(norm):
+        return _v3plus(shape, num_classes, aspp_pool, upsampling, dropout)
+
+
+def _v3plus(shape, num_classes, aspp_pool, upsampling, dropout):
     p_aspp, p_head = _rates(dropout)
     inp = L.Input(shape=shape)
     c, c1, c2, c5 = _xception(inp, with_bam=False)
@@ -149,8 +155,13 @@ def Xception_DeepLabV3_Plus(shape=(512, 512, 3), num_classes=2, aspp_pool=32, up
     return Model(inputs=inp, outputs=out, name="Xception_DeepLabV3_Plus")
 
 
-def Xception_DeepLabV3_Plus_bam(shape=(512, 512, 3), num_classes=2, aspp_pool=32, upsampling="nearest", dropout=None):
-    """`dropout` as Xception_DeepLabV3_Plus."""
+def Xception_DeepLabV3_Plus_bam(shape=(512, 512, 3), num_classes=2, aspp_pool=32, upsampling="nearest", dropout=None, norm="batch"):
+    """`dropout` and `norm` as Xception_DeepLabV3_Plus (the BAM blocks' normalisations behind Dense included)."""
+    with L.norm_scope(norm):
+        return _v3plus_bam(shape, num_classes, aspp_pool, upsampling, dropout)
+
+
+def _v3plus_bam(shape, num_classes, aspp_pool, upsampling, dropout):
     p_aspp, p_head = _rates(dropout)
     inp = L.Input(shape=shape)
     _, c1, c2, c5 = _xception(inp, with_bam=True)

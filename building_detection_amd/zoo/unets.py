@@ -42,13 +42,15 @@ class ResNetFamily:
     """`ResNetFamily(input_shape).run_model('res34')` (predict.py:19-20).  Layer names follow the reference
     (conv1_1.., pool1..4, conv{2-5}_{i}_{1,2}[_BN/_AC], upsame_{1-4})."""
 
-    def __init__(self, input_shape=(512, 512, 3)):
+    def __init__(self, input_shape=(512, 512, 3), norm="batch"):
         self.inputs = L.Input(input_shape)
         self.f_size = 64
+        self.norm = norm   # "batch" | "group" | ("group", G): see zoo.Xception_DeepLabV3_Plus
+        L.parse_norm(norm)
 
     def bn_conv_a(self, x, f, name):
         x = L.Conv2D(f, 3, padding="same", name=name, kernel_initializer="he_normal")(x)
-        x = L.BatchNormalization(name=f"{name}_BN")(x)
+        x = L.Normalization(name=f"{name}_BN")(x)
         return L.Activation("relu", name=f"{name}_AC")(x)
 
     def res_block1(self, x, f, name):
@@ -85,8 +87,8 @@ class ResNetFamily:
     def attention_demo(x):
         c = x.shape[-1]
         g = L.GlobalAveragePooling2D()(x)
-        g = L.ReLU()(L.BatchNormalization()(L.Dense(c // 2)(g)))
-        g = L.Activation("sigmoid")(L.BatchNormalization()(L.Dense(c)(g)))
+        g = L.ReLU()(L.Normalization()(L.Dense(c // 2)(g)))
+        g = L.Activation("sigmoid")(L.Normalization()(L.Dense(c)(g)))
         return L.multiply([x, L.Reshape((1, 1, c))(g)])
 
     def upsame_feature(self, low, high, name):
@@ -111,14 +113,15 @@ class ResNetFamily:
     def run_model(self, name):
         if name != "res34":
             raise ValueError("This network does not exist.")
-        out = self.feature_fusion(self.res34(self.inputs))
+        with L.norm_scope(self.norm):
+            out = self.feature_fusion(self.res34(self.inputs))
         return Model(self.inputs, out, name="res34_unet")
 
 
 # -------------------------------------------------------------------------------------------------- HRNet
 def _cbr(x, filters, kernel_size=3, strides=1, activate=True):
     x = L.Conv2D(filters, kernel_size, strides, padding="same")(x)
-    x = L.BatchNormalization()(x)
+    x = L.Normalization()(x)
     return L.Activation("relu")(x) if activate else x
 
 
@@ -160,8 +163,14 @@ def _fuse2(b):
     return g0, g1, g2
 
 
-def HRNet(shape=(512, 512, 3), num_classes=2, dropout=None):
-    """`dropout` = p_head: Dropout(p_head) in front of the head (None, the reference: no node)."""
+def HRNet(shape=(512, 512, 3), num_classes=2, dropout=None, norm="batch"):
+    """`dropout` = p_head: Dropout(p_head) in front of the head (None, the reference: no node).  `norm` as
+    zoo.Xception_DeepLabV3_Plus."""
+    with L.norm_scope(norm):
+        return _hrnet(shape, num_classes, dropout)
+
+
+def _hrnet(shape, num_classes, dropout):
     inp = L.Input(shape=shape)
     x = _cbr(inp, 64, strides=2)
     x = _bottleneck(x, 256, project=True)

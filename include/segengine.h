@@ -497,6 +497,27 @@ int sg_bn_infer(sg_ctx* ctx, void* stream, int dtype, int64_t rows, int C, const
                 const void* gamma, const void* beta, const void* moving_mean, const void* moving_var,
                 void* y, float eps, int relu);
 
+/* ------------------------------------------------------------------------------------- GroupNormalization
+ * tf.keras.layers.GroupNormalization on NHWC [N][hw][C] (a 2-D [N][C] tensor: hw = 1): G groups of C / G adjacent channels,
+ * mean and biased variance per (image, group) over hw * C / G elements, y = gamma_c (x - mean) invstd + beta_c [ReLU],
+ * invstd = 1 / sqrt(var + eps).  Training and inference are the same call.  dtype: the storage type of x, y, dy, dx; gamma, beta,
+ * dgamma, dbeta [C] and save_mean, save_invstd [N * G] are fp32.  gamma / beta NULL: 1 / 0 (scale=False / center=False), and
+ * dgamma / dbeta must then be NULL too.
+ * fwd: three launches (per-(n, c) sums about a per-channel pivot; fp64 fold of a group's channels with the parallel-variance
+ *   combination; apply).  bwd: three launches (per-(n, c) sums of g and g xhat, g = dy masked by the fused ReLU, which is
+ *   recomputed from x with the forward's expression - y is not read; fp64 fold; apply, which also writes dgamma / dbeta).
+ * Every sum has a fixed order that depends on (hw, C, G) only: the same bits on every run, and an image's y / dx do not depend
+ * on the other images of the batch.  16-byte accesses when C % 4 == 0 (SG_BF16: C % 8 == 0 for the full width) and every
+ * operand is 16-byte aligned, scalar otherwise; a group boundary may fall anywhere.  ws: sg_gn_ws_bytes (16-byte aligned).
+ * SG_EINVAL, nothing launched or written: C % G != 0, G < 1, N < 1 or N > 65535, hw < 1, a null tensor, an unknown dtype
+ * (the query then answers 0); SG_EWORKSPACE: a short workspace. */
+size_t sg_gn_ws_bytes(const sg_ctx* ctx, int dtype, int N, int64_t hw, int C, int G);
+int sg_gn_fwd(sg_ctx* ctx, void* stream, int dtype, int N, int64_t hw, int C, int G, const void* x, const void* gamma,
+              const void* beta, void* y, void* save_mean, void* save_invstd, float eps, int relu, void* ws, size_t ws_bytes);
+int sg_gn_bwd(sg_ctx* ctx, void* stream, int dtype, int N, int64_t hw, int C, int G, const void* x, const void* dy,
+              const void* gamma, const void* beta, const void* save_mean, const void* save_invstd, void* dx, void* dgamma,
+              void* dbeta, int relu, void* ws, size_t ws_bytes);
+
 /* The plan one BatchNormalization call runs by (csrc/norm.hip, plan_bn - the six entry points above and sg_bn_ws_bytes read the same
  * one), for this storage type and the SG_BN_COLS / SG_SEG_FUSED / SG_FINALIZE_LANES switches.  pass: SG_BN_FWD (sg_bn_train_fwd:
  * statistics and apply), SG_BN_APPLY (sg_bn_apply, sg_bn_infer), SG_BN_BWD (sg_bn_train_bwd: reduce and apply), SG_BN_BWD_APPLY,
